@@ -13,19 +13,32 @@ Multi-GPU (`--gpus N`, launched by torch.distributed.run), two modes:
                              a C3 window fits one GPU, and north_star shards a window only "when
                              the window exceeds one GPU", so more GPUs = more windows, with no
                              data-path collective (weak scaling; the same workload and unit as the
-                             N = 1 line). For N > 1 rank 0 then runs the sharded C5 job below as a
+                             N = 1 line). With --full and N > 1 rank 0 then runs the sharded C5 job below as a
                              child process group (bounded by a timeout, killed by its process
                              group id if it overruns) and embeds its line as "shard_run".
   --mode shard               ONE window split over the ranks by landmark:
                              BASELINE.json configs[4] (C5, 1000 KF, "report 1/2/4/8 scaling")
                              for every N > 1 (`--config C4` gives configs[3]); partial reduced
                              camera systems summed with RCCL all-reduces inside the captured step
-                             graph (strong scaling); rank 0 also times the same window unsharded on
+                             graph (strong scaling); with --full rank 0 also times the same window unsharded on
                              its GPU ("scaling_reference", the curve's 1-GPU point);
                              `--transport host` rehearses it with gloo.
 The barrier and max-over-ranks timing use torch.distributed in both.
 
-Extra JSON objects:
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline figure needs: it sets
+up the window, warms up, times the K steps, writes the outputs of the last timed step when
+`--dump-outputs DIR` is given, and prints the result line. Everything below that takes runs of
+its own — the kernel-timed step behind `roofline` / `kernels`, the end-to-end call on new
+windows, the host mirror, the concurrent windows, the CPU baseline, and for N > 1 the embedded
+sharded run and the unsharded scaling reference — is measured only with `--full`.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64): the
+step's return values (`iters`, `chi2`) and the estimates and edge errors it left on the device,
+read back with the g2o-style calls (`kf_Tcw`, `pt_xyz`, `ln_orth`, `ept_chi2`, `ept_depth_ok`,
+`eln_chi2`). The window is generated from a fixed seed, so two builds given the same arguments
+solve identical inputs. Arrays are capped at 64 MB in all by a fixed, seeded row sample.
+
+Extra JSON objects (`--full`):
   roofline      dominant kernel (by device time), algorithmic bytes per launch / avg launch
                 time measured with HIP events on the solver stream; traffic from the committed
                 rocprofv3 PMC summary (profiles/pmc_<cfg>.json) when present.
@@ -58,6 +71,12 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--config", default="C3")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: kernel-timed step (roofline, "
+                        "kernels), end-to-end call, host mirror, concurrent windows, CPU baseline, and for "
+                        "N > 1 the embedded sharded run / scaling reference (off: only the timed steps)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (float64)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-runs", type=int, default=5)
     p.add_argument("--device", type=int, default=None, help="override LOCAL_RANK (multi-rank rehearsal on 1 GPU)")
@@ -71,7 +90,10 @@ def parse():
                    help="N = 1: also time this many independent windows solved concurrently on the one GPU "
                         "(one context + stream each, one host thread each), reported as 'concurrent_windows' "
                         "beside the single-window value (0 disables)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
 
 
 def cpu_model() -> str:
@@ -221,6 +243,30 @@ def host_mirror(cfg: str, dev: int, calls: int = 3, background=None, scan_calls:
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(s, r, path: str, write: bool):
+    """--dump-outputs: what the last timed step computed — its return values and the state it left
+    on the device, read back with the g2o-style calls (no further solve) — as <path>/<name>.npy in
+    float64. An array over its share of the 64 MB budget is cut to a fixed, seeded sample of its
+    rows. Every rank reads back (a sharded window gathers its landmarks); `write` ranks store."""
+    T, P, O = s.download()
+    pc, pd, lc = s.edge_chi2()
+    arrays = {"iters": r["iters"], "chi2": r["chi2"], "kf_Tcw": T, "pt_xyz": P, "ln_orth": O,
+              "ept_chi2": pc, "ept_depth_ok": pd, "eln_chi2": lc}
+    if not write:
+        return
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, np.float64)
+        if arr.nbytes > share:
+            keep = share // (arr.nbytes // len(arr))
+            arr = arr[np.sort(np.random.default_rng(20240).choice(len(arr), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def relaunch_distributed(a) -> int:
     """`--gpus N` (N > 1) without a torch.distributed launcher: start N ranks of this same command
     under torch.distributed.run (127.0.0.1) as a child process, before anything touches the GPU,
@@ -263,7 +309,7 @@ def shard_child(a, world: int):
                         "ROLE_RANK", "ROLE_NAME", "ROLE_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")
            and not k.startswith("TORCHELASTIC_")}
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--mode", "shard",
-           "--steps", str(max(1, min(a.steps, 10))), "--warmup", "1", "--no-cpu-baseline",
+           "--steps", str(max(1, min(a.steps, 10))), "--warmup", "1", "--full", "--no-cpu-baseline",
            "--transport", a.transport] + (["--device", str(a.device)] if a.device is not None else [])
     t0 = time.perf_counter()
     p = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
@@ -289,6 +335,73 @@ def shard_child(a, world: int):
             d["child_wall_s"] = wall
             return d
     return {"error": f"exit {p.returncode}, no JSON line", "stderr_tail": err[-2000:]}
+
+
+def kernel_sections(a, g, r, ktimes: dict, info: dict):
+    """--full: the `roofline` and `kernels` objects from the one instrumented (kernel-timed) step."""
+    # dominant kernel by device time in the instrumented step
+    name, (kms, nl) = max(((k, v) for k, v in ktimes.items() if v[1] > 0), key=lambda kv: kv[1][0])
+    avg_ms = kms / max(nl, 1)
+    # rocprofv3 names the banded factorisation by its template (k_rcs_factor_band<BW>)
+    prof_name = name
+    if name == "k_rcs_factor" and info.get("banded"):
+        if info.get("bcr_rows"):
+            prof_name = "k_rcs_factor_bcr"
+        else:
+            prof_name = "k_rcs_factor_twisted" if info.get("twisted") else "k_rcs_factor_band"
+            if info.get("column_lane"):
+                prof_name += "_cl"
+    alg = kernel_bytes(g, prof_name if prof_name == "k_rcs_factor_bcr" else name, info)
+    # block pivot steps on the factorisation's critical path (forward chain + backward chain)
+    chain = None
+    if name == "k_rcs_factor" and info.get("banded") and not info.get("bcr_rows"):
+        nf_, bw_ = int(info["nf"]), int(info["bw"])
+        if info.get("twisted"):
+            chain = 2 * ((nf_ - bw_ + 1) // 2 + bw_)
+        else:
+            chain = 2 * nf_
+    achieved = alg / (avg_ms * 1e-3) / 1e9
+    pmc_path = os.path.join(ROOT, "profiles", f"pmc_{a.config}.json")
+    traffic = None
+    if os.path.exists(pmc_path):
+        try:
+            traffic = json.load(open(pmc_path)).get(prof_name, {}).get("hbm_bytes_per_launch")
+        except Exception:
+            traffic = None
+    per_kernel = {}
+    # the iteration kernels exit at once on steps without a new linearisation (ITER_GUARD): their
+    # bandwidth is over the launches that worked — one per outer iteration of the LBA
+    lin_per_lba = int(sum(max(int(x), 0) for x in r["iters"]))
+    for k, (ms_k, n_k) in ktimes.items():
+        if n_k <= 0:
+            continue
+        b = kernel_bytes(g, "k_rcs_factor_bcr" if (k == "k_rcs_factor" and info.get("bcr_rows")) else k, info)
+        us = ms_k / n_k * 1e3
+        work = min(n_k, lin_per_lba) if k in ("k_linearize", "k_iter_reduce") else n_k
+        us_w = ms_k / max(work, 1) * 1e3
+        per_kernel[k] = {"us_per_launch": round(us, 2), "launches_per_lba": n_k, "working_launches": work,
+                         "us_per_working_launch": round(us_w, 2),
+                         "alg_bytes": int(b), "GBs": round(b / (us_w * 1e-6) / 1e9, 1) if b else None}
+    roofline = {
+        "kernel": prof_name,
+        # the factorisation is a serial chain of block pivots: its limiter is latency, the HBM
+        # fraction is reported per the contract (peak = HBM) but is not its bound
+        "bound": "latency" if name == "k_rcs_factor" else "hbm",
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS,
+        "traffic": traffic,
+        "alg_bytes_per_launch": alg,
+        "avg_launch_us": avg_ms * 1e3,
+        "launches_per_lba": nl,
+        "critical_path_block_steps": chain,
+        "us_per_block_step": avg_ms * 1e3 / chain if chain else None,
+        "note": ("latency-bound factorisation of the reduced camera system (a serial chain of 6x6 "
+                 "pivot blocks or of dense super-row eliminations) + back substitution + pose update; "
+                 "bytes/launch are tiny by nature — see DESIGN.md §4"),
+    }
+    return roofline, per_kernel
 
 
 def main():
@@ -371,27 +484,29 @@ def main():
         s.reset()
         return s.lba_plucker(want_outputs=False, with_trace=with_trace)
 
+    r = None
     for _ in range(a.warmup):
-        step()
-    # one instrumented (kernel-timed) step outside the timed region, for the roofline
-    s.L.plba_enable_kernel_timing(s.ctx, 1)
-    r = step()
-    ktimes = s.kernel_times()
+        r = step()
+    ktimes = None
+    if a.full:
+        # one instrumented (kernel-timed) step outside the timed region, for the roofline
+        s.L.plba_enable_kernel_timing(s.ctx, 1)
+        r = step()
+        ktimes = s.kernel_times()
+        s.L.plba_enable_kernel_timing(s.ctx, 0)
     info = s.structure_stats()
-    s.L.plba_enable_kernel_timing(s.ctx, 0)
-    ph = phases(ktimes, info.get("device_steps")) if shard else None
+    ph = phases(ktimes, info.get("device_steps")) if shard and a.full else None
 
     s.synchronize()
     if dist is not None:
         dist.barrier()
     t0 = time.perf_counter()
     iters = 0
-    trials = 0
-    trials_per_lba = int(sum(t["trials"] for t in r["trace"]))  # the instrumented step's (same window)
+    # the last untimed step's trial count (same window, same solve); None without any untimed step
+    trials_per_lba = int(sum(t["trials"] for t in r["trace"])) if r is not None else None
     for _ in range(a.steps):
         r = step(with_trace=False)
         iters += int(r["iters"][0] + r["iters"][1])
-        trials += trials_per_lba
     s.synchronize()
     if dist is not None:
         dist.barrier()
@@ -407,12 +522,15 @@ def main():
             dist.all_reduce(ti, op=dist.ReduceOp.SUM)
             tot_iters = int(ti.item())
 
-    # End-to-end LBA call on a NEW window of the same config: upload (host
+    if a.dump_outputs:
+        dump_outputs(s, r, a.dump_outputs, write=rank == 0)
+
+    # --full: End-to-end LBA call on a NEW window of the same config: upload (host
     # marshalling + one pinned copy) + step-graph capture + the two-stage solve + download of every
     # output, as the drop-in use pays it per call; the second of two windows is reported (the
     # first pays one-time arena / code-object costs). Outside the timed region.
     e2e = []
-    for k in range(2):
+    for k in range(2 if a.full else 0):
         # (sharded: every rank uploads the same window — each keeps its landmark share)
         g2 = synth.generate(a.config, seed=base_seed + 7919 * (k + 1) + (0 if shard else 97 * rank))
         if dist is not None:
@@ -428,7 +546,7 @@ def main():
     # the same window unsharded on one GPU (rank 0, outside the timed region): the N = 1 point of
     # the sharded strong-scaling curve
     scaling_ref = None
-    if shard and world > 1:
+    if a.full and shard and world > 1:
         if rank == 0:
             ref = Solver(device=dev)
             ref.upload(g)
@@ -455,7 +573,7 @@ def main():
         dist.barrier()
 
     hmirror = hmirror_map = None
-    if world == 1 and not shard and not a.no_host_mirror:
+    if a.full and world == 1 and not shard and not a.no_host_mirror:
         try:
             hmirror = host_mirror(a.config, dev)
         except Exception as e:  # informational: must never hide the single-window number
@@ -469,7 +587,7 @@ def main():
                 hmirror_map = {"error": repr(e)}
 
     conc = None
-    if world == 1 and not shard and a.windows > 1:
+    if a.full and world == 1 and not shard and a.windows > 1:
         try:
             conc = concurrent_windows(a, dev, a.windows)
         except Exception as e:  # informational: must never hide the single-window number
@@ -477,55 +595,12 @@ def main():
 
     # replicas, N > 1: the sharded C5 window on the same GPUs (child job; the other ranks wait)
     shard_run = None
-    if not shard and world > 1 and not a.no_shard_run:
+    if a.full and not shard and world > 1 and not a.no_shard_run:
         if rank == 0:
             shard_run = shard_child(a, world)
         dist.barrier()
 
     if rank == 0:
-        # dominant kernel by device time in the instrumented step
-        name, (kms, nl) = max(((k, v) for k, v in ktimes.items() if v[1] > 0), key=lambda kv: kv[1][0])
-        avg_ms = kms / max(nl, 1)
-        # rocprofv3 names the banded factorisation by its template (k_rcs_factor_band<BW>)
-        prof_name = name
-        if name == "k_rcs_factor" and info.get("banded"):
-            if info.get("bcr_rows"):
-                prof_name = "k_rcs_factor_bcr"
-            else:
-                prof_name = "k_rcs_factor_twisted" if info.get("twisted") else "k_rcs_factor_band"
-                if info.get("column_lane"):
-                    prof_name += "_cl"
-        alg = kernel_bytes(g, prof_name if prof_name == "k_rcs_factor_bcr" else name, info)
-        # block pivot steps on the factorisation's critical path (forward chain + backward chain)
-        chain = None
-        if name == "k_rcs_factor" and info.get("banded") and not info.get("bcr_rows"):
-            nf_, bw_ = int(info["nf"]), int(info["bw"])
-            if info.get("twisted"):
-                chain = 2 * ((nf_ - bw_ + 1) // 2 + bw_)
-            else:
-                chain = 2 * nf_
-        achieved = alg / (avg_ms * 1e-3) / 1e9
-        pmc_path = os.path.join(ROOT, "profiles", f"pmc_{a.config}.json")
-        traffic = None
-        if os.path.exists(pmc_path):
-            try:
-                traffic = json.load(open(pmc_path)).get(prof_name, {}).get("hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
-        per_kernel = {}
-        # the iteration kernels exit at once on steps without a new linearisation (ITER_GUARD): their
-        # bandwidth is over the launches that worked — one per outer iteration of the LBA
-        lin_per_lba = int(sum(max(int(x), 0) for x in r["iters"]))
-        for k, (ms_k, n_k) in ktimes.items():
-            if n_k <= 0:
-                continue
-            b = kernel_bytes(g, "k_rcs_factor_bcr" if (k == "k_rcs_factor" and info.get("bcr_rows")) else k, info)
-            us = ms_k / n_k * 1e3
-            work = min(n_k, lin_per_lba) if k in ("k_linearize", "k_iter_reduce") else n_k
-            us_w = ms_k / max(work, 1) * 1e3
-            per_kernel[k] = {"us_per_launch": round(us, 2), "launches_per_lba": n_k, "working_launches": work,
-                             "us_per_working_launch": round(us_w, 2),
-                             "alg_bytes": int(b), "GBs": round(b / (us_w * 1e-6) / 1e9, 1) if b else None}
         it_per_lba = tot_iters / max(a.steps * (1 if shard else world), 1)
         iter_bytes = synth.algorithmic_bytes_per_iter(g)
         out = {
@@ -535,6 +610,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": dt / a.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong" if shard else "weak",
@@ -551,13 +627,13 @@ def main():
                 # visibility rejection leaves ~4.7 (C3: 112,416 of the nominal 120,000 edges)
                 "survey_nominal_edges": int(5 * (g.n_pt + g.n_ln)),
                 "lm_iterations_per_lba": it_per_lba,
-                "trials_per_lba": trials / a.steps,
+                "trials_per_lba": trials_per_lba,
                 "ms_per_lm_iteration": dt / max(iters, 1) * 1e3,
                 # plba_create pre-warms the context (code objects, first device build, pinned
                 # staging): create_ms is that one-time cost, upload_ms the process's first window
                 "create_ms": create_ms,
                 "upload_ms": upload_ms,
-                "end_to_end": e2e[-1],
+                "end_to_end": e2e[-1] if e2e else None,
                 "factorisation": ("block cyclic reduction over %d super-rows" % info["bcr_rows"] if info.get("bcr_rows")
                                   else "dense blocked LDLT (MFMA)" if not info.get("banded")
                                   else "%s%s band LDLT (bw %d)" % ("two-sided " if info.get("twisted") else "",
@@ -568,33 +644,15 @@ def main():
                 "parallelism": (f"landmark-sharded window over {world} GPU(s)" if shard
                                 else f"{world} independent windows (1 per GPU)"),
             },
-            "roofline": {
-                "kernel": prof_name,
-                # the factorisation is a serial chain of block pivots: its limiter is latency, the HBM
-                # fraction is reported per the contract (peak = HBM) but is not its bound
-                "bound": "latency" if name == "k_rcs_factor" else "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "alg_bytes_per_launch": alg,
-                "avg_launch_us": avg_ms * 1e3,
-                "launches_per_lba": nl,
-                "critical_path_block_steps": chain,
-                "us_per_block_step": avg_ms * 1e3 / chain if chain else None,
-                "note": ("latency-bound factorisation of the reduced camera system (a serial chain of 6x6 "
-                         "pivot blocks or of dense super-row eliminations) + back substitution + pose update; "
-                         "bytes/launch are tiny by nature — see DESIGN.md §4"),
-            },
             "iteration_roofline": {
                 "alg_bytes_per_iter": iter_bytes,
                 "achieved_GBs": iter_bytes * (tot_iters / dt) / 1e9,
                 "frac": iter_bytes * (tot_iters / dt) / 1e9 / HBM_PEAK_GBS,
             },
-            "kernels": per_kernel,
         }
         out["final_chi2_gpu"] = [float(r["chi2"][0]), float(r["chi2"][1])]
+        if a.full:
+            out["roofline"], out["kernels"] = kernel_sections(a, g, r, ktimes, info)
         if ph is not None:
             out["phases"] = ph
         if shard:
@@ -619,7 +677,7 @@ def main():
             out["host_mirror"] = hmirror
         if hmirror_map is not None:
             out["host_mirror_c5_map"] = hmirror_map
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 cb = cpu_baseline(a.config, a.cpu_runs if a.config in ("C1", "C1L", "C2", "C3") else 1)
                 out["final_chi2_cpu"] = cb.pop("final_chi2")
