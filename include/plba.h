@@ -143,13 +143,24 @@ int plba_enable_kernel_timing(plba_ctx *ctx, int32_t on);   /* HIP-event timing 
  * the column-lane factorisation (the context then keeps that factorisation), [17]=trial slots
  * a step evaluates at most (speculative damped trials, 1 = off), [18]=their policy
  * (0 off, 1 always, 2 after a rejection in the iteration, 3 after the first rejection of the
- * optimize() call), [19]=device steps the last schedule took, [20]=unused (always 0; it was the
- * four-segment column-lane factorisation, removed in round 5), [21]=window structure built on the
+ * optimize() call), [19]=device steps the last schedule took, [20]=block cyclic reduction runs its back
+ * substitution inside the forward launch (1; 0 with PLBA_BCR_SPLIT=1 or without BCR), [21]=window structure built on the
  * device (1) or on the host (0).
  * Counts are this rank's when the window is sharded. */
 int plba_structure_stats(plba_ctx *ctx, int64_t *out, int32_t cap);
 int plba_kernel_times(plba_ctx *ctx, const char **names, double *ms, int32_t *launches,
                       int32_t cap, int32_t *n);
+/* The factorisation plba_upload would choose, under the current environment switches, for a
+ * window of nf free poses whose envelope is bw pose blocks wide, on a device that holds
+ * `resident` block-cyclic-reduction workgroups at once. Needs no context and touches no device.
+ * flags: 1 = block cyclic reduction ruled out (the context fell back before), 2 = sharded window,
+ * 4 = the window has Schur triples (trial slots are possible).
+ * out[0]=mode (0 dense scalar, 1 dense MFMA, 2 band, 3 band two-sided, 4 column-lane,
+ * 5 column-lane two-sided, 6 block cyclic reduction), [1]=BCR super-rows, [2]=BCR back
+ * substitution fused, [3]=two-sided split row, [4]=band kernels' ring slots, [5]=trial slots,
+ * [6]=their policy, [7]=mode a BCR window falls back to after a hand-off timeout (-1: none),
+ * [8]=its split row. Entries past cap are not written. */
+int plba_factor_plan(int32_t bw, int32_t nf, int32_t resident, int32_t flags, int32_t *out, int32_t cap);
 
 /* ---- Hand-rolled Levenberg–Marquardt local BA:
  *   int MapHandler::levMarquardtOptimizationLBAForPluker(X_aux, kf_list, pt_list, ls_list,

@@ -28,6 +28,7 @@
 #include "../../include/plba.h"
 #include "plba_build.hpp"
 #include "plba_kernels.hpp"
+#include "plba_plan.hpp"
 
 namespace plba {
 
@@ -86,7 +87,7 @@ struct plba_ctx {
         size_t off;
         const void *dsrc = nullptr;  // device source (copied D2D after the arena is carved)
     };
-    std::vector<Item> plan;
+    std::vector<Item> arena_plan;  // the window's arrays in carving order (alloc .. commit_plan)
     BuildMem bmemA, bmemB;   // device window build scratch (plba_build.hip), grow-only
     char *arena = nullptr, *staging = nullptr;
     size_t arena_cap = 0, staging_cap = 0;
@@ -113,7 +114,7 @@ struct plba_ctx {
     std::vector<int64_t> graph_sig;  // launch signature the executable graphs were built for
     // the same step captured 2, 4, 8, 16 times back to back: a batch of N steps is launched as
     // its binary decomposition (a graph-to-graph transition costs ~8 us on the device)
-    static constexpr int kMultiLevels = 4;
+    static constexpr int kMultiLevels = kGraphLevelsMax;
     hipGraph_t multi_graph[kMultiLevels] = {};
     hipGraphExec_t multi_exec[kMultiLevels] = {};
     int last_steps = 16;     // steps the previous schedule needed (first batch size)
@@ -127,7 +128,8 @@ struct plba_ctx {
     int bcr_fallbacks = 0;
     bool pool_hold = false;  // this context keeps the device pool's release threshold raised (prewarm)
     int dev_build = 0;  // the last upload's window structure was built on the device
-    int fb_cl = 0, fb_twisted = 0, fb_tw_m = 0;  // the factorisation the window falls back to
+    Tuning tuning;      // environment switches as sampled by the last upload
+    FactorPlan plan;    // the factorisation chosen by the last upload (its fallback included)
     double *bk_T = nullptr, *bk_X = nullptr, *bk_xp = nullptr, *bk_xk = nullptr, *bk_Lpb = nullptr, *bk_XL = nullptr,
            *bk_xl = nullptr;
     uint8_t *bk_level = nullptr;
@@ -159,7 +161,7 @@ struct plba_ctx {
     // and re-instantiating five executable graphs (capture_step).
     void free_all() {
         graphs_stale = true;
-        plan.clear();
+        arena_plan.clear();
         d = Dev{};
         bk_T = bk_X = bk_xp = bk_xk = bk_Lpb = bk_XL = bk_xl = nullptr;
         bk_level = nullptr;
@@ -173,25 +175,25 @@ struct plba_ctx {
     void alloc(T *&p, size_t count, const void *src = nullptr, bool zero = false) {
         p = nullptr;
         const size_t sb = count * sizeof(T);
-        plan.push_back(Item{(void **)&p, std::max(sb, (size_t)128), src ? sb : 0, src, zero, 0});
+        arena_plan.push_back(Item{(void **)&p, std::max(sb, (size_t)128), src ? sb : 0, src, zero, 0});
     }
     // a device array filled from device memory (the device window build's outputs)
     template <typename T>
     void alloc_dev(T *&p, size_t count, const void *dsrc) {
         p = nullptr;
         const size_t sb = count * sizeof(T);
-        plan.push_back(Item{(void **)&p, std::max(sb, (size_t)128), sb, nullptr, false, 0, dsrc});
+        arena_plan.push_back(Item{(void **)&p, std::max(sb, (size_t)128), sb, nullptr, false, 0, dsrc});
     }
     int commit_plan() {
         auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         size_t up = 0, tot = 0;
-        for (auto &it : plan)
+        for (auto &it : arena_plan)
             if (it.src) { it.off = up; up = al(up + it.bytes); }
         size_t dv = up;  // device-sourced arrays after the host-sourced ones, outside the memset
-        for (auto &it : plan)
+        for (auto &it : arena_plan)
             if (it.dsrc) { it.off = dv; dv = al(dv + it.bytes); }
         tot = dv;
-        for (auto &it : plan)
+        for (auto &it : arena_plan)
             if (!it.src && !it.dsrc) { it.off = tot; tot = al(tot + it.bytes); }
         if (tot > arena_cap) {
             // stream-ordered: hipFree / hipMalloc would synchronise the whole device, which fails
@@ -221,7 +223,7 @@ struct plba_ctx {
             }
             staging_cap = cap;
         }
-        for (auto &it : plan) {
+        for (auto &it : arena_plan) {
             *it.field = arena + it.off;
             if (it.src) {
                 if (it.src_bytes) std::memcpy(staging + it.off, it.src, it.src_bytes);
@@ -237,11 +239,11 @@ struct plba_ctx {
         // contract of alloc) — one memset of [up, tot) unless the rest is poisoned
         hipError_t e = pz ? hipMemsetAsync(arena + up, 0, dv - up, stream) : hipSuccess;
         if (e == hipSuccess) e = pz ? hipMemsetAsync(arena + dv, 0xFF, tot - dv, stream) : hipMemsetAsync(arena + up, 0, tot - up, stream);
-        for (auto &it : plan)
+        for (auto &it : arena_plan)
             if (it.dsrc && it.src_bytes && e == hipSuccess)
                 e = hipMemcpyAsync(arena + it.off, it.dsrc, it.src_bytes, hipMemcpyDeviceToDevice, stream);
         if (e == hipSuccess && pz)
-            for (auto &it : plan)
+            for (auto &it : arena_plan)
                 if (it.zero && e == hipSuccess) e = hipMemsetAsync(arena + it.off, 0, it.bytes, stream);
         if (e == hipSuccess && up) e = hipMemcpyAsync(arena, staging, up, hipMemcpyHostToDevice, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
@@ -305,176 +307,81 @@ void shard_plan(const plba_graph *g, int R, int32_t *pt_owner, int32_t *ln_owner
     }
 }
 
-inline bool env_flag(const char *name) {
-    const char *v = getenv(name);
-    return v && v[0] == '1';
-}
-inline size_t band_lds_bytes(int bw) { return sizeof(double) * band_lds_doubles(bw, 0); }
-template <int... B>
-const void *band_kernel_impl(int bw, std::integer_sequence<int, B...>) {
+// the instance K<bw> of a kernel template for bw in 0..Max (nullptr outside)
+template <typename F, int... B>
+const void *kernel_for(int bw, F pick, std::integer_sequence<int, B...>) {
     const void *k = nullptr;
-    ((bw == B ? (k = (const void *)k_rcs_factor_band<B>, 0) : 0), ...);
+    ((bw == B ? (k = pick(std::integral_constant<int, B>{}), 0) : 0), ...);
     return k;
 }
-inline const void *band_kernel(int bw) {
-    return band_kernel_impl(bw, std::make_integer_sequence<int, kBandMax + 1>{});
-}
-template <int... B>
-const void *twisted_kernel_impl(int bw, std::integer_sequence<int, B...>) {
-    const void *k = nullptr;
-    ((bw == B ? (k = (const void *)k_rcs_factor_twisted<B>, 0) : 0), ...);
-    return k;
-}
-inline const void *twisted_kernel(int bw) {
-    return twisted_kernel_impl(bw, std::make_integer_sequence<int, kBandMax + 1>{});
-}
-static_assert(band_lds_doubles(kBandMax, 1) * sizeof(double) + band_static_bytes(kBandMax) <= 158 * 1024,
-              "kBandMax window must fit LDS");
-inline int band_ring(int bw, int nf) {
-    const size_t budget = 158 * 1024 - band_static_bytes(bw), base = band_lds_bytes(bw);
-    const size_t per = sizeof(double) * ((size_t)bw * 36 + 36 + 6);
-    int R = base + per < budget ? (int)((budget - base - per) / per) : 1;
-    return std::max(1, std::min(R, 16));
-}
-inline size_t band_lds_bytes(int bw, int nf) { return sizeof(double) * band_lds_doubles(bw, band_ring(bw, nf)); }
-inline size_t twisted_lds_bytes(int bw, int nf) {
-    // x_p staging [nf][6], then the separator merge or (bw >= 11) the streamed back substitution
-    const size_t tail = std::max(twisted_merge_doubles(bw), bw * 6 > 64 ? bstream_doubles(bw) : (size_t)0);
-    return std::max(band_lds_bytes(bw, nf), sizeof(double) * ((size_t)nf * 6 + tail));
-}
-template <int... B>
-const void *cl_kernel_impl(int bw, bool twisted, std::integer_sequence<int, B...>) {
-    const void *k = nullptr;
-    ((bw == B ? (k = twisted ? (const void *)k_rcs_factor_twisted_cl<B> : (const void *)k_rcs_factor_band_cl<B>, 0) : 0),
-     ...);
-    return k;
-}
-// column-lane factorisation (plba_band_cl.hpp) for bandwidths up to kClMaxBW
-inline bool use_cl(int bw) {
-    const char *f = getenv("PLBA_FACTOR");
-    if (f && std::string(f) == "band") return false;
-    return bw >= 1 && bw <= kClMaxBW && !env_flag("PLBA_NO_CL");
-}
-// Two-sided split: rows 0..m-1 top-down, nf-1..m+bw bottom-up. An odd remainder goes to the top
-// segment, so workgroup 0 usually arrives last and merges with the separator window already in
-// its LDS (workgroup 1 as the last arriver must first reload segment 0's window from global
-// memory): C3 hand-off + merge 10.9 k -> 8.1 k cycles, factorisation 74.8 -> 73.3 µs.
-inline int tw_split(int nf, int bw) { return (nf - bw + 1) / 2; }
-inline size_t cl_lds_bytes(int bw, int nf, bool twisted) {
-    return sizeof(double) * (cl_lds_doubles(bw) + (twisted ? (size_t)nf * 6 : 0));
-}
-template <int... B>
-const void *bcr_kernel_impl(int bw, std::integer_sequence<int, B...>) {
-    const void *k = nullptr;
-    ((bw == B ? (k = (const void *)k_rcs_factor_bcr<B>, 0) : 0), ...);
-    return k;
-}
-inline const void *bcr_kernel(int bw) { return bcr_kernel_impl(bw, std::make_integer_sequence<int, kBcrMaxBW + 1>{}); }
-inline size_t bcr_lds_bytes(int bw) { return sizeof(double) * bcr_lds_doubles(bw); }
-// n up to which the dense solve keeps y in LDS; PLBA_SOLVE_LDS_N lowers it (tests: the global-y path
-// at sizes the oracle finishes)
-inline int solve_lds_limit() {
-    const char *e = getenv("PLBA_SOLVE_LDS_N");
-    return e && e[0] ? std::min(atoi(e), kSolveLdsN) : kSolveLdsN;
-}
-// Factorisation mode of a banded window: PLBA_FACTOR=bcr|cl|band forces one (diagnostics / A-B
-// runs); by default block cyclic reduction once the window has enough super-rows for its
-// log-depth chain to beat the two-sided column-lane chain of (nf+bw)/2 pivot steps.
-inline size_t bcr_back_lds_bytes(int bw) { return sizeof(double) * bcr_back_lds_doubles(bw); }
-template <int... B>
-const void *bcr_back_kernel_impl(int bw, std::integer_sequence<int, B...>) {
-    const void *k = nullptr;
-    ((bw == B ? (k = (const void *)k_rcs_bcr_back<B>, 0) : 0), ...);
-    return k;
-}
-inline const void *bcr_back_kernel(int bw) {
-    return bcr_back_kernel_impl(bw, std::make_integer_sequence<int, kBcrMaxBW + 1>{});
+#define PLBA_KERNEL(name, max, bw) \
+    kernel_for(bw, [](auto b) { return (const void *)name<decltype(b)::value>; }, std::make_integer_sequence<int, (max) + 1>{})
+// the kernel of a banded factorisation mode and its launch geometry (grid y = trial slots)
+struct KernelLaunch {
+    const void *fn;
+    int grid_x, block;
+    size_t lds_bytes;
+};
+KernelLaunch factor_kernel(int mode, int bw, int nf) {
+    const int N = bw > 0 ? (nf + bw - 1) / bw : 0;  // BCR super-rows
+    switch (mode) {
+    case kBand: return {PLBA_KERNEL(k_rcs_factor_band, kBandMax, bw), 1, band_nt(bw), band_lds_bytes(bw, nf)};
+    case kBandTw: return {PLBA_KERNEL(k_rcs_factor_twisted, kBandMax, bw), 2, band_nt(bw), twisted_lds_bytes(bw, nf)};
+    case kCl: return {PLBA_KERNEL(k_rcs_factor_band_cl, kClMaxBW, bw), 1, kClNT, cl_lds_bytes(bw, nf, false)};
+    case kClTw: return {PLBA_KERNEL(k_rcs_factor_twisted_cl, kClMaxBW, bw), 2, kClNT, cl_lds_bytes(bw, nf, true)};
+    case kBcr: return {PLBA_KERNEL(k_rcs_factor_bcr, kBcrMaxBW, bw), N, kBcrNT, bcr_lds_bytes(bw)};
+    case kBcrBack: return {PLBA_KERNEL(k_rcs_bcr_back, kBcrMaxBW, bw), N, kBcrBackNT, bcr_back_lds_bytes(bw)};
+    default: return {nullptr, 0, 0, 0};  // the dense modes launch from launch_step
+    }
 }
 // Workgroups of the BCR forward kernel the device holds at once: CUs x occupancy (LDS-bound, one
-// per CU above 80 KB). PLBA_BCR_RESIDENT overrides it (tests: force the column-lane choice).
-inline int bcr_resident(int device, int bw) {
-    const char *e = getenv("PLBA_BCR_RESIDENT");
-    if (e && e[0]) return atoi(e);
-    if (bw < 1 || bw > kBcrMaxBW || bcr_lds_bytes(bw) > 159 * 1024) return 0;
+// per CU above 80 KB).
+int bcr_resident(int device, int bw, int nf) {
+    if (bw < 1 || bw > kBcrMaxBW) return 0;
+    const KernelLaunch k = factor_kernel(kBcr, bw, nf);
     int cus = 0, occ = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
-        hipFuncSetAttribute(bcr_kernel(bw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bcr_lds_bytes(bw)) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, bcr_kernel(bw), kBcrNT, bcr_lds_bytes(bw)) != hipSuccess) {
+    if (k.lds_bytes > kLdsLimit ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
+        hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_bytes) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k.fn, k.block, k.lds_bytes) != hipSuccess) {
         (void)hipGetLastError();
         return 0;
     }
     return cus * occ;
 }
-// Factorisation mode of a banded window: PLBA_FACTOR=bcr|cl|band forces one (diagnostics / A-B
-// runs); by default block cyclic reduction once the window has enough super-rows for its
-// log-depth chain to beat the two-sided column-lane chain of (nf+bw)/2 pivot steps. BCR only when
-// its N workgroups fit the device at once (`resident`): a launch that cannot hold them all still
-// completes (ticket order, plba_bcr.hpp) but serialises the levels it exists to overlap.
-inline bool want_bcr(int bw, int nf, int resident) {
-    if (bw < 1 || bw > kBcrMaxBW) return false;
-    const int N = (nf + bw - 1) / bw;
-    if (N < 2 || N > resident || bcr_lds_bytes(bw) > 159 * 1024) return false;
-    const char *f = getenv("PLBA_FACTOR");
-    if (f && f[0]) return std::string(f) == "bcr";
-    // latency model calibrated on C3/C4/C5 (profiles/r02): the two-sided column-lane
-    // chain costs ~1.3 µs per pivot block, (nf + bw)/2 of them; BCR ~(2.6·bw + 4.8) µs per level,
-    // ceil(log2 N) + 1 levels. C3 (N = 13): 76 vs 116 µs -> column lane; C4 (N = 52): 230 vs
-    // 157 µs and C5 (N = 129): 539 vs 198 µs -> BCR.
-    int levels = 1;
-    while ((1 << (levels - 1)) < N) ++levels;
-    const double t_cl = 1.3 * (nf + bw) / 2.0, t_bcr = levels * (2.6 * bw + 4.8);
-    return t_bcr < t_cl;
+// The Dev fields the kernels read the factorisation from. A FactorChoice alone is what a BCR
+// window's fallback rewrites (run_schedule): bcr_fused and the trial slots stay as uploaded.
+void apply_plan(Dev &d, const FactorChoice &c) {
+    d.bcr = c.mode == kBcr;
+    if (!d.bcr) d.bcr_N = 0;
+    d.cl = c.mode == kCl || c.mode == kClTw;
+    d.twisted = c.mode == kBandTw || c.mode == kClTw;
+    d.tw_m = c.tw_m;
 }
-// Trial slots per step and when to use them (DESIGN §2 "Speculative trials"). PLBA_SPEC=<slots>
-// and PLBA_SPEC_POLICY=<0 off | 1 always | 2 after a rejection in the iteration | 3 after the first
-// rejection of the optimize() call> override (A/B runs; results are identical in every setting).
-struct SpecChoice {
-    int slots, policy;
-};
-// bcr_fit: how many BCR factorisations the device holds at once (resident workgroups / super-rows);
-// trial slots of a BCR window run side by side only if they all fit (else the second slot's
-// super-rows would wait for the first's to retire and the levels would serialise). A/B at C4
-// (DESIGN §2): 1,551 -> 1,817 LM it/s (31 -> 22 steps per LBA); PLBA_SPEC_BCR=0 disables.
-inline SpecChoice spec_choice(bool band1, bool wide, bool bcr, int bcr_fit, bool sharded, bool has_trials) {
-    SpecChoice r{1, kSpecOff};
-    if (sharded || !has_trials || !(band1 || bcr)) return r;
-    int cap = kMaxSpec;
-    if (bcr) {
-        const char *b = getenv("PLBA_SPEC_BCR");
-        if ((b && b[0] == '0') || bcr_fit < 2) return r;
-        cap = std::min(cap, bcr_fit);
-    }
-    // wide bands (bw > 9: the register-window kernel, ≈0.5 ms a factorisation at C3R) take every
-    // slot: C3R 21 -> 17 steps per LBA, 1,000 -> 1,194 LM it/s (2 / 3 / 4 slots); so do
-    // BCR windows, as far as the device holds the slots' super-rows (C4: 4 fit, 22 -> 17 steps,
-    // 1,822 -> 1,851 LM it/s); the column-lane windows keep two (C3: 3 slots 5,248 vs 5,304)
-    r.slots = (wide || bcr) ? kMaxSpec : 2;
-    r.policy = kSpecSticky;
-    const char *e = getenv("PLBA_SPEC");
-    if (e && e[0]) r.slots = std::max(1, std::min(atoi(e), kMaxSpec));
-    r.slots = std::min(r.slots, cap);
-    const char *p = getenv("PLBA_SPEC_POLICY");
-    if (p && p[0]) r.policy = std::max(0, std::min(atoi(p), 3));
-    if (r.policy == kSpecOff) r.slots = 1;
-    if (r.slots == 1) r.policy = kSpecOff;
-    return r;
+void apply_plan(Dev &d, const FactorPlan &p) {
+    d.band_mode = p.mode >= kBand;
+    d.dense_mfma = p.mode == kDenseMfma;
+    d.bcr_N = p.bcr_N;
+    d.bcr_fused = p.bcr_fused;
+    d.ring = p.ring;
+    d.spec_max = p.slots;
+    d.spec_policy = p.policy;
+    d.nbs = d.spec_max + 1;
+    d.nbx = d.spec_max > 1 ? d.spec_max + 1 : 1;
+    apply_plan(d, static_cast<const FactorChoice &>(p));
+}
+inline int factor_mode(const Dev &d) {  // (inverse of apply_plan on a banded window)
+    return d.bcr ? kBcr : d.cl ? (d.twisted ? kClTw : kCl) : (d.twisted ? kBandTw : kBand);
 }
 // the banded factorisation's launch(es); the first failing launch's status is returned
 inline hipError_t launch_band(Dev &d, hipStream_t s) {
     void *args[] = {&d};
-    if (d.bcr) {  // forward elimination, then back substitution + pose update (plba_bcr.hpp)
-        hipError_t e = hipLaunchKernel(bcr_kernel(d.bw), dim3(d.bcr_N, d.spec_max), dim3(kBcrNT), args, bcr_lds_bytes(d.bw), s);
-        if (e != hipSuccess || d.bcr_fused) return e;
-        return hipLaunchKernel(bcr_back_kernel(d.bw), dim3(d.bcr_N, d.spec_max), dim3(kBcrBackNT), args,
-                               bcr_back_lds_bytes(d.bw), s);
-    }
-    if (d.cl) {
-        const void *k = cl_kernel_impl(d.bw, d.twisted != 0, std::make_integer_sequence<int, kClMaxBW + 1>{});
-        return hipLaunchKernel(k, dim3(d.twisted ? 2 : 1, d.spec_max), dim3(kClNT), args, cl_lds_bytes(d.bw, d.nf, d.twisted != 0), s);
-    }
-    if (d.twisted)
-        return hipLaunchKernel(twisted_kernel(d.bw), dim3(2, d.spec_max), dim3(band_nt(d.bw)), args, twisted_lds_bytes(d.bw, d.nf), s);
-    return hipLaunchKernel(band_kernel(d.bw), dim3(1, d.spec_max), dim3(band_nt(d.bw)), args, band_lds_bytes(d.bw, d.nf), s);
+    const int mode = factor_mode(d);
+    const KernelLaunch k = factor_kernel(mode, d.bw, d.nf);
+    const hipError_t e = hipLaunchKernel(k.fn, dim3(k.grid_x, d.spec_max), dim3(k.block), args, k.lds_bytes, s);
+    if (e != hipSuccess || mode != kBcr || d.bcr_fused) return e;
+    const KernelLaunch b = factor_kernel(kBcrBack, d.bw, d.nf);  // back substitution + pose update
+    return hipLaunchKernel(b.fn, dim3(b.grid_x, d.spec_max), dim3(b.block), args, b.lds_bytes, s);
 }
 
 // time a launch when kernel timing is enabled
@@ -649,13 +556,8 @@ std::vector<int32_t> rcm_from_adj(std::vector<std::vector<int32_t>> &adj) {
 }
 
 int allreduce(plba_ctx *ctx, const double *send, double *recv, size_t n);
-// Sharded windows: the RCS exchange. PLBA_SHARD_XCHG=allreduce restores the all-reduce of the
-// whole partial system (A/B runs); the default all-gathers each rank's nonzero runs.
-inline bool xchg_gather() {
-    const char *e = getenv("PLBA_SHARD_XCHG");
-    return !(e && std::string(e) == "allreduce");
-}
-int do_upload(plba_ctx *ctx, const plba_graph *g) {
+// ---- upload, phase by phase (do_upload, at the end, is the sequence)
+int validate_graph(plba_ctx *ctx, const plba_graph *g, bool host_build) {
     if (!g || g->n_kf < 0 || g->n_pt < 0 || g->n_ln < 0 || g->n_ept < 0 || g->n_eln < 0) {
         ctx->set_error("invalid graph sizes");
         return PLBA_E_INVALID;
@@ -667,116 +569,152 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
         ctx->set_error("null array in graph");
         return PLBA_E_INVALID;
     }
-    // Window structure on the device (plba_build.hip: sorts / scans / scatters on the solver
-    // stream) unless PLBA_HOST_BUILD=1 (the host build below, kept as the reference the device
-    // build is tested against bit for bit, and for windows whose envelope needs the RCM order).
-    const bool devb_wanted = g->n_kf > 0 && !env_flag("PLBA_HOST_BUILD");
-    if (!devb_wanted) {  // (the device build validates the edges itself)
-        for (int e = 0; e < g->n_ept; ++e)
-            if (g->ept_lm[e] < 0 || g->ept_lm[e] >= g->n_pt || g->ept_kf[e] < 0 || g->ept_kf[e] >= g->n_kf) {
-                ctx->set_error("point edge %d references a missing vertex", e);
-                return PLBA_E_INVALID;
-            }
-        for (int e = 0; e < g->n_eln; ++e)
-            if (g->eln_lm[e] < 0 || g->eln_lm[e] >= g->n_ln || g->eln_kf[e] < 0 || g->eln_kf[e] >= g->n_kf) {
-                ctx->set_error("line edge %d references a missing vertex", e);
-                return PLBA_E_INVALID;
-            }
-    }
-    auto tmark = std::chrono::steady_clock::now();
-    auto mark = [&](const char *what) {
+    if (g->n_kf > 0 && !host_build) return PLBA_OK;  // (the device build validates the edges itself)
+    for (int e = 0; e < g->n_ept; ++e)
+        if (g->ept_lm[e] < 0 || g->ept_lm[e] >= g->n_pt || g->ept_kf[e] < 0 || g->ept_kf[e] >= g->n_kf) {
+            ctx->set_error("point edge %d references a missing vertex", e);
+            return PLBA_E_INVALID;
+        }
+    for (int e = 0; e < g->n_eln; ++e)
+        if (g->eln_lm[e] < 0 || g->eln_lm[e] >= g->n_ln || g->eln_kf[e] < 0 || g->eln_kf[e] >= g->n_kf) {
+            ctx->set_error("line edge %d references a missing vertex", e);
+            return PLBA_E_INVALID;
+        }
+    return PLBA_OK;
+}
+// the "[plba upload]" phase log of PLBA_TIMING (tools/upload_timing.py and DESIGN quote the labels)
+struct PhaseLog {
+    bool on;
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void operator()(const char *what) {
         const auto t = std::chrono::steady_clock::now();
-        if (env_flag("PLBA_TIMING"))
-            fprintf(stderr, "[plba upload] %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - tmark).count());
-        tmark = t;
+        if (on) fprintf(stderr, "[plba upload] %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - last).count());
+        last = t;
+    }
+};
+// What the window build hands on, from the host or from the device (plba_build.hip; bit for bit
+// the same arrays): free poses, envelope, this rank's counts and the landmark-major edge arrays
+// — host vectors, or (devb) wb's device arrays. The output maps (lm_gpos, e_orig), the free-edge
+// count and the level mirror go to the context directly.
+struct WindowStructure {
+    bool devb = false;
+    int nf = 0, bw = 0, n_pt = 0, n_ln = 0, Ep = 0, El = 0;
+    std::vector<int32_t> kf_hidx, first_blk;
+    std::vector<int32_t> e_lm, e_kf, e_hidx, e_gpos, lm_off, pe_off, pe_list, trip;
+    std::vector<double> e_obs, e_info;
+    WindowBuild wb;
+};
+// keyframes in vertex-id order (buildIndexMapping)
+std::vector<int32_t> kf_id_order(const plba_graph *g) {
+    std::vector<int32_t> korder(g->n_kf);
+    std::iota(korder.begin(), korder.end(), 0);
+    std::stable_sort(korder.begin(), korder.end(), [&](int a, int b) { return g->kf_id[a] < g->kf_id[b]; });
+    return korder;
+}
+// Hessian indices after the free poses are reordered: rcm[i] = the old index placed at position i
+std::vector<int32_t> permute_hidx(const std::vector<int32_t> &hidx, const std::vector<int32_t> &rcm) {
+    std::vector<int32_t> pos(rcm.size()), h2(hidx.size(), -1);
+    for (size_t i = 0; i < rcm.size(); ++i) pos[rcm[i]] = (int32_t)i;
+    for (size_t k = 0; k < hidx.size(); ++k) h2[k] = hidx[k] >= 0 ? pos[hidx[k]] : -1;
+    return h2;
+}
+// Window structure on the device (sorts / scans / scatters on the solver stream).
+int build_structure_device(plba_ctx *ctx, const plba_graph *g, PhaseLog &mark, WindowStructure &ws) {
+    const int n_kf = g->n_kf;
+    WindowBuild &wb = ws.wb;
+    // free poses by vertex id and the id rank of every keyframe
+    const std::vector<int32_t> korder = kf_id_order(g);
+    std::vector<int32_t> kpos(n_kf);
+    ws.kf_hidx.assign(n_kf, -1);
+    for (int i = 0; i < n_kf; ++i) {
+        kpos[korder[i]] = i;
+        if (!g->kf_fixed[korder[i]]) ws.kf_hidx[korder[i]] = ws.nf++;
+    }
+    const int nf = ws.nf;
+    wb.g = g;
+    wb.nranks = ctx->comm.nranks;
+    wb.rank = ctx->comm.rank;
+    wb.nf = nf;
+    wb.kpos = kpos.data();
+    wb.stream = ctx->stream;
+    wb.timing = ctx->tuning.timing_any;
+    auto stage1 = [&](const std::vector<int32_t> &hidx, int &bw) {  // the build and its envelope width
+        char msg[256] = {0};
+        wb.kf_hidx = hidx.data();
+        const int rc = build_stage1(ctx->bmemA, wb, msg, sizeof msg);
+        if (rc) ctx->set_error("%s", msg);
+        bw = 0;
+        for (int h = 0; h < nf && !rc; ++h) bw = std::max(bw, h - wb.first_blk[h]);
+        return rc;
     };
-    ctx->free_all();
-    mark("free");
+    int rc = stage1(ws.kf_hidx, ws.bw);
+    if (rc) return rc;
+    // an envelope the banded kernels cannot take may narrow under the RCM order (the host
+    // build's rule, same permutation: rcm_order over the whole graph): build again with the
+    // reordered free poses, kept when the envelope narrows, else built once more in id order
+    if (ws.bw > kClMaxBW && nf > 2 && !ctx->tuning.no_rcm) {
+        const std::vector<int32_t> h2 = permute_hidx(ws.kf_hidx, rcm_order(g, ws.kf_hidx, nf));
+        int bw2 = 0;
+        if ((rc = stage1(h2, bw2))) return rc;
+        if (bw2 < ws.bw) {
+            ws.kf_hidx = h2;
+            ws.bw = bw2;
+        } else if ((rc = stage1(ws.kf_hidx, bw2))) {
+            return rc;
+        }
+        wb.kf_hidx = ws.kf_hidx.data();  // (h2 dies with this block)
+        mark("device build (RCM order)");
+    }
+    ws.first_blk = wb.first_blk;
+    ws.devb = true;
+    mark("device build (stage 1 proper)");
+    ws.n_pt = wb.n_pt; ws.n_ln = wb.n_ln; ws.Ep = wb.Ep; ws.El = wb.El;
+    ctx->n_free_edges = wb.n_free_edges;
+    // host mirrors of the output maps (plba_download / plba_get_edge_chi2)
+    ctx->lm_gpos.resize(wb.n_lm);
+    ctx->e_orig.resize(wb.E);
+    if (wb.n_lm)
+        PLBA_CHECK(hipMemcpyAsync(ctx->lm_gpos.data(), wb.lm_gpos, sizeof(int32_t) * wb.n_lm, hipMemcpyDeviceToHost, ctx->stream));
+    if (wb.E)
+        PLBA_CHECK(hipMemcpyAsync(ctx->e_orig.data(), wb.e_orig, sizeof(int32_t) * wb.E, hipMemcpyDeviceToHost, ctx->stream));
+    PLBA_CHECK(hipStreamSynchronize(ctx->stream));
+    ctx->h_level.assign(wb.E, 0);
+    mark("device build (stage 1)");
+    return PLBA_OK;
+}
+// first_blk[h] = the lowest free pose sharing a landmark with free pose h (over the WHOLE window);
+// returns the envelope width in pose blocks
+int envelope(const plba_graph *g, const std::vector<int32_t> &hidx, std::vector<int32_t> &fb) {
+    const int nf = (int)fb.size(), np_ = g->n_pt;
+    for (int h = 0; h < nf; ++h) fb[h] = h;
+    std::vector<int32_t> lmin(np_ + g->n_ln, INT32_MAX);
+    for (int e = 0; e < g->n_ept; ++e) {
+        const int h = hidx[g->ept_kf[e]];
+        if (h >= 0) lmin[g->ept_lm[e]] = std::min(lmin[g->ept_lm[e]], h);
+    }
+    for (int e = 0; e < g->n_eln; ++e) {
+        const int h = hidx[g->eln_kf[e]];
+        if (h >= 0) lmin[np_ + g->eln_lm[e]] = std::min(lmin[np_ + g->eln_lm[e]], h);
+    }
+    for (int e = 0; e < g->n_ept; ++e) {
+        const int h = hidx[g->ept_kf[e]];
+        if (h >= 0) fb[h] = std::min(fb[h], lmin[g->ept_lm[e]]);
+    }
+    for (int e = 0; e < g->n_eln; ++e) {
+        const int h = hidx[g->eln_kf[e]];
+        if (h >= 0) fb[h] = std::min(fb[h], lmin[np_ + g->eln_lm[e]]);
+    }
+    int w = 0;
+    for (int h = 0; h < nf; ++h) w = std::max(w, h - fb[h]);
+    return w;
+}
+// Window structure on the host (PLBA_HOST_BUILD=1, or a window without keyframes): the reference
+// the device build is tested against bit for bit.
+int build_structure_host(plba_ctx *ctx, const plba_graph *g, PhaseLog &mark, WindowStructure &ws) {
     const int n_kf = g->n_kf, n_pt_g = g->n_pt, n_ln_g = g->n_ln, Ep_g = g->n_ept, El_g = g->n_eln;
     const int R = ctx->comm.nranks, rank = ctx->comm.rank;
-    ctx->n_kf = n_kf; ctx->n_pt = n_pt_g; ctx->n_ln = n_ln_g; ctx->Ep = Ep_g; ctx->El = El_g;
-
-    std::vector<int32_t> lm_gpos, kf_hidx, first_blk, e_lm, e_kf, e_hidx, e_orig, e_gpos, lm_off, pe_off, pe_list;
-    std::vector<double> e_obs, e_info;
-    int n_pt = 0, n_ln = 0, Ep = 0, El = 0, nf = 0, bw = 0;
-    WindowBuild wb;
-    bool devb = false;
-    if (devb_wanted) {
-        // free poses by vertex id (buildIndexMapping) and the id rank of every keyframe
-        std::vector<int32_t> korder(n_kf), kpos(n_kf);
-        std::iota(korder.begin(), korder.end(), 0);
-        std::stable_sort(korder.begin(), korder.end(), [&](int a, int b) { return g->kf_id[a] < g->kf_id[b]; });
-        kf_hidx.assign(n_kf, -1);
-        for (int i = 0; i < n_kf; ++i) {
-            kpos[korder[i]] = i;
-            if (!g->kf_fixed[korder[i]]) kf_hidx[korder[i]] = nf++;
-        }
-        wb.g = g;
-        wb.nranks = R;
-        wb.rank = rank;
-        wb.nf = nf;
-        wb.kf_hidx = kf_hidx.data();
-        wb.kpos = kpos.data();
-        wb.stream = ctx->stream;
-        char msg[256] = {0};
-        const int brc = build_stage1(ctx->bmemA, wb, msg, sizeof msg);
-        if (brc) {
-            ctx->set_error("%s", msg);
-            return brc;
-        }
-        first_blk = wb.first_blk;
-        for (int h = 0; h < nf; ++h) bw = std::max(bw, h - first_blk[h]);
-        // an envelope the banded kernels cannot take may narrow under the RCM order (the host
-        // build's rule, same permutation: rcm_order over the whole graph): build again with the
-        // reordered free poses, kept when the envelope narrows, else built once more in id order
-        if (bw > kClMaxBW && nf > 2 && !env_flag("PLBA_NO_RCM")) {
-            const std::vector<int32_t> rcm = rcm_order(g, kf_hidx, nf);
-            std::vector<int32_t> pos(nf), h2(n_kf, -1);
-            for (int i = 0; i < nf; ++i) pos[rcm[i]] = i;
-            for (int k = 0; k < n_kf; ++k) h2[k] = kf_hidx[k] >= 0 ? pos[kf_hidx[k]] : -1;
-            wb.kf_hidx = h2.data();
-            int brc2 = build_stage1(ctx->bmemA, wb, msg, sizeof msg);
-            int bw2 = 0;
-            for (int h = 0; h < nf && !brc2; ++h) bw2 = std::max(bw2, h - wb.first_blk[h]);
-            if (!brc2 && bw2 < bw) {
-                kf_hidx = h2;
-                wb.kf_hidx = kf_hidx.data();  // (h2 dies with this block)
-                first_blk = wb.first_blk;
-                bw = bw2;
-            } else {
-                wb.kf_hidx = kf_hidx.data();
-                if (!brc2) brc2 = build_stage1(ctx->bmemA, wb, msg, sizeof msg);
-            }
-            if (brc2) {
-                ctx->set_error("%s", msg);
-                return brc2;
-            }
-            mark("device build (RCM order)");
-        }
-        devb = true;
-        mark("device build (stage 1 proper)");
-        if (devb) {
-            n_pt = wb.n_pt; n_ln = wb.n_ln; Ep = wb.Ep; El = wb.El;
-            ctx->n_free_edges = wb.n_free_edges;
-            // host mirrors of the output maps (plba_download / plba_get_edge_chi2)
-            lm_gpos.resize(wb.n_lm);
-            e_orig.resize(wb.E);
-            if (wb.n_lm)
-                PLBA_CHECK(hipMemcpyAsync(lm_gpos.data(), wb.lm_gpos, sizeof(int32_t) * wb.n_lm, hipMemcpyDeviceToHost, ctx->stream));
-            if (wb.E)
-                PLBA_CHECK(hipMemcpyAsync(e_orig.data(), wb.e_orig, sizeof(int32_t) * wb.E, hipMemcpyDeviceToHost, ctx->stream));
-            PLBA_CHECK(hipStreamSynchronize(ctx->stream));
-            ctx->lm_gpos = lm_gpos;
-            ctx->e_orig = e_orig;
-            ctx->h_level.assign(wb.E, 0);
-        } else {
-            bw = 0;
-            nf = 0;
-        }
-        mark("device build (stage 1)");
-    }
-    ctx->dev_build = devb ? 1 : 0;
-    if (!devb) {
+    int &n_pt = ws.n_pt, &n_ln = ws.n_ln, &nf = ws.nf;
+    const std::vector<int32_t> korder = kf_id_order(g);
     // landmarks owned by this rank (all of them unless the window is sharded)
     std::vector<int32_t> pt_owner(n_pt_g, 0), ln_owner(n_ln_g, 0);
     if (R > 1) shard_plan(g, R, pt_owner.data(), ln_owner.data());
@@ -784,13 +722,11 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
     // keyframe of their first observation, so the edges of one pose — and the landmarks one RCS
     // block couples — sit in a narrow range of the landmark-major edge array (cache locality of
     // the pose reduction and the Schur assembly; any order gives the same solution).
-    std::vector<int32_t> pt_loc(n_pt_g, -1), ln_loc(n_ln_g, -1);
+    std::vector<int32_t> pt_loc(n_pt_g, -1), ln_loc(n_ln_g, -1), &lm_gpos = ctx->lm_gpos;
     lm_gpos.clear();
     {
-        std::vector<int32_t> korder_(n_kf), kpos(n_kf);
-        std::iota(korder_.begin(), korder_.end(), 0);
-        std::stable_sort(korder_.begin(), korder_.end(), [&](int a, int b) { return g->kf_id[a] < g->kf_id[b]; });
-        for (int i = 0; i < n_kf; ++i) kpos[korder_[i]] = i;
+        std::vector<int32_t> kpos(n_kf);
+        for (int i = 0; i < n_kf; ++i) kpos[korder[i]] = i;
         std::vector<int32_t> key_pt(n_pt_g, INT32_MAX), key_ln(n_ln_g, INT32_MAX);
         for (int e = Ep_g - 1; e >= 0; --e) key_pt[g->ept_lm[e]] = kpos[g->ept_kf[e]];
         for (int e = El_g - 1; e >= 0; --e) key_ln[g->eln_lm[e]] = kpos[g->eln_kf[e]];
@@ -814,72 +750,43 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
         order(n_pt_g, pt_owner, key_pt, pt_loc, n_pt, 0);
         order(n_ln_g, ln_owner, key_ln, ln_loc, n_ln, n_pt_g);
     }
-    ctx->lm_gpos = lm_gpos;
-    for (int e = 0; e < Ep_g; ++e) Ep += pt_loc[g->ept_lm[e]] >= 0;
-    for (int e = 0; e < El_g; ++e) El += ln_loc[g->eln_lm[e]] >= 0;
-    const int n_lm = n_pt + n_ln, E = Ep + El;
+    for (int e = 0; e < Ep_g; ++e) ws.Ep += pt_loc[g->ept_lm[e]] >= 0;
+    for (int e = 0; e < El_g; ++e) ws.El += ln_loc[g->eln_lm[e]] >= 0;
+    const int n_lm = n_pt + n_ln, E = ws.Ep + ws.El;
 
     // free poses ordered by vertex id (buildIndexMapping)
-    std::vector<int32_t> korder(n_kf);
-    std::iota(korder.begin(), korder.end(), 0);
-    std::stable_sort(korder.begin(), korder.end(), [&](int a, int b) { return g->kf_id[a] < g->kf_id[b]; });
-    kf_hidx.assign(n_kf, -1);
+    ws.kf_hidx.assign(n_kf, -1);
     for (int k : korder)
-        if (!g->kf_fixed[k]) kf_hidx[k] = nf++;
-    first_blk.assign(nf, 0);
-    auto envelope = [&](const std::vector<int32_t> &hidx, std::vector<int32_t> &fb) {
-        for (int h = 0; h < nf; ++h) fb[h] = h;
-        std::vector<int32_t> lmin(n_pt_g + n_ln_g, INT32_MAX);
-        for (int e = 0; e < Ep_g; ++e) {
-            const int h = hidx[g->ept_kf[e]];
-            if (h >= 0) lmin[g->ept_lm[e]] = std::min(lmin[g->ept_lm[e]], h);
-        }
-        for (int e = 0; e < El_g; ++e) {
-            const int h = hidx[g->eln_kf[e]];
-            if (h >= 0) lmin[n_pt_g + g->eln_lm[e]] = std::min(lmin[n_pt_g + g->eln_lm[e]], h);
-        }
-        for (int e = 0; e < Ep_g; ++e) {
-            const int h = hidx[g->ept_kf[e]];
-            if (h >= 0) fb[h] = std::min(fb[h], lmin[g->ept_lm[e]]);
-        }
-        for (int e = 0; e < El_g; ++e) {
-            const int h = hidx[g->eln_kf[e]];
-            if (h >= 0) fb[h] = std::min(fb[h], lmin[n_pt_g + g->eln_lm[e]]);
-        }
-        int w = 0;
-        for (int h = 0; h < nf; ++h) w = std::max(w, h - fb[h]);
-        return w;
-    };
-    bw = envelope(kf_hidx, first_blk);
+        if (!g->kf_fixed[k]) ws.kf_hidx[k] = nf++;
+    ws.first_blk.assign(nf, 0);
+    ws.bw = envelope(g, ws.kf_hidx, ws.first_blk);
     // Reverse Cuthill–McKee on the free-pose coupling graph when the natural (id) order leaves an
     // envelope wider than the column-lane / BCR kernels take: windows that revisit old keyframes
     // couple poses a loop apart. LinearSolverEigen orders the same matrix by AMD; any symmetric
     // permutation gives the same exact LDLᵀ solution (rounding aside). PLBA_NO_RCM=1 disables.
-    if (bw > kClMaxBW && nf > 2 && !env_flag("PLBA_NO_RCM")) {
-        std::vector<int32_t> rcm = rcm_order(g, kf_hidx, nf);
-        std::vector<int32_t> pos(nf), h2(n_kf, -1), fb2(nf);
-        for (int i = 0; i < nf; ++i) pos[rcm[i]] = i;
-        for (int k = 0; k < n_kf; ++k) h2[k] = kf_hidx[k] >= 0 ? pos[kf_hidx[k]] : -1;
-        const int bw2 = envelope(h2, fb2);
-        if (bw2 < bw) {
-            kf_hidx = h2;
-            first_blk = fb2;
-            bw = bw2;
+    if (ws.bw > kClMaxBW && nf > 2 && !ctx->tuning.no_rcm) {
+        const std::vector<int32_t> h2 = permute_hidx(ws.kf_hidx, rcm_order(g, ws.kf_hidx, nf));
+        std::vector<int32_t> fb2(nf);
+        const int bw2 = envelope(g, h2, fb2);
+        if (bw2 < ws.bw) {
+            ws.kf_hidx = h2;
+            ws.first_blk = fb2;
+            ws.bw = bw2;
         }
     }
     mark("envelope (+ RCM)");
 
     // landmark-major CSR of the local landmarks (stable within a landmark = g2o insertion order)
-    std::vector<int32_t> lm_cnt(n_lm + 1, 0);
+    std::vector<int32_t> &e_lm = ws.e_lm, &e_kf = ws.e_kf, &e_hidx = ws.e_hidx, &e_gpos = ws.e_gpos, &e_orig = ctx->e_orig;
+    ws.lm_off.assign(n_lm + 1, 0);
     for (int e = 0; e < Ep_g; ++e)
-        if (pt_loc[g->ept_lm[e]] >= 0) lm_cnt[pt_loc[g->ept_lm[e]] + 1]++;
+        if (pt_loc[g->ept_lm[e]] >= 0) ws.lm_off[pt_loc[g->ept_lm[e]] + 1]++;
     for (int e = 0; e < El_g; ++e)
-        if (ln_loc[g->eln_lm[e]] >= 0) lm_cnt[n_pt + ln_loc[g->eln_lm[e]] + 1]++;
-    lm_off.assign(n_lm + 1, 0);
-    for (int l = 0; l < n_lm; ++l) lm_off[l + 1] = lm_off[l] + lm_cnt[l + 1];
-    std::vector<int32_t> fill(lm_off.begin(), lm_off.end() - 1);
+        if (ln_loc[g->eln_lm[e]] >= 0) ws.lm_off[n_pt + ln_loc[g->eln_lm[e]] + 1]++;
+    for (int l = 0; l < n_lm; ++l) ws.lm_off[l + 1] += ws.lm_off[l];
+    std::vector<int32_t> fill(ws.lm_off.begin(), ws.lm_off.end() - 1);
     e_lm.assign(E, 0); e_kf.assign(E, 0); e_hidx.assign(E, 0); e_orig.assign(E, 0); e_gpos.assign(E, 0);
-    e_obs.assign((size_t)E * 4, 0.0); e_info.assign(E, 0.0);
+    ws.e_obs.assign((size_t)E * 4, 0.0); ws.e_info.assign(E, 0.0);
     for (int e = 0; e < Ep_g; ++e) {
         const int l = pt_loc[g->ept_lm[e]];
         if (l < 0) continue;
@@ -888,9 +795,9 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
         e_kf[pos] = g->ept_kf[e];
         e_orig[pos] = e;
         e_gpos[pos] = e;
-        e_obs[(size_t)pos * 4] = g->ept_obs[2 * e];
-        e_obs[(size_t)pos * 4 + 1] = g->ept_obs[2 * e + 1];
-        e_info[pos] = g->ept_info[e];
+        ws.e_obs[(size_t)pos * 4] = g->ept_obs[2 * e];
+        ws.e_obs[(size_t)pos * 4 + 1] = g->ept_obs[2 * e + 1];
+        ws.e_info[pos] = g->ept_info[e];
     }
     for (int e = 0; e < El_g; ++e) {
         if (ln_loc[g->eln_lm[e]] < 0) continue;
@@ -899,68 +806,72 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
         e_kf[pos] = g->eln_kf[e];
         e_orig[pos] = e;
         e_gpos[pos] = Ep_g + e;
-        for (int k = 0; k < 4; ++k) e_obs[(size_t)pos * 4 + k] = g->eln_obs[4 * e + k];
-        e_info[pos] = g->eln_info[e];
+        for (int k = 0; k < 4; ++k) ws.e_obs[(size_t)pos * 4 + k] = g->eln_obs[4 * e + k];
+        ws.e_info[pos] = g->eln_info[e];
     }
-    for (int e = 0; e < E; ++e) e_hidx[e] = kf_hidx[e_kf[e]];
+    for (int e = 0; e < E; ++e) e_hidx[e] = ws.kf_hidx[e_kf[e]];
     ctx->n_free_edges = std::count_if(e_hidx.begin(), e_hidx.end(), [](int32_t h) { return h >= 0; });
-    ctx->e_orig = e_orig;
     ctx->h_level.assign(E, 0);
-
     mark("landmark order + CSR");
     // free-pose-major edge lists (ascending CSR edge index)
-    pe_off.assign(nf + 1, 0);
+    ws.pe_off.assign(nf + 1, 0);
     for (int e = 0; e < E; ++e)
-        if (e_hidx[e] >= 0) pe_off[e_hidx[e] + 1]++;
-    for (int h = 0; h < nf; ++h) pe_off[h + 1] += pe_off[h];
-    pe_list.assign(pe_off[nf], 0);
-    {
-        std::vector<int32_t> f(pe_off.begin(), pe_off.end() - 1);
-        for (int e = 0; e < E; ++e)
-            if (e_hidx[e] >= 0) pe_list[f[e_hidx[e]]++] = e;
-    }
-    }  // host build
-    const int n_lm = n_pt + n_ln, E = Ep + El;
+        if (e_hidx[e] >= 0) ws.pe_off[e_hidx[e] + 1]++;
+    for (int h = 0; h < nf; ++h) ws.pe_off[h + 1] += ws.pe_off[h];
+    ws.pe_list.assign(ws.pe_off[nf], 0);
+    std::vector<int32_t> f(ws.pe_off.begin(), ws.pe_off.end() - 1);
+    for (int e = 0; e < E; ++e)
+        if (e_hidx[e] >= 0) ws.pe_list[f[e_hidx[e]]++] = e;
+    return PLBA_OK;
+}
 
-    // Reduced-camera block pattern: the envelope of the lower triangle. first_blk[i2] = the lowest
-    // free pose sharing a landmark with free pose i2, over the WHOLE window on every rank (the
-    // all-reduced value array must have one layout). Blocks are indexed densely within the
-    // envelope in (i2, i1) order; Schur triples (e1 at pose i1 <= e2 at pose i2, same landmark,
-    // local landmarks only) are counting-sorted by block, landmark order inside a block.
-    // PLBA_FORCE_DENSE=1 (diagnostics only) routes a narrow envelope through the dense path.
-    const char *force_dense = getenv("PLBA_FORCE_DENSE");
-    const bool band_mode = bw <= kBandMax && !(force_dense && force_dense[0] == '1');
-    std::vector<int64_t> blk_base(nf + 1, 0);
+// Reduced-camera block pattern: the envelope of the lower triangle. Blocks are indexed densely
+// within the envelope in (i2, i1) order (one layout on every rank: the all-reduced value array);
+// Schur triples (e1 at pose i1 <= e2 at pose i2, same landmark, local landmarks only) are
+// counting-sorted by block, landmark order inside a block, and cut into assembly chunks.
+struct BlockPattern {
+    int nblk = 0, nch = 0, n = 0, ntiles = 0;
+    std::vector<int64_t> blk_base;
+    std::vector<int32_t> blk_i1, blk_i2, blk_off, ch_blk, ch_off, blk_ch, tile_first, tile_last;
+};
+int build_block_pattern(plba_ctx *ctx, WindowStructure &ws, PhaseLog &mark, BlockPattern &bp) {
+    const int nf = ws.nf;
+    const std::vector<int32_t> &first_blk = ws.first_blk;
+    std::vector<int64_t> &blk_base = bp.blk_base;
+    blk_base.assign(nf + 1, 0);
     for (int h = 0; h < nf; ++h) blk_base[h + 1] = blk_base[h] + (h - first_blk[h] + 1);
     if (blk_base[nf] > INT32_MAX / 64) {
         ctx->set_error("reduced camera envelope too large (%lld blocks)", (long long)blk_base[nf]);
         return PLBA_E_INVALID;
     }
-    const int nblk = (int)blk_base[nf];
-    std::vector<int32_t> blk_i1(nblk), blk_i2(nblk), blk_off(nblk + 1, 0), trip;
+    const int nblk = bp.nblk = (int)blk_base[nf];
+    std::vector<int32_t> &blk_off = bp.blk_off;
+    bp.blk_i1.resize(nblk);
+    bp.blk_i2.resize(nblk);
+    blk_off.assign(nblk + 1, 0);
     for (int h = 0; h < nf; ++h)
         for (int i1 = first_blk[h]; i1 <= h; ++i1) {
             const int b = (int)(blk_base[h] + (i1 - first_blk[h]));
-            blk_i1[b] = i1;
-            blk_i2[b] = h;
+            bp.blk_i1[b] = i1;
+            bp.blk_i2[b] = h;
         }
-    if (devb) {  // device build, stage 2: Schur triples sorted by block on the device
+    if (ws.devb) {  // device build, stage 2: Schur triples sorted by block on the device
         char msg[256] = {0};
-        const int brc = build_stage2(ctx->bmemA, ctx->bmemB, wb, blk_base, nblk, msg, sizeof msg);
+        const int brc = build_stage2(ctx->bmemA, ctx->bmemB, ws.wb, blk_base, nblk, msg, sizeof msg);
         if (brc) {
             ctx->set_error("%s", msg);
             return brc;
         }
-        blk_off = wb.h_blk_off;
-        ctx->n_triples = (size_t)wb.n_triples;
+        blk_off = ws.wb.h_blk_off;
+        ctx->n_triples = (size_t)ws.wb.n_triples;
     } else {
         auto for_pairs = [&](auto &&f) {
-            for (int l = 0; l < n_lm; ++l)
-                for (int a = lm_off[l]; a < lm_off[l + 1]; ++a) {
-                    const int i1 = e_hidx[a];
+            for (int l = 0; l < ws.n_pt + ws.n_ln; ++l)
+                for (int a = ws.lm_off[l]; a < ws.lm_off[l + 1]; ++a) {
+                    const int i1 = ws.e_hidx[a];
                     if (i1 < 0) continue;
-                    for (int b = lm_off[l]; b < lm_off[l + 1]; ++b) {
-                        const int i2 = e_hidx[b];
+                    for (int b = ws.lm_off[l]; b < ws.lm_off[l + 1]; ++b) {
+                        const int i2 = ws.e_hidx[b];
                         if (i2 < i1) continue;
                         f(a, b, (int)(blk_base[i2] + (i1 - first_blk[i2])));
                     }
@@ -968,12 +879,12 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
         };
         for_pairs([&](int, int, int blk) { blk_off[blk + 1]++; });
         for (int k = 0; k < nblk; ++k) blk_off[k + 1] += blk_off[k];
-        trip.resize(2 * (size_t)blk_off[nblk]);
+        ws.trip.resize(2 * (size_t)blk_off[nblk]);
         std::vector<int32_t> pos(blk_off.begin(), blk_off.end() - 1);
         for_pairs([&](int a, int b, int blk) {
             const size_t t = (size_t)pos[blk]++;
-            trip[2 * t] = a;
-            trip[2 * t + 1] = b;
+            ws.trip[2 * t] = a;
+            ws.trip[2 * t + 1] = b;
         });
         ctx->n_triples = (size_t)blk_off[nblk];
     }
@@ -985,209 +896,187 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
     // assembly being one round of waves there (C3: 25.5 -> 23.9 µs; C5 keeps 256: 115.3 vs 117.9);
     // PLBA_CHUNK_TRIPLES overrides (<= kChunk)
     int chunk = ctx->n_triples <= 600000 ? kChunk / 2 : kChunk;
-    if (const char *ce = getenv("PLBA_CHUNK_TRIPLES")) chunk = std::max(1, std::min(atoi(ce), kChunk));
-    std::vector<int32_t> ch_blk, ch_off, blk_ch(nblk + 1, 0);
+    if (ctx->tuning.chunk_triples) chunk = ctx->tuning.chunk_triples;
+    bp.blk_ch.assign(nblk + 1, 0);
     for (int k = 0; k < nblk; ++k) {
-        blk_ch[k] = (int32_t)ch_blk.size();
+        bp.blk_ch[k] = (int32_t)bp.ch_blk.size();
         int t = blk_off[k];
         do {
-            ch_blk.push_back(k);
-            ch_off.push_back(t);
+            bp.ch_blk.push_back(k);
+            bp.ch_off.push_back(t);
             t += chunk;
         } while (t < blk_off[k + 1]);
     }
-    blk_ch[nblk] = (int32_t)ch_blk.size();
-    ch_off.push_back(blk_off[nblk]);
-    const int nch = (int)ch_blk.size();
+    bp.blk_ch[nblk] = (int32_t)bp.ch_blk.size();
+    bp.ch_off.push_back(blk_off[nblk]);
+    bp.nch = (int)bp.ch_blk.size();
     // envelope of the lower triangle (per 6-row pose block: first pose block column)
-    const int n = 6 * nf;
-    const int ntiles = (n + kTile - 1) / kTile;
-    std::vector<int32_t> tile_first(std::max(ntiles, 1), 0), tile_last(std::max(ntiles, 1), 0);
+    const int n = bp.n = 6 * nf, ntiles = bp.ntiles = (n + kTile - 1) / kTile;
+    bp.tile_first.assign(std::max(ntiles, 1), 0);
+    bp.tile_last.assign(std::max(ntiles, 1), 0);
     for (int I = 0; I < ntiles; ++I) {
         int f = I;
         for (int r = I * kTile; r < std::min(n, (I + 1) * kTile); ++r) f = std::min(f, (6 * first_blk[r / 6]) / kTile);
-        tile_first[I] = f;
+        bp.tile_first[I] = f;
     }
     for (int K = 0; K < ntiles; ++K) {
         int last = K;
         for (int I = K; I < ntiles; ++I)
-            if (tile_first[I] <= K) last = I;
-        tile_last[K] = last;
+            if (bp.tile_first[I] <= K) last = I;
+        bp.tile_last[K] = last;
     }
-    ctx->h_tile_last = tile_last;
-
+    ctx->h_tile_last = bp.tile_last;
     mark("chunks + envelope");
-    // ---- device allocation
+    return PLBA_OK;
+}
+
+// sizes, options and launch grids of the window (everything in Dev that is not a pointer or part
+// of the factorisation plan)
+void describe_window(plba_ctx *ctx, const plba_graph *g, const WindowStructure &ws, const BlockPattern &bp) {
     Dev &d = ctx->d;
-    d.n_kf = n_kf; d.n_pt = n_pt; d.n_ln = n_ln; d.n_lm = n_lm; d.Ep = Ep; d.El = El; d.E = E;
-    d.nf = nf; d.n = n; d.nblk = nblk; d.ntiles = ntiles;
+    d.n_kf = g->n_kf; d.n_pt = ws.n_pt; d.n_ln = ws.n_ln; d.n_lm = ws.n_pt + ws.n_ln;
+    d.Ep = ws.Ep; d.El = ws.El; d.E = ws.Ep + ws.El;
+    d.nf = ws.nf; d.n = bp.n; d.nblk = bp.nblk; d.ntiles = bp.ntiles; d.nch = bp.nch;
     // any transport selects the sharded code path (a 1-rank RCCL window exercises it on one GPU)
-    const bool sharded = ctx->comm.kind != plba_ctx::Comm::NONE;
-    d.sharded = sharded ? 1 : 0;
-    d.nranks = R;
-    d.rank = rank;
-    d.n_lm_g = n_pt_g + n_ln_g;
-    d.E_g = Ep_g + El_g;
-    d.bw = bw;
-    d.band_mode = band_mode ? 1 : 0;
-    // dense RCS: multi-workgroup blocked LDLᵀ with MFMA trailing updates; PLBA_DENSE_SCALAR=1
-    // selects the single-workgroup scalar k_rcs_factor (A/B runs)
-    d.dense_mfma = !band_mode && !env_flag("PLBA_DENSE_SCALAR") ? 1 : 0;
-    d.ring = band_ring(bw, nf);
-    // two-sided factorisation when the chain is long enough to halve and the separator's dense
-    // system fits next to the band window in LDS (PLBA_NO_TWIST=1 disables, diagnostics only)
-    const char *no_twist = getenv("PLBA_NO_TWIST");
-    const int bcr_res = band_mode && !ctx->no_bcr ? bcr_resident(ctx->opts.device, bw) : 0;
-    const bool bcr = band_mode && !ctx->no_bcr && want_bcr(bw, nf, bcr_res);
-    d.bcr = bcr ? 1 : 0;
-    d.bcr_N = bcr ? (nf + bw - 1) / bw : 0;
-    // BCR back substitution inside the forward launch (PLBA_BCR_SPLIT=1: the second launch)
-    d.bcr_fused = bcr && !env_flag("PLBA_BCR_SPLIT") ? 1 : 0;
-    const bool cl = band_mode && !bcr && use_cl(bw);
-    const bool twisted = band_mode && !bcr && bw >= 1 && nf >= 2 * bw + 16 &&
-                         (cl ? cl_lds_bytes(bw, nf, true) : twisted_lds_bytes(bw, nf) + band_static_bytes(bw)) <= 159 * 1024 &&
-                         !(no_twist && no_twist[0] == '1');
-    // the column-lane factorisation a BCR window falls back to (run_schedule) and its arrays
-    // (the same checks as the normal column-lane choice; without it, the one-sweep band kernel)
-    static_assert(kBcrMaxBW <= kClMaxBW, "a BCR window must be able to fall back to the column-lane kernel");
-    const bool fb_cl = bcr && use_cl(bw) && cl_lds_bytes(bw, nf, false) <= 159 * 1024;
-    const bool fb_tw = fb_cl && nf >= 2 * bw + 16 && cl_lds_bytes(bw, nf, true) <= 159 * 1024 &&
-                       !(no_twist && no_twist[0] == '1');
-    ctx->fb_cl = fb_cl ? 1 : 0;
-    ctx->fb_twisted = fb_tw ? 1 : 0;
-    ctx->fb_tw_m = fb_tw ? tw_split(nf, bw) : 0;
-    d.cl = cl && cl_lds_bytes(bw, nf, twisted) <= 159 * 1024 ? 1 : 0;
-    d.twisted = twisted ? 1 : 0;
-    d.tw_m = twisted ? tw_split(nf, bw) : 0;
+    d.sharded = ctx->comm.kind != plba_ctx::Comm::NONE ? 1 : 0;
+    d.nranks = ctx->comm.nranks;
+    d.rank = ctx->comm.rank;
+    d.n_lm_g = g->n_pt + g->n_ln;
+    d.E_g = g->n_ept + g->n_eln;
+    d.bw = ws.bw;
     d.corrected = ctx->opts.corrected_line_jacobian;
-    // Speculative trials: worth it where the step is bound by the serial factorisation
-    // chain and the rest of the chip idles during it — the banded one- or two-workgroup
-    // factorisations (column-lane, LDS window) and BCR windows whose slots' super-rows all fit the device at once;
-    // the extra slots' edge and landmark kernels are then the price. Not for the dense path or
-    // sharded windows (collectives per slot).
-    {
-        const SpecChoice sp = spec_choice(band_mode && !bcr, band_mode && !bcr && !d.cl, bcr, bcr ? bcr_res / std::max(d.bcr_N, 1) : 0, sharded,
-                                          n_lm > 0 && nch > 0);
-        d.spec_max = sp.slots;
-        d.spec_policy = sp.policy;
-        d.nbs = d.spec_max + 1;
-        d.nbx = d.spec_max > 1 ? d.spec_max + 1 : 1;
-    }
-    {  // timing experiments only (wrong results): PLBA_DIAG bit mask read by some kernels
-        const char *dg = getenv("PLBA_DIAG");
-        d.diag = dg ? atoi(dg) : 0;
-    }
-    d.solve_lds_n = solve_lds_limit();
+    d.diag = ctx->tuning.diag;
+    d.solve_lds_n = ctx->tuning.solve_lds_n;
     d.cam = Cam{g->fx, g->fy, g->cx, g->cy};
     d.huber_pt = g->huber_pt;
     d.huber_ln = g->huber_ln;
     d.tau = ctx->opts.tau;
-    d.n_lin_blocks = blocks_for(E);
-    d.n_lm_blocks = blocks_for(n_lm, kLmBlock);
-    d.n_lms_blocks = blocks_for(n_lm * kLmLanes, kLmsNT);
-    d.n_kf_blocks = blocks_for(n_kf);
+    d.n_lin_blocks = blocks_for(d.E);
+    d.n_lm_blocks = blocks_for(d.n_lm, kLmBlock);
+    d.n_lms_blocks = blocks_for(d.n_lm * kLmLanes, kLmsNT);
+    d.n_kf_blocks = blocks_for(d.n_kf);
+    d.fold = d.sharded ? 0 : 1;
+    d.fold_init = d.fold && !ctx->tuning.no_fold_init;
+    d.xg_host = ctx->comm.kind == plba_ctx::Comm::HOST ? 1 : 0;
+}
 
-    std::vector<double> T(g->kf_Tcw, g->kf_Tcw + (size_t)n_kf * 12), X;
-    if (!devb) {
-        X.assign((size_t)n_lm * 4, 0.0);
-        for (int p = 0; p < n_pt; ++p)
-            for (int k = 0; k < 3; ++k) X[(size_t)p * 4 + k] = g->pt_xyz[3 * (size_t)lm_gpos[p] + k];
-        for (int l = 0; l < n_ln; ++l)
-            for (int k = 0; k < 4; ++k)
-                X[(size_t)(n_pt + l) * 4 + k] = g->ln_orth[4 * (size_t)(lm_gpos[n_pt + l] - n_pt_g) + k];
+int allreduce(plba_ctx *ctx, const double *send, double *recv, size_t n);
+// Sharded windows, all-gather exchange of the RCS (the default; PLBA_SHARD_XCHG=allreduce restores
+// the all-reduce of the whole partial system): this rank's block-row range [lo, hi]
+// (rows of the blocks that hold one of its Schur triples — every local edge of a free pose has its
+// diagonal triple), as two runs of red_rcs; every rank's runs are exchanged here, so all ranks
+// size the same record (P doubles per rank)
+struct ShardRanges {
+    std::vector<int64_t> rng;
+    int64_t P = 0;
+};
+int exchange_shard_ranges(plba_ctx *ctx, int nf, const BlockPattern &bp, ShardRanges &xg) {
+    if (!ctx->d.sharded || bp.nblk <= 0 || !ctx->tuning.shard_gather) return PLBA_OK;
+    const int R = ctx->comm.nranks, rank = ctx->comm.rank;
+    int lo = nf, hi = -1;
+    for (int b = 0; b < bp.nblk; ++b)
+        if (bp.blk_off[b + 1] > bp.blk_off[b]) {
+            lo = std::min(lo, bp.blk_i2[b]);
+            hi = std::max(hi, bp.blk_i2[b]);
+        }
+    std::vector<double> mine(4 * (size_t)R, 0.0);
+    if (hi >= lo) {
+        mine[4 * rank + 0] = (double)(bp.blk_base[lo] * 36);
+        mine[4 * rank + 1] = (double)((bp.blk_base[hi + 1] - bp.blk_base[lo]) * 36);
+        mine[4 * rank + 2] = (double)((int64_t)bp.nblk * 36 + 6 * (int64_t)lo);
+        mine[4 * rank + 3] = (double)(6 * (int64_t)(hi - lo + 1));
     }
+    double *tmp = nullptr;
+    PLBA_CHECK(hipMallocAsync((void **)&tmp, mine.size() * sizeof(double), ctx->stream));
+    PLBA_CHECK(hipMemcpyAsync(tmp, mine.data(), mine.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    int xrc = allreduce(ctx, tmp, tmp, mine.size());
+    if (!xrc) {
+        xrc = hipMemcpyAsync(mine.data(), tmp, mine.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) ==
+                      hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess
+                  ? PLBA_OK : PLBA_E_DEVICE;
+    }
+    (void)hipFreeAsync(tmp, ctx->stream);
+    if (xrc) {
+        if (xrc == PLBA_E_DEVICE) ctx->set_error("shard range exchange: device copy failed");
+        return xrc;
+    }
+    xg.rng.resize(4 * (size_t)R);
+    for (int r = 0; r < R; ++r) {
+        for (int k = 0; k < 4; ++k) xg.rng[4 * r + k] = (int64_t)mine[4 * r + k];
+        xg.P = std::max(xg.P, xg.rng[4 * r + 1] + xg.rng[4 * r + 3]);
+    }
+    xg.P = std::max<int64_t>(xg.P, 2);
+    return PLBA_OK;
+}
 
-    // sharded, all-gather exchange: this rank's block-row range [lo, hi] (rows of the blocks that
-    // hold one of its Schur triples — every local edge of a free pose has its diagonal triple), as
-    // two runs of red_rcs; every rank's runs are exchanged here, so all ranks size the same record
-    std::vector<int64_t> xg_rng;
-    int64_t xg_P = 0;
-    if (sharded && nblk > 0 && xchg_gather()) {
-        int lo = nf, hi = -1;
-        for (int b = 0; b < nblk; ++b)
-            if (blk_off[b + 1] > blk_off[b]) {
-                lo = std::min(lo, blk_i2[b]);
-                hi = std::max(hi, blk_i2[b]);
-            }
-        std::vector<double> mine(4 * (size_t)R, 0.0);
-        if (hi >= lo) {
-            mine[4 * rank + 0] = (double)(blk_base[lo] * 36);
-            mine[4 * rank + 1] = (double)((blk_base[hi + 1] - blk_base[lo]) * 36);
-            mine[4 * rank + 2] = (double)((int64_t)nblk * 36 + 6 * (int64_t)lo);
-            mine[4 * rank + 3] = (double)(6 * (int64_t)(hi - lo + 1));
-        }
-        double *tmp = nullptr;
-        PLBA_CHECK(hipMallocAsync((void **)&tmp, mine.size() * sizeof(double), ctx->stream));
-        PLBA_CHECK(hipMemcpyAsync(tmp, mine.data(), mine.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        int xrc = allreduce(ctx, tmp, tmp, mine.size());
-        if (!xrc) {
-            xrc = hipMemcpyAsync(mine.data(), tmp, mine.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) ==
-                          hipSuccess && hipStreamSynchronize(ctx->stream) == hipSuccess
-                      ? PLBA_OK : PLBA_E_DEVICE;
-        }
-        (void)hipFreeAsync(tmp, ctx->stream);
-        if (xrc) {
-            if (xrc == PLBA_E_DEVICE) ctx->set_error("shard range exchange: device copy failed");
-            return xrc;
-        }
-        xg_rng.resize(4 * (size_t)R);
-        for (int r = 0; r < R; ++r) {
-            for (int k = 0; k < 4; ++k) xg_rng[4 * r + k] = (int64_t)mine[4 * r + k];
-            xg_P = std::max(xg_P, xg_rng[4 * r + 1] + xg_rng[4 * r + 3]);
-        }
-        xg_P = std::max<int64_t>(xg_P, 2);
-    }
-    std::vector<int32_t> h_kf(bcr ? nf : 0, 0);
-    for (int k = 0; k < n_kf && bcr; ++k)
-        if (kf_hidx[k] >= 0) h_kf[kf_hidx[k]] = k;
-    // every device array of the window, carved from the arena (commit_plan assigns the pointers)
+// Every device array of the window, carved from the arena: commit_plan assigns the pointers IN
+// CALL ORDER, so the order of the lines below is the arena layout (addresses, PLBA_POISON
+// coverage) and must not change. Host sources must live until commit_plan (stage_arrays).
 #define ALLOC(p, n_) ctx->alloc(p, (size_t)(n_))
 #define ZALLOC(p, n_) ctx->alloc(p, (size_t)(n_), nullptr, true)
 #define UPLOAD(p, v) ctx->alloc(p, (v).size(), (v).data())
 // host vector (host build) or the device build's array of n_ elements
-#define UPLOAD_D(p, v, dptr, n_)                           \
-    do {                                                  \
-        if (devb) ctx->alloc_dev(p, (size_t)(n_), (dptr)); \
-        else UPLOAD(p, v);                                \
+#define UPLOAD_D(p, v, dptr, n_)                             \
+    do {                                                     \
+        if (ws.devb) ctx->alloc_dev(p, (size_t)(n_), (dptr)); \
+        else UPLOAD(p, v);                                   \
     } while (0)
+struct StagedHost {  // host sources built for the staging only
+    std::vector<double> T, X;
+    std::vector<int32_t> ln_gidx, h_kf;
+};
+// first part: states, edges, per-iteration and per-slot arrays
+void stage_state_arrays(plba_ctx *ctx, const plba_graph *g, const WindowStructure &ws, StagedHost &h) {
+    Dev &d = ctx->d;
+    const WindowBuild &wb = ws.wb;
+    const int n_kf = d.n_kf, n_pt = d.n_pt, n_ln = d.n_ln, n_lm = d.n_lm, E = d.E, nf = d.nf, n_pt_g = g->n_pt, n_ln_g = g->n_ln;
+    const std::vector<int32_t> &lm_gpos = ctx->lm_gpos;
+    h.T.assign(g->kf_Tcw, g->kf_Tcw + (size_t)n_kf * 12);
+    if (!ws.devb) {
+        h.X.assign((size_t)n_lm * 4, 0.0);
+        for (int p = 0; p < n_pt; ++p)
+            for (int k = 0; k < 3; ++k) h.X[(size_t)p * 4 + k] = g->pt_xyz[3 * (size_t)lm_gpos[p] + k];
+        for (int l = 0; l < n_ln; ++l)
+            for (int k = 0; k < 4; ++k)
+                h.X[(size_t)(n_pt + l) * 4 + k] = g->ln_orth[4 * (size_t)(lm_gpos[n_pt + l] - n_pt_g) + k];
+    }
     const int nbs = d.nbs, nbx = d.nbx, W = d.spec_max;
-    UPLOAD(d.T_init, T);
-    UPLOAD(d.Tb[0], T);
-    for (int b = 1; b < nbs; ++b) ALLOC(d.Tb[b], T.size());
-    UPLOAD_D(d.X_init, X, wb.X, (size_t)n_lm * 4);
-    UPLOAD_D(d.Xb[0], X, wb.X, (size_t)n_lm * 4);
+    UPLOAD(d.T_init, h.T);
+    UPLOAD(d.Tb[0], h.T);
+    for (int b = 1; b < nbs; ++b) ALLOC(d.Tb[b], h.T.size());
+    UPLOAD_D(d.X_init, h.X, wb.X, (size_t)n_lm * 4);
+    UPLOAD_D(d.Xb[0], h.X, wb.X, (size_t)n_lm * 4);
     for (int b = 1; b < nbs; ++b) ALLOC(d.Xb[b], (size_t)n_lm * 4);
     for (int b = 0; b < nbs; ++b) ALLOC(d.xk[b], (size_t)n_kf * 6);
     // hand-rolled GBA: endpoint lines in the reference's (global) order, their 6x6 blocks
     for (int b = 0; b < nbs; ++b) ALLOC(d.XL[b], (size_t)std::max(n_ln_g, 1) * 6);
     ALLOC(d.Hl6, (size_t)std::max(n_ln, 1) * 21);
     ALLOC(d.bl6, (size_t)std::max(n_ln, 1) * 6);
-    std::vector<int32_t> ln_gidx(std::max(n_ln, 1), 0);
-    for (int i = 0; i < n_ln; ++i) ln_gidx[i] = lm_gpos[n_pt + i] - n_pt_g;
-    UPLOAD(d.ln_gidx, ln_gidx);
+    h.ln_gidx.assign(std::max(n_ln, 1), 0);
+    for (int i = 0; i < n_ln; ++i) h.ln_gidx[i] = lm_gpos[n_pt + i] - n_pt_g;
+    UPLOAD(d.ln_gidx, h.ln_gidx);
     for (int b = 0; b < nbs; ++b) ALLOC(d.Lpb[b], (size_t)std::max(n_ln, 1) * 8);
-    UPLOAD(d.kf_hidx, kf_hidx);
-    UPLOAD_D(d.e_lm, e_lm, wb.e_lm, E);
-    UPLOAD_D(d.e_kf, e_kf, wb.e_kf, E);
-    UPLOAD_D(d.e_hidx, e_hidx, wb.e_hidx, E);
-    UPLOAD_D(d.e_obs, e_obs, wb.e_obs, (size_t)E * 4);
-    UPLOAD_D(d.e_info, e_info, wb.e_info, E);
+    UPLOAD(d.kf_hidx, ws.kf_hidx);
+    UPLOAD_D(d.e_lm, ws.e_lm, wb.e_lm, E);
+    UPLOAD_D(d.e_kf, ws.e_kf, wb.e_kf, E);
+    UPLOAD_D(d.e_hidx, ws.e_hidx, wb.e_hidx, E);
+    UPLOAD_D(d.e_obs, ws.e_obs, wb.e_obs, (size_t)E * 4);
+    UPLOAD_D(d.e_info, ws.e_info, wb.e_info, E);
     ZALLOC(d.e_level, E);
     ALLOC(d.e_active, E);
-    UPLOAD_D(d.lm_off, lm_off, wb.lm_off, n_lm + 1);
+    UPLOAD_D(d.lm_off, ws.lm_off, wb.lm_off, n_lm + 1);
     ALLOC(d.lm_active, n_lm);
-    UPLOAD_D(d.pe_off, pe_off, wb.pe_off, nf + 1);
-    UPLOAD_D(d.pe_list, pe_list, wb.pe_list, ctx->n_free_edges);
+    UPLOAD_D(d.pe_off, ws.pe_off, wb.pe_off, nf + 1);
+    UPLOAD_D(d.pe_list, ws.pe_list, wb.pe_list, ctx->n_free_edges);
     ALLOC(d.A, (size_t)E * 12);
     ALLOC(d.cvec, (size_t)E * 2);
     ALLOC(d.B, (size_t)E * 8);
     for (int b = 0; b < nbx; ++b) ZALLOC(d.chi2b[b], E);
-    // Hpp | b_p | #active edges | χ² | active | landmark max per rank: one array, all-reduced when sharded
     // unsharded: Hpp | b_p | active | χ² | any | max; sharded: diag(Hpp) | b_p | active | χ² | any |
     // per-rank maxima, all-reduced (the full partial Hpp stays local: Hpp_w)
-    ALLOC(d.red_iter, (size_t)nf * (sharded ? 13 : 43) + 2 + R);
-    if (sharded) {
-        ALLOC(d.red_iter_loc, (size_t)nf * 13 + 2 + R);
+    ALLOC(d.red_iter, (size_t)nf * (d.sharded ? 13 : 43) + 2 + d.nranks);
+    if (d.sharded) {
+        ALLOC(d.red_iter_loc, (size_t)nf * 13 + 2 + d.nranks);
         ALLOC(d.Hpp_w, (size_t)nf * 36);
     }
     ALLOC(d.Hll, (size_t)n_lm * 10);
@@ -1196,25 +1085,33 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
     ALLOC(d.Z, (size_t)W * E * 8);
     ALLOC(d.q, (size_t)W * E * 2);
     for (int b = 0; b < nbx; ++b) ZALLOC(d.xlb[b], (size_t)n_lm * 4);
-    UPLOAD(d.blk_i1, blk_i1);
-    UPLOAD(d.blk_i2, blk_i2);
-    UPLOAD(d.blk_off, blk_off);
-    UPLOAD_D(d.trip, trip, wb.trip, 2 * (size_t)ctx->n_triples);
-    d.nch = nch;
-    UPLOAD(d.ch_blk, ch_blk);
-    UPLOAD(d.ch_off, ch_off);
-    UPLOAD(d.blk_ch, blk_ch);
-    d.nch = nch;  // (sl_chp)
+}
+// second part: the reduced camera system, its factorisation scratch, reductions, outputs
+void stage_system_arrays(plba_ctx *ctx, const plba_graph *g, const WindowStructure &ws, const BlockPattern &bp,
+                         const ShardRanges &xg, StagedHost &h) {
+    Dev &d = ctx->d;
+    const WindowBuild &wb = ws.wb;
+    const FactorPlan &plan = ctx->plan;
+    const int n_kf = d.n_kf, n_pt = d.n_pt, n_ln = d.n_ln, n_lm = d.n_lm, Ep = d.Ep, E = d.E, nf = d.nf, n = d.n, nblk = d.nblk,
+              bw = d.bw, R = d.nranks, n_ln_g = g->n_ln, nbx = d.nbx, W = d.spec_max;
+    const bool two_sided = d.twisted || plan.fallback.mode == kClTw;
+    UPLOAD(d.blk_i1, bp.blk_i1);
+    UPLOAD(d.blk_i2, bp.blk_i2);
+    UPLOAD(d.blk_off, bp.blk_off);
+    UPLOAD_D(d.trip, ws.trip, wb.trip, 2 * (size_t)ctx->n_triples);
+    UPLOAD(d.ch_blk, bp.ch_blk);
+    UPLOAD(d.ch_off, bp.ch_off);
+    UPLOAD(d.blk_ch, bp.blk_ch);
     ALLOC(d.ch_part, (size_t)W * sl_chp(d));
-    ALLOC(d.Ad, band_mode ? 1 : (size_t)n * n);
-    UPLOAD(d.first_blk, first_blk);
+    ALLOC(d.Ad, d.band_mode ? 1 : (size_t)n * n);
+    UPLOAD(d.first_blk, ws.first_blk);
     // band blocks outside the envelope (w > i - first_blk[i]) are never assembled and must
     // read as zero: the band kernels sweep all BW block columns of every row
     ZALLOC(d.Bd, (size_t)W * sl_band(d));
     ALLOC(d.Lband, (size_t)W * sl_band(d));
     ALLOC(d.Kinv, (size_t)W * nf * 36);
     ALLOC(d.zb, (size_t)W * nf * 6);
-    if (twisted || fb_tw) {
+    if (two_sided) {  // (of the plan or of the fallback a BCR window may switch to)
         ZALLOC(d.Bd2, (size_t)W * sl_tw(d));
         ALLOC(d.bs2, (size_t)W * nf * 6);
         ALLOC(d.Lband2, (size_t)W * sl_tw(d));
@@ -1224,7 +1121,7 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
         ZALLOC(d.tw_fail, 2 * (size_t)W);
         ZALLOC(d.tw_count, (size_t)W);
     }
-    if (bcr) {  // flags carry epochs from bcr_ctl[0]: start from a clean slate (one set per trial slot)
+    if (d.bcr) {  // flags carry epochs from bcr_ctl[0]: start from a clean slate (one set per trial slot)
         const int64_t N = d.bcr_N;
         d.bcr_sl[0] = N * (int64_t)bcr_pub_doubles(bw);
         d.bcr_sl[1] = N * (int64_t)bcr_xrec(bw);
@@ -1235,36 +1132,36 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
         ALLOC(d.bcr_pub, (size_t)W * d.bcr_sl[0]);
         ALLOC(d.bcr_x, (size_t)W * d.bcr_sl[1]);
         ALLOC(d.bcr_X, (size_t)W * d.bcr_sl[2]);
-
-        UPLOAD(d.h_kf, h_kf);
+        h.h_kf.assign(nf, 0);
+        for (int k = 0; k < n_kf; ++k)
+            if (ws.kf_hidx[k] >= 0) h.h_kf[ws.kf_hidx[k]] = k;
+        UPLOAD(d.h_kf, h.h_kf);
         ZALLOC(d.bcr_flag, (size_t)W * d.bcr_sl[3]);
         ZALLOC(d.bcr_ctl, (size_t)W * kBcrCtl);
         ZALLOC(d.bcr_stamps, (size_t)W * d.bcr_sl[5]);
         // the schedule's starting state, restored if a hand-off wait times out (run_schedule)
-        ctx->alloc(ctx->bk_T, (size_t)n_kf * 12);
-        ctx->alloc(ctx->bk_X, (size_t)std::max(n_lm, 1) * 4);
-        ctx->alloc(ctx->bk_xp, (size_t)std::max(n, 6));
-        ctx->alloc(ctx->bk_xk, (size_t)n_kf * 6);
-        ctx->alloc(ctx->bk_Lpb, (size_t)std::max(n_ln, 1) * 8);
-        ctx->alloc(ctx->bk_XL, (size_t)std::max(n_ln_g, 1) * 6);
-        ctx->alloc(ctx->bk_level, (size_t)std::max(E, 1));
-        ctx->alloc(ctx->bk_xl, (size_t)std::max(n_lm, 1) * 4);
+        ALLOC(ctx->bk_T, (size_t)n_kf * 12);
+        ALLOC(ctx->bk_X, (size_t)std::max(n_lm, 1) * 4);
+        ALLOC(ctx->bk_xp, (size_t)std::max(n, 6));
+        ALLOC(ctx->bk_xk, (size_t)n_kf * 6);
+        ALLOC(ctx->bk_Lpb, (size_t)std::max(n_ln, 1) * 8);
+        ALLOC(ctx->bk_XL, (size_t)std::max(n_ln_g, 1) * 6);
+        ALLOC(ctx->bk_level, (size_t)std::max(E, 1));
+        ALLOC(ctx->bk_xl, (size_t)std::max(n_lm, 1) * 4);
     }
-    if (!band_mode) ZALLOC(d.bcr_stamps, kBcrStamps);  // dense-path phase stamps (PLBA_DIAG bit 8)
+    if (!d.band_mode) ZALLOC(d.bcr_stamps, kBcrStamps);  // dense-path phase stamps (PLBA_DIAG bit 8)
     ALLOC(d.bs, (size_t)W * n);
     // k_lm_solve reads x_p[6·max(h, 0) ..] for fixed-pose slots too
     for (int b = 0; b < nbx; ++b) ZALLOC(d.xpb[b], std::max(n, 6));
     ALLOC(d.Wbuf, (size_t)std::max(n, 1) * (kTile + 1));  // W panel + y of the dense path
-    UPLOAD(d.tile_first, tile_first);
-    UPLOAD(d.tile_last, tile_last);
+    UPLOAD(d.tile_first, bp.tile_first);
+    UPLOAD(d.tile_last, bp.tile_last);
     ALLOC(d.part_chi2, d.n_lin_blocks);
     ALLOC(d.part_any, d.n_lm_blocks);
     ALLOC(d.part_max, nf + d.n_lm_blocks);
     ALLOC(d.pose_part, (size_t)std::max(nf, 1) * kPoseParts * kPP);
     ALLOC(d.part_lm, (size_t)W * sl_lms(d));
     ALLOC(d.part_lms, (size_t)W * sl_lms(d));
-    d.fold = sharded ? 0 : 1;
-    d.fold_init = d.fold && !getenv("PLBA_NO_FOLD_INIT");
     // arrival counters: lm_solve, iter_reduce (top), RCS blocks, poses, iter_reduce groups
     const int nred = kPoseParts * nf + (d.n_lm > 0 ? d.n_lm_blocks : 0), ngrp = (nred + kRedGrp - 1) / kRedGrp;
     ZALLOC(d.cnt, 2 + (size_t)nblk + nf + ngrp);
@@ -1278,26 +1175,25 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
     ALLOC(ctx->d_depth, Ep);
     ALLOC(d.red_rcs, (size_t)nblk * 36 + (size_t)nf * 6);
     ALLOC(d.red_dec, 3);
-    if (sharded) {
+    if (d.sharded) {
         ALLOC(d.red_rcs_loc, (size_t)nblk * 36 + (size_t)nf * 6);
         ALLOC(d.red_dec_loc, 4);  // + the hand-off error agreement slot (agree_dev_error)
     }
     d.xg_P = 0;
-    d.xg_host = ctx->comm.kind == plba_ctx::Comm::HOST ? 1 : 0;
-    if (sharded && xg_rng.size()) {
-        d.xg_P = xg_P;
-        UPLOAD(d.xg_rng, xg_rng);
+    if (d.sharded && xg.rng.size()) {
+        d.xg_P = xg.P;
+        UPLOAD(d.xg_rng, xg.rng);
         // zeroed once: blockpart rewrites the same in-run positions every step, the padding (and,
         // host transport, the other ranks' slots) stays zero
-        ZALLOC(d.xg_send, (size_t)(d.xg_host ? R : 1) * xg_P);
-        ALLOC(d.xg_recv, (size_t)R * xg_P);
+        ZALLOC(d.xg_send, (size_t)(d.xg_host ? R : 1) * xg.P);
+        ALLOC(d.xg_recv, (size_t)R * xg.P);
     }
     // output maps (local landmark / edge -> whole-window position): the download scatter
     // (k_out_scatter) or, sharded, the final gather of the full window X | χ² | depth | level
-    UPLOAD_D(d.lm_gpos, lm_gpos, wb.lm_gpos, n_lm);
-    UPLOAD_D(d.e_gpos, e_gpos, wb.e_gpos, E);
-    if (sharded) {
-        ALLOC(d.gat, (size_t)(n_pt_g + n_ln_g) * 4 + 3 * (size_t)(Ep_g + El_g));
+    UPLOAD_D(d.lm_gpos, ctx->lm_gpos, wb.lm_gpos, n_lm);
+    UPLOAD_D(d.e_gpos, ws.e_gpos, wb.e_gpos, E);
+    if (d.sharded) {
+        ALLOC(d.gat, (size_t)d.n_lm_g * 4 + 3 * (size_t)d.E_g);
     } else {
         // one staging block: Tcw | pt_xyz | ln_orth | χ² (doubles), then the byte outputs
         ALLOC(ctx->d_outd, out_doubles(n_kf, n_pt, n_ln, E) + ((size_t)Ep + E + 7) / 8);
@@ -1305,56 +1201,83 @@ int do_upload(plba_ctx *ctx, const plba_graph *g) {
 #if defined(PLBA_STAMPS) || defined(PLBA_PHASE_STAMPS) || defined(PLBA_LMS_STAMPS)
     ZALLOC(d.stamps, 17 * 8);
 #endif
+}
 #undef ALLOC
 #undef ZALLOC
 #undef UPLOAD
 #undef UPLOAD_D
+// stages every array and fills the arena while the host sources are alive
+int stage_arrays(plba_ctx *ctx, const plba_graph *g, const WindowStructure &ws, const BlockPattern &bp,
+                 const ShardRanges &xg, PhaseLog &mark) {
+    StagedHost h;
+    stage_state_arrays(ctx, g, ws, h);
+    stage_system_arrays(ctx, g, ws, bp, xg, h);
     mark("host arrays staged");
-    int rc = ctx->commit_plan();
-    if (rc) return rc;
-    // slot 0's buffers for the kernels that never run speculatively (one χ² / solve buffer then)
+    return ctx->commit_plan();
+}
+// views into the arena's arrays: slot 0's buffers for the kernels that never run speculatively
+// (one χ² / solve buffer then) and the sections of the per-iteration reduction record
+void bind_views(Dev &d) {
+    const size_t nf = (size_t)d.nf;
     d.xp = d.xpb[0];
     d.xl = d.xlb[0];
     d.chi2_last = d.chi2b[0];
-    if (sharded) {
+    if (d.sharded) {
         d.Hpp = nullptr;
         d.Hdg = d.red_iter;
-        d.bp = d.red_iter + (size_t)nf * 6;
-        d.pact = d.red_iter + (size_t)nf * 12;
+        d.bp = d.red_iter + nf * 6;
+        d.pact = d.red_iter + nf * 12;
         d.Hdg_w = d.red_iter_loc;
-        d.bp_w = d.red_iter_loc + (size_t)nf * 6;
-        d.pact_w = d.red_iter_loc + (size_t)nf * 12;
+        d.bp_w = d.red_iter_loc + nf * 6;
+        d.pact_w = d.red_iter_loc + nf * 12;
     } else {
         d.Hpp = d.red_iter;
-        d.bp = d.red_iter + (size_t)nf * 36;
-        d.pact = d.red_iter + (size_t)nf * 42;
+        d.bp = d.red_iter + nf * 36;
+        d.pact = d.red_iter + nf * 42;
         d.red_iter_loc = d.red_iter;
         d.Hpp_w = d.red_iter_loc;
-        d.bp_w = d.red_iter_loc + (size_t)nf * 36;
-        d.pact_w = d.red_iter_loc + (size_t)nf * 42;
+        d.bp_w = d.red_iter_loc + nf * 36;
+        d.pact_w = d.red_iter_loc + nf * 42;
         d.Hdg = d.Hdg_w = nullptr;
     }
-    if (band_mode) PLBA_CHECK(hipFuncSetAttribute(band_kernel(bw), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)band_lds_bytes(bw, nf)));
-    if (bcr) {
-        PLBA_CHECK(hipFuncSetAttribute(bcr_kernel(bw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bcr_lds_bytes(bw)));
-        PLBA_CHECK(hipFuncSetAttribute(bcr_back_kernel(bw), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)bcr_back_lds_bytes(bw)));
-        if (fb_tw) {
-            const void *k = cl_kernel_impl(bw, true, std::make_integer_sequence<int, kClMaxBW + 1>{});
-            PLBA_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cl_lds_bytes(bw, nf, true)));
-        } else {
-            const void *k = cl_kernel_impl(bw, false, std::make_integer_sequence<int, kClMaxBW + 1>{});
-            PLBA_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cl_lds_bytes(bw, nf, false)));
-        }
+}
+// dynamic LDS above the default limit: every kernel the plan or its fallback may launch
+int raise_lds_limits(plba_ctx *ctx) {
+    const FactorPlan &p = ctx->plan;
+    const int modes[] = {p.mode, p.mode == kBcr && !p.bcr_fused ? kBcrBack : -1, p.fallback.mode};
+    for (int m : modes) {
+        const KernelLaunch k = factor_kernel(m, ctx->d.bw, ctx->d.nf);
+        if (k.fn) PLBA_CHECK(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds_bytes));
     }
-    if (d.cl) {  // the column-lane kernel's LDS grows with nf (x_p staging of the two-sided variant)
-        const void *k = cl_kernel_impl(bw, twisted, std::make_integer_sequence<int, kClMaxBW + 1>{});
-        PLBA_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cl_lds_bytes(bw, nf, twisted)));
-    }
-    if (twisted)
-        PLBA_CHECK(hipFuncSetAttribute(twisted_kernel(bw), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)twisted_lds_bytes(bw, nf)));
+    return PLBA_OK;
+}
+
+int do_upload(plba_ctx *ctx, const plba_graph *g) {
+    const Tuning &t = ctx->tuning = read_tuning();
+    int rc = validate_graph(ctx, g, t.host_build);
+    if (rc) return rc;
+    PhaseLog mark{t.timing};
+    ctx->free_all();
+    mark("free");
+    ctx->n_kf = g->n_kf; ctx->n_pt = g->n_pt; ctx->n_ln = g->n_ln; ctx->Ep = g->n_ept; ctx->El = g->n_eln;
+    // Window structure on the device unless PLBA_HOST_BUILD=1 (or there is no keyframe)
+    WindowStructure ws;
+    rc = g->n_kf > 0 && !t.host_build ? build_structure_device(ctx, g, mark, ws) : build_structure_host(ctx, g, mark, ws);
+    if (rc) return rc;
+    ctx->dev_build = ws.devb ? 1 : 0;
+    BlockPattern bp;
+    if ((rc = build_block_pattern(ctx, ws, mark, bp))) return rc;
+    Dev &d = ctx->d;
+    describe_window(ctx, g, ws, bp);
+    const int resident =
+        band_mode(ws.bw, t) && !ctx->no_bcr && !t.bcr_resident_set ? bcr_resident(ctx->opts.device, ws.bw, ws.nf) : 0;
+    ctx->plan = plan_factor(ws.bw, ws.nf, resident, ctx->no_bcr, d.sharded != 0, d.n_lm > 0 && bp.nch > 0, t);
+    apply_plan(d, ctx->plan);
+    ShardRanges xg;
+    if ((rc = exchange_shard_ranges(ctx, ws.nf, bp, xg))) return rc;
+    if ((rc = stage_arrays(ctx, g, ws, bp, xg, mark))) return rc;
+    bind_views(d);
+    if ((rc = raise_lds_limits(ctx))) return rc;
     mark("alloc + copy + memset");
     ctx->uploaded = true;
     ctx->initialized = false;
@@ -1431,16 +1354,12 @@ int allgather(plba_ctx *ctx, const double *send, double *recv, size_t P) {
 // k_rcs_chunk keeps resident (1.75 waves per SIMD x 1024 SIMDs) — per slot, so that the choice
 // (and the rounding) does not depend on the trial-slot count; PLBA_CHUNK_HALF_MIN overrides the
 // threshold (0: always, a huge value: never)
-bool chunk_half(const Dev &d) {
-    const char *e = getenv("PLBA_CHUNK_HALF_MIN");  // (read per capture: tests switch it)
-    const long long thr = e ? atoll(e) : 1792LL;
-    return (long long)d.nch > thr;
-}
+bool chunk_half(const plba_ctx *ctx) { return (long long)ctx->d.nch > ctx->tuning.chunk_half_min; }
 int launch_step(plba_ctx *ctx) {
     Dev &d = ctx->d;
     hipStream_t s = ctx->stream;
     // PLBA_CHUNK_DIRECT=1: per-lane A/Z row loads in the Schur assembly (A/B of the staged copy)
-    const bool chunk_direct = getenv("PLBA_CHUNK_DIRECT") != nullptr;  // (read per capture: tests switch it)
+    const bool chunk_direct = ctx->tuning.chunk_direct;
 
     if (d.E > 0) LAUNCH(K_LINEARIZE, hipLaunchKernelGGL(k_linearize, dim3(d.n_lin_blocks), dim3(kBlock), 0, s, d));
     if (d.nf > 0 || d.n_lm > 0) {
@@ -1459,7 +1378,7 @@ int launch_step(plba_ctx *ctx) {
     }
     if (d.n > 0) {
         if (!d.band_mode) LAUNCH(K_MEMSET, (void)hipMemsetAsync(d.Ad, 0, sizeof(double) * (size_t)d.n * d.n, s));
-        if (d.nch > 0) LAUNCH(K_ASSEMBLE, hipLaunchKernelGGL(chunk_direct ? k_rcs_chunk<false> : chunk_half(d) ? k_rcs_chunk_h : k_rcs_chunk<true>, dim3(8 * ((d.nch + 7) / 8), d.spec_max), dim3(64), 0, s, d));
+        if (d.nch > 0) LAUNCH(K_ASSEMBLE, hipLaunchKernelGGL(chunk_direct ? k_rcs_chunk<false> : chunk_half(ctx) ? k_rcs_chunk_h : k_rcs_chunk<true>, dim3(8 * ((d.nch + 7) / 8), d.spec_max), dim3(64), 0, s, d));
         if (d.sharded) {
             LAUNCH(K_PACK, hipLaunchKernelGGL(k_rcs_blockpart, dim3(blocks_for(d.nblk * 42)), dim3(kBlock), 0, s, d));
             if (d.xg_P > 0) {  // all-gather of every rank's nonzero runs, summed in rank order
@@ -1558,16 +1477,11 @@ int capture_steps(plba_ctx *ctx, int nsteps, hipGraph_t &graph, hipGraphExec_t &
 // Which kernels (template instances) a step launches, in which order: an executable graph is
 // updated in place only for a window with the same signature (hipGraphExecUpdate changes kernel
 // arguments and grids, never the kernel a node runs).
-// multi-step graphs captured: 2, 4, .. 2^L steps (PLBA_GRAPH_LEVELS overrides, for measurements)
-int graph_levels() {  // (read per capture: tests switch it)
-    const char *e = getenv("PLBA_GRAPH_LEVELS");
-    return e ? std::max(0, std::min(atoi(e), (int)plba_ctx::kMultiLevels)) : (int)plba_ctx::kMultiLevels;
-}
 std::vector<int64_t> launch_signature(const plba_ctx *ctx) {
     const Dev &d = ctx->d;
     return {d.E > 0, d.nf > 0, d.n_lm > 0, d.n > 0, d.nch > 0, d.band_mode, d.dense_mfma, d.dense_mfma ? d.ntiles : 0,
             d.bw, d.bcr, d.bcr_fused, d.cl, d.twisted, d.sharded, d.xg_P, d.fold, d.fold_init, d.n_kf > 0, d.spec_max,
-            (int64_t)(getenv("PLBA_CHUNK_DIRECT") != nullptr), (int64_t)chunk_half(d), (int64_t)ctx->comm.kind};
+            (int64_t)ctx->tuning.chunk_direct, (int64_t)chunk_half(ctx), (int64_t)ctx->comm.kind};
 }
 int capture_step(plba_ctx *ctx) {
     if (ctx->step_exec && !ctx->graphs_stale) return PLBA_OK;
@@ -1577,16 +1491,16 @@ int capture_step(plba_ctx *ctx) {
     ctx->graph_sig = sig;
     const auto t0 = std::chrono::steady_clock::now();
     int rc = capture_steps(ctx, 1, ctx->step_graph, ctx->step_exec);
-    for (int i = 0; i < graph_levels() && !rc; ++i)
+    for (int i = 0; i < ctx->tuning.graph_levels && !rc; ++i)  // 2, 4, .. 2^L steps
         rc = capture_steps(ctx, 2 << i, ctx->multi_graph[i], ctx->multi_exec[i]);
-    if (env_flag("PLBA_TIMING"))
+    if (ctx->tuning.timing)
         fprintf(stderr, "[plba upload] %-24s %8.3f ms\n", "graph capture",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return rc;
 }
 // launch n replays of the step as the binary decomposition of n over the captured graphs
 int launch_steps_graph(plba_ctx *ctx, int n) {
-    const int L = graph_levels();
+    const int L = ctx->tuning.graph_levels;
     if (L == 0) {
         for (int i = 0; i < n; ++i) PLBA_CHECK(hipGraphLaunch(ctx->step_exec, ctx->stream));
         return PLBA_OK;
@@ -1692,7 +1606,7 @@ int run_schedule_once(plba_ctx *ctx, const Ctrl &init, bool &dev_error) {
     };
     int launched = 0;
     int batch = std::max(4, ctx->last_steps);
-    const bool tlog = env_flag("PLBA_TIMING");
+    const bool tlog = ctx->tuning.timing;
     auto tb0 = std::chrono::steady_clock::now();
     const int max_steps = init.n_stages * 10 * (init.max_iters[0] + init.max_iters[1] + 2) + 8;
     for (;;) {
@@ -1761,11 +1675,7 @@ int run_schedule(plba_ctx *ctx, const Ctrl &init) {
     if (ctx->opts.verbose)
         fprintf(stderr, "[plba] BCR hand-off timed out; re-solving with the column-lane factorisation\n");
     destroy_graphs(ctx);
-    d.bcr = 0;
-    d.bcr_N = 0;
-    d.cl = ctx->fb_cl;
-    d.twisted = ctx->fb_twisted;
-    d.tw_m = ctx->fb_tw_m;
+    apply_plan(d, ctx->plan.fallback);
     ctx->no_bcr = true;
     ++ctx->bcr_fallbacks;
     ctx->err.clear();
@@ -2401,8 +2311,19 @@ int plba_structure_stats(plba_ctx *ctx, int64_t *out, int32_t cap) {
                            ctx->d.band_mode, ctx->d.nch, ctx->n_free_edges, ctx->d.Ep,
                            ctx->step_exec != nullptr, ctx->d.sharded, ctx->d.twisted, ctx->d.cl, ctx->d.bcr_N,
                            ctx->d.dense_mfma, ctx->bcr_fallbacks, ctx->d.spec_max, ctx->d.spec_policy,
-                           ctx->h_ctrl ? ctx->h_ctrl->steps : 0, 0, ctx->dev_build};  // [20]: unused
+                           ctx->h_ctrl ? ctx->h_ctrl->steps : 0, ctx->d.bcr_fused, ctx->dev_build};
     for (int i = 0; i < cap && i < 22; ++i) out[i] = v[i];
+    return PLBA_OK;
+}
+
+// The factorisation an upload would choose for a window of nf free poses and envelope width bw
+// (plan_factor under the current environment): no context, no device. flags: 1 no_bcr (the
+// context fell back before), 2 sharded, 4 the window has Schur triples to assemble.
+int plba_factor_plan(int32_t bw, int32_t nf, int32_t resident, int32_t flags, int32_t *out, int32_t cap) {
+    if (!out || bw < 0 || nf < 0) return PLBA_E_INVALID;
+    const FactorPlan p = plan_factor(bw, nf, resident, flags & 1, flags & 2, flags & 4, read_tuning());
+    const int32_t v[9] = {p.mode, p.bcr_N, p.bcr_fused, p.tw_m, p.ring, p.slots, p.policy, p.fallback.mode, p.fallback.tw_m};
+    for (int i = 0; i < cap && i < 9; ++i) out[i] = v[i];
     return PLBA_OK;
 }
 
@@ -2585,6 +2506,7 @@ int plba_pgo_optimize(plba_ctx *ctx, const plba_pgo_graph *g, const plba_pgo_par
         }
     }
     (void)hipSetDevice(ctx->opts.device);
+    const Tuning tuning = read_tuning();  // (PLBA_NO_RCM, PLBA_SOLVE_LDS_N: sampled per call)
     const auto t0 = std::chrono::steady_clock::now();
     // ---- SparseOptimizer::initializeOptimization(): active edges (not all vertices fixed) in
     //      creation order; Hessian index of the active free vertices in id order
@@ -2691,7 +2613,7 @@ int plba_pgo_optimize(plba_ctx *ctx, const plba_pgo_graph *g, const plba_pgo_par
     };
     {
         int bwp = envelope_of(hidx, first_h);
-        if (bwp > 1 && nfree > 2 && !env_flag("PLBA_NO_RCM")) {
+        if (bwp > 1 && nfree > 2 && !tuning.no_rcm) {
             std::vector<std::vector<int32_t>> adj(nfree);
             for (int e : act) {
                 const int a = hidx[g->e_v[2 * e]], b = hidx[g->e_v[2 * e + 1]];
@@ -2699,10 +2621,8 @@ int plba_pgo_optimize(plba_ctx *ctx, const plba_pgo_graph *g, const plba_pgo_par
                 adj[a].push_back(b);
                 adj[b].push_back(a);
             }
-            const std::vector<int32_t> rcm = rcm_from_adj(adj);
-            std::vector<int32_t> pos(nfree), h2(nv, -1), fh2(nfree);
-            for (int i = 0; i < nfree; ++i) pos[rcm[i]] = i;
-            for (int v = 0; v < nv; ++v) h2[v] = hidx[v] >= 0 ? pos[hidx[v]] : -1;
+            const std::vector<int32_t> h2 = permute_hidx(hidx, rcm_from_adj(adj));
+            std::vector<int32_t> fh2(nfree);
             if (envelope_of(h2, fh2) < bwp) {
                 hidx = h2;
                 first_h = fh2;
@@ -2816,7 +2736,7 @@ int plba_pgo_optimize(plba_ctx *ctx, const plba_pgo_graph *g, const plba_pgo_par
     P.T[0] = T0; P.T[1] = T1;
     P.blk_r = blk_r_d; P.blk_c = blk_c_d; P.blk_off = blk_off_d; P.blk_con = blk_con_d;
     dd.n = n; dd.ntiles = ntiles; dd.Ad = Ad; dd.bs = P.b; dd.xp = P.x; dd.ctrl = ctrl_d;
-    dd.solve_lds_n = solve_lds_limit();
+    dd.solve_lds_n = tuning.solve_lds_n;
     dd.tile_first = tf_d; dd.tile_last = tl_d;
     double *hout = ctx->pgo_hout;
     auto fetch = [&]() -> int {

@@ -396,7 +396,7 @@ int build_stage1(BuildMem &A, WindowBuild &wb, char *err, size_t errlen) {
     const plba_graph *g = wb.g;
     hipStream_t st = wb.stream;
     // PLBA_TIMING: phase marks of the stage (each waits for the stream: timing runs only)
-    const bool tmg = getenv("PLBA_TIMING") != nullptr;
+    const bool tmg = wb.timing;
     auto tlast = std::chrono::steady_clock::now();
     auto tmark = [&](const char *what) {
         if (!tmg) return;

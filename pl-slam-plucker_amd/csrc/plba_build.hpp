@@ -4,7 +4,7 @@
 // sort / scan / scatter kernels on the solver stream (csrc/plba_build.hip, rocPRIM radix sorts),
 // instead of O(E) and O(Σ track²) host loops.
 //
-// The outputs are bit-for-bit the arrays the host build (plba.hip do_upload) produces: the same
+// The outputs are bit-for-bit the arrays the host build (plba.hip build_structure_host) produces: the same
 // orders (stable sorts by the same keys), so the solve is unchanged.
 //
 // Reference: MapHandler::localBundleAdjustmentForPlukerWithG2O graph build
@@ -39,6 +39,7 @@ struct WindowBuild {
     const int32_t *kf_hidx = nullptr; // [n_kf] Hessian index of each free pose, -1 fixed
     const int32_t *kpos = nullptr;    // [n_kf] rank of each keyframe by vertex id
     hipStream_t stream = nullptr;
+    bool timing = false;              // PLBA_TIMING set at all (Tuning::timing_any): stage phase log
     // ---- outputs of stage 1 (device pointers into BuildMem A unless noted)
     int n_pt = 0, n_ln = 0, n_lm = 0, Ep = 0, El = 0, E = 0;
     int64_t n_free_edges = 0;

@@ -27,7 +27,7 @@ EXPORTED = [
     "plba_refresh_edge_errors", "plba_get_edge_chi2", "plba_download", "plba_lba_plucker", "plba_get_trace",
     "plba_synchronize", "plba_enable_kernel_timing", "plba_kernel_times", "plba_structure_stats",
     "plba_shard_plan", "plba_comm_unique_id", "plba_comm_init_rccl", "plba_comm_init_host",
-    "plba_comm_info",
+    "plba_comm_info", "plba_factor_plan",
     "plba_hlm_default_params", "plba_hlm_lba",
     "plba_pgo_default_params", "plba_pgo_optimize",
 ]
@@ -80,6 +80,7 @@ def load(path: Optional[str] = None):
     L.plba_comm_init_rccl.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
     L.plba_comm_init_host.argtypes = [vp, C.c_int32, C.c_int32, HOST_ALLREDUCE_FN, vp]
     L.plba_comm_info.argtypes = [vp, ip, C.c_int32]
+    L.plba_factor_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32]
     L.plba_hlm_default_params.argtypes = [C.POINTER(capi.PlbaHlmParams)]
     L.plba_hlm_default_params.restype = None
     L.plba_hlm_lba.argtypes = [vp, C.POINTER(capi.PlbaHlmState), C.POINTER(capi.PlbaHlmParams),
@@ -304,7 +305,7 @@ class Solver:
                     chunks=st[7], free_edges=st[8], point_edges=st[9], graph=st[10], sharded=st[11],
                     twisted=st[12], column_lane=st[13], bcr_rows=st[14], dense_mfma=st[15],
                     bcr_fallbacks=st[16], spec_slots=st[17], spec_policy=st[18], device_steps=st[19],
-                    unused20=st[20], device_build=st[21])
+                    bcr_fused=st[20], device_build=st[21])
 
     def synchronize(self):
         self._check(self.L.plba_synchronize(self.ctx), "plba_synchronize")

@@ -160,7 +160,7 @@ def test_column_lane_factorisation_bandwidths(solver, monkeypatch, tmax, n_kf):
     assert np.abs(cl["kf_Tcw"] - old["kf_Tcw"]).max() < 1e-9
 
 
-# Every environment switch the library reads (DESIGN §6 "Switches"), on a window the oracle
+# Every environment switch the library reads (the table on struct Tuning, csrc/plba_plan.hpp), on a window the oracle
 # finishes in seconds: the A/B and diagnostic switches must keep the oracle parity, and those that
 # only change scheduling, load paths, staging or logging must be bitwise the default solve.
 ENV_SWITCHES = [
@@ -175,6 +175,8 @@ ENV_SWITCHES = [
     ({"PLBA_FORCE_DENSE": "1"}, False),        # dense MFMA factorisation of a banded window
     ({"PLBA_DENSE_SCALAR": "1", "PLBA_FORCE_DENSE": "1"}, False),
     ({"PLBA_FACTOR": "bcr", "PLBA_SPEC_BCR": "0"}, False),
+    ({"PLBA_FACTOR": "bcr", "PLBA_SPEC_BCR": "0", "PLBA_BCR_SPLIT": "1"}, False),  # split BCR back substitution
+    ({"PLBA_NO_CL": "1"}, False),              # LDS-window band kernel instead of column-lane
     ({"PLBA_FACTOR": "band"}, False),           # 16-wave band kernel
     ({"PLBA_NO_TWIST": "1"}, False),
     ({"PLBA_SPEC": "1"}, True),                # one trial slot
@@ -354,20 +356,35 @@ def test_column_lane_large_nf_lds(solver):
     _check(out, ref, elem=1e3)  # 468 free poses, tracks up to 10 KFs: elements agree to 1e-7
 
 
-@pytest.mark.parametrize("tmax,n_kf", [(2, 12), (3, 30), (5, 40), (8, 64), (8, 100), (10, 60), (10, 130)])
-def test_block_cyclic_reduction_matches_oracle(solver, monkeypatch, tmax, n_kf):
+@pytest.mark.parametrize("tmax,n_kf,split", [(2, 12, 0), (3, 30, 0), (3, 30, 1), (5, 40, 0), (8, 64, 0), (8, 100, 0),
+                                             (8, 100, 1), (10, 60, 0), (10, 130, 0)],
+                         ids=["2-12", "3-30", "3-30-split", "5-40", "8-64", "8-100", "8-100-split", "10-60", "10-130"])
+def test_block_cyclic_reduction_matches_oracle(solver, monkeypatch, tmax, n_kf, split):
     """Block cyclic reduction over super-rows of bw pose blocks (plba_bcr.hpp), forced on, at
     bandwidths 1..9 and super-row counts 2..16 (odd and even, powers of two and not), against
-    the oracle and against the column-lane factorisation of the same window."""
+    the oracle and against the column-lane factorisation of the same window. split = 1
+    (PLBA_BCR_SPLIT=1: back substitution as a second launch, k_rcs_bcr_back) on the two smallest
+    shapes with more than two levels, also against the fused solve: the two sum in different
+    slice counts, so they agree to the BCR / column-lane bound, not bitwise."""
     g = synth.generate("C1L", n_kf=n_kf, n_pt=25 * n_kf, n_ln=5 * n_kf, seed=500 + tmax + n_kf,
                        track_min=2, track_max=tmax, fixed_frac=0.1)
     ref = oa.lba_plucker(g)
     monkeypatch.setenv("PLBA_FACTOR", "bcr")
+    fused = None
+    if split:
+        solver.upload(g)
+        assert solver.structure_stats()["bcr_fused"] == 1
+        fused = solver.lba_plucker()
+        monkeypatch.setenv("PLBA_BCR_SPLIT", "1")
     solver.upload(g)
+    monkeypatch.delenv("PLBA_BCR_SPLIT", raising=False)
     st = solver.structure_stats()
     assert st["banded"] == 1 and st["bcr_rows"] == -(-st["nf"] // st["bw"]) >= 2, st
+    assert st["bcr_fused"] == 1 - split, st
     out = solver.lba_plucker()
     _check(out, ref)
+    if split:
+        assert np.abs(out["kf_Tcw"] - fused["kf_Tcw"]).max() < 1e-9
     solver.reset()
     again = solver.lba_plucker()          # epoch-tagged hand-offs: a rerun is bitwise identical
     for k in ("kf_Tcw", "pt_xyz", "ln_orth"):
@@ -400,6 +417,7 @@ def test_bcr_handoff_timeout_falls_back_to_column_lane(monkeypatch):
         out = s.lba_plucker()
         st = s.structure_stats()
         assert st["bcr_fallbacks"] == 1 and st["bcr_rows"] == 0 and st["column_lane"] == 1, st
+        assert st["twisted"] == (1 if st["nf"] >= 2 * st["bw"] + 16 else 0), st
         _check(out, ref)
         s.reset()
         again = s.lba_plucker()           # same context after the fallback
