@@ -179,7 +179,8 @@ int plba_factor_plan(int32_t bw, int32_t nf, int32_t resident, int32_t flags, in
 typedef struct plba_hlm_state {
     const double *kf_x;        /* [n_kf][6] KeyFrame::x_kf_w = X_aux pose blocks [t; ω] (:1518)   */
     const double *ln_pluker;   /* [n_ln][6] MapLine::NDw of the map (first linearisation, :1744)  */
-    const double *ln_line3d;   /* GBA only: [n_ln][6] MapLine::line3D endpoints [P; Q] (:3089)    */
+    const double *ln_line3d;   /* GBA / LBA_ENDPOINTS: [n_ln][6] MapLine::line3D endpoints [P; Q]
+                                  (:3089, :1464)                                                  */
 } plba_hlm_state;
 
 typedef struct plba_hlm_params {
@@ -192,7 +193,7 @@ typedef struct plba_hlm_params {
     int32_t err_per_obs;       /* 0 = the reference: err /= (Npt_obs + Nls_obs), both counters stay
                                   0 (:1642,1731,1849) so err becomes +inf and every step after the
                                   first is accepted; 1 = divide by the observation count instead */
-    int32_t variant;           /* PLBA_HLM_LBA_PLUCKER or PLBA_HLM_GBA                            */
+    int32_t variant;           /* PLBA_HLM_LBA_PLUCKER, PLBA_HLM_GBA or PLBA_HLM_LBA_ENDPOINTS    */
     int32_t pad;
 } plba_hlm_params;
 
@@ -203,9 +204,22 @@ typedef struct plba_hlm_params {
  * eln_obs[.][0..2]; residual e = (l·π(P), l·π(Q)); from the second linearisation on both
  * endpoints are read from X at the aliased offset 6Nkf+3Npt+3·j (:3547-3548); Hmax is an int
  * (:3386, truncation); the stop tests use numeric_limits<double>::epsilon() (pass it as
- * min_error / min_error_change). */
-#define PLBA_HLM_LBA_PLUCKER 0
-#define PLBA_HLM_GBA         1
+ * min_error / min_error_change).
+ * PLBA_HLM_LBA_ENDPOINTS = MapHandler::levMarquardtOptimizationLBA (src/mapHandler.cpp:2334-3016,
+ * window of localBundleAdjustment :1392-1502), the local BA of a build without USE_LINE_PLUKER:
+ * a KF is free iff local && kf_idx != 0 (:1403, kf_fixed[k] == 0), every other observing KF is
+ * fixed and its observations add to the landmark block and g only (:2417-2423, :2530-2536); lines
+ * and observations as in GBA (state_ln_line3d, eln_obs[.][0..2] = (a, b, c)), with the same aliased
+ * reads of both endpoints from the second linearisation on (:2697-2698) and the map pose T_kf_w for
+ * every line observation (:2700); Hmax is a double (:2555); err is divided by Npt_obs + Nls_obs == 0
+ * on the first linearisation (:2551, +inf) and by the landmark counts Npt + Nls afterwards (:2796,
+ * finite; err_per_obs = 1 divides both by the observation count); the later line linearisations
+ * hard-code the homogeneous threshold 1e-7 (:2717-2760) where the first one and the points read
+ * homog_th; the stop tests use min_error_change / min_error (:2798, :2834). Unsharded windows only,
+ * as GBA. ln_pluker is not read. */
+#define PLBA_HLM_LBA_PLUCKER   0
+#define PLBA_HLM_GBA           1
+#define PLBA_HLM_LBA_ENDPOINTS 2
 
 typedef struct plba_hlm_result {
     double  *kf_x;             /* [n_kf][6] X pose blocks at exit (KFs not in kf_list: input x)   */
@@ -221,7 +235,7 @@ typedef struct plba_hlm_result {
     double   lambda;           /* λ at exit                                                       */
     double   dx_norm;          /* ‖DX‖ of the last solve                                          */
     double   solve_ms;         /* wall time of the loop                                           */
-    double  *ln_line3d;        /* GBA: [n_ln][6] line3D at exit                                   */
+    double  *ln_line3d;        /* GBA / LBA_ENDPOINTS: [n_ln][6] line3D at exit                   */
 } plba_hlm_result;
 
 void plba_hlm_default_params(plba_hlm_params *p);

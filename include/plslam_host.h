@@ -112,6 +112,16 @@ typedef struct plslam_hlm_stats {
     double  err, lambda, gather_ms, solve_ms, writeback_ms;
 } plslam_hlm_stats;
 int plslam_local_ba_plucker(plslam_map *m, plslam_hlm_stats *stats);
+/* ---- MapHandler::localBundleAdjustment() (src/mapHandler.cpp:1392-1502), the local BA of a build
+ * without USE_LINE_PLUKER: levMarquardtOptimizationLBA (:2334-3016) on the GPU (plba_hlm_lba,
+ * variant PLBA_HLM_LBA_ENDPOINTS whatever plslam_set_hlm_params set) through the same solver hook,
+ * and its write-back (:2841-2882: T_kf_w = expmap_se3(X_i); point3D / line3D = X with inlier = false
+ * when the landmark moved more than 0.01; nothing when vo_status == VO_INSERTING_KF). Lines are
+ * their endpoints line3D (plslam_set_line_geometry) and each line observation is the image line
+ * equation (a, b, c) in obs[0..2] of plslam_add_line / plslam_line_add_observation. stats->ret is
+ * the reference's return value: -1 with no observation or while VO inserts a KF, else 0. The
+ * observation-removal loop of :2884-3006 acts on a flag that nothing in :2334-2840 sets: no-op. */
+int plslam_local_ba(plslam_map *m, plslam_hlm_stats *stats);
 
 /* ---- the rest of the Plücker local-mapping step around the LBA ---- */
 /* SlamConfig::minLMObs / minLMCovGraph / minKFLocalMap (src/slamConfig.cpp:48,61-62; defaults

@@ -2180,23 +2180,27 @@ void plba_hlm_default_params(plba_hlm_params *p) {
 // window: the captured step graph with the Ctrl::hlm variants of each kernel, one step per
 // iteration (linearise -> [stop] -> Schur solve -> decide), no host round trip inside a batch.
 int plba_hlm_lba(plba_ctx *ctx, const plba_hlm_state *st, const plba_hlm_params *p, plba_hlm_result *res) {
-    if (!ctx || !st || (ctx->n_kf && !st->kf_x) || (ctx->n_ln && !st->ln_pluker)) return PLBA_E_INVALID;
+    if (!ctx || !st || (ctx->n_kf && !st->kf_x)) return PLBA_E_INVALID;
     if (!ctx->uploaded) return PLBA_E_STATE;
     (void)hipSetDevice(ctx->opts.device);
     plba_hlm_params prm;
     if (p) prm = *p;
     else plba_hlm_default_params(&prm);
-    if (prm.max_iters < 1 || (prm.variant != PLBA_HLM_LBA_PLUCKER && prm.variant != PLBA_HLM_GBA)) {
-        ctx->set_error("max_iters must be >= 1 and variant PLBA_HLM_LBA_PLUCKER or PLBA_HLM_GBA");
+    if (prm.max_iters < 1 || (prm.variant != PLBA_HLM_LBA_PLUCKER && prm.variant != PLBA_HLM_GBA &&
+                              prm.variant != PLBA_HLM_LBA_ENDPOINTS)) {
+        ctx->set_error("max_iters must be >= 1 and variant PLBA_HLM_LBA_PLUCKER, PLBA_HLM_GBA or PLBA_HLM_LBA_ENDPOINTS");
         return PLBA_E_INVALID;
     }
-    const bool gba = prm.variant == PLBA_HLM_GBA;
+    // endpoint lines (6-dim landmarks line3D): GBA and levMarquardtOptimizationLBA (:2334-3016)
+    const bool lba_ep = prm.variant == PLBA_HLM_LBA_ENDPOINTS;
+    const bool gba = prm.variant == PLBA_HLM_GBA || lba_ep;
+    if (!lba_ep && ctx->n_ln && !st->ln_pluker) return PLBA_E_INVALID;  // (the new variant never reads NDw)
     if (gba && ctx->n_ln && !st->ln_line3d) {
-        ctx->set_error("the GBA variant needs state ln_line3d");
+        ctx->set_error("the endpoint-line variants need state ln_line3d");
         return PLBA_E_INVALID;
     }
     if (gba && ctx->d.sharded) {
-        ctx->set_error("the GBA variant runs on unsharded windows only");
+        ctx->set_error("the endpoint-line variants run on unsharded windows only");
         return PLBA_E_STATE;
     }
     int rc = plba_reset_estimates(ctx);
@@ -2220,13 +2224,15 @@ int plba_hlm_lba(plba_ctx *ctx, const plba_hlm_state *st, const plba_hlm_params 
     c.max_iters[0] = prm.max_iters;
     c.stage_robust[0] = 0;
     c.stage_level[0] = 0;
-    c.hlm = gba ? 2 : 1;
+    c.hlm = lba_ep ? 3 : gba ? 2 : 1;
     c.hlm_lambda0 = prm.lambda0;
     c.hlm_k = prm.lambda_k;
     c.hlm_homog = prm.homog_th;
     c.hlm_minerr = prm.min_error;
     c.hlm_minchg = prm.min_error_change;
     c.hlm_nobs = prm.err_per_obs ? (double)(ctx->Ep + ctx->El) : 0.0;
+    // :2796 divides by the landmark counts Npt + Nls from the second linearisation on
+    c.hlm_nobs2 = prm.err_per_obs ? c.hlm_nobs : (double)(ctx->n_pt + ctx->n_ln);
     c.err_prev = 999999999.9;  // :1634
     rc = run_schedule(ctx, c);
     PLBA_CHECK(hipStreamSynchronize(ctx->stream));

@@ -86,11 +86,15 @@ struct Ctrl {
     int32_t dev_error;                                 // a bounded in-kernel wait timed out
     // hand-rolled LM (plba_hlm_lba, src/mapHandler.cpp:1618-2332): the same step graph with the
     // scalar-residual linearisation, Marquardt damping, se(3) pose update and its own decision
-    int32_t hlm;                                       // 0: g2o Levenberg, 1: levMarquardtOptimizationLBAForPluker
+    int32_t hlm;                                       // 0: g2o Levenberg, 1: levMarquardtOptimizationLBAForPluker,
+                                                       // 2: levMarquardtOptimizationGBA, 3: levMarquardtOptimizationLBA
+                                                       // (2 and 3: 6-dim endpoint lines, hlm >= 2)
     int32_t hlm_lin, hlm_solves, hlm_acc;              // linearisations, solves, applied updates
     int32_t pad[2];
     double hlm_lambda0, hlm_k, hlm_homog, hlm_minerr, hlm_minchg;
     double hlm_nobs;                                   // err divisor (0 = the reference's Npt_obs+Nls_obs)
+    double hlm_nobs2;                                  // hlm 3: err divisor of the later linearisations (Npt+Nls,
+                                                       // src/mapHandler.cpp:2796); hlm 1/2: not read
     double err_prev, dx2;                              // err of the previous linearisation, ‖DX‖² of the last solve
 };
 
@@ -476,15 +480,18 @@ __global__ __launch_bounds__(kBlock) void k_linearize(Dev d) {
             double Jl6[6] = {0, 0, 0, 0, 0, 0};
             if (e < d.Ep) {
                 hlm_point(Tcur(d) + (size_t)kf * 12, Xcur(d) + (size_t)lm * 4, obs, d.cam, cc->hlm_homog, r, w, Jp, Jl);
-            } else if (cc->hlm == 2) {
+            } else if (cc->hlm >= 2) {
                 // GBA: map pose, endpoints line3D on the first linearisation, then both read from
                 // the aliased X.block(6Nkf+3Npt+3·j) (src/mapHandler.cpp:3547-3548)
+                // endpoint-line LBA (hlm 3): the same reads (:2453-2456, :2697-2700); its later
+                // linearisations hard-code the homogeneous threshold 1e-7 (:2717-2760)
                 const int j = d.ln_gidx[lm - d.n_pt];
                 const double *XLc = d.XL[cc->cur];
                 const bool first = cc->iter == 0;
                 const double *P = XLc + (first ? (size_t)j * 6 : (size_t)j * 3);
                 const double *Q = XLc + (first ? (size_t)j * 6 + 3 : (size_t)j * 3);
-                gba_line(d.T_init + (size_t)kf * 12, P, Q, obs, d.cam, cc->hlm_homog, r, w, Jp, Jl6);
+                const double hth = cc->hlm == 3 && !first ? 0.0000001 : cc->hlm_homog;
+                gba_line(d.T_init + (size_t)kf * 12, P, Q, obs, d.cam, hth, r, w, Jp, Jl6);
             } else {
                 const double *Lc = d.Lpb[cc->cur] + (size_t)(lm - d.n_pt) * 8;
                 double L[6];
@@ -503,7 +510,7 @@ __global__ __launch_bounds__(kBlock) void k_linearize(Dev d) {
             }
             c[0] = sw * r;
             c[1] = 0.0;
-            if (e >= d.Ep && cc->hlm == 2) {  // 6-dim landmark row, flat in B
+            if (e >= d.Ep && cc->hlm >= 2) {  // 6-dim landmark row, flat in B
 #pragma unroll
                 for (int k = 0; k < 6; ++k) B[k] = sw * Jl6[k];
                 B[6] = B[7] = 0.0;
@@ -719,7 +726,7 @@ __device__ __forceinline__ void landmark_reduce(const Dev &d, int lb, double &mx
             d.lm_active[l] = act ? 1 : 0;
         }
         any = d.lm_active[l] != 0;
-        if (l >= d.n_pt && d.ctrl->hlm == 2) {  // GBA line: 6x6 block (flat 6-vector rows in B)
+        if (l >= d.n_pt && d.ctrl->hlm >= 2) {  // GBA / LBA endpoint line: 6x6 block (flat 6-vector rows in B)
             double H6[21], b6[6];
 #pragma unroll
             for (int k = 0; k < 21; ++k) H6[k] = 0.0;
@@ -890,11 +897,14 @@ __device__ __forceinline__ void iter_init_ctrl(const Dev &d, double chi, double 
             }
         }
         if (c->hlm) {  // src/mapHandler.cpp:1849-1858 (first linearisation), :2108-2112 (later)
-            const double err = chi / c->hlm_nobs;  // reference: / (Npt_obs + Nls_obs) == / 0
+            // reference: / (Npt_obs + Nls_obs) == / 0; the endpoint-line LBA divides its later
+            // linearisations by the landmark counts Npt + Nls instead (src/mapHandler.cpp:2796)
+            const double err = chi / (c->hlm == 3 && c->iter > 0 ? c->hlm_nobs2 : c->hlm_nobs);
             c->hlm_lin += 1;
             if (c->iter == 0) {
                 c->maxdiag = mx;
-                // GBA keeps Hmax in an int (src/mapHandler.cpp:3386): truncated toward zero
+                // GBA keeps Hmax in an int (src/mapHandler.cpp:3386): truncated toward zero; the
+                // endpoint-line LBA in a double (:2555)
                 c->lambda = c->hlm_lambda0 * (c->hlm == 2 ? (double)(long long)mx : mx);
             } else if (fabs(err - c->err_prev) < c->hlm_minchg || err < c->hlm_minerr) {
                 if (c->ntrace < kTraceCap)
@@ -2808,7 +2818,7 @@ __device__ __forceinline__ void lm_chol(const Dev &d, int l, double lam, bool mu
 // ~32 cache lines; see k_linearize)
 __device__ __forceinline__ void edge_schur_body(const Dev &d, int e, double *Z, double *qe) {
     const int l = d.e_lm[e];
-    if (e >= d.Ep && d.ctrl->hlm == 2) {  // GBA line: 6x6 (Hl6 + λ·diag) = L Lᵀ, Z_e = L⁻¹ b_e, q_e = Z_e·L⁻¹ b_l
+    if (e >= d.Ep && d.ctrl->hlm >= 2) {  // GBA / LBA endpoint line: 6x6 (Hl6 + λ·diag) = L Lᵀ, Z_e = L⁻¹ b_e, q_e = Z_e·L⁻¹ b_l
         const double lam = d.lam;
         const int li = l - d.n_pt;
         double H[21], L6[21], g6[6], bb[6], z[6];
@@ -3297,7 +3307,7 @@ __global__ __launch_bounds__(kLmsNT) void k_lm_solve(Dev d0) {
     double chi = 0.0, sc = 0.0;
     // r = b_l − Σ_e Hpl_eᵀ x_p,  Hpl_eᵀ x_p = B_eᵀ (A_e x_p)  (edges of a fixed pose: 0)
     double u[4] = {0, 0, 0, 0}, u45[2] = {0, 0};
-    const bool gba_ln = cg->hlm == 2 && live && !is_point_lm(d, l);  // uniform across the quad
+    const bool gba_ln = cg->hlm >= 2 && live && !is_point_lm(d, l);  // uniform across the quad
     if (act && solve && !(d.diag & 4)) {
         if (gba_ln) {
 #pragma unroll
@@ -3322,7 +3332,7 @@ __global__ __launch_bounds__(kLmsNT) void k_lm_solve(Dev d0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) u[i] = quad_sum(u[i]);  // all lanes: DPP reads the whole quad
     LMS_T(lt1);
-    if (cg->hlm == 2) {
+    if (cg->hlm >= 2) {
         u45[0] = quad_sum(u45[0]);
         u45[1] = quad_sum(u45[1]);
     }

@@ -229,6 +229,8 @@ int plslam_set_hlm_solver(plslam_map *m, plslam_hlm_solve_fn fn, void *user) {
     return PLBA_OK;
 }
 
+static int hand_rolled_local_ba(plslam_map *m, plslam_hlm_stats *stats, bool endpoints);
+
 int plslam_set_hlm_params(plslam_map *m, const plba_hlm_params *p, int32_t vo_inserting_kf) {
     if (!m) return PLBA_E_INVALID;
     if (p) m->mh.hlm_params = *p;
@@ -237,10 +239,13 @@ int plslam_set_hlm_params(plslam_map *m, const plba_hlm_params *p, int32_t vo_in
     return PLBA_OK;
 }
 
-int plslam_local_ba_plucker(plslam_map *m, plslam_hlm_stats *stats) {
+int plslam_local_ba_plucker(plslam_map *m, plslam_hlm_stats *stats) { return hand_rolled_local_ba(m, stats, false); }
+int plslam_local_ba(plslam_map *m, plslam_hlm_stats *stats) { return hand_rolled_local_ba(m, stats, true); }
+
+static int hand_rolled_local_ba(plslam_map *m, plslam_hlm_stats *stats, bool endpoints) {
     if (!m) return PLBA_E_INVALID;
     HlmStats st;
-    const int rc = m->mh.localBundleAdjustmentForPluker(&st);
+    const int rc = endpoints ? m->mh.localBundleAdjustment(&st) : m->mh.localBundleAdjustmentForPluker(&st);
     if (rc) return rc;
     if (stats) {
         stats->ret = st.ret;

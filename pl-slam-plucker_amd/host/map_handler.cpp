@@ -1070,7 +1070,15 @@ Vec6 logmap_se3(const Mat4 &T) {  // src2/auxiliar.cpp:143-173
     return x;
 }
 
-int MapHandler::localBundleAdjustmentForPluker(HlmStats *stats) {
+int MapHandler::localBundleAdjustmentForPluker(HlmStats *stats) { return handRolledLocalBa(stats, false); }
+
+// MapHandler::localBundleAdjustment() (src/mapHandler.cpp:1392-1502) with
+// levMarquardtOptimizationLBA (:2334-3016): the same window lists as the Plücker function, the
+// lines as their endpoints line3D (:1464) observed as image line equations (obs_list[i], a
+// Vector3d there: the first three entries of this mirror's 4-wide NDw_obs_list rows).
+int MapHandler::localBundleAdjustment(HlmStats *stats) { return handRolledLocalBa(stats, true); }
+
+int MapHandler::handRolledLocalBa(HlmStats *stats, bool endpoints) {
     using clk = std::chrono::steady_clock;
     HlmStats st;
     const auto t0 = clk::now();
@@ -1083,8 +1091,8 @@ int MapHandler::localBundleAdjustmentForPluker(HlmStats *stats) {
     for (auto *p : map_points)
         if (p && p->local) pts.push_back(p);  // :1527-1565
     for (auto *l : map_lines)
-        if (l && l->local) {  // :1567-1607 (orthNDw is written here, a side effect)
-            l->orthNDw = MapLine::changePlukerToOrth(l->NDw);
+        if (l && l->local) {  // :1567-1607 (orthNDw is written here, a side effect); :1458-1493
+            if (!endpoints) l->orthNDw = MapLine::changePlukerToOrth(l->NDw);
             lns.push_back(l);
         }
     // observations: pt_obs_list / ls_obs_list; an observation whose KF slot is NULL is skipped by
@@ -1110,7 +1118,7 @@ int MapHandler::localBundleAdjustmentForPluker(HlmStats *stats) {
         add_kf(map_keyframes[o], true);
         return (int)kf_id.size() - 1;
     };
-    std::vector<double> pt_xyz, ept_obs, ln_orth, ln_plk, eln_obs;
+    std::vector<double> pt_xyz, ept_obs, ln_orth, ln_plk, ln_l3d, eln_obs;
     std::vector<int32_t> pt_id, ln_id, ept_lm, ept_kf, eln_lm, eln_kf;
     for (size_t i = 0; i < pts.size(); ++i) {
         MapPoint *p = pts[i];
@@ -1129,15 +1137,16 @@ int MapHandler::localBundleAdjustmentForPluker(HlmStats *stats) {
     for (size_t i = 0; i < lns.size(); ++i) {
         MapLine *l = lns[i];
         ln_id.push_back(l->idx);
-        for (int k = 0; k < 4; ++k) ln_orth.push_back(l->orthNDw[k]);
+        for (int k = 0; k < 4; ++k) ln_orth.push_back(endpoints ? 0.0 : l->orthNDw[k]);  // (not read with endpoints)
         for (int k = 0; k < 6; ++k) ln_plk.push_back(l->NDw[k]);
+        for (int k = 0; k < 6; ++k) ln_l3d.push_back(l->line3D[k]);
         for (size_t o = 0; o < l->kf_obs_list.size(); ++o) {
             ++st.n_ls_obs;
             const int kp = observer(l->kf_obs_list[o]);
             if (kp < 0) continue;
             eln_lm.push_back((int32_t)i);
             eln_kf.push_back(kp);
-            for (int k = 0; k < 4; ++k) eln_obs.push_back(l->NDw_obs_list[o][k]);
+            for (int k = 0; k < 4; ++k) eln_obs.push_back(endpoints && k == 3 ? 0.0 : l->NDw_obs_list[o][k]);
         }
     }
     st.n_kf_list = (int)kf_list.size();
@@ -1158,19 +1167,25 @@ int MapHandler::localBundleAdjustmentForPluker(HlmStats *stats) {
     g.pt_xyz = pt_xyz.data(); g.pt_id = pt_id.data(); g.ln_orth = ln_orth.data(); g.ln_id = ln_id.data();
     g.ept_lm = ept_lm.data(); g.ept_kf = ept_kf.data(); g.ept_obs = ept_obs.data(); g.ept_info = ept_info.data();
     g.eln_lm = eln_lm.data(); g.eln_kf = eln_kf.data(); g.eln_obs = eln_obs.data(); g.eln_info = eln_info.data();
-    plba_hlm_state hs{kf_x.data(), ln_plk.data(), nullptr};
-    std::vector<double> x_out(kf_x.size()), T_out(kf_Tcw.size()), xyz_out(pt_xyz.size()), orth_out(ln_orth.size());
+    plba_hlm_state hs{kf_x.data(), ln_plk.data(), endpoints ? ln_l3d.data() : nullptr};
+    std::vector<double> x_out(kf_x.size()), T_out(kf_Tcw.size()), xyz_out(pt_xyz.size()), orth_out(ln_orth.size()),
+        l3d_out(endpoints ? ln_l3d.size() : 0);
     plba_hlm_result r{};
     r.kf_x = x_out.data(); r.kf_Tcw = T_out.data(); r.pt_xyz = xyz_out.data(); r.ln_orth = orth_out.data();
+    plba_hlm_params prm = hlm_params;
+    if (endpoints) {
+        prm.variant = PLBA_HLM_LBA_ENDPOINTS;
+        r.ln_line3d = l3d_out.data();
+    }
     const auto t1 = clk::now();
     int rc;
     if (hlm_fn_) {
-        rc = hlm_fn_(hlm_user_, &g, &hs, &hlm_params, &r);
+        rc = hlm_fn_(hlm_user_, &g, &hs, &prm, &r);
         if (rc) setError("hand-rolled LM solver hook returned %d", rc);
     } else {
         rc = ensureCtx();
         if (!rc) rc = plba_upload(ctx_, &g);
-        if (!rc) rc = plba_hlm_lba(ctx_, &hs, &hlm_params, &r);
+        if (!rc) rc = plba_hlm_lba(ctx_, &hs, &prm, &r);
         if (rc) setError("plba: %s", plba_last_error(ctx_));
     }
     if (rc) return rc;
@@ -1199,7 +1214,20 @@ int MapHandler::localBundleAdjustmentForPluker(HlmStats *stats) {
             for (int k = 0; k < 3; ++k) pts[i]->point3D[k] = xyz_out[i * 3 + k];
             markLandmarkChanged(1, pts[i]->idx);
         }
-        for (size_t i = 0; i < lns.size(); ++i) {
+        for (size_t i = 0; i < lns.size() && endpoints; ++i) {  // :2868-2882: line3D = X, inlier by ‖X − line3D‖
+            double n2 = 0;
+            for (int k = 0; k < 6; ++k) {
+                const double dx = l3d_out[i * 6 + k] - lns[i]->line3D[k];
+                n2 += dx * dx;
+            }
+            if (std::sqrt(n2) > 0.01) {
+                lns[i]->inlier = false;
+                ++st.ln_outliers;
+            }
+            for (int k = 0; k < 6; ++k) lns[i]->line3D[k] = l3d_out[i * 6 + k];
+            markLandmarkChanged(2, lns[i]->idx);
+        }
+        for (size_t i = 0; i < lns.size() && !endpoints; ++i) {
             // NDw = changeOrthToPluker(DX) with DX = X − orthNDw: the reference converts the
             // difference, not the new estimate (:2190-2196) — reproduced
             Vec4 dx;
@@ -1216,7 +1244,10 @@ int MapHandler::localBundleAdjustmentForPluker(HlmStats *stats) {
             markLandmarkChanged(2, lns[i]->idx);
         }
         // "Remove bad observations" (:2200-2322) acts on observations flagged -1 in column 5,
-        // which nothing sets (:1549, 1591): no-op, as in the reference
+        // which nothing sets (:1549, 1591): no-op, as in the reference. The endpoint-line function
+        // has the same loop (:2884-3006) keyed on the same column, set to 1 by its gather (:1436,
+        // 1477) and never written by levMarquardtOptimizationLBA (:2334-2840 only read columns 0-4):
+        // a no-op there too
         st.ret = 0;
     }
     const auto t3 = clk::now();

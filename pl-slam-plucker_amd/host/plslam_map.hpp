@@ -223,6 +223,12 @@ class MapHandler {
     // hand-rolled LM LBA of the Plücker map (dead code in the reference's localMappingThread,
     // :1277, kept callable). Returns PLBA_OK (stats->ret carries the reference's 0 / -1).
     int localBundleAdjustmentForPluker(HlmStats *stats = nullptr);
+    // src/mapHandler.cpp:1392-1502 + levMarquardtOptimizationLBA (:2334-3016): the local BA of a
+    // build without USE_LINE_PLUKER — lines are their endpoints line3D, observed as image line
+    // equations (the first three entries of NDw_obs_list[i]); write-back :2841-2882 (T_kf_w =
+    // expmap_se3(X_i), point3D / line3D = X with inlier = false when they moved more than 0.01).
+    // hlm_params with the variant forced to PLBA_HLM_LBA_ENDPOINTS; stats->ret as above.
+    int localBundleAdjustment(HlmStats *stats = nullptr);
     plba_hlm_params hlm_params{1e-5, 10.0, 1e-7, 1e-7, 1e-7, 15, 0, PLBA_HLM_LBA_PLUCKER, 0};
     bool vo_inserting_kf = false;  // vo_status == VO_INSERTING_KF (:2160): nothing is written back
 
@@ -264,6 +270,8 @@ class MapHandler {
     int checkIncrementalGather(std::string *why = nullptr);
 
   private:
+    // the body of both hand-rolled local BAs: Plücker lines (orthNDw / NDw) or endpoint lines (line3D)
+    int handRolledLocalBa(HlmStats *stats, bool endpoints);
     int gatherScan(Window &w, std::vector<uint8_t> &observer);
     int gatherIncremental(Window &w, std::vector<uint8_t> &observer, int *dirty);
     int finishGather(Window &w, const std::vector<uint8_t> &observer);

@@ -144,6 +144,7 @@ class PlbaHlmParams(C.Structure):
 
 HLM_LBA_PLUCKER = 0
 HLM_GBA = 1
+HLM_LBA_ENDPOINTS = 2
 DBL_EPSILON = float(np.finfo(np.float64).eps)
 
 
@@ -157,6 +158,15 @@ class PlbaHlmResult(C.Structure):
 def gba_params(**kw) -> "PlbaHlmParams":
     """levMarquardtOptimizationGBA: the LBA defaults with ε stop tests (src/mapHandler.cpp:3664,3694)."""
     p = hlm_params(min_error=DBL_EPSILON, min_error_change=DBL_EPSILON, variant=HLM_GBA)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def lba_params(**kw) -> "PlbaHlmParams":
+    """levMarquardtOptimizationLBA (src/mapHandler.cpp:2350-2352): lambdaLbaLM, lambdaLbaK and maxItersLba
+    with the Config stop tests, the same defaults as the Plücker hand-rolled LM, on endpoint lines."""
+    p = hlm_params(variant=HLM_LBA_ENDPOINTS)
     for k, v in kw.items():
         setattr(p, k, v)
     return p

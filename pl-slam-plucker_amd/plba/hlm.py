@@ -25,7 +25,7 @@ class HlmWindow:
     graph: Graph            # kf_Tcw = inverse_se3(T_kf_w); ln_orth = changePlukerToOrth(NDw)
     kf_x: np.ndarray        # (n_kf, 6) x_kf_w
     ln_pluker: np.ndarray   # (n_ln, 6) NDw
-    ln_line3d: Optional[np.ndarray] = None   # (n_ln, 6) line3D endpoints (GBA)
+    ln_line3d: Optional[np.ndarray] = None   # (n_ln, 6) line3D endpoints (GBA, endpoint-line LBA)
 
 
 def hlm_window(g: Graph) -> HlmWindow:
@@ -41,6 +41,16 @@ def hlm_window(g: Graph) -> HlmWindow:
         L = L / np.linalg.norm(L[:, 3:], axis=1, keepdims=True)   # unit direction, |n| = distance
         h.ln_orth = np.ascontiguousarray(geo.pluker_to_orth(L))
     return HlmWindow(h, np.ascontiguousarray(x), np.ascontiguousarray(L))
+
+
+def lba_window(g: Graph) -> HlmWindow:
+    """``MapHandler::localBundleAdjustment`` (src/mapHandler.cpp:1392-1502) on a synthetic window:
+    ``gba_window``'s line inputs (endpoints ``line3D``, image-line observations) with the window's
+    own ``kf_fixed`` kept — a KF is free iff local && kf_idx != 0 (:1403), every other observer is
+    fixed (``kf_idx_loc == -1``)."""
+    w = gba_window(g)
+    w.graph.kf_fixed = np.ascontiguousarray(g.kf_fixed, np.uint8).copy()
+    return w
 
 
 def gba_window(g: Graph) -> HlmWindow:

@@ -252,7 +252,9 @@ class Solver:
         return out
 
     def hlm_lba(self, win, params=None, with_trace: bool = True) -> dict:
-        """levMarquardtOptimizationLBAForPluker (src/mapHandler.cpp:1618-2332) on the uploaded window.
+        """levMarquardtOptimizationLBAForPluker (src/mapHandler.cpp:1618-2332) on the uploaded window;
+        ``params.variant`` selects levMarquardtOptimizationGBA (capi.gba_params) or the endpoint-line
+        levMarquardtOptimizationLBA (capi.lba_params), whose lines come back as ``ln_line3d``.
 
         ``win`` is a plba.hlm.HlmWindow whose ``graph`` was uploaded with :meth:`upload`."""
         g = self.graph

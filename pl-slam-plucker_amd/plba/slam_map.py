@@ -225,7 +225,7 @@ HOST_EXPORTED = [
     "plslam_set_inlier", "plslam_set_params", "plslam_set_max_kf_idx", "plslam_kf_lines_idx_set", "plslam_kf_lines_idx_get",
     "plslam_form_local_map", "plslam_remove_bad_landmarks_pluker", "plslam_local_mapping_step", "plslam_exists",
     "plslam_set_keyframe_x", "plslam_get_keyframe_x", "plslam_set_hlm_solver", "plslam_set_hlm_params",
-    "plslam_local_ba_plucker",
+    "plslam_local_ba_plucker", "plslam_local_ba",
     "plslam_set_loop_closure", "plslam_get_lc_idx_list", "plslam_set_pgo_params", "plslam_set_pgo_solver",
     "plslam_loop_closure_optimization", "plslam_set_line_geometry", "plslam_get_line_geometry",
     "plslam_set_incremental", "plslam_mark_landmark_changed", "plslam_check_incremental_gather",
@@ -290,6 +290,7 @@ def load_host(path: Optional[str] = None):
     L.plslam_set_hlm_solver.argtypes = [vp, HLM_SOLVE_FN, vp]
     L.plslam_set_hlm_params.argtypes = [vp, C.POINTER(capi.PlbaHlmParams), C.c_int32]
     L.plslam_local_ba_plucker.argtypes = [vp, C.POINTER(PlslamHlmStats)]
+    L.plslam_local_ba.argtypes = [vp, C.POINTER(PlslamHlmStats)]
     L.plslam_set_loop_closure.argtypes = [vp, C.c_int32, ip, C.c_int32, ip, C.c_int32, dp]
     L.plslam_get_lc_idx_list.argtypes = [vp, ip, C.c_int32, ip]
     L.plslam_set_pgo_params.argtypes = [vp, C.c_int32, C.c_int32]
@@ -504,6 +505,14 @@ class HostMap:
     def local_ba_hlm(self) -> dict:
         st = PlslamHlmStats()
         self._check(self.L.plslam_local_ba_plucker(self.h, C.byref(st)), "local_ba_plucker")
+        return st.as_dict()
+
+    def local_ba_endpoints(self) -> dict:
+        """MapHandler::localBundleAdjustment() (src/mapHandler.cpp:1392-1502): the endpoint-line
+        hand-rolled LM (plslam_local_ba). Lines need ``set_line_geometry`` and image-line
+        observations (a, b, c, 0); ``ret`` is the reference's 0 / -1."""
+        st = PlslamHlmStats()
+        self._check(self.L.plslam_local_ba(self.h, C.byref(st)), "local_ba")
         return st.as_dict()
 
     # ---- loop-closure pose graph (src/mapHandler.cpp:5070-5531)
