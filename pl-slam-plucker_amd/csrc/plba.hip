@@ -5,7 +5,7 @@
 //   SparseOptimizer::initializeOptimization(level)   -> plba_initialize_optimization
 //   SparseOptimizer::optimize(n)                     -> plba_optimize
 //     OptimizationAlgorithmLevenberg::solve(it)      -> one iteration launch + trial launches
-// The numerical work is all on the device (plba_kernels.hpp); the host only reads back the
+// The numerical work is all on the device (plba_kernels.hpp and the headers it includes); the host only reads back the
 // 80-byte control block after each trial to decide whether another trial runs.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -1081,7 +1081,7 @@ void stage_state_arrays(plba_ctx *ctx, const plba_graph *g, const WindowStructur
     }
     ALLOC(d.Hll, (size_t)n_lm * 10);
     ALLOC(d.bl, (size_t)n_lm * 4);
-    // λ-dependent arrays: one copy per trial slot, back to back (slot_view, sl_* in plba_kernels.hpp)
+    // λ-dependent arrays: one copy per trial slot, back to back (slot_view, sl_* in plba_dev.hpp)
     ALLOC(d.Z, (size_t)W * E * 8);
     ALLOC(d.q, (size_t)W * E * 2);
     for (int b = 0; b < nbx; ++b) ZALLOC(d.xlb[b], (size_t)n_lm * 4);
@@ -1578,7 +1578,7 @@ int run_schedule_once(plba_ctx *ctx, const Ctrl &init, bool &dev_error) {
     Dev &d = ctx->d;
     *ctx->h_ctrl = init;
     PLBA_CHECK(hipMemcpyAsync(d.ctrl, ctx->h_ctrl, sizeof(Ctrl), hipMemcpyHostToDevice, ctx->stream));
-    if (d.n_ln > 0 && !init.hlm) {  // Plücker vectors of the current line states (read by k_linearize;
+    if (d.n_ln > 0 && !lm_hand_rolled(init.hlm)) {  // Plücker vectors of the current line states (read by k_linearize;
                                      // the hand-rolled LM starts from the map's NDw, uploaded instead)
         hipLaunchKernelGGL(k_line_pluker, dim3(blocks_for(d.n_ln)), dim3(kBlock), 0, ctx->stream, d); PLBA_LAUNCHED(ctx, "k_line_pluker");
         PLBA_CHECK(hipGetLastError());
@@ -2224,7 +2224,7 @@ int plba_hlm_lba(plba_ctx *ctx, const plba_hlm_state *st, const plba_hlm_params 
     c.max_iters[0] = prm.max_iters;
     c.stage_robust[0] = 0;
     c.stage_level[0] = 0;
-    c.hlm = lba_ep ? 3 : gba ? 2 : 1;
+    c.hlm = lba_ep ? kLmLbaEndpoints : gba ? kLmGba : kLmLbaPlucker;
     c.hlm_lambda0 = prm.lambda0;
     c.hlm_k = prm.lambda_k;
     c.hlm_homog = prm.homog_th;

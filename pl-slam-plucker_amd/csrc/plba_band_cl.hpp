@@ -26,6 +26,12 @@
 // lane-local 6x6 LDLᵀ of each pivot block are exactly LDLᵀ pivots of the system, so a zero one
 // fails the solve the same way.
 
+#pragma once
+
+#include "plba_band.hpp"
+
+namespace plba {
+
 constexpr int kClNT = 512;     // 1 critical wave + 7 worker waves (2 waves per SIMD)
 constexpr int kClMaxBW = 9;    // 6(bw+1) column lanes + 1 rhs lane must fit one wave
 constexpr int kClPD = 4;       // worker prefetch distance in steps (= unroll factor of the step loop)
@@ -38,7 +44,7 @@ __host__ __device__ constexpr size_t cl_lds_doubles(int bw) {
            2 * ((size_t)(bw + 1) * 36 + 6);
 }
 
-// (rcp_nr1, ltri, ldl6_inplace, ldl6_solve: plba_kernels.hpp, shared with the register-window band kernel)
+// (rcp_nr1, ltri, ldl6_inplace, ldl6_solve: plba_band.hpp, shared with the register-window band kernel)
 
 // Eliminates block rows k0..k1-1 of an nrows-row band (g.nrows). The LDS window (row i in slot
 // i mod (bw+2), block (i, i-w) row-major) is loaded for rows k0..k0+bw+1 when load_window is
@@ -458,3 +464,5 @@ __global__ __launch_bounds__(kClNT) void k_rcs_factor_twisted_cl(Dev d0) {
         pose_update_wg<kClNT>(d, s_fail != 0);  // applied even after a failed solve, with the previous x_p (A13)
     }
 }
+
+}  // namespace plba

@@ -50,6 +50,12 @@
 // selects BCR only when the N workgroups fit the device at once (occupancy x CUs), since a
 // partly serialised launch loses the log-depth chain it is chosen for.
 
+#pragma once
+
+#include "plba_band.hpp"  // rcp_nr
+
+namespace plba {
+
 constexpr int kBcrNT = 512;
 constexpr int kBcrMaxBW = 9;
 constexpr int kBcrMaxRows = 240;   // co-residency margin below the 256 CUs
@@ -613,7 +619,7 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
                 }
                 ps[t] = v;
             }
-            const bool hlm0 = d.ctrl->hlm != 0;
+            const bool hlm0 = lm_hand_rolled(d.ctrl->hlm);
             for (int k = m + N * tid; k < d.n_kf; k += N * NT)
                 if (d.kf_hidx[k] < 0) {
 #pragma unroll
@@ -757,7 +763,7 @@ __global__ __launch_bounds__(kBcrBackNT) void k_rcs_bcr_back(Dev d0) {
             ps[t] = v;
         }
         if (tid == 0) ps[BW * 24] = d.lam;
-        const bool hlm0 = d.ctrl->hlm != 0;
+        const bool hlm0 = lm_hand_rolled(d.ctrl->hlm);
         for (int k = m + N * tid; k < d.n_kf; k += N * NT)
             if (d.kf_hidx[k] < 0) {
 #pragma unroll
@@ -816,7 +822,7 @@ __global__ __launch_bounds__(kBcrBackNT) void k_rcs_bcr_back(Dev d0) {
                 if (!failed)
 #pragma unroll
                     for (int q = 0; q < 6; ++q) d.xp[6 * h + q] = x[q];
-                if (d.ctrl->hlm) {  // hand-rolled LM: se(3) update, ‖DX‖² part
+                if (lm_hand_rolled(d.ctrl->hlm)) {  // hand-rolled LM: se(3) update, ‖DX‖² part
                     const int kf = s_kf[tid];
                     double xn[6];
 #pragma unroll
@@ -846,3 +852,5 @@ __global__ __launch_bounds__(kBcrBackNT) void k_rcs_bcr_back(Dev d0) {
         }
     }
 }
+
+}  // namespace plba

@@ -23,6 +23,248 @@
 // B lane l -> B[k=l>>4][l&15]; C/D (f64 form) reg i -> row (l>>4)+4i, col l&15.
 #pragma once
 
+#include "plba_rcs.hpp"
+
+namespace plba {
+
+constexpr int kFacThreads = 1024;
+constexpr int kSolveLdsN = 6144;  // y held in (dynamic) LDS up to this n (48 KiB), in Wbuf beyond
+constexpr int kSolveTilesLds = 256;  // tile_first staged in LDS for the first 256 tiles
+// PLBA_DIAG bit 8 (diagnostics only): phase timestamps of the dense solve (slots 12-15)
+#define SOLVE_STAMP(slot)                                                                         \
+    do {                                                                                         \
+        if ((d.diag & 8) && d.bcr_stamps && blockIdx.x == 0 && threadIdx.x == 0)                 \
+            d.bcr_stamps[slot] = __builtin_amdgcn_s_memrealtime();                              \
+    } while (0)
+// ---- solve L D Lᵀ x = b_s through the envelope-aware dense factor in Ad (unit L below the
+// diagonal, D on it), tile by tile; one workgroup of kFacThreads. x -> xp.
+// Forward: wave 0 solves the diagonal tile (its row of L in registers, y_j broadcast by
+// readlane) while the other waves prefetch their rows' coefficients of the tile's columns
+// (independent of y); then those rows are updated. Backward: 32 partial column sums per tile
+// (lanes along rows), then wave 0 adds them and solves the tile. y lives in LDS (LY).
+// y of the dense path's fused forward substitution: behind the W panel in Wbuf
+__device__ __forceinline__ double *dense_yd(const Dev &d) { return d.Wbuf + (size_t)kTile * d.n; }
+
+// FWD: y = L⁻¹b already in dense_yd (the MFMA factorisation did the forward substitution)
+template <bool LY, bool FWD = false>
+__device__ __forceinline__ void dense_solve_wg(const Dev &d) {
+    extern __shared__ double y_lds[];
+    __shared__ double red[kFacThreads / kTile][kTile + 1];
+    __shared__ int tfs[kSolveTilesLds];  // tile_first in LDS (the envelope tests of every row)
+    const int tid = threadIdx.x;
+    const int n = d.n;
+    const int nt = d.ntiles;
+    const double *Ad = d.Ad;
+    double *y = LY ? y_lds : d.Wbuf;
+    const double *y0 = FWD ? dense_yd(d) : d.bs;
+    for (int i = tid; i < n; i += kFacThreads) y[i] = y0[i];
+    for (int t = tid; t < kSolveTilesLds; t += kFacThreads) tfs[t] = t < nt ? d.tile_first[t] : 0;
+    auto tile_first = [&](int t) { return t < kSolveTilesLds ? tfs[t] : d.tile_first[t]; };
+    __syncthreads();
+    constexpr int kRowThreads = kFacThreads - 64;
+    for (int K = 0; K < (FWD ? 0 : nt); ++K) {
+        const int k0 = K * kTile, kb = min(kTile, n - k0);
+        const int fend = min(n, (d.tile_last[K] + 1) * kTile);
+        const int i1 = k0 + kb + tid - 64;  // this thread's first row of the update
+        double cf[kTile];
+        if (K == 5) SOLVE_STAMP(16);
+        if (tid < 64) {
+            double yi = (tid < kb) ? y[k0 + tid] : 0.0;
+            // loads at clamped (always valid) addresses, selected after: no per-element branches
+            const double *row = Ad + (size_t)(k0 + min(tid, kb - 1)) + (size_t)k0 * n;
+            double l[kTile];
+#pragma unroll
+            for (int j = 0; j < kTile; ++j) l[j] = row[(size_t)min(j, kb - 1) * n];
+#pragma unroll
+            for (int j = 0; j < kTile; ++j) {
+                const double yj = readlane_f64(yi, j);
+                if (tid > j && tid < kb) yi -= l[j] * yj;
+            }
+            if (tid < kb) y[k0 + tid] = yi;
+            if (K == 5) SOLVE_STAMP(17);
+        } else {
+            const double *row = Ad + (size_t)min(i1, n - 1) + (size_t)k0 * n;
+#pragma unroll
+            for (int p = 0; p < kTile; ++p) cf[p] = row[(size_t)min(p, kb - 1) * n];
+        }
+        __syncthreads();
+        if (K == 5) SOLVE_STAMP(18);
+        if (tid >= 64) {
+            if (i1 < fend && tile_first(i1 / kTile) <= K) {
+                double s = 0.0;
+#pragma unroll
+                for (int p = 0; p < kTile; ++p)
+                    if (p < kb) s += cf[p] * y[k0 + p];
+                y[i1] -= s;
+            }
+            for (int i = i1 + kRowThreads; i < fend; i += kRowThreads) {  // n > ~kFacThreads only
+                if (tile_first(i / kTile) > K) continue;
+                double s = 0.0;
+                for (int p = 0; p < kb; ++p) s += Ad[(size_t)i + (size_t)(k0 + p) * n] * y[k0 + p];
+                y[i] -= s;
+            }
+        }
+        __syncthreads();
+        if (K == 5) SOLVE_STAMP(19);
+    }
+    for (int i = tid; i < n; i += kFacThreads) y[i] = y[i] / Ad[(size_t)i + (size_t)i * n];
+    __syncthreads();
+    SOLVE_STAMP(13);
+    // backward: Lᵀ x = y, tile by tile from the bottom
+    for (int K = nt - 1; K >= 0; --K) {
+        const int k0 = K * kTile, kb = min(kTile, n - k0);
+        // y_K -= Σ_{i > tile} L[i][k] y[i]   (column k of L below the tile): 32 partial sums per
+        // column (rows i ≡ part mod 32), added in part order; part runs along the lanes so a
+        // wave reads two columns, 32 consecutive rows each
+        const int bend = min(n, (d.tile_last[K] + 1) * kTile);
+        {
+            // one tile of rows per step (the stride is kTile rows): U tiles' loads in flight at
+            // once, clamped valid addresses, masked after; summed in row order
+            static_assert(kFacThreads / kTile == kTile, "one row of each tile per partial");
+            constexpr int U = 8;
+            const int part = tid % kTile, c = tid / kTile;
+            double s = 0.0;
+            if (c < kb) {
+                const double *colp = Ad + (size_t)(k0 + c) * n;
+                for (int m0 = K + 1; m0 * kTile < bend; m0 += U) {
+                    double v[U], yy[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const int i = (m0 + u) * kTile + part;
+                        const bool ok = i < bend && tile_first(min(m0 + u, nt - 1)) <= K;
+                        const int ic = min(i, n - 1);
+                        v[u] = colp[ic];
+                        yy[u] = ok ? y[ic] : 0.0;
+                        v[u] = ok ? v[u] : 0.0;
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) s += v[u] * yy[u];
+                }
+            }
+            red[part][c] = s;
+        }
+        double l[kTile];
+        if (tid < 64) {  // column of L of the diagonal tile in registers
+            const double *col = Ad + (size_t)k0 + (size_t)(k0 + min(tid, kb - 1)) * n;
+#pragma unroll
+            for (int j = 0; j < kTile; ++j) l[j] = col[min(j, kb - 1)];
+        }
+        __syncthreads();
+        if (tid < 64) {
+            double yi = 0.0;
+            if (tid < kb) {
+                double s = 0.0;
+                for (int p = 0; p < kFacThreads / kTile; ++p) s += red[p][tid];
+                yi = y[k0 + tid] - s;
+            }
+#pragma unroll
+            for (int j = kTile - 1; j >= 0; --j) {
+                const double yj = readlane_f64(yi, j);
+                if (tid < j && j < kb) yi -= l[j] * yj;
+            }
+            if (tid < kb) y[k0 + tid] = yi;
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < n; i += kFacThreads) d.xp[i] = y[i];
+}
+
+// Envelope-aware tiled LDLᵀ of the lower triangle + solve, one workgroup of 1024 threads.
+// Semantics of Eigen::SimplicialLDLT as used by LinearSolverEigen: fails iff a pivot is 0.
+__global__ __launch_bounds__(kFacThreads) void k_rcs_factor(Dev d0) {
+    TRIAL_SLOT(0)
+    __shared__ double T[kTile][kTile + 1];
+    __shared__ double Dk[kTile];
+    __shared__ int s_fail;
+    const int tid = threadIdx.x;
+    const int n = d.n;
+    double *Ad = d.Ad;
+    if (tid == 0) s_fail = 0;
+    const int nt = d.ntiles;
+    for (int K = 0; K < nt; ++K) {
+        const int k0 = K * kTile;
+        const int kb = min(kTile, n - k0);
+        __syncthreads();
+        {   // load diagonal tile
+            const int r = tid >> 5, c = tid & 31;
+            if (r < kb && c <= r) T[r][c] = Ad[(size_t)(k0 + r) + (size_t)(k0 + c) * n];
+        }
+        __syncthreads();
+        for (int j = 0; j < kb; ++j) {
+            const int r = tid >> 5, c = tid & 31;
+            const double djj = T[j][j];
+            if (djj == 0.0) {
+                if (tid == 0) s_fail = 1;
+            } else if (r > j && c > j && c <= r && r < kb) {
+                T[r][c] -= (T[r][j] / djj) * T[c][j];
+            }
+            __syncthreads();
+        }
+        if (s_fail) break;
+        {   // L = T / D, store to global
+            const int r = tid >> 5, c = tid & 31;
+            if (r < kb && c < r) {
+                const double l = T[r][c] / T[c][c];
+                Ad[(size_t)(k0 + r) + (size_t)(k0 + c) * n] = l;
+            }
+            if (tid < kb) {
+                Dk[tid] = T[tid][tid];
+                Ad[(size_t)(k0 + tid) + (size_t)(k0 + tid) * n] = T[tid][tid];
+            }
+        }
+        __syncthreads();
+        {   // convert T strict lower to L (in LDS)
+            const int r = tid >> 5, c = tid & 31;
+            double l = 0.0;
+            if (r < kb && c < r) l = T[r][c] / Dk[c];
+            __syncthreads();
+            if (r < kb && c < r) T[r][c] = l;
+        }
+        __syncthreads();
+        // panel rows: i >= k0+kb with tile_first[tile(i)] <= K
+        const int rows0 = k0 + kb;
+        const int rows_end = min(n, (d.tile_last[K] + 1) * kTile);
+        for (int i = rows0 + tid; i < rows_end; i += kFacThreads) {
+            if (d.tile_first[i / kTile] > K) continue;
+            double *w = d.Wbuf + (size_t)i * kTile;   // W = L·D for this row (re-read by the update)
+            for (int c = 0; c < kb; ++c) {
+                double a = Ad[(size_t)i + (size_t)(k0 + c) * n];
+                for (int p = 0; p < c; ++p) a -= w[p] * T[c][p];
+                w[c] = a;
+                Ad[(size_t)i + (size_t)(k0 + c) * n] = a / Dk[c];
+            }
+        }
+        __syncthreads();
+        // trailing update: A[i][j] -= Σ_c W[i][c] L[j][c], for rows/cols in the panel, j <= i
+        const int m = n - rows0;
+        if (m > 0) {
+            // iterate over trailing tiles (I, J) with K < J <= I, both in the envelope of K
+            for (int I = K + 1; I <= d.tile_last[K]; ++I) {
+                if (d.tile_first[I] > K) continue;
+                for (int J = K + 1; J <= I; ++J) {
+                    if (d.tile_first[J] > K) continue;
+                    const int r = tid >> 5, c = tid & 31;
+                    const int i = I * kTile + r, j = J * kTile + c;
+                    if (i < n && j < n && j <= i) {
+                        double s = 0.0;
+                        for (int p = 0; p < kb; ++p)
+                            s += d.Wbuf[(size_t)i * kTile + p] * Ad[(size_t)j + (size_t)(k0 + p) * n];
+                        Ad[(size_t)i + (size_t)j * n] -= s;
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) *d.solve_okp = s_fail ? 0 : 1;
+    if (!s_fail) {  // on failure x_p keeps its previous value (g2o leaves _x untouched)
+        if (n <= d.solve_lds_n) dense_solve_wg<true>(d);
+        else dense_solve_wg<false>(d);
+    }
+    __syncthreads();
+    pose_update_wg<kFacThreads>(d, s_fail != 0);  // the update is applied even after a failed solve (A13)
+}
+
 constexpr int kDT = 32;            // tile
 constexpr int kDensePanelNT = 64;  // one wave: two row tiles per workgroup
 // PLBA_DIAG bit 8 (diagnostics only): phase timestamps of panel / update K = 5, workgroup 0
@@ -235,3 +477,5 @@ __global__ __launch_bounds__(kFacThreads) void k_dense_solve(Dev d0) {
     pose_update_wg<kFacThreads>(d, !ok);  // applied even after a failed solve, with the previous x_p (A13)
     SOLVE_STAMP(15);
 }
+
+}  // namespace plba

@@ -20,6 +20,10 @@
 // like the oracle (oracle/refpgo.cpp), so the two agree to rounding in the solve.
 #pragma once
 
+#include "plba_dense.hpp"
+
+namespace plba {
+
 struct PgoDev {
     int32_t nv, ne, nact, nfree, n, nblk;
     const int32_t *e_v;               // [ne][2] vertex positions
@@ -388,3 +392,5 @@ __global__ void k_pgo_maxdiag(PgoDev p) {
     for (int k = 0; k < p.n; ++k) m = fmax(m, fabs(p.Hd[(size_t)k + (size_t)k * p.n]));
     p.out[2] = m;
 }
+
+}  // namespace plba

@@ -79,7 +79,8 @@ inline Tuning read_tuning() {
     return t;
 }
 
-// ---- dynamic LDS of the banded factorisation kernels
+// ---- dynamic LDS of the banded factorisation kernels (the element counts: plba_band.hpp,
+// plba_band_cl.hpp, plba_bcr.hpp)
 inline int band_ring(int bw, int nf) {
     const size_t budget = 158 * 1024 - band_static_bytes(bw), base = sizeof(double) * band_lds_doubles(bw, 0);
     const size_t per = sizeof(double) * ((size_t)bw * 36 + 36 + 6);
@@ -103,9 +104,9 @@ constexpr size_t kLdsLimit = 159 * 1024;
 
 // ---- the factorisation of one window
 enum FactorMode : int {
-    kDenseScalar,  // single-workgroup scalar LDLᵀ (k_rcs_factor)
+    kDenseScalar,  // single-workgroup scalar LDLᵀ (k_rcs_factor, plba_dense.hpp)
     kDenseMfma,    // blocked LDLᵀ with MFMA trailing updates (plba_dense.hpp)
-    kBand,         // LDS-window band kernel, one sweep
+    kBand,         // LDS-window band kernel (plba_band.hpp), one sweep
     kBandTw,       // the same from both ends
     kCl,           // column-lane (plba_band_cl.hpp), bw <= kClMaxBW
     kClTw,         // column-lane from both ends
