@@ -300,6 +300,79 @@ void plba_pgo_default_params(plba_pgo_params *p);
  * assembly, multi-workgroup LDLᵀ with MFMA trailing updates, one host decision per trial). */
 int plba_pgo_optimize(plba_ctx *ctx, const plba_pgo_graph *g, const plba_pgo_params *p, plba_pgo_result *res);
 
+/* ---- Loop-closure relative pose, the verification step between place recognition and the pose graph:
+ *   bool MapHandler::computeRelativePoseRobustGN(lc_points, lc_lines, lc_pt_idx, lc_ls_idx, pose_inc)
+ *                                                           (src/mapHandler.cpp:4677-5068)
+ *   bool MapHandler::computeRelativePoseGN(...)             (src/mapHandler.cpp:4413-4675)
+ * called by isLoopClosure (:4303-4411) with the descriptor matches of the two keyframes. A robust
+ * pose-only Gauss–Newton: the 3-D points P and line endpoints sP, eP of the old keyframe kf0 are
+ * moved by T_inc and projected into the new keyframe kf1, against its pixel pl and its normalised
+ * image line le. One scalar residual r = ‖e‖ per match with the Cauchy weight w = 1/(1+r²),
+ * H += w·JJᵀ, g += w·J·r, e += w·r², e /= active matches; x = H⁻¹g by ColPivHouseholderQR;
+ * T_inc ← T_inc·inverse_se3(expmap_se3(x)). At most max_iters_first passes, then every active
+ * match with ‖e‖ > sqrt(7.815) becomes an outlier, then (RobustGN) at most max_iters refinement
+ * passes on the inliers, err_prev carried over. Stop tests: |e − err_prev| < ε, e < ε (before the
+ * solve), ‖x‖ < ε (after the update), ε = numeric_limits<double>::epsilon().
+ * The accept test: e < lc_res, the largest eigenvalue of H⁻¹ < lc_unc, inliers / matches > lc_inl
+ * (forced true in RobustGN, :5014), ‖x_inc[0:3]‖ < lc_trs, ‖x_inc[3:6]‖·180/π < lc_rot, with
+ * x_inc = logmap_se3(T_inc). pose_inc is what loopClosure() pushes onto lc_pose_list (:4080-4081).
+ * Kept from the reference: the Jacobian rows use fx for both image directions (:4719); the step of
+ * this left-perturbation Jacobian is applied on the right (:4815).
+ * Defined where the reference is not: a candidate with no active match (none given, or none left by
+ * the outlier pass; the reference divides by zero) has accepted = 0, its T_inc is left as it was
+ * and its other numbers are unspecified; a singular H has unc = +inf and accepted = 0 (the
+ * reference's H.inverse() is inf / NaN there). Neither disturbs the rest of the batch.
+ * A call verifies a batch of candidate pairs in one kernel launch, one workgroup per candidate. */
+typedef struct plba_lcpose_batch {      /* K candidate pairs, concatenated */
+    int32_t n;                          /* candidates                                        */
+    const int32_t *pt_off, *ln_off;     /* [n+1] feature ranges                              */
+    const double *pt_P;                 /* [pt_off[n]][3] stereo_pt[i1]->P of kf0 (:4341)    */
+    const double *pt_obs;               /* [pt_off[n]][2] stereo_pt[i2]->pl of kf1 (:4342)   */
+    const double *ln_sP, *ln_eP;        /* [ln_off[n]][3] (:4367-4368)                       */
+    const double *ln_le;                /* [ln_off[n]][3] le of kf1 (:4369)                  */
+    double fx, fy, cx, cy;
+} plba_lcpose_batch;
+
+/* plba_lcpose_params.variant */
+#define PLBA_LCPOSE_ROBUST_GN 0         /* computeRelativePoseRobustGN (what isLoopClosure calls)   */
+#define PLBA_LCPOSE_GN        1         /* computeRelativePoseGN: no refinement, lc_inl tested,
+                                           pose_inc = logmap(inverse(T_inc)) (:4669)                */
+
+typedef struct plba_lcpose_params {
+    double  homog_th;          /* Config::homogTh()      1e-7 (src2/config.cpp:80)                  */
+    double  lc_res;            /* SlamConfig::lcRes()    1.0  (src/slamConfig.cpp:73-77)            */
+    double  lc_unc;            /* SlamConfig::lcUnc()    0.01                                       */
+    double  lc_inl;            /* SlamConfig::lcInl()    0.3                                        */
+    double  lc_trs;            /* SlamConfig::lcTrs()    1.5                                        */
+    double  lc_rot;            /* SlamConfig::lcRot()    35                                         */
+    int32_t max_iters_first;   /* SlamConfig::maxIters()    5 (src2/config.cpp:82-83)               */
+    int32_t max_iters;         /* SlamConfig::maxItersRef() 10                                      */
+    int32_t variant;           /* PLBA_LCPOSE_ROBUST_GN or PLBA_LCPOSE_GN                           */
+    int32_t pad;
+} plba_lcpose_params;
+
+typedef struct plba_lcpose_out {
+    int32_t accepted;          /* the reference's return value                                      */
+    int32_t conditions;        /* bit 0 res, 1 unc, 2 inl, 3 trs, 4 rot                             */
+    int32_t iters_first;       /* passes (H / g builds) of the first loop                           */
+    int32_t iters_ref;         /* passes of the refinement loop (0 in PLBA_LCPOSE_GN)               */
+    int32_t n_inl_pt, n_inl_ln;/* matches still active after the outlier pass                       */
+    double  e, unc, t, r_deg;  /* the four tested figures (e: last pass)                            */
+    double  x_inc[6];          /* logmap_se3(T_inc), [t; ω]                                         */
+    double  pose_inc[6];       /* RobustGN: logmap(inverse(expmap(x_inc))) (:5062)                  */
+    double  T_inc[12];         /* row-major 3x4                                                     */
+    double  H[36];             /* last pass, row-major                                              */
+} plba_lcpose_out;
+
+void plba_lcpose_default_params(plba_lcpose_params *p);
+/* Runs on the context's stream; needs no uploaded window and leaves one intact; its device buffers
+ * are kept and reused across calls. out: [n]. pt_inlier [pt_off[n]] / ln_inlier [ln_off[n]] receive
+ * the inlier flags (each may be NULL). p == NULL: the defaults. PLBA_E_INVALID for a NULL batch /
+ * out / array, n < 0, decreasing (or negative) offsets, negative iteration caps or an unknown
+ * variant; n == 0 does nothing and returns PLBA_OK. */
+int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *p,
+                          plba_lcpose_out *out, uint8_t *pt_inlier, uint8_t *ln_inlier);
+
 /* ---- Sharded windows: one context per GPU, one window split over nranks.
  * Landmarks (with all their edges) are partitioned by the keyframe range of their first
  * observation (kf_obs_list[0], the base KF of map_points_kf_idx); poses are replicated.

@@ -160,7 +160,9 @@ int plslam_get_line(plslam_map *m, int32_t idx, double NDw[6], int32_t *inlier, 
  * their landmarks (point3D, med_obs_dir, dir_list; line3D, med_obs_dir, dir_list) and every
  * later KF corrected, lc_idx_list[.][2] = 0, lc_state = LC_IDLE. loopClosureFuseLandmarks()
  * (:5533, descriptor matching) is the caller's. lc_idxs / lc_idx_list: [n][3] int, lc_pose_list:
- * [n][6] ([t; ω], include/mapHandler.h:186-187). */
+ * [n][6] ([t; ω], include/mapHandler.h:186-187). The lists are filled by plslam_loop_closure_step
+ * below (the relative pose of each accepted loop comes from plba_lc_relative_pose);
+ * plslam_set_loop_closure sets them directly, for a caller that keeps its own verification. */
 int plslam_set_loop_closure(plslam_map *m, int32_t n_lc_idxs, const int32_t *lc_idxs, int32_t n_lc_idx_list,
                             const int32_t *lc_idx_list, int32_t n_lc_pose_list, const double *lc_pose_list);
 int plslam_get_lc_idx_list(plslam_map *m, int32_t *out, int32_t cap, int32_t *n);
@@ -174,6 +176,45 @@ typedef struct plslam_pgo_stats {
     double  chi2_initial, chi2_final, solve_ms;
 } plslam_pgo_stats;
 int plslam_loop_closure_optimization(plslam_map *m, int32_t ess, plslam_pgo_stats *stats);
+/* ---- MapHandler::loopClosure() (src/mapHandler.cpp:4053-4116) after lookForLoopCandidates (DBoW2)
+ * and the descriptor matching of isLoopClosure (:4327-4380), which stay the caller's: the
+ * inlier-ratio gate (:4384-4409; a zero feature count makes the ratio NaN or 0, so false),
+ * computeRelativePoseRobustGN (:4677-5068) through plba_lc_relative_pose or the hook, and the state
+ * machine. An accepted loop extends lc_poses, lc_pose_list (pose_inc), lc_idxs, lc_idx_list
+ * ((kf_prev_idx, kf_curr_idx, 1)) and lc_pt_idxs / lc_ls_idxs (the index rows of the inliers, which
+ * the landmark fusion needs) and turns LC_IDLE into LC_ACTIVE; anything else turns LC_ACTIVE into
+ * LC_READY. On LC_READY loopClosureOptimizationCovGraphG2O runs (as plslam_loop_closure_optimization
+ * with ess = 0) and the state returns to LC_IDLE (:4109-4115). */
+typedef struct plslam_lc_candidate {
+    int32_t kf_prev_idx, kf_curr_idx;
+    int32_t n_pt_0, n_pt_1, n_ls_0, n_ls_1; /* stereo_pt / stereo_ls sizes of kf0 and kf1 (:4313-4316) */
+    int32_t has_points, has_lines;          /* SlamConfig::hasPoints() / hasLines()                    */
+    int32_t n_pt, n_ln;                     /* matches; then as in plba_lcpose_batch for one candidate */
+    const double *pt_P, *pt_obs, *ln_sP, *ln_eP, *ln_le;
+    const int32_t *pt_idx, *ls_idx;         /* [n][4] lc_pt_idx / lc_ls_idx rows (:4346-4351); may be NULL */
+} plslam_lc_candidate;
+typedef struct plslam_lc_stats {
+    int32_t is_candidate, ratio_ok;         /* a candidate was given / it passed the inlier-ratio gate */
+    int32_t accepted, conditions;           /* plba_lcpose_out of the candidate (0 when not solved)    */
+    int32_t n_inl_pt, n_inl_ln;
+    int32_t state_before, state_after;      /* lc_state: 0 LC_IDLE, 1 LC_ACTIVE, 2 LC_READY            */
+    int32_t pgo_ran, pad;
+    double  inl_ratio_pt, inl_ratio_ls, e, unc, t, r_deg, pose_ms;
+    plslam_pgo_stats pgo;                   /* of the pose graph, when it ran                          */
+} plslam_lc_stats;
+typedef int (*plslam_lcpose_solve_fn)(void *user, const plba_lcpose_batch *b, const plba_lcpose_params *p,
+                                      plba_lcpose_out *out, uint8_t *pt_inlier, uint8_t *ln_inlier);
+int plslam_set_lcpose_solver(plslam_map *m, plslam_lcpose_solve_fn fn, void *user); /* NULL = plba_lc_relative_pose */
+int plslam_set_lcpose_params(plslam_map *m, const plba_lcpose_params *p);           /* NULL = the defaults          */
+/* c == NULL: lookForLoopCandidates found none. lc_inlier_ratio: SlamConfig::lcInlierRatio(), 30
+ * (src/slamConfig.cpp:83). */
+int plslam_loop_closure_step(plslam_map *m, const plslam_lc_candidate *c, double lc_inlier_ratio,
+                             plslam_lc_stats *st);
+int plslam_get_lc_state(plslam_map *m, int32_t *state);
+/* lc_pose_list [n][6]; the kept index rows of loop `loop` (kind 1 points, 2 lines), [n][4] */
+int plslam_get_lc_pose_list(plslam_map *m, double *out, int32_t cap, int32_t *n);
+int plslam_get_lc_feature_idxs(plslam_map *m, int32_t kind, int32_t loop, int32_t *out, int32_t cap, int32_t *n);
+
 /* MapLine::line3D / med_obs_dir (include/mapFeatures.h:93-94; never set in Plücker mode) */
 int plslam_set_line_geometry(plslam_map *m, int32_t idx, const double line3D[6], const double med_obs_dir[3]);
 int plslam_get_line_geometry(plslam_map *m, int32_t idx, double line3D[6], double med_obs_dir[3]);

@@ -28,6 +28,7 @@
 #include "../../include/plba.h"
 #include "plba_build.hpp"
 #include "plba_kernels.hpp"
+#include "plba_lcpose.hpp"
 #include "plba_plan.hpp"
 
 namespace plba {
@@ -146,6 +147,10 @@ struct plba_ctx {
     char *pgo_mem = nullptr;
     size_t pgo_cap = 0;
     double *pgo_hout = nullptr;  // pinned [4]
+    // loop-closure relative pose (plba_lc_relative_pose): a grow-only device block and its pinned
+    // host image (inputs up, results and inlier flags down), kept across calls
+    char *lc_mem = nullptr, *lc_host = nullptr;
+    size_t lc_cap = 0, lc_host_cap = 0;
 
     void set_error(const char *fmt, ...) {
         char buf[512];
@@ -1972,6 +1977,8 @@ int plba_destroy(plba_ctx *ctx) {
     ctx->bmemB.release(ctx->stream);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->pgo_hout) (void)hipHostFree(ctx->pgo_hout);
+    if (ctx->lc_mem) (void)hipFreeAsync(ctx->lc_mem, ctx->stream);
+    if (ctx->lc_host) (void)hipHostFree(ctx->lc_host);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
     if (ctx->comm.hbuf) (void)hipHostFree(ctx->comm.hbuf);
     if (ctx->comm.nccl) (void)ncclCommDestroy(ctx->comm.nccl);
@@ -2833,6 +2840,129 @@ int plba_pgo_optimize(plba_ctx *ctx, const plba_pgo_graph *g, const plba_pgo_par
         PLBA_CHECK(hipStreamSynchronize(s));
     }
     res->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- loop-closure relative pose
+// MapHandler::computeRelativePoseRobustGN / computeRelativePoseGN (src/mapHandler.cpp:4677-5068,
+// :4413-4675) for a batch of candidate pairs: one upload, one launch of k_lcpose
+// (csrc/plba_lcpose.hpp, one workgroup per candidate), one read-back.
+void plba_lcpose_default_params(plba_lcpose_params *p) {
+    if (!p) return;
+    p->homog_th = 1e-7;       // src2/config.cpp:80
+    p->lc_res = 1.0;          // src/slamConfig.cpp:73-77
+    p->lc_unc = 0.01;
+    p->lc_inl = 0.3;
+    p->lc_trs = 1.5;
+    p->lc_rot = 35.0;
+    p->max_iters_first = 5;   // src2/config.cpp:82
+    p->max_iters = 10;        // src2/config.cpp:83
+    p->variant = PLBA_LCPOSE_ROBUST_GN;
+    p->pad = 0;
+}
+
+int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
+                          uint8_t *pt_inlier, uint8_t *ln_inlier) {
+    if (!ctx) return PLBA_E_INVALID;
+    if (!b || b->n < 0) {
+        ctx->set_error("relative pose: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    const int n = b->n;
+    if (n == 0) return PLBA_OK;
+    plba_lcpose_params prm;
+    if (pp) prm = *pp;
+    else plba_lcpose_default_params(&prm);
+    if (!out || !b->pt_off || !b->ln_off) {
+        ctx->set_error("relative pose: NULL out / pt_off / ln_off");
+        return PLBA_E_INVALID;
+    }
+    if ((prm.variant != PLBA_LCPOSE_ROBUST_GN && prm.variant != PLBA_LCPOSE_GN) || prm.max_iters_first < 0 ||
+        prm.max_iters < 0) {
+        ctx->set_error("relative pose: unknown variant %d or a negative iteration cap", prm.variant);
+        return PLBA_E_INVALID;
+    }
+    for (const int32_t *off : {b->pt_off, b->ln_off}) {
+        if (off[0] < 0) {
+            ctx->set_error("relative pose: negative feature offset");
+            return PLBA_E_INVALID;
+        }
+        for (int c = 0; c < n; ++c)
+            if (off[c + 1] < off[c]) {
+                ctx->set_error("relative pose: feature offsets decrease at candidate %d", c);
+                return PLBA_E_INVALID;
+            }
+    }
+    const size_t np = (size_t)b->pt_off[n], nl = (size_t)b->ln_off[n];
+    if ((np && (!b->pt_P || !b->pt_obs)) || (nl && (!b->ln_sP || !b->ln_eP || !b->ln_le))) {
+        ctx->set_error("relative pose: NULL feature array");
+        return PLBA_E_INVALID;
+    }
+    (void)hipSetDevice(ctx->opts.device);
+    // one block, the same layout on the device and in pinned host memory:
+    //   inputs  pt_off | ln_off | pt_P | pt_obs | ln_sP | ln_eP | ln_le      (host -> device)
+    //   outputs out[n] | pt flags | ln flags                                  (device -> host)
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_ptoff = 0, o_lnoff = o_ptoff + al(sizeof(int32_t) * (n + 1)), o_P = o_lnoff + al(sizeof(int32_t) * (n + 1)),
+                 o_obs = o_P + al(sizeof(double) * 3 * np), o_sP = o_obs + al(sizeof(double) * 2 * np),
+                 o_eP = o_sP + al(sizeof(double) * 3 * nl), o_le = o_eP + al(sizeof(double) * 3 * nl),
+                 o_out = o_le + al(sizeof(double) * 3 * nl), o_pin = o_out + al(sizeof(plba_lcpose_out) * (size_t)n),
+                 o_lin = o_pin + al(np), tot = o_lin + al(nl);
+    if (tot > ctx->lc_cap) {
+        if (ctx->lc_mem) (void)hipFreeAsync(ctx->lc_mem, ctx->stream);  // stream-ordered, as the pose graph's block
+        ctx->lc_mem = nullptr;
+        ctx->lc_cap = 0;
+        if (hipMallocAsync((void **)&ctx->lc_mem, tot, ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->set_error("relative pose: cannot allocate %zu bytes", tot);
+            return PLBA_E_NOMEM;
+        }
+        ctx->lc_cap = tot;
+    }
+    if (tot > ctx->lc_host_cap) {
+        if (ctx->lc_host) (void)hipHostFree(ctx->lc_host);
+        ctx->lc_host = nullptr;
+        ctx->lc_host_cap = 0;
+        if (hipHostMalloc((void **)&ctx->lc_host, tot) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->set_error("relative pose: cannot allocate %zu bytes of pinned memory", tot);
+            return PLBA_E_NOMEM;
+        }
+        ctx->lc_host_cap = tot;
+    }
+    char *h = ctx->lc_host, *dv = ctx->lc_mem;
+    memcpy(h + o_ptoff, b->pt_off, sizeof(int32_t) * (n + 1));
+    memcpy(h + o_lnoff, b->ln_off, sizeof(int32_t) * (n + 1));
+    if (np) {
+        memcpy(h + o_P, b->pt_P, sizeof(double) * 3 * np);
+        memcpy(h + o_obs, b->pt_obs, sizeof(double) * 2 * np);
+    }
+    if (nl) {
+        memcpy(h + o_sP, b->ln_sP, sizeof(double) * 3 * nl);
+        memcpy(h + o_eP, b->ln_eP, sizeof(double) * 3 * nl);
+        memcpy(h + o_le, b->ln_le, sizeof(double) * 3 * nl);
+    }
+    hipStream_t s = ctx->stream;
+    PLBA_CHECK(hipMemcpyAsync(dv, h, o_out, hipMemcpyHostToDevice, s));
+    LcDev L{};
+    L.pt_off = (const int32_t *)(dv + o_ptoff);
+    L.ln_off = (const int32_t *)(dv + o_lnoff);
+    L.pt_P = (const double *)(dv + o_P);
+    L.pt_obs = (const double *)(dv + o_obs);
+    L.ln_sP = (const double *)(dv + o_sP);
+    L.ln_eP = (const double *)(dv + o_eP);
+    L.ln_le = (const double *)(dv + o_le);
+    L.out = (plba_lcpose_out *)(dv + o_out);
+    L.pt_in = (uint8_t *)(dv + o_pin);
+    L.ln_in = (uint8_t *)(dv + o_lin);
+    L.cam = Cam{b->fx, b->fy, b->cx, b->cy};
+    L.prm = prm;
+    hipLaunchKernelGGL(k_lcpose, dim3(n), dim3(kLcNT), 0, s, L); PLBA_LAUNCHED(ctx, "k_lcpose");
+    PLBA_CHECK(hipMemcpyAsync(h + o_out, dv + o_out, tot - o_out, hipMemcpyDeviceToHost, s));
+    PLBA_CHECK(hipStreamSynchronize(s));
+    memcpy(out, h + o_out, sizeof(plba_lcpose_out) * (size_t)n);
+    if (pt_inlier && np) memcpy(pt_inlier, h + o_pin, np);
+    if (ln_inlier && nl) memcpy(ln_inlier, h + o_lin, nl);
     return PLBA_OK;
 }
 

@@ -1,0 +1,448 @@
+// Loop-closure relative pose on the device (plba_lc_relative_pose):
+// MapHandler::computeRelativePoseRobustGN (src/mapHandler.cpp:4677-5068, what isLoopClosure calls)
+// and MapHandler::computeRelativePoseGN (:4413-4675). A robust pose-only Gauss–Newton over the 3-D
+// points and line endpoints of the old keyframe reprojected into the new one: a first loop, an
+// outlier pass, (RobustGN) a refinement loop and a five-way accept test.
+//
+//   k_lcpose   one workgroup of 256 threads per candidate pair, the whole function in one launch.
+//              Threads stride over the candidate's active points, then its active lines, with the 21
+//              upper entries of H, g, e and the active count in registers; the sums are reduced by
+//              an xor butterfly inside each wave and over the four waves through LDS in wave order
+//              (the same input gives bitwise the same output). Thread 0 then runs the serial part:
+//              the stop tests, x = H⁻¹g by column-pivoted Householder QR, T_inc ← T_inc·exp(x)⁻¹.
+//              The continue / stop decision goes through LDS and is read by every thread after a
+//              barrier, so every thread of the workgroup reaches every barrier.
+// Kept from the reference: fx in both Jacobian rows, the left-perturbation step applied on the
+// right, err_prev carried from the first loop into the refinement, lc_inl forced true in RobustGN.
+// Defined where the reference is not: a candidate with no active feature (empty, or emptied by the
+// outlier pass) is rejected with T_inc left as it was; a singular H is rejected (unc = +inf).
+// No FMA contraction, like the checker (tests/ref_lcpose.py) and the se(3) maps of plba_math.hpp.
+#pragma once
+
+#include <float.h>
+
+#include "../../include/plba.h"
+#include "plba_math.hpp"
+
+namespace plba {
+
+constexpr int kLcNT = 256;                // threads of a candidate's workgroup
+constexpr int kLcWaves = kLcNT / 64;
+constexpr int kLcAcc = 29;                // 21 upper entries of H | 6 of g | e | active count
+
+struct LcDev {
+    const int32_t *pt_off, *ln_off;       // [n+1] feature ranges of each candidate
+    const double *pt_P, *pt_obs;          // [.][3] P of kf0, [.][2] pl of kf1
+    const double *ln_sP, *ln_eP, *ln_le;  // [.][3] endpoints of kf0, [.][3] image line of kf1
+    uint8_t *pt_in, *ln_in;               // [.] inlier flags
+    plba_lcpose_out *out;                 // [n]
+    Cam cam;
+    plba_lcpose_params prm;
+};
+
+namespace lcp {
+#pragma clang fp contract(off)
+
+// T.block(0,0,3,3)·P + T.col(3).head(3) of a row-major 4x4 (or 3x4)
+__device__ __forceinline__ void xform(const double *T, const double *P, double *G) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) G[i] = ((T[4 * i] * P[0] + T[4 * i + 1] * P[1]) + T[4 * i + 2] * P[2]) + T[4 * i + 3];
+}
+
+// the six entries the reference writes for one projected point G and the image direction (a, b)
+// (:4724-4729, :4769-4774): fx scales both image directions
+__device__ __forceinline__ void jrow(const Cam &c, double hth, const double *G, double a, double b, double *J) {
+#pragma clang fp contract(off)
+    const double gx = G[0], gy = G[1], gz = G[2];
+    const double gz2 = gz * gz;
+    const double fgz2 = c.fx / fmax(hth, gz2);
+    J[0] = +fgz2 * a * gz;
+    J[1] = +fgz2 * b * gz;
+    J[2] = -fgz2 * (gx * a + gy * b);
+    J[3] = -fgz2 * (gx * gy * a + gy * gy * b + gz * gz * b);
+    J[4] = +fgz2 * (gx * gx * a + gz * gz * a + gx * gy * b);
+    J[5] = +fgz2 * (gx * gz * b - gy * gz * a);
+}
+
+__device__ __forceinline__ void project(const Cam &c, const double *G, double &u, double &v) {
+#pragma clang fp contract(off)
+    u = c.cx + c.fx * G[0] / G[2];
+    v = c.cy + c.fy * G[1] / G[2];
+}
+
+// point residual (dx, dy) and the projected point
+__device__ __forceinline__ double point_res(const Cam &c, const double *T, const double *P, const double *obs, double *G,
+                                            double &dx, double &dy) {
+#pragma clang fp contract(off)
+    xform(T, P, G);
+    double u, v;
+    project(c, G, u, v);
+    dx = u - obs[0];
+    dy = v - obs[1];
+    return sqrt(dx * dx + dy * dy);
+}
+
+// line residual (ds, de): the distances of both projected endpoints to the observed image line
+__device__ __forceinline__ double line_res(const Cam &c, const double *T, const double *sP, const double *eP,
+                                           const double *le, double *Gs, double *Ge, double &ds, double &de) {
+#pragma clang fp contract(off)
+    xform(T, sP, Gs);
+    xform(T, eP, Ge);
+    double us, vs, ue, ve;
+    project(c, Gs, us, vs);
+    project(c, Ge, ue, ve);
+    ds = le[0] * us + le[1] * vs + le[2];
+    de = le[0] * ue + le[1] * ve + le[2];
+    return sqrt(ds * ds + de * de);
+}
+
+// H += J·Jᵀ·w, g += J·r·w, e += r·r·w, N += 1 (Cauchy weight w = 1/(1+r²), src2/auxiliar.cpp:556-559)
+__device__ __forceinline__ void accumulate(double *acc, const double *J, double r) {
+#pragma clang fp contract(off)
+    const double w = 1.0 / (1.0 + r * r);
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) acc[q++] += J[i] * J[j] * w;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] += J[i] * r * w;
+    acc[27] += r * r * w;
+    acc[28] += 1.0;
+}
+
+// Thread 0's workspace (LDS: the small dense routines index it dynamically)
+struct Work {
+    double A[36], W[36], c[6], y[6];
+    int perm[6];
+};
+
+// x = H⁻¹g as Eigen's ColPivHouseholderQR solves it: Householder reflections with the largest
+// remaining column first, rank = the pivots above Eigen's threshold, the rest of x zero.
+__device__ void qr_solve(const double *H, const double *g, double *x, Work &w) {
+#pragma clang fp contract(off)
+    double *A = w.A, *c = w.c, *y = w.y;
+    int *perm = w.perm;
+    double maxn2 = 0.0;
+    for (int j = 0; j < 6; ++j) {
+        double s = 0.0;
+        for (int i = 0; i < 6; ++i) {
+            A[6 * i + j] = H[6 * i + j];
+            s += H[6 * i + j] * H[6 * i + j];
+        }
+        maxn2 = fmax(maxn2, s);
+        perm[j] = j;
+        c[j] = g[j];
+    }
+    const double th = sqrt(maxn2) * DBL_EPSILON / 6.0, thr = th * th;
+    int nz = 6;
+    for (int k = 0; k < 6; ++k) {
+        int best = k;
+        double bn = -1.0;
+        for (int j = k; j < 6; ++j) {
+            double s = 0.0;
+            for (int i = k; i < 6; ++i) s += A[6 * i + j] * A[6 * i + j];
+            if (s > bn) {
+                bn = s;
+                best = j;
+            }
+        }
+        if (nz == 6 && bn < thr * (double)(6 - k)) nz = k;
+        if (best != k) {
+            for (int i = 0; i < 6; ++i) {
+                const double t = A[6 * i + k];
+                A[6 * i + k] = A[6 * i + best];
+                A[6 * i + best] = t;
+            }
+            const int t = perm[k];
+            perm[k] = perm[best];
+            perm[best] = t;
+        }
+        // makeHouseholderInPlace: v = [1; essential], H_k = I − τ·v·vᵀ
+        const double c0 = A[6 * k + k];
+        double tail = 0.0;
+        for (int i = k + 1; i < 6; ++i) tail += A[6 * i + k] * A[6 * i + k];
+        double tau = 0.0, beta = c0;
+        if (tail > DBL_MIN) {
+            beta = sqrt(c0 * c0 + tail);
+            if (c0 >= 0.0) beta = -beta;
+            for (int i = k + 1; i < 6; ++i) A[6 * i + k] /= (c0 - beta);
+            tau = (beta - c0) / beta;
+        } else {
+            for (int i = k + 1; i < 6; ++i) A[6 * i + k] = 0.0;
+        }
+        A[6 * k + k] = beta;
+        for (int j = k + 1; j <= 6; ++j) {  // the trailing columns, then Qᵀg (j == 6)
+            double s = (j < 6) ? A[6 * k + j] : c[k];
+            for (int i = k + 1; i < 6; ++i) s += A[6 * i + k] * ((j < 6) ? A[6 * i + j] : c[i]);
+            s *= tau;
+            if (j < 6) {
+                A[6 * k + j] -= s;
+                for (int i = k + 1; i < 6; ++i) A[6 * i + j] -= s * A[6 * i + k];
+            } else {
+                c[k] -= s;
+                for (int i = k + 1; i < 6; ++i) c[i] -= s * A[6 * i + k];
+            }
+        }
+    }
+    for (int i = 0; i < 6; ++i) x[i] = 0.0;
+    for (int i = nz - 1; i >= 0; --i) {
+        double s = c[i];
+        for (int j = i + 1; j < nz; ++j) s -= A[6 * i + j] * y[j];
+        y[i] = s / A[6 * i + i];
+    }
+    for (int i = 0; i < nz; ++i) x[perm[i]] = y[i];
+}
+
+// smallest eigenvalue of the symmetric 6x6 H by cyclic Jacobi rotations on its upper triangle
+__device__ double min_eig(const double *H, Work &w) {
+#pragma clang fp contract(off)
+    double *a = w.W;
+    for (int k = 0; k < 36; ++k) a[k] = H[k];
+    for (int sweep = 0; sweep < 50; ++sweep) {
+        double sm = 0.0;
+        for (int p = 0; p < 5; ++p)
+            for (int q = p + 1; q < 6; ++q) sm += fabs(a[6 * p + q]);
+        if (sm == 0.0) break;
+        for (int p = 0; p < 5; ++p)
+            for (int q = p + 1; q < 6; ++q) {
+                const double apq = a[6 * p + q], gg = 100.0 * fabs(apq);
+                const double app = a[6 * p + p], aqq = a[6 * q + q];
+                if (sweep > 3 && fabs(app) + gg == fabs(app) && fabs(aqq) + gg == fabs(aqq)) {
+                    a[6 * p + q] = 0.0;
+                    continue;
+                }
+                if (apq == 0.0) continue;
+                double h = aqq - app, t;
+                if (fabs(h) + gg == fabs(h)) {
+                    t = apq / h;
+                } else {
+                    const double theta = 0.5 * h / apq;
+                    t = 1.0 / (fabs(theta) + sqrt(1.0 + theta * theta));
+                    if (theta < 0.0) t = -t;
+                }
+                const double cs = 1.0 / sqrt(1.0 + t * t), sn = t * cs, tau = sn / (1.0 + cs);
+                h = t * apq;
+                a[6 * p + p] = app - h;
+                a[6 * q + q] = aqq + h;
+                a[6 * p + q] = 0.0;
+                for (int j = 0; j < 6; ++j) {
+                    if (j == p || j == q) continue;
+                    double *u = j < p ? &a[6 * j + p] : &a[6 * p + j];
+                    double *v = j < q ? &a[6 * j + q] : &a[6 * q + j];
+                    const double gu = *u, hv = *v;
+                    *u = gu - sn * (hv + gu * tau);
+                    *v = hv + sn * (gu - hv * tau);
+                }
+            }
+    }
+    double m = a[0];
+    for (int i = 1; i < 6; ++i) m = fmin(m, a[7 * i]);
+    return m;
+}
+
+}  // namespace lcp
+
+__global__ __launch_bounds__(kLcNT) void k_lcpose(LcDev d) {
+#pragma clang fp contract(off)
+    __shared__ double s_part[kLcWaves][kLcAcc];
+    __shared__ int s_cnt[kLcWaves][2];
+    __shared__ double s_T[16];   // T_inc, row-major 4x4
+    __shared__ double s_H[36], s_g[6];
+    __shared__ lcp::Work s_w;
+    __shared__ int s_stop;       // the pass's continue / stop decision, read by every thread
+    const int cand = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p0 = d.pt_off[cand], p1 = d.pt_off[cand + 1], l0 = d.ln_off[cand], l1 = d.ln_off[cand + 1];
+    const Cam cam = d.cam;
+    const double hth = d.prm.homog_th;
+    const double out_th = sqrt(7.815);
+    // every feature starts as an inlier. A flag is only ever touched by the thread that owns its
+    // index (the same stride in every phase), so the flags need no barrier of their own.
+    for (int i = p0 + tid; i < p1; i += kLcNT) d.pt_in[i] = 1;
+    for (int i = l0 + tid; i < l1; i += kLcNT) d.ln_in[i] = 1;
+    if (tid == 0) {
+        for (int k = 0; k < 16; ++k) s_T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+        for (int k = 0; k < 36; ++k) s_H[k] = 0.0;
+        s_stop = 0;
+    }
+    __syncthreads();
+    // thread 0's scalars (data only; no branch of another thread depends on them)
+    double err_prev = 999999999.9, e_last = 0.0;
+    int iters[2] = {0, 0}, empty = 0;
+    const int nphase = d.prm.variant == PLBA_LCPOSE_ROBUST_GN ? 2 : 1;
+    for (int phase = 0; phase < nphase; ++phase) {
+        const int cap = phase == 0 ? d.prm.max_iters_first : d.prm.max_iters;
+        for (int it = 0; it < cap; ++it) {
+            double T[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] = s_T[k];
+            double acc[kLcAcc];
+#pragma unroll
+            for (int k = 0; k < kLcAcc; ++k) acc[k] = 0.0;
+            for (int i = p0 + tid; i < p1; i += kLcNT) {
+                if (!d.pt_in[i]) continue;
+                double G[3], dx, dy, J[6];
+                const double r = lcp::point_res(cam, T, d.pt_P + 3 * (size_t)i, d.pt_obs + 2 * (size_t)i, G, dx, dy);
+                lcp::jrow(cam, hth, G, dx, dy, J);
+                const double m = fmax(hth, r);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) J[k] = J[k] / m;
+                lcp::accumulate(acc, J, r);
+            }
+            for (int i = l0 + tid; i < l1; i += kLcNT) {
+                if (!d.ln_in[i]) continue;
+                const double *le = d.ln_le + 3 * (size_t)i;
+                double Gs[3], Ge[3], ds, de, Js[6], Je[6], J[6];
+                const double r = lcp::line_res(cam, T, d.ln_sP + 3 * (size_t)i, d.ln_eP + 3 * (size_t)i, le, Gs, Ge, ds, de);
+                lcp::jrow(cam, hth, Gs, le[0], le[1], Js);
+                lcp::jrow(cam, hth, Ge, le[0], le[1], Je);
+                const double m = fmax(hth, r);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) J[k] = (Js[k] * ds + Je[k] * de) / m;
+                lcp::accumulate(acc, J, r);
+            }
+            // fixed-order reduction: butterfly inside the wave, the four waves in index order
+#pragma unroll
+            for (int k = 0; k < kLcAcc; ++k) {
+                double v = acc[k];
+#pragma unroll
+                for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+                if (lane == 0) s_part[wave][k] = v;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                double S[kLcAcc];
+#pragma unroll
+                for (int k = 0; k < kLcAcc; ++k) {
+                    double v = s_part[0][k];
+#pragma unroll
+                    for (int wv = 1; wv < kLcWaves; ++wv) v += s_part[wv][k];
+                    S[k] = v;
+                }
+                int stop = 0;
+                ++iters[phase];
+                if (S[28] == 0.0) {  // no active feature: rejected, T_inc stays
+                    empty = 1;
+                    stop = 1;
+                } else {
+                    int q = 0;
+#pragma unroll
+                    for (int i = 0; i < 6; ++i)
+#pragma unroll
+                        for (int j = i; j < 6; ++j) {
+                            s_H[6 * i + j] = S[q];
+                            s_H[6 * j + i] = S[q];
+                            ++q;
+                        }
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) s_g[i] = S[21 + i];
+                    const double e = S[27] / S[28];
+                    e_last = e;
+                    if (fabs(e - err_prev) < DBL_EPSILON || e < DBL_EPSILON) {
+                        stop = 1;
+                    } else {
+                        double x[6], E[16], Ei[12], Tn[12];
+                        lcp::qr_solve(s_H, s_g, x, s_w);
+                        se3_exp(x, E);
+                        se3_inv34(E, Ei);
+                        // T_inc ← T_inc · inverse_se3(expmap_se3(x)): the step on the right
+                        for (int i = 0; i < 3; ++i)
+                            for (int j = 0; j < 4; ++j) {
+                                double s = 0.0;
+                                for (int k = 0; k < 3; ++k) s += s_T[4 * i + k] * Ei[4 * k + j];
+                                s += s_T[4 * i + 3] * (j == 3 ? 1.0 : 0.0);
+                                Tn[4 * i + j] = s;
+                            }
+                        for (int k = 0; k < 12; ++k) s_T[k] = Tn[k];
+                        double n2 = 0.0;
+                        for (int k = 0; k < 6; ++k) n2 += x[k] * x[k];
+                        if (sqrt(n2) < DBL_EPSILON) stop = 1;
+                        else err_prev = e;
+                    }
+                }
+                s_stop = stop;
+            }
+            __syncthreads();
+            if (s_stop) break;  // an LDS value: the same for every thread of the workgroup
+        }
+        if (phase == 0) {  // the outlier pass at the pose of the first loop (:4829-4860)
+            double T[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) T[k] = s_T[k];
+            for (int i = p0 + tid; i < p1; i += kLcNT) {
+                if (!d.pt_in[i]) continue;
+                double G[3], dx, dy;
+                if (lcp::point_res(cam, T, d.pt_P + 3 * (size_t)i, d.pt_obs + 2 * (size_t)i, G, dx, dy) > out_th)
+                    d.pt_in[i] = 0;
+            }
+            for (int i = l0 + tid; i < l1; i += kLcNT) {
+                if (!d.ln_in[i]) continue;
+                double Gs[3], Ge[3], ds, de;
+                if (lcp::line_res(cam, T, d.ln_sP + 3 * (size_t)i, d.ln_eP + 3 * (size_t)i, d.ln_le + 3 * (size_t)i, Gs, Ge, ds,
+                                  de) > out_th)
+                    d.ln_in[i] = 0;
+            }
+        }
+    }
+    // inlier counts, then the tail on thread 0
+    int npi = 0, nli = 0;
+    for (int i = p0 + tid; i < p1; i += kLcNT) npi += d.pt_in[i] ? 1 : 0;
+    for (int i = l0 + tid; i < l1; i += kLcNT) nli += d.ln_in[i] ? 1 : 0;
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) {
+        npi += __shfl_xor(npi, m, 64);
+        nli += __shfl_xor(nli, m, 64);
+    }
+    if (lane == 0) {
+        s_cnt[wave][0] = npi;
+        s_cnt[wave][1] = nli;
+    }
+    __syncthreads();
+    if (tid != 0) return;  // (no barrier below)
+    npi = nli = 0;
+    for (int wv = 0; wv < kLcWaves; ++wv) {
+        npi += s_cnt[wv][0];
+        nli += s_cnt[wv][1];
+    }
+    plba_lcpose_out &o = d.out[cand];
+    double x_inc[6], pose[6], Ti[12];
+    se3_log(s_T, x_inc);
+    const double t = sqrt(x_inc[0] * x_inc[0] + x_inc[1] * x_inc[1] + x_inc[2] * x_inc[2]);
+    const double r_deg = sqrt(x_inc[3] * x_inc[3] + x_inc[4] * x_inc[4] + x_inc[5] * x_inc[5]) * 180.0 / 3.14159265358979323846;
+    const double lmin = lcp::min_eig(s_H, s_w);
+    const double unc = lmin > 0.0 ? 1.0 / lmin : INFINITY;  // the largest eigenvalue of H⁻¹
+    if (d.prm.variant == PLBA_LCPOSE_ROBUST_GN) {  // logmap(inverse(expmap(x_inc))) (:5062)
+        double E[16];
+        se3_exp(x_inc, E);
+        se3_inv34(E, Ti);
+    } else {                                       // logmap(inverse(T_inc)) (:4669)
+        se3_inv34(s_T, Ti);
+    }
+    se3_log(Ti, pose);
+    const int n_all = (p1 - p0) + (l1 - l0);
+    int cond = 0;
+    if (e_last < d.prm.lc_res) cond |= 1;
+    if (unc < d.prm.lc_unc) cond |= 2;
+    if (d.prm.variant == PLBA_LCPOSE_ROBUST_GN || (double)(npi + nli) / (double)n_all > d.prm.lc_inl) cond |= 4;
+    if (t < d.prm.lc_trs) cond |= 8;
+    if (r_deg < d.prm.lc_rot) cond |= 16;
+    o.accepted = (cond == 31 && !empty) ? 1 : 0;
+    o.conditions = cond;
+    o.iters_first = iters[0];
+    o.iters_ref = iters[1];
+    o.n_inl_pt = npi;
+    o.n_inl_ln = nli;
+    o.e = e_last;
+    o.unc = unc;
+    o.t = t;
+    o.r_deg = r_deg;
+    for (int k = 0; k < 6; ++k) {
+        o.x_inc[k] = x_inc[k];
+        o.pose_inc[k] = pose[k];
+    }
+    for (int k = 0; k < 12; ++k) o.T_inc[k] = s_T[k];
+    for (int k = 0; k < 36; ++k) o.H[k] = s_H[k];
+}
+
+}  // namespace plba

@@ -312,6 +312,76 @@ int plslam_loop_closure_optimization(plslam_map *m, int32_t ess, plslam_pgo_stat
     return PLBA_OK;
 }
 
+int plslam_set_lcpose_solver(plslam_map *m, plslam_lcpose_solve_fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    m->mh.setLcposeSolver(fn, user);
+    return PLBA_OK;
+}
+
+int plslam_set_lcpose_params(plslam_map *m, const plba_lcpose_params *p) {
+    if (!m) return PLBA_E_INVALID;
+    if (p) m->mh.lcpose_params = *p;
+    else plba_lcpose_default_params(&m->mh.lcpose_params);
+    return PLBA_OK;
+}
+
+int plslam_loop_closure_step(plslam_map *m, const plslam_lc_candidate *c, double lc_inlier_ratio, plslam_lc_stats *stats) {
+    if (!m) return PLBA_E_INVALID;
+    LcCandidate cc;
+    if (c) {
+        cc.kf_prev_idx = c->kf_prev_idx; cc.kf_curr_idx = c->kf_curr_idx;
+        cc.n_pt_0 = c->n_pt_0; cc.n_pt_1 = c->n_pt_1; cc.n_ls_0 = c->n_ls_0; cc.n_ls_1 = c->n_ls_1;
+        cc.has_points = c->has_points != 0; cc.has_lines = c->has_lines != 0;
+        cc.n_pt = c->n_pt; cc.n_ln = c->n_ln;
+        cc.pt_P = c->pt_P; cc.pt_obs = c->pt_obs; cc.ln_sP = c->ln_sP; cc.ln_eP = c->ln_eP; cc.ln_le = c->ln_le;
+        cc.pt_idx = c->pt_idx; cc.ls_idx = c->ls_idx;
+    }
+    LcStats st;
+    const int rc = m->mh.loopClosureStep(c ? &cc : nullptr, lc_inlier_ratio, &st);
+    if (rc) return rc;
+    if (stats) {
+        stats->is_candidate = st.is_candidate; stats->ratio_ok = st.ratio_ok;
+        stats->accepted = st.accepted; stats->conditions = st.conditions;
+        stats->n_inl_pt = st.n_inl_pt; stats->n_inl_ln = st.n_inl_ln;
+        stats->state_before = st.state_before; stats->state_after = st.state_after;
+        stats->pgo_ran = st.pgo_ran; stats->pad = 0;
+        stats->inl_ratio_pt = st.inl_ratio_pt; stats->inl_ratio_ls = st.inl_ratio_ls;
+        stats->e = st.e; stats->unc = st.unc; stats->t = st.t; stats->r_deg = st.r_deg; stats->pose_ms = st.pose_ms;
+        const PgoStats &g = st.pgo;
+        stats->pgo.kf_prev_idx = g.kf_prev_idx; stats->pgo.kf_curr_idx = g.kf_curr_idx;
+        stats->pgo.n_vertices = g.n_vertices; stats->pgo.n_fixed = g.n_fixed; stats->pgo.n_edges = g.n_edges;
+        stats->pgo.n_loop_edges = g.n_loop_edges; stats->pgo.iterations = g.iterations; stats->pgo.trials = g.trials;
+        stats->pgo.chi2_initial = g.chi2_initial; stats->pgo.chi2_final = g.chi2_final; stats->pgo.solve_ms = g.solve_ms;
+    }
+    return PLBA_OK;
+}
+
+int plslam_get_lc_state(plslam_map *m, int32_t *state) {
+    if (!m || !state) return PLBA_E_INVALID;
+    *state = m->mh.lc_state;
+    return PLBA_OK;
+}
+
+int plslam_get_lc_pose_list(plslam_map *m, double *out, int32_t cap, int32_t *n) {
+    if (!m) return PLBA_E_INVALID;
+    const auto &l = m->mh.lc_pose_list;
+    if (n) *n = (int32_t)l.size();
+    for (int i = 0; i < (int)l.size() && i < cap && out; ++i)
+        for (int k = 0; k < 6; ++k) out[6 * i + k] = l[i][k];
+    return PLBA_OK;
+}
+
+int plslam_get_lc_feature_idxs(plslam_map *m, int32_t kind, int32_t loop, int32_t *out, int32_t cap, int32_t *n) {
+    if (!m || (kind != 1 && kind != 2)) return PLBA_E_INVALID;
+    const auto &ll = kind == 1 ? m->mh.lc_pt_idxs : m->mh.lc_ls_idxs;
+    if (loop < 0 || loop >= (int)ll.size()) return PLBA_E_INVALID;
+    const auto &l = ll[loop];
+    if (n) *n = (int32_t)l.size();
+    for (int i = 0; i < (int)l.size() && i < cap && out; ++i)
+        for (int k = 0; k < 4; ++k) out[4 * i + k] = l[i][k];
+    return PLBA_OK;
+}
+
 int plslam_set_line_geometry(plslam_map *m, int32_t idx, const double line3D[6], const double med_obs_dir[3]) {
     if (!m || idx < 0 || idx >= (int)m->mh.map_lines.size() || !m->mh.map_lines[idx]) return PLBA_E_INVALID;
     MapLine *ml = m->mh.map_lines[idx];

@@ -1,7 +1,10 @@
 // Host mirror of MapHandler::loopClosureOptimizationEssGraphG2O (src/mapHandler.cpp:5070-5299)
 // and MapHandler::loopClosureOptimizationCovGraphG2O (:5301-5531) around the GPU pose-graph
 // solve (plba_pgo_optimize), with the g2o SE3Quat conversions the reference goes through
-// (SE3Quat::exp / log, SE3Quat <-> Isometry3 via Eigen's quaternion).
+// (SE3Quat::exp / log, SE3Quat <-> Isometry3 via Eigen's quaternion); and of MapHandler::loopClosure()
+// (:4053-4116) from the candidate on: the inlier-ratio gate of isLoopClosure, the relative pose on
+// the GPU (plba_lc_relative_pose), the loop lists and the LC_IDLE / LC_ACTIVE / LC_READY states.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <map>
@@ -329,6 +332,98 @@ int MapHandler::loopClosurePGO(bool ess, PgoStats *stats) {
     }
     for (Vec3i &l : lc_idx_list) l[2] = 0;  // mark as optimised (:5290-5292)
     lc_state = 0;                            // LC_IDLE (:5296), after loopClosureFuseLandmarks()
+    if (stats) *stats = st;
+    return PLBA_OK;
+}
+
+// MapHandler::loopClosure() (src/mapHandler.cpp:4053-4116) from the candidate on, with the tail of
+// isLoopClosure (:4382-4409) and computeRelativePoseRobustGN (:4677-5068, on the GPU) inside.
+int MapHandler::loopClosureStep(const LcCandidate *c, double lc_inlier_ratio, LcStats *stats) {
+    using clk = std::chrono::steady_clock;
+    LcStats st;
+    st.state_before = lc_state;
+    bool isLC = false;
+    if (c) {
+        st.is_candidate = 1;
+        if (c->n_pt < 0 || c->n_ln < 0 || (c->n_pt && (!c->pt_P || !c->pt_obs)) ||
+            (c->n_ln && (!c->ln_sP || !c->ln_eP || !c->ln_le))) {
+            setError("loop closure: candidate with negative counts or NULL feature arrays");
+            return PLBA_E_INVALID;
+        }
+        // the matching runs only for an enabled kind with features in both keyframes (:4331, :4357)
+        const bool use_pt = c->has_points && c->n_pt_0 > 0 && c->n_pt_1 > 0;
+        const bool use_ls = c->has_lines && c->n_ls_0 > 0 && c->n_ls_1 > 0;
+        const int common_pt = use_pt ? c->n_pt : 0, common_ls = use_ls ? c->n_ln : 0;
+        // :4384-4385 — a zero count gives NaN or 0 here, and the comparisons below are then false
+        const double inl_ratio_pt = std::max(100.0 * common_pt / c->n_pt_0, 100.0 * common_pt / c->n_pt_1);
+        const double inl_ratio_ls = std::max(100.0 * common_ls / c->n_ls_0, 100.0 * common_ls / c->n_ls_1);
+        st.inl_ratio_pt = inl_ratio_pt;
+        st.inl_ratio_ls = inl_ratio_ls;
+        bool cond = false;
+        if (c->has_points && c->has_lines) cond = inl_ratio_pt > lc_inlier_ratio && inl_ratio_ls > lc_inlier_ratio;
+        else if (c->has_points) cond = inl_ratio_pt > lc_inlier_ratio;
+        else if (c->has_lines) cond = inl_ratio_ls > lc_inlier_ratio;
+        st.ratio_ok = cond ? 1 : 0;
+        if (cond) {
+            const int32_t pt_off[2] = {0, common_pt}, ln_off[2] = {0, common_ls};
+            plba_lcpose_batch b{};
+            b.n = 1;
+            b.pt_off = pt_off;
+            b.ln_off = ln_off;
+            b.pt_P = c->pt_P; b.pt_obs = c->pt_obs;
+            b.ln_sP = c->ln_sP; b.ln_eP = c->ln_eP; b.ln_le = c->ln_le;
+            b.fx = fx_; b.fy = fy_; b.cx = cx_; b.cy = cy_;
+            plba_lcpose_out o{};
+            std::vector<uint8_t> pin((size_t)std::max(common_pt, 1), 0), lin((size_t)std::max(common_ls, 1), 0);
+            const auto t0 = clk::now();
+            int rc;
+            if (lcpose_fn_) {
+                rc = lcpose_fn_(lcpose_user_, &b, &lcpose_params, &o, pin.data(), lin.data());
+                if (rc) setError("relative-pose solver hook returned %d", rc);
+            } else {
+                rc = ensureCtx();
+                if (!rc) rc = plba_lc_relative_pose(ctx_, &b, &lcpose_params, &o, pin.data(), lin.data());
+                if (rc) setError("plba: %s", plba_last_error(ctx_));
+            }
+            if (rc) return rc;
+            st.pose_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+            st.accepted = o.accepted;
+            st.conditions = o.conditions;
+            st.n_inl_pt = o.n_inl_pt; st.n_inl_ln = o.n_inl_ln;
+            st.e = o.e; st.unc = o.unc; st.t = o.t; st.r_deg = o.r_deg;
+            isLC = o.accepted != 0;
+            if (isLC) {
+                // the outliers leave lc_pt_idx / lc_ls_idx (:5025-5056); the rows are kept for the
+                // landmark fusion (:4078-4079)
+                std::vector<Vec4i> pt_rows, ls_rows;
+                for (int i = 0; i < common_pt && c->pt_idx; ++i)
+                    if (pin[i]) pt_rows.push_back(Vec4i{c->pt_idx[4 * i], c->pt_idx[4 * i + 1], c->pt_idx[4 * i + 2], c->pt_idx[4 * i + 3]});
+                for (int i = 0; i < common_ls && c->ls_idx; ++i)
+                    if (lin[i]) ls_rows.push_back(Vec4i{c->ls_idx[4 * i], c->ls_idx[4 * i + 1], c->ls_idx[4 * i + 2], c->ls_idx[4 * i + 3]});
+                lc_pt_idxs.push_back(std::move(pt_rows));
+                lc_ls_idxs.push_back(std::move(ls_rows));
+                Vec6 pose_inc;
+                for (int k = 0; k < 6; ++k) pose_inc[k] = o.pose_inc[k];
+                lc_poses.push_back(pose_inc);
+                lc_pose_list.push_back(pose_inc);
+                const Vec3i lc_idx{c->kf_prev_idx, c->kf_curr_idx, 1};
+                lc_idxs.push_back(lc_idx);
+                lc_idx_list.push_back(lc_idx);
+            }
+        }
+    }
+    if (isLC) {
+        if (lc_state == LC_IDLE) lc_state = LC_ACTIVE;
+    } else {
+        if (lc_state == LC_ACTIVE) lc_state = LC_READY;
+    }
+    if (lc_state == LC_READY) {  // (:4109-4115)
+        const int rc = loopClosureOptimizationCovGraphG2O(&st.pgo);
+        if (rc) return rc;
+        st.pgo_ran = 1;
+        lc_state = LC_IDLE;
+    }
+    st.state_after = lc_state;
     if (stats) *stats = st;
     return PLBA_OK;
 }

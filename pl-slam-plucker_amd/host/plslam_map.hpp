@@ -183,6 +183,29 @@ struct PgoStats {
     double chi2_initial = 0, chi2_final = 0, solve_ms = 0;
 };
 
+using LcposeSolveFn = int (*)(void *user, const plba_lcpose_batch *b, const plba_lcpose_params *p, plba_lcpose_out *out,
+                              uint8_t *pt_inlier, uint8_t *ln_inlier);
+using Vec4i = std::array<int, 4>;
+
+// What isLoopClosure (src/mapHandler.cpp:4303-4411) has after its descriptor matching: the feature
+// counts of both keyframes and the matched features with their lc_pt_idx / lc_ls_idx rows.
+struct LcCandidate {
+    int kf_prev_idx = 0, kf_curr_idx = 0;
+    int n_pt_0 = 0, n_pt_1 = 0, n_ls_0 = 0, n_ls_1 = 0;  // stereo_pt / stereo_ls sizes of kf0, kf1
+    bool has_points = true, has_lines = true;            // SlamConfig::hasPoints() / hasLines()
+    int n_pt = 0, n_ln = 0;                              // matches
+    const double *pt_P = nullptr, *pt_obs = nullptr, *ln_sP = nullptr, *ln_eP = nullptr, *ln_le = nullptr;
+    const int32_t *pt_idx = nullptr, *ls_idx = nullptr;  // [n][4]
+};
+
+// One loopClosure() step (src/mapHandler.cpp:4053-4116) after lookForLoopCandidates.
+struct LcStats {
+    int is_candidate = 0, ratio_ok = 0, accepted = 0, conditions = 0;
+    int n_inl_pt = 0, n_inl_ln = 0, state_before = 0, state_after = 0, pgo_ran = 0;
+    double inl_ratio_pt = 0, inl_ratio_ls = 0, e = 0, unc = 0, t = 0, r_deg = 0, pose_ms = 0;
+    PgoStats pgo;
+};
+
 struct CullStats {
     int points_removed = 0, lines_removed = 0;
 };
@@ -243,6 +266,17 @@ class MapHandler {
     std::vector<Vec3i> lc_idxs, lc_idx_list;
     std::vector<Vec6> lc_poses, lc_pose_list;
     int lc_state = 0;  // LC_IDLE = 0
+    enum { LC_IDLE = 0, LC_ACTIVE = 1, LC_READY = 2 };  // include/mapHandler.h:195-197
+
+    // src/mapHandler.cpp:4053-4116, loopClosure() after lookForLoopCandidates (DBoW2) and the
+    // descriptor matching of isLoopClosure (:4327-4380), both the caller's: the inlier-ratio gate
+    // (:4384-4409), computeRelativePoseRobustGN on the GPU (plba_lc_relative_pose), the lists and
+    // the LC_IDLE / LC_ACTIVE / LC_READY state machine, and on LC_READY the pose graph above.
+    // c == nullptr: lookForLoopCandidates found no candidate.
+    int loopClosureStep(const LcCandidate *c, double lc_inlier_ratio, LcStats *stats = nullptr);
+    std::vector<std::vector<Vec4i>> lc_pt_idxs, lc_ls_idxs;  // inlier-filtered rows, one list per loop (:4078-4079)
+    plba_lcpose_params lcpose_params{1e-7, 1.0, 0.01, 0.3, 1.5, 35.0, 5, 10, PLBA_LCPOSE_ROBUST_GN, 0};
+    void setLcposeSolver(LcposeSolveFn fn, void *user) { lcpose_fn_ = fn; lcpose_user_ = user; }
 
     void setSolver(SolveFn fn, void *user) { solve_fn_ = fn; solve_user_ = user; }
     void setPgoSolver(PgoSolveFn fn, void *user) { pgo_fn_ = fn; pgo_user_ = user; }
@@ -294,6 +328,8 @@ class MapHandler {
     void *hlm_user_ = nullptr;
     PgoSolveFn pgo_fn_ = nullptr;
     void *pgo_user_ = nullptr;
+    LcposeSolveFn lcpose_fn_ = nullptr;
+    void *lcpose_user_ = nullptr;
     int loopClosurePGO(bool ess, PgoStats *stats);
     std::string err_;
     // per-call scratch reused across LBA calls (capacity kept; see Window::clear)

@@ -263,3 +263,71 @@ class PgoResultBuffers:
         return dict(v_T=self.v_T.copy(), iterations=s.iterations, trials=s.trials, solve_fails=s.solve_fails,
                     n_free=s.n_free, chi2_initial=s.chi2_initial, chi2_final=s.chi2_final,
                     lambda_final=s.lambda_final, solve_ms=s.solve_ms, trace=trace_to_array(self.trace, s.n_trace))
+
+
+# ---- loop-closure relative pose (plba_lcpose_* / plba_lc_relative_pose)
+LCPOSE_ROBUST_GN = 0
+LCPOSE_GN = 1
+
+
+class PlbaLcposeBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pt_off", _ip), ("ln_off", _ip), ("pt_P", _dp), ("pt_obs", _dp),
+                ("ln_sP", _dp), ("ln_eP", _dp), ("ln_le", _dp),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class PlbaLcposeParams(C.Structure):
+    _fields_ = [("homog_th", C.c_double), ("lc_res", C.c_double), ("lc_unc", C.c_double), ("lc_inl", C.c_double),
+                ("lc_trs", C.c_double), ("lc_rot", C.c_double),
+                ("max_iters_first", C.c_int32), ("max_iters", C.c_int32), ("variant", C.c_int32), ("pad", C.c_int32)]
+
+
+class PlbaLcposeOut(C.Structure):
+    _fields_ = [("accepted", C.c_int32), ("conditions", C.c_int32), ("iters_first", C.c_int32),
+                ("iters_ref", C.c_int32), ("n_inl_pt", C.c_int32), ("n_inl_ln", C.c_int32),
+                ("e", C.c_double), ("unc", C.c_double), ("t", C.c_double), ("r_deg", C.c_double),
+                ("x_inc", C.c_double * 6), ("pose_inc", C.c_double * 6), ("T_inc", C.c_double * 12),
+                ("H", C.c_double * 36)]
+
+
+def lcpose_params(**kw) -> PlbaLcposeParams:
+    """plba_lcpose_default_params: src2/config.cpp:80-83 and src/slamConfig.cpp:73-77."""
+    p = PlbaLcposeParams(homog_th=1e-7, lc_res=1.0, lc_unc=0.01, lc_inl=0.3, lc_trs=1.5, lc_rot=35.0,
+                         max_iters_first=5, max_iters=10, variant=LCPOSE_ROBUST_GN, pad=0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class LcposeBatchView:
+    """Concatenates candidate pairs (objects with pt_P, pt_obs, ln_sP, ln_eP, ln_le and cam, e.g.
+    plba.lcpose.LcProblem) into contiguous arrays and the PlbaLcposeBatch over them."""
+
+    def __init__(self, problems):
+        def cat(name, w):
+            rows = [np.asarray(getattr(q, name), np.float64).reshape(-1, w) for q in problems]
+            return np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, w)))
+
+        self.pt_P, self.pt_obs = cat("pt_P", 3), cat("pt_obs", 2)
+        self.ln_sP, self.ln_eP, self.ln_le = cat("ln_sP", 3), cat("ln_eP", 3), cat("ln_le", 3)
+        self.pt_off = np.zeros(len(problems) + 1, np.int32)
+        self.ln_off = np.zeros(len(problems) + 1, np.int32)
+        for i, q in enumerate(problems):
+            self.pt_off[i + 1] = self.pt_off[i] + len(np.asarray(q.pt_P).reshape(-1, 3))
+            self.ln_off[i + 1] = self.ln_off[i] + len(np.asarray(q.ln_sP).reshape(-1, 3))
+        cam = problems[0].cam if problems else (1.0, 1.0, 0.0, 0.0)
+        if any(tuple(q.cam) != tuple(cam) for q in problems):
+            raise ValueError("the candidates of one batch share one camera")
+        self.struct = PlbaLcposeBatch(
+            n=len(problems), pt_off=_ptr(self.pt_off, _ip), ln_off=_ptr(self.ln_off, _ip),
+            pt_P=_ptr(self.pt_P, _dp), pt_obs=_ptr(self.pt_obs, _dp), ln_sP=_ptr(self.ln_sP, _dp),
+            ln_eP=_ptr(self.ln_eP, _dp), ln_le=_ptr(self.ln_le, _dp), fx=cam[0], fy=cam[1], cx=cam[2], cy=cam[3])
+
+
+def lcpose_out_to_dict(o: PlbaLcposeOut, pt_inlier, ln_inlier) -> dict:
+    return dict(accepted=int(o.accepted), conditions=int(o.conditions), iters_first=int(o.iters_first),
+                iters_ref=int(o.iters_ref), n_inl_pt=int(o.n_inl_pt), n_inl_ln=int(o.n_inl_ln),
+                e=float(o.e), unc=float(o.unc), t=float(o.t), r_deg=float(o.r_deg),
+                x_inc=np.array(o.x_inc[:]), pose_inc=np.array(o.pose_inc[:]),
+                T_inc=np.array(o.T_inc[:]).reshape(3, 4), H=np.array(o.H[:]).reshape(6, 6),
+                pt_inlier=np.array(pt_inlier, np.uint8), ln_inlier=np.array(ln_inlier, np.uint8))

@@ -30,6 +30,7 @@ EXPORTED = [
     "plba_comm_info", "plba_factor_plan",
     "plba_hlm_default_params", "plba_hlm_lba",
     "plba_pgo_default_params", "plba_pgo_optimize",
+    "plba_lcpose_default_params", "plba_lc_relative_pose",
 ]
 
 # int (*plba_host_allreduce_fn)(void *user, double *buf, int64_t n)
@@ -89,9 +90,14 @@ def load(path: Optional[str] = None):
     L.plba_pgo_default_params.restype = None
     L.plba_pgo_optimize.argtypes = [vp, C.POINTER(capi.PlbaPgoGraph), C.POINTER(capi.PlbaPgoParams),
                                     C.POINTER(capi.PlbaPgoResult)]
+    L.plba_lcpose_default_params.argtypes = [C.POINTER(capi.PlbaLcposeParams)]
+    L.plba_lcpose_default_params.restype = None
+    L.plba_lc_relative_pose.argtypes = [vp, C.POINTER(capi.PlbaLcposeBatch), C.POINTER(capi.PlbaLcposeParams),
+                                        C.POINTER(capi.PlbaLcposeOut), bp, bp]
     for name in EXPORTED:
         f = getattr(L, name)
-        if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params"):
+        if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
+                        "plba_lcpose_default_params"):
             f.restype = C.c_int
     _lib = L
     return L
@@ -282,6 +288,24 @@ class Solver:
         self._check(self.L.plba_pgo_optimize(self.ctx, C.byref(gv.struct), C.byref(params), C.byref(rb.struct)),
                     "plba_pgo_optimize")
         return rb.as_dict()
+
+    def lc_relative_pose(self, problems, params=None) -> list:
+        """Loop-closure relative pose (plba_lc_relative_pose; computeRelativePoseRobustGN /
+        computeRelativePoseGN, src/mapHandler.cpp:4677-5068 / :4413-4675) of a batch of candidate
+        pairs (plba.lcpose.LcProblem), verified in one launch. One dict per candidate, with its
+        inlier flags. Needs no uploaded window and leaves one intact."""
+        if params is None:
+            params = capi.PlbaLcposeParams()
+            self.L.plba_lcpose_default_params(C.byref(params))
+        bv = capi.LcposeBatchView(list(problems))
+        n = bv.struct.n
+        out = (capi.PlbaLcposeOut * max(n, 1))()
+        pin = np.zeros(max(int(bv.pt_off[-1]), 1), np.uint8)
+        lin = np.zeros(max(int(bv.ln_off[-1]), 1), np.uint8)
+        self._check(self.L.plba_lc_relative_pose(self.ctx, C.byref(bv.struct), C.byref(params), out,
+                                                 _p(pin, C.c_uint8), _p(lin, C.c_uint8)), "plba_lc_relative_pose")
+        return [capi.lcpose_out_to_dict(out[i], pin[bv.pt_off[i]:bv.pt_off[i + 1]], lin[bv.ln_off[i]:bv.ln_off[i + 1]])
+                for i in range(n)]
 
     def trace(self) -> np.ndarray:
         n = C.c_int32(0)

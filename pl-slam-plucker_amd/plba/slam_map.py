@@ -216,6 +216,33 @@ class PlslamHlmStats(C.Structure):
     def as_dict(self):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
+LCPOSE_SOLVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaLcposeBatch), C.POINTER(capi.PlbaLcposeParams),
+                              C.POINTER(capi.PlbaLcposeOut), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8))
+LC_IDLE, LC_ACTIVE, LC_READY = 0, 1, 2   # include/mapHandler.h:195-197
+
+
+class PlslamLcCandidate(C.Structure):
+    _fields_ = [("kf_prev_idx", C.c_int32), ("kf_curr_idx", C.c_int32), ("n_pt_0", C.c_int32), ("n_pt_1", C.c_int32),
+                ("n_ls_0", C.c_int32), ("n_ls_1", C.c_int32), ("has_points", C.c_int32), ("has_lines", C.c_int32),
+                ("n_pt", C.c_int32), ("n_ln", C.c_int32),
+                ("pt_P", C.POINTER(C.c_double)), ("pt_obs", C.POINTER(C.c_double)), ("ln_sP", C.POINTER(C.c_double)),
+                ("ln_eP", C.POINTER(C.c_double)), ("ln_le", C.POINTER(C.c_double)),
+                ("pt_idx", C.POINTER(C.c_int32)), ("ls_idx", C.POINTER(C.c_int32))]
+
+
+class PlslamLcStats(C.Structure):
+    _fields_ = [("is_candidate", C.c_int32), ("ratio_ok", C.c_int32), ("accepted", C.c_int32),
+                ("conditions", C.c_int32), ("n_inl_pt", C.c_int32), ("n_inl_ln", C.c_int32),
+                ("state_before", C.c_int32), ("state_after", C.c_int32), ("pgo_ran", C.c_int32), ("pad", C.c_int32),
+                ("inl_ratio_pt", C.c_double), ("inl_ratio_ls", C.c_double), ("e", C.c_double), ("unc", C.c_double),
+                ("t", C.c_double), ("r_deg", C.c_double), ("pose_ms", C.c_double), ("pgo", PlslamPgoStats)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f not in ("pad", "pgo")}
+        d["pgo"] = self.pgo.as_dict()
+        return d
+
+
 HOST_EXPORTED = [
     "plslam_map_create", "plslam_map_destroy", "plslam_map_last_error", "plslam_set_solver", "plslam_add_keyframe",
     "plslam_add_point", "plslam_point_add_observation", "plslam_add_line", "plslam_line_add_observation",
@@ -229,6 +256,8 @@ HOST_EXPORTED = [
     "plslam_set_loop_closure", "plslam_get_lc_idx_list", "plslam_set_pgo_params", "plslam_set_pgo_solver",
     "plslam_loop_closure_optimization", "plslam_set_line_geometry", "plslam_get_line_geometry",
     "plslam_set_incremental", "plslam_mark_landmark_changed", "plslam_check_incremental_gather",
+    "plslam_set_lcpose_solver", "plslam_set_lcpose_params", "plslam_loop_closure_step", "plslam_get_lc_state",
+    "plslam_get_lc_pose_list", "plslam_get_lc_feature_idxs",
 ]
 
 
@@ -301,6 +330,12 @@ def load_host(path: Optional[str] = None):
     L.plslam_set_incremental.argtypes = [vp, C.c_int32]
     L.plslam_mark_landmark_changed.argtypes = [vp, C.c_int32, C.c_int32]
     L.plslam_check_incremental_gather.argtypes = [vp, ip]
+    L.plslam_set_lcpose_solver.argtypes = [vp, LCPOSE_SOLVE_FN, vp]
+    L.plslam_set_lcpose_params.argtypes = [vp, C.POINTER(capi.PlbaLcposeParams)]
+    L.plslam_loop_closure_step.argtypes = [vp, C.POINTER(PlslamLcCandidate), C.c_double, C.POINTER(PlslamLcStats)]
+    L.plslam_get_lc_state.argtypes = [vp, ip]
+    L.plslam_get_lc_pose_list.argtypes = [vp, dp, C.c_int32, ip]
+    L.plslam_get_lc_feature_idxs.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, ip]
     for n in HOST_EXPORTED:
         if n not in ("plslam_map_last_error", "plslam_pluker_to_orth", "plslam_orth_to_pluker"):
             getattr(L, n).restype = C.c_int
@@ -556,6 +591,81 @@ class HostMap:
         st = PlslamPgoStats()
         self._check(self.L.plslam_loop_closure_optimization(self.h, int(ess), C.byref(st)), "loop_closure")
         return st.as_dict()
+
+    # ---- loopClosure() from the candidate on (src/mapHandler.cpp:4053-4116)
+    def set_lcpose_solver(self, fn: Optional[Callable]):
+        """fn(batch, params, out, pt_inlier, ln_inlier) -> int, or None for the MI355X backend
+        (plba_lc_relative_pose)."""
+        if fn is None:
+            self._lcb = None
+            self._check(self.L.plslam_set_lcpose_solver(self.h, C.cast(None, LCPOSE_SOLVE_FN), None),
+                        "set_lcpose_solver")
+            return
+
+        def tramp(user, bp_, pp, op, pin, lin):
+            try:
+                return int(fn(bp_.contents, pp.contents, op, pin, lin))
+            except Exception:  # never unwind through C
+                import traceback
+                traceback.print_exc()
+                return -1
+        self._lcb = LCPOSE_SOLVE_FN(tramp)
+        self._check(self.L.plslam_set_lcpose_solver(self.h, self._lcb, None), "set_lcpose_solver")
+
+    def set_lcpose_params(self, params=None):
+        self._check(self.L.plslam_set_lcpose_params(self.h, C.byref(params) if params is not None else None),
+                    "set_lcpose_params")
+
+    def loop_closure_step(self, candidate=None, kf_prev_idx: int = 0, kf_curr_idx: int = 0, n_feat=None,
+                          pt_idx=None, ls_idx=None, has_points: bool = True, has_lines: bool = True,
+                          lc_inlier_ratio: float = 30.0) -> dict:
+        """loopClosure() after lookForLoopCandidates and the descriptor matching. ``candidate``: the
+        matched features (plba.lcpose.LcProblem) or None when there is no candidate; ``n_feat`` =
+        (n_pt_0, n_pt_1, n_ls_0, n_ls_1), the feature counts of both keyframes; ``pt_idx`` /
+        ``ls_idx``: [n][4] lc_pt_idx / lc_ls_idx rows."""
+        st = PlslamLcStats()
+        if candidate is None:
+            self._check(self.L.plslam_loop_closure_step(self.h, None, lc_inlier_ratio, C.byref(st)), "loop_closure_step")
+            return st.as_dict()
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        keep = [np.ascontiguousarray(np.asarray(getattr(candidate, k), np.float64).reshape(-1, w))
+                for k, w in (("pt_P", 3), ("pt_obs", 2), ("ln_sP", 3), ("ln_eP", 3), ("ln_le", 3))]
+        n_pt, n_ln = len(keep[0]), len(keep[2])
+        idx = [None if a is None else np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1, 4)) for a in (pt_idx, ls_idx)]
+        if (idx[0] is not None and len(idx[0]) != n_pt) or (idx[1] is not None and len(idx[1]) != n_ln):
+            raise ValueError("one index row per match")
+        nf = n_feat if n_feat is not None else (n_pt, n_pt, n_ln, n_ln)
+        c = PlslamLcCandidate(kf_prev_idx=kf_prev_idx, kf_curr_idx=kf_curr_idx, n_pt_0=nf[0], n_pt_1=nf[1],
+                              n_ls_0=nf[2], n_ls_1=nf[3], has_points=int(has_points), has_lines=int(has_lines),
+                              n_pt=n_pt, n_ln=n_ln, pt_P=keep[0].ctypes.data_as(dp), pt_obs=keep[1].ctypes.data_as(dp),
+                              ln_sP=keep[2].ctypes.data_as(dp), ln_eP=keep[3].ctypes.data_as(dp),
+                              ln_le=keep[4].ctypes.data_as(dp),
+                              pt_idx=idx[0].ctypes.data_as(ip) if idx[0] is not None else None,
+                              ls_idx=idx[1].ctypes.data_as(ip) if idx[1] is not None else None)
+        self._check(self.L.plslam_loop_closure_step(self.h, C.byref(c), lc_inlier_ratio, C.byref(st)), "loop_closure_step")
+        return st.as_dict()
+
+    def lc_state(self) -> int:
+        v = C.c_int32(0)
+        self._check(self.L.plslam_get_lc_state(self.h, C.byref(v)), "get_lc_state")
+        return v.value
+
+    def lc_pose_list(self) -> np.ndarray:
+        n = C.c_int32(0)
+        self._check(self.L.plslam_get_lc_pose_list(self.h, None, 0, C.byref(n)), "get_lc_pose_list")
+        out = np.zeros((max(n.value, 1), 6))
+        self._check(self.L.plslam_get_lc_pose_list(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), n.value,
+                                                   C.byref(n)), "get_lc_pose_list")
+        return out[:n.value]
+
+    def lc_feature_idxs(self, kind: int, loop: int) -> np.ndarray:
+        """The kept lc_pt_idx (kind 1) / lc_ls_idx (kind 2) rows of accepted loop ``loop``."""
+        n = C.c_int32(0)
+        self._check(self.L.plslam_get_lc_feature_idxs(self.h, kind, loop, None, 0, C.byref(n)), "get_lc_feature_idxs")
+        out = np.zeros((max(n.value, 1), 4), np.int32)
+        self._check(self.L.plslam_get_lc_feature_idxs(self.h, kind, loop, out.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      n.value, C.byref(n)), "get_lc_feature_idxs")
+        return out[:n.value]
 
     def set_line_geometry(self, idx: int, line3d, med_obs_dir):
         a, pa = _d(line3d)
