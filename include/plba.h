@@ -373,6 +373,45 @@ void plba_lcpose_default_params(plba_lcpose_params *p);
 int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *p,
                           plba_lcpose_out *out, uint8_t *pt_inlier, uint8_t *ln_inlier);
 
+/* ---- Descriptor matching, what feeds the relative pose above and every other matching step of
+ * the back end:
+ *   int StVO::match(desc1, desc2, nnr, matches_12)          (src2/matching.cpp:63-91)
+ *   int StVO::matchNNR(desc1, desc2, nnr, matches_12)       (src2/matching.cpp:41-61)
+ * called by isLoopClosure (src/mapHandler.cpp:4334, :4360), matchKF2KFPoints / Lines (:280, :427),
+ * matchMap2KFPoints / Lines (:762, :877) and the VO's tracking (src2/stereoFrameHandler.cpp:141,
+ * :164). BFMatcher(NORM_HAMMING).knnMatch(k = 2) in both directions, a nearest-neighbour-ratio test
+ * and a left/right cross-check. Integer work: the results are exact.
+ * Nearest neighbours, per pair and direction: for each query row the smallest and second-smallest
+ * Hamming distance over the train rows, scanned in increasing train index; a distance replaces the
+ * best only if strictly smaller, otherwise the second only if strictly smaller, so ties go to the
+ * lowest train index (OpenCV's batch distance; matchGrid's own loop, matching.cpp:152-157).
+ * Ratio test: a row is matched if (float)d0 < (float)d1 * nnr, a single-precision product and
+ * compare (matching.cpp:54: DMatch::distance and nnr are floats). In double it would differ, e.g.
+ * for nnr = 0.6f, d0 = 6, d1 = 10.
+ * Cross-check: with best_lr a match i1 -> i2 survives only if the reverse pass, with the same
+ * ratio, matched i2 -> i1 (:80-86). matches_12 is local to the pair: the row index within the
+ * pair's own desc2 slice, or -1. n_matches[k] is the surviving count, the function's return value.
+ * Defined where the reference is not: a pair with fewer than 2 train rows in a direction has no
+ * match in that direction (the reference reads matches_[idx][1] out of range); a pair with 0 rows
+ * on either side has 0 matches. Neither disturbs the rest of the batch.
+ * A call matches a batch of descriptor-set pairs, both directions, in two kernel launches. */
+typedef struct plba_match_batch {       /* B descriptor-set pairs, concatenated */
+    int32_t n;                          /* pairs                                              */
+    int32_t desc_bytes;                 /* bytes per descriptor: a multiple of 4 in [4, 64];
+                                           ORB and LBD are 32                                 */
+    const int32_t *off1, *off2;         /* [n+1] row ranges into desc1 / desc2                */
+    const uint8_t *desc1, *desc2;       /* [off1[n]][desc_bytes], [off2[n]][desc_bytes]       */
+    const float   *nnr;                 /* [n] ratio per pair (minRatio12P / minRatio12L as float) */
+    int32_t best_lr;                    /* Config::bestLRMatches(): 1 = cross-check (default) */
+    int32_t pad;
+} plba_match_batch;
+/* Runs on the context's stream; needs no uploaded window and leaves one intact; its device block
+ * and pinned host image are kept and reused across calls. matches_12: [off1[n]], n_matches: [n].
+ * PLBA_E_INVALID for a NULL batch or array (desc1 / matches_12 may be NULL when off1[n] == 0,
+ * desc2 when off2[n] == 0), n < 0, decreasing or negative offsets or a bad desc_bytes; n == 0 does
+ * nothing and returns PLBA_OK. */
+int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
+
 /* ---- Sharded windows: one context per GPU, one window split over nranks.
  * Landmarks (with all their edges) are partitioned by the keyframe range of their first
  * observation (kf_obs_list[0], the base KF of map_points_kf_idx); poses are replicated.

@@ -176,8 +176,10 @@ typedef struct plslam_pgo_stats {
     double  chi2_initial, chi2_final, solve_ms;
 } plslam_pgo_stats;
 int plslam_loop_closure_optimization(plslam_map *m, int32_t ess, plslam_pgo_stats *stats);
-/* ---- MapHandler::loopClosure() (src/mapHandler.cpp:4053-4116) after lookForLoopCandidates (DBoW2)
- * and the descriptor matching of isLoopClosure (:4327-4380), which stay the caller's: the
+/* ---- MapHandler::loopClosure() (src/mapHandler.cpp:4053-4116) after lookForLoopCandidates (DBoW2),
+ * which stays the caller's: the descriptor matching of isLoopClosure (:4327-4380, through
+ * plba_desc_match or the hook, in plslam_loop_closure_step_kf below; plslam_loop_closure_step takes
+ * the matched candidate from a caller that keeps its own matcher), the
  * inlier-ratio gate (:4384-4409; a zero feature count makes the ratio NaN or 0, so false),
  * computeRelativePoseRobustGN (:4677-5068) through plba_lc_relative_pose or the hook, and the state
  * machine. An accepted loop extends lc_poses, lc_pose_list (pose_inc), lc_idxs, lc_idx_list
@@ -210,6 +212,40 @@ int plslam_set_lcpose_params(plslam_map *m, const plba_lcpose_params *p);       
  * (src/slamConfig.cpp:83). */
 int plslam_loop_closure_step(plslam_map *m, const plslam_lc_candidate *c, double lc_inlier_ratio,
                              plslam_lc_stats *st);
+/* ---- isLoopClosure from two keyframe indices (src/mapHandler.cpp:4303-4411).
+ * What it reads of a keyframe's stereo_frame: pdesc_l / ldesc_l (one descriptor row per feature) and,
+ * per point feature, P (3-D, camera frame) and pl (pixel); per line feature sP, eP (3-D endpoints) and
+ * le (normalised image line). The counts are those given to plslam_add_keyframe; an array of a kind
+ * with no feature may be NULL. desc_bytes as in plba_match_batch. */
+int plslam_set_keyframe_features(plslam_map *m, int32_t kf_idx, int32_t desc_bytes, const uint8_t *pdesc,
+                                 const double *pt_P, const double *pt_pl, const uint8_t *ldesc, const double *ls_sP,
+                                 const double *ls_eP, const double *ls_le);
+/* Matcher hook, in the style of plslam_set_lcpose_solver: NULL = plba_desc_match. */
+typedef int (*plslam_match_fn)(void *user, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
+int plslam_set_match_fn(plslam_map *m, plslam_match_fn fn, void *user);
+typedef struct plslam_match_params {
+    float   min_ratio_12_p, min_ratio_12_l; /* SlamConfig::minRatio12P() / minRatio12L(), 0.9 (src2/config.cpp:60,68) */
+    int32_t best_lr;                        /* Config::bestLRMatches(), 1 (src2/config.cpp:51)         */
+    int32_t has_points, has_lines;          /* SlamConfig::hasPoints() / hasLines(), 1                 */
+    int32_t pad;
+} plslam_match_params;
+/* loopClosure() with isLoopClosure(kf_prev, kf_curr) whole: one match call with two pairs (points,
+ * lines; a kind that is disabled or empty on either side, :4331 / :4357, is an empty pair), lc_points /
+ * lc_lines / lc_pt_idx / lc_ls_idx built in i1 order (:4336-4379), then as plslam_loop_closure_step.
+ * mp == NULL: the defaults. A bad keyframe index, or a keyframe whose features were not set, returns
+ * PLBA_E_INVALID and leaves the map untouched. */
+int plslam_loop_closure_step_kf(plslam_map *m, int32_t kf_prev_idx, int32_t kf_curr_idx, const plslam_match_params *mp,
+                                double lc_inlier_ratio, plslam_lc_stats *st);
+/* K candidates kf_prev_idx[0..n) for one new keyframe: one match call with 2n pairs, then one
+ * plba_lc_relative_pose call with the candidates that pass the gate. accepted [n], pose_inc [n][6]
+ * (zero where not accepted), n_matches [n][2] (points, lines); each may be NULL. No map state is
+ * changed. A bad keyframe index returns PLBA_E_INVALID. */
+int plslam_verify_loop_candidates(plslam_map *m, int32_t kf_curr_idx, int32_t n, const int32_t *kf_prev_idx,
+                                  const plslam_match_params *mp, double lc_inlier_ratio, int32_t *accepted,
+                                  double *pose_inc, int32_t *n_matches);
+/* tools/descmatch_bench.py only, not a product path: a single-threaded popcount restatement of
+ * plba_desc_match's semantics on the CPU, with the signature of the matcher hook. */
+int plslam_desc_match_cpu(void *user, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
 int plslam_get_lc_state(plslam_map *m, int32_t *state);
 /* lc_pose_list [n][6]; the kept index rows of loop `loop` (kind 1 points, 2 lines), [n][4] */
 int plslam_get_lc_pose_list(plslam_map *m, double *out, int32_t cap, int32_t *n);

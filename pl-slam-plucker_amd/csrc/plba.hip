@@ -29,6 +29,7 @@
 #include "plba_build.hpp"
 #include "plba_kernels.hpp"
 #include "plba_lcpose.hpp"
+#include "plba_match.hpp"
 #include "plba_plan.hpp"
 
 namespace plba {
@@ -151,6 +152,9 @@ struct plba_ctx {
     // host image (inputs up, results and inlier flags down), kept across calls
     char *lc_mem = nullptr, *lc_host = nullptr;
     size_t lc_cap = 0, lc_host_cap = 0;
+    // descriptor matching (plba_desc_match): the same, a block of its own
+    char *dm_mem = nullptr, *dm_host = nullptr;
+    size_t dm_cap = 0, dm_host_cap = 0;
 
     void set_error(const char *fmt, ...) {
         char buf[512];
@@ -1979,6 +1983,8 @@ int plba_destroy(plba_ctx *ctx) {
     if (ctx->pgo_hout) (void)hipHostFree(ctx->pgo_hout);
     if (ctx->lc_mem) (void)hipFreeAsync(ctx->lc_mem, ctx->stream);
     if (ctx->lc_host) (void)hipHostFree(ctx->lc_host);
+    if (ctx->dm_mem) (void)hipFreeAsync(ctx->dm_mem, ctx->stream);
+    if (ctx->dm_host) (void)hipHostFree(ctx->dm_host);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
     if (ctx->comm.hbuf) (void)hipHostFree(ctx->comm.hbuf);
     if (ctx->comm.nccl) (void)ncclCommDestroy(ctx->comm.nccl);
@@ -2963,6 +2969,115 @@ int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_
     memcpy(out, h + o_out, sizeof(plba_lcpose_out) * (size_t)n);
     if (pt_inlier && np) memcpy(pt_inlier, h + o_pin, np);
     if (ln_inlier && nl) memcpy(ln_inlier, h + o_lin, nl);
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- descriptor matching
+// StVO::match / matchNNR (src2/matching.cpp:41-91) for a batch of descriptor-set pairs: one upload,
+// k_desc_nn (both directions of every pair) and k_desc_cross (csrc/plba_match.hpp), one read-back.
+int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
+    if (!ctx) return PLBA_E_INVALID;
+    if (!b || b->n < 0) {
+        ctx->set_error("descriptor matching: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    const int n = b->n;
+    if (n == 0) return PLBA_OK;
+    if (b->desc_bytes < 4 || b->desc_bytes > 64 || b->desc_bytes % 4) {
+        ctx->set_error("descriptor matching: desc_bytes %d is no multiple of 4 in [4, 64]", b->desc_bytes);
+        return PLBA_E_INVALID;
+    }
+    if (!b->off1 || !b->off2 || !b->nnr || !n_matches) {
+        ctx->set_error("descriptor matching: NULL off1 / off2 / nnr / n_matches");
+        return PLBA_E_INVALID;
+    }
+    int max_rows = 0;
+    for (const int32_t *off : {b->off1, b->off2}) {
+        if (off[0] < 0) {
+            ctx->set_error("descriptor matching: negative row offset");
+            return PLBA_E_INVALID;
+        }
+        for (int k = 0; k < n; ++k) {
+            if (off[k + 1] < off[k]) {
+                ctx->set_error("descriptor matching: row offsets decrease at pair %d", k);
+                return PLBA_E_INVALID;
+            }
+            max_rows = std::max(max_rows, off[k + 1] - off[k]);
+        }
+    }
+    if ((max_rows + kDmNT - 1) / kDmNT > 65535) {  // the row tiles are the grid's second dimension
+        ctx->set_error("descriptor matching: a set of %d rows is more than %d", max_rows, 65535 * kDmNT);
+        return PLBA_E_INVALID;
+    }
+    const size_t n1 = (size_t)b->off1[n], n2 = (size_t)b->off2[n], db = (size_t)b->desc_bytes;
+    if ((n1 && (!b->desc1 || !matches_12)) || (n2 && !b->desc2)) {
+        ctx->set_error("descriptor matching: NULL desc1 / desc2 / matches_12");
+        return PLBA_E_INVALID;
+    }
+    (void)hipSetDevice(ctx->opts.device);
+    // one block, the same layout on the device and in pinned host memory:
+    //   inputs  off1 | off2 | nnr | desc1 | desc2        (host -> device)
+    //   outputs matches_12 | n_matches                    (device -> host)
+    //   scratch nn12 | nn21                               (device only)
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_off1 = 0, o_off2 = o_off1 + al(sizeof(int32_t) * (n + 1)), o_nnr = o_off2 + al(sizeof(int32_t) * (n + 1)),
+                 o_d1 = o_nnr + al(sizeof(float) * n), o_d2 = o_d1 + al(db * n1), o_m12 = o_d2 + al(db * n2),
+                 o_cnt = o_m12 + al(sizeof(int32_t) * n1), o_nn12 = o_cnt + al(sizeof(int32_t) * n),
+                 o_nn21 = o_nn12 + al(sizeof(int32_t) * n1), tot = o_nn21 + al(sizeof(int32_t) * n2);
+    if (tot > ctx->dm_cap) {
+        if (ctx->dm_mem) (void)hipFreeAsync(ctx->dm_mem, ctx->stream);  // stream-ordered, as the relative pose's block
+        ctx->dm_mem = nullptr;
+        ctx->dm_cap = 0;
+        if (hipMallocAsync((void **)&ctx->dm_mem, tot, ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->set_error("descriptor matching: cannot allocate %zu bytes", tot);
+            return PLBA_E_NOMEM;
+        }
+        ctx->dm_cap = tot;
+    }
+    if (o_nn12 > ctx->dm_host_cap) {
+        if (ctx->dm_host) (void)hipHostFree(ctx->dm_host);
+        ctx->dm_host = nullptr;
+        ctx->dm_host_cap = 0;
+        if (hipHostMalloc((void **)&ctx->dm_host, o_nn12) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->set_error("descriptor matching: cannot allocate %zu bytes of pinned memory", o_nn12);
+            return PLBA_E_NOMEM;
+        }
+        ctx->dm_host_cap = o_nn12;
+    }
+    char *h = ctx->dm_host, *dv = ctx->dm_mem;
+    memcpy(h + o_off1, b->off1, sizeof(int32_t) * (n + 1));
+    memcpy(h + o_off2, b->off2, sizeof(int32_t) * (n + 1));
+    memcpy(h + o_nnr, b->nnr, sizeof(float) * n);
+    if (n1) memcpy(h + o_d1, b->desc1, db * n1);
+    if (n2) memcpy(h + o_d2, b->desc2, db * n2);
+    hipStream_t s = ctx->stream;
+    PLBA_CHECK(hipMemcpyAsync(dv, h, o_m12, hipMemcpyHostToDevice, s));
+    DmDev D{};
+    D.off1 = (const int32_t *)(dv + o_off1);
+    D.off2 = (const int32_t *)(dv + o_off2);
+    D.nnr = (const float *)(dv + o_nnr);
+    D.desc1 = (const uint32_t *)(dv + o_d1);
+    D.desc2 = (const uint32_t *)(dv + o_d2);
+    D.m12 = (int32_t *)(dv + o_m12);
+    D.count = (int32_t *)(dv + o_cnt);
+    D.nn12 = (int32_t *)(dv + o_nn12);
+    D.nn21 = (int32_t *)(dv + o_nn21);
+    D.n = n;
+    D.dwords = b->desc_bytes / 4;
+    D.best_lr = b->best_lr != 0;
+    if (max_rows > 0) {  // a workgroup past its pair's rows in its direction returns at once
+        const dim3 grid(n, (max_rows + kDmNT - 1) / kDmNT, 2);
+        if (D.dwords <= 8) hipLaunchKernelGGL(k_desc_nn<8>, grid, dim3(kDmNT), 0, s, D);
+        else hipLaunchKernelGGL(k_desc_nn<16>, grid, dim3(kDmNT), 0, s, D);
+        PLBA_LAUNCHED(ctx, "k_desc_nn");
+    }
+    hipLaunchKernelGGL(k_desc_cross, dim3(n), dim3(kDmNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_desc_cross");
+    PLBA_CHECK(hipMemcpyAsync(h + o_m12, dv + o_m12, o_nn12 - o_m12, hipMemcpyDeviceToHost, s));
+    PLBA_CHECK(hipStreamSynchronize(s));
+    if (n1) memcpy(matches_12, h + o_m12, sizeof(int32_t) * n1);
+    memcpy(n_matches, h + o_cnt, sizeof(int32_t) * n);
     return PLBA_OK;
 }
 

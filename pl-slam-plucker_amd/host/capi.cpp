@@ -325,6 +325,23 @@ int plslam_set_lcpose_params(plslam_map *m, const plba_lcpose_params *p) {
     return PLBA_OK;
 }
 
+namespace {
+void export_lc_stats(const LcStats &st, plslam_lc_stats *stats) {
+    stats->is_candidate = st.is_candidate; stats->ratio_ok = st.ratio_ok;
+    stats->accepted = st.accepted; stats->conditions = st.conditions;
+    stats->n_inl_pt = st.n_inl_pt; stats->n_inl_ln = st.n_inl_ln;
+    stats->state_before = st.state_before; stats->state_after = st.state_after;
+    stats->pgo_ran = st.pgo_ran; stats->pad = 0;
+    stats->inl_ratio_pt = st.inl_ratio_pt; stats->inl_ratio_ls = st.inl_ratio_ls;
+    stats->e = st.e; stats->unc = st.unc; stats->t = st.t; stats->r_deg = st.r_deg; stats->pose_ms = st.pose_ms;
+    const PgoStats &g = st.pgo;
+    stats->pgo.kf_prev_idx = g.kf_prev_idx; stats->pgo.kf_curr_idx = g.kf_curr_idx;
+    stats->pgo.n_vertices = g.n_vertices; stats->pgo.n_fixed = g.n_fixed; stats->pgo.n_edges = g.n_edges;
+    stats->pgo.n_loop_edges = g.n_loop_edges; stats->pgo.iterations = g.iterations; stats->pgo.trials = g.trials;
+    stats->pgo.chi2_initial = g.chi2_initial; stats->pgo.chi2_final = g.chi2_final; stats->pgo.solve_ms = g.solve_ms;
+}
+}  // namespace
+
 int plslam_loop_closure_step(plslam_map *m, const plslam_lc_candidate *c, double lc_inlier_ratio, plslam_lc_stats *stats) {
     if (!m) return PLBA_E_INVALID;
     LcCandidate cc;
@@ -339,21 +356,69 @@ int plslam_loop_closure_step(plslam_map *m, const plslam_lc_candidate *c, double
     LcStats st;
     const int rc = m->mh.loopClosureStep(c ? &cc : nullptr, lc_inlier_ratio, &st);
     if (rc) return rc;
-    if (stats) {
-        stats->is_candidate = st.is_candidate; stats->ratio_ok = st.ratio_ok;
-        stats->accepted = st.accepted; stats->conditions = st.conditions;
-        stats->n_inl_pt = st.n_inl_pt; stats->n_inl_ln = st.n_inl_ln;
-        stats->state_before = st.state_before; stats->state_after = st.state_after;
-        stats->pgo_ran = st.pgo_ran; stats->pad = 0;
-        stats->inl_ratio_pt = st.inl_ratio_pt; stats->inl_ratio_ls = st.inl_ratio_ls;
-        stats->e = st.e; stats->unc = st.unc; stats->t = st.t; stats->r_deg = st.r_deg; stats->pose_ms = st.pose_ms;
-        const PgoStats &g = st.pgo;
-        stats->pgo.kf_prev_idx = g.kf_prev_idx; stats->pgo.kf_curr_idx = g.kf_curr_idx;
-        stats->pgo.n_vertices = g.n_vertices; stats->pgo.n_fixed = g.n_fixed; stats->pgo.n_edges = g.n_edges;
-        stats->pgo.n_loop_edges = g.n_loop_edges; stats->pgo.iterations = g.iterations; stats->pgo.trials = g.trials;
-        stats->pgo.chi2_initial = g.chi2_initial; stats->pgo.chi2_final = g.chi2_final; stats->pgo.solve_ms = g.solve_ms;
-    }
+    if (stats) export_lc_stats(st, stats);
     return PLBA_OK;
+}
+
+int plslam_set_keyframe_features(plslam_map *m, int32_t kf_idx, int32_t desc_bytes, const uint8_t *pdesc,
+                                 const double *pt_P, const double *pt_pl, const uint8_t *ldesc, const double *ls_sP,
+                                 const double *ls_eP, const double *ls_le) {
+    if (!m || !slot_ok(m->mh.map_keyframes, kf_idx) || desc_bytes < 4 || desc_bytes > 64 || desc_bytes % 4)
+        return PLBA_E_INVALID;
+    StereoFrame &f = m->mh.map_keyframes[kf_idx]->stereo_frame;
+    const size_t np = f.stereo_pt_idx.size(), nl = f.stereo_ls_idx.size(), db = (size_t)desc_bytes;
+    if ((np && (!pdesc || !pt_P || !pt_pl)) || (nl && (!ldesc || !ls_sP || !ls_eP || !ls_le))) return PLBA_E_INVALID;
+    f.desc_bytes = desc_bytes;
+    f.pdesc_l.assign(pdesc, pdesc + (np ? np * db : 0));
+    f.pt_P.assign(pt_P, pt_P + (np ? 3 * np : 0));
+    f.pt_pl.assign(pt_pl, pt_pl + (np ? 2 * np : 0));
+    f.ldesc_l.assign(ldesc, ldesc + (nl ? nl * db : 0));
+    f.ls_sP.assign(ls_sP, ls_sP + (nl ? 3 * nl : 0));
+    f.ls_eP.assign(ls_eP, ls_eP + (nl ? 3 * nl : 0));
+    f.ls_le.assign(ls_le, ls_le + (nl ? 3 * nl : 0));
+    f.has_features = true;
+    return PLBA_OK;
+}
+
+int plslam_set_match_fn(plslam_map *m, plslam_match_fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    m->mh.setMatchFn(fn, user);
+    return PLBA_OK;
+}
+
+namespace {
+MatchParams match_params(const plslam_match_params *mp) {
+    MatchParams p;
+    if (mp) {
+        p.min_ratio_12_p = mp->min_ratio_12_p; p.min_ratio_12_l = mp->min_ratio_12_l;
+        p.best_lr = mp->best_lr != 0; p.has_points = mp->has_points != 0; p.has_lines = mp->has_lines != 0;
+    }
+    return p;
+}
+
+}  // namespace
+
+int plslam_loop_closure_step_kf(plslam_map *m, int32_t kf_prev_idx, int32_t kf_curr_idx, const plslam_match_params *mp,
+                                double lc_inlier_ratio, plslam_lc_stats *stats) {
+    if (!m) return PLBA_E_INVALID;
+    LcStats st;
+    const int rc = m->mh.isLoopClosure(kf_prev_idx, kf_curr_idx, match_params(mp), lc_inlier_ratio, &st);
+    if (rc) return rc;
+    if (stats) export_lc_stats(st, stats);
+    return PLBA_OK;
+}
+
+int plslam_verify_loop_candidates(plslam_map *m, int32_t kf_curr_idx, int32_t n, const int32_t *kf_prev_idx,
+                                  const plslam_match_params *mp, double lc_inlier_ratio, int32_t *accepted,
+                                  double *pose_inc, int32_t *n_matches) {
+    if (!m) return PLBA_E_INVALID;
+    return m->mh.verifyLoopCandidates(kf_curr_idx, n, kf_prev_idx, match_params(mp), lc_inlier_ratio, accepted, pose_inc,
+                                      n_matches);
+}
+
+int plslam_desc_match_cpu(void *user, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
+    (void)user;
+    return descMatchCpu(b, matches_12, n_matches);
 }
 
 int plslam_get_lc_state(plslam_map *m, int32_t *state) {

@@ -3,10 +3,14 @@
 // solve (plba_pgo_optimize), with the g2o SE3Quat conversions the reference goes through
 // (SE3Quat::exp / log, SE3Quat <-> Isometry3 via Eigen's quaternion); and of MapHandler::loopClosure()
 // (:4053-4116) from the candidate on: the inlier-ratio gate of isLoopClosure, the relative pose on
-// the GPU (plba_lc_relative_pose), the loop lists and the LC_IDLE / LC_ACTIVE / LC_READY states.
+// the GPU (plba_lc_relative_pose), the loop lists and the LC_IDLE / LC_ACTIVE / LC_READY states;
+// and of isLoopClosure (:4303-4411) from two keyframe indices, its descriptor matching
+// (StVO::match, src2/matching.cpp:63-91) on the GPU (plba_desc_match).
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
+#include <cstring>
 #include <map>
 
 #include "plslam_map.hpp"
@@ -350,19 +354,8 @@ int MapHandler::loopClosureStep(const LcCandidate *c, double lc_inlier_ratio, Lc
             setError("loop closure: candidate with negative counts or NULL feature arrays");
             return PLBA_E_INVALID;
         }
-        // the matching runs only for an enabled kind with features in both keyframes (:4331, :4357)
-        const bool use_pt = c->has_points && c->n_pt_0 > 0 && c->n_pt_1 > 0;
-        const bool use_ls = c->has_lines && c->n_ls_0 > 0 && c->n_ls_1 > 0;
-        const int common_pt = use_pt ? c->n_pt : 0, common_ls = use_ls ? c->n_ln : 0;
-        // :4384-4385 — a zero count gives NaN or 0 here, and the comparisons below are then false
-        const double inl_ratio_pt = std::max(100.0 * common_pt / c->n_pt_0, 100.0 * common_pt / c->n_pt_1);
-        const double inl_ratio_ls = std::max(100.0 * common_ls / c->n_ls_0, 100.0 * common_ls / c->n_ls_1);
-        st.inl_ratio_pt = inl_ratio_pt;
-        st.inl_ratio_ls = inl_ratio_ls;
-        bool cond = false;
-        if (c->has_points && c->has_lines) cond = inl_ratio_pt > lc_inlier_ratio && inl_ratio_ls > lc_inlier_ratio;
-        else if (c->has_points) cond = inl_ratio_pt > lc_inlier_ratio;
-        else if (c->has_lines) cond = inl_ratio_ls > lc_inlier_ratio;
+        int common_pt, common_ls;
+        const bool cond = inlierRatioGate(*c, lc_inlier_ratio, common_pt, common_ls, st.inl_ratio_pt, st.inl_ratio_ls);
         st.ratio_ok = cond ? 1 : 0;
         if (cond) {
             const int32_t pt_off[2] = {0, common_pt}, ln_off[2] = {0, common_ls};
@@ -376,15 +369,7 @@ int MapHandler::loopClosureStep(const LcCandidate *c, double lc_inlier_ratio, Lc
             plba_lcpose_out o{};
             std::vector<uint8_t> pin((size_t)std::max(common_pt, 1), 0), lin((size_t)std::max(common_ls, 1), 0);
             const auto t0 = clk::now();
-            int rc;
-            if (lcpose_fn_) {
-                rc = lcpose_fn_(lcpose_user_, &b, &lcpose_params, &o, pin.data(), lin.data());
-                if (rc) setError("relative-pose solver hook returned %d", rc);
-            } else {
-                rc = ensureCtx();
-                if (!rc) rc = plba_lc_relative_pose(ctx_, &b, &lcpose_params, &o, pin.data(), lin.data());
-                if (rc) setError("plba: %s", plba_last_error(ctx_));
-            }
+            const int rc = lcRelativePose(b, &o, pin.data(), lin.data());
             if (rc) return rc;
             st.pose_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
             st.accepted = o.accepted;
@@ -425,6 +410,261 @@ int MapHandler::loopClosureStep(const LcCandidate *c, double lc_inlier_ratio, Lc
     }
     st.state_after = lc_state;
     if (stats) *stats = st;
+    return PLBA_OK;
+}
+
+// The tail of isLoopClosure before the relative pose (:4384-4402).
+bool MapHandler::inlierRatioGate(const LcCandidate &c, double lc_inlier_ratio, int &common_pt, int &common_ls,
+                                 double &ratio_pt, double &ratio_ls) {
+    // the matching runs only for an enabled kind with features in both keyframes (:4331, :4357)
+    const bool use_pt = c.has_points && c.n_pt_0 > 0 && c.n_pt_1 > 0;
+    const bool use_ls = c.has_lines && c.n_ls_0 > 0 && c.n_ls_1 > 0;
+    common_pt = use_pt ? c.n_pt : 0;
+    common_ls = use_ls ? c.n_ln : 0;
+    // :4384-4385 — a zero count gives NaN or 0 here, and the comparisons below are then false
+    ratio_pt = std::max(100.0 * common_pt / c.n_pt_0, 100.0 * common_pt / c.n_pt_1);
+    ratio_ls = std::max(100.0 * common_ls / c.n_ls_0, 100.0 * common_ls / c.n_ls_1);
+    if (c.has_points && c.has_lines) return ratio_pt > lc_inlier_ratio && ratio_ls > lc_inlier_ratio;
+    if (c.has_points) return ratio_pt > lc_inlier_ratio;
+    if (c.has_lines) return ratio_ls > lc_inlier_ratio;
+    return false;
+}
+
+int MapHandler::lcRelativePose(const plba_lcpose_batch &b, plba_lcpose_out *out, uint8_t *pin, uint8_t *lin) {
+    int rc;
+    if (lcpose_fn_) {
+        rc = lcpose_fn_(lcpose_user_, &b, &lcpose_params, out, pin, lin);
+        if (rc) setError("relative-pose solver hook returned %d", rc);
+    } else {
+        rc = ensureCtx();
+        if (!rc) {
+            rc = plba_lc_relative_pose(ctx_, &b, &lcpose_params, out, pin, lin);
+            if (rc) setError("plba: %s", plba_last_error(ctx_));
+        }
+    }
+    return rc;
+}
+
+// What isLoopClosure holds after its matching (:4327-4380) for one pair of keyframes.
+struct MapHandler::LcBuilt {
+    std::vector<double> pt_P, pt_obs, ln_sP, ln_eP, ln_le;
+    std::vector<int32_t> pt_idx, ls_idx;
+    int n_pt_0 = 0, n_pt_1 = 0, n_ls_0 = 0, n_ls_1 = 0, common_pt = 0, common_ls = 0;
+    LcCandidate candidate(int kf0, int kf1, const MatchParams &mp) const {
+        LcCandidate c;
+        c.kf_prev_idx = kf0; c.kf_curr_idx = kf1;
+        c.n_pt_0 = n_pt_0; c.n_pt_1 = n_pt_1; c.n_ls_0 = n_ls_0; c.n_ls_1 = n_ls_1;
+        c.has_points = mp.has_points; c.has_lines = mp.has_lines;
+        c.n_pt = common_pt; c.n_ln = common_ls;
+        c.pt_P = pt_P.data(); c.pt_obs = pt_obs.data();
+        c.ln_sP = ln_sP.data(); c.ln_eP = ln_eP.data(); c.ln_le = ln_le.data();
+        c.pt_idx = pt_idx.data(); c.ls_idx = ls_idx.data();
+        return c;
+    }
+};
+
+int MapHandler::buildLoopCandidates(int kf1_idx, int n, const int32_t *kf_prev_idx, const MatchParams &mp,
+                                    std::vector<LcBuilt> &out) {
+    auto frame = [&](int idx) -> const StereoFrame * {
+        if (idx < 0 || idx >= (int)map_keyframes.size() || !map_keyframes[idx]) return nullptr;
+        const StereoFrame &f = map_keyframes[idx]->stereo_frame;
+        return f.has_features ? &f : nullptr;
+    };
+    const StereoFrame *f1 = frame(kf1_idx);
+    if (n < 0 || (n && !kf_prev_idx) || !f1) {
+        setError("loop closure: keyframe %d does not exist or has no features set", kf1_idx);
+        return PLBA_E_INVALID;
+    }
+    for (int k = 0; k < n; ++k) {
+        const StereoFrame *f0 = frame(kf_prev_idx[k]);
+        if (!f0 || f0->desc_bytes != f1->desc_bytes) {
+            setError("loop closure: keyframe %d does not exist, has no features set or has descriptors of another size",
+                     kf_prev_idx[k]);
+            return PLBA_E_INVALID;
+        }
+    }
+    out.assign((size_t)n, LcBuilt{});
+    if (n == 0) return PLBA_OK;
+    // pairs 2k (points) and 2k + 1 (lines) of candidate k; desc1 = kf0 (:4334, :4360). A kind that
+    // is disabled or empty on either side is not matched (:4331, :4357): an empty pair.
+    const size_t db = (size_t)f1->desc_bytes;
+    const int n_pt_1 = (int)f1->stereo_pt_idx.size(), n_ls_1 = (int)f1->stereo_ls_idx.size();
+    std::vector<int32_t> off1(2 * (size_t)n + 1, 0), off2(2 * (size_t)n + 1, 0), cnt(2 * (size_t)n, 0);
+    std::vector<float> nnr(2 * (size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const StereoFrame &f0 = *frame(kf_prev_idx[k]);
+        const int n_pt_0 = (int)f0.stereo_pt_idx.size(), n_ls_0 = (int)f0.stereo_ls_idx.size();
+        const bool use_pt = mp.has_points && n_pt_0 > 0 && n_pt_1 > 0, use_ls = mp.has_lines && n_ls_0 > 0 && n_ls_1 > 0;
+        off1[2 * k + 1] = off1[2 * k] + (use_pt ? n_pt_0 : 0);
+        off2[2 * k + 1] = off2[2 * k] + (use_pt ? n_pt_1 : 0);
+        off1[2 * k + 2] = off1[2 * k + 1] + (use_ls ? n_ls_0 : 0);
+        off2[2 * k + 2] = off2[2 * k + 1] + (use_ls ? n_ls_1 : 0);
+        nnr[2 * k] = mp.min_ratio_12_p;
+        nnr[2 * k + 1] = mp.min_ratio_12_l;
+    }
+    std::vector<uint8_t> d1((size_t)off1[2 * n] * db + 1), d2((size_t)off2[2 * n] * db + 1);
+    for (int k = 0; k < n; ++k) {
+        const StereoFrame &f0 = *frame(kf_prev_idx[k]);
+        if (off1[2 * k + 1] > off1[2 * k]) {
+            std::memcpy(&d1[(size_t)off1[2 * k] * db], f0.pdesc_l.data(), f0.pdesc_l.size());
+            std::memcpy(&d2[(size_t)off2[2 * k] * db], f1->pdesc_l.data(), f1->pdesc_l.size());
+        }
+        if (off1[2 * k + 2] > off1[2 * k + 1]) {
+            std::memcpy(&d1[(size_t)off1[2 * k + 1] * db], f0.ldesc_l.data(), f0.ldesc_l.size());
+            std::memcpy(&d2[(size_t)off2[2 * k + 1] * db], f1->ldesc_l.data(), f1->ldesc_l.size());
+        }
+    }
+    std::vector<int32_t> m12((size_t)off1[2 * n] + 1, -1);
+    plba_match_batch b{};
+    b.n = 2 * n;
+    b.desc_bytes = (int32_t)db;
+    b.off1 = off1.data(); b.off2 = off2.data();
+    b.desc1 = d1.data(); b.desc2 = d2.data();
+    b.nnr = nnr.data();
+    b.best_lr = mp.best_lr ? 1 : 0;
+    int rc;
+    if (match_fn_) {
+        rc = match_fn_(match_user_, &b, m12.data(), cnt.data());
+        if (rc) setError("matcher hook returned %d", rc);
+    } else {
+        rc = ensureCtx();
+        if (!rc) {
+            rc = plba_desc_match(ctx_, &b, m12.data(), cnt.data());
+            if (rc) setError("plba: %s", plba_last_error(ctx_));
+        }
+    }
+    if (rc) return rc;
+    for (int k = 0; k < n; ++k) {
+        const StereoFrame &f0 = *frame(kf_prev_idx[k]);
+        LcBuilt &o = out[k];
+        o.n_pt_0 = (int)f0.stereo_pt_idx.size(); o.n_pt_1 = n_pt_1;
+        o.n_ls_0 = (int)f0.stereo_ls_idx.size(); o.n_ls_1 = n_ls_1;
+        o.common_pt = cnt[2 * k];      // match()'s return value (:4334)
+        o.common_ls = cnt[2 * k + 1];  // (:4360)
+        for (int i1 = 0; i1 < off1[2 * k + 1] - off1[2 * k]; ++i1) {  // (:4336-4352)
+            const int i2 = m12[off1[2 * k] + i1];
+            if (i2 < 0) continue;
+            o.pt_P.insert(o.pt_P.end(), &f0.pt_P[3 * i1], &f0.pt_P[3 * i1] + 3);
+            o.pt_obs.insert(o.pt_obs.end(), &f1->pt_pl[2 * i2], &f1->pt_pl[2 * i2] + 2);
+            const int32_t row[4] = {f0.stereo_pt_idx[i1], i1, f1->stereo_pt_idx[i2], i2};
+            o.pt_idx.insert(o.pt_idx.end(), row, row + 4);
+        }
+        for (int i1 = 0; i1 < off1[2 * k + 2] - off1[2 * k + 1]; ++i1) {  // (:4362-4379)
+            const int i2 = m12[off1[2 * k + 1] + i1];
+            if (i2 < 0) continue;
+            o.ln_sP.insert(o.ln_sP.end(), &f0.ls_sP[3 * i1], &f0.ls_sP[3 * i1] + 3);
+            o.ln_eP.insert(o.ln_eP.end(), &f0.ls_eP[3 * i1], &f0.ls_eP[3 * i1] + 3);
+            o.ln_le.insert(o.ln_le.end(), &f1->ls_le[3 * i2], &f1->ls_le[3 * i2] + 3);
+            const int32_t row[4] = {f0.stereo_ls_idx[i1], i1, f1->stereo_ls_idx[i2], i2};
+            o.ls_idx.insert(o.ls_idx.end(), row, row + 4);
+        }
+        if ((int)o.pt_idx.size() != 4 * o.common_pt || (int)o.ls_idx.size() != 4 * o.common_ls) {
+            setError("matcher: the counts of candidate %d do not equal its matches", k);
+            return PLBA_E_INVALID;
+        }
+    }
+    return PLBA_OK;
+}
+
+int MapHandler::isLoopClosure(int kf0_idx, int kf1_idx, const MatchParams &mp, double lc_inlier_ratio, LcStats *stats) {
+    std::vector<LcBuilt> built;
+    const int32_t prev = kf0_idx;
+    const int rc = buildLoopCandidates(kf1_idx, 1, &prev, mp, built);
+    if (rc) return rc;
+    const LcCandidate c = built[0].candidate(kf0_idx, kf1_idx, mp);
+    return loopClosureStep(&c, lc_inlier_ratio, stats);
+}
+
+int MapHandler::verifyLoopCandidates(int kf_curr_idx, int n, const int32_t *kf_prev_idx, const MatchParams &mp,
+                                     double lc_inlier_ratio, int32_t *accepted, double *pose_inc, int32_t *n_matches) {
+    std::vector<LcBuilt> built;
+    int rc = buildLoopCandidates(kf_curr_idx, n, kf_prev_idx, mp, built);
+    if (rc) return rc;
+    for (int k = 0; k < n; ++k) {
+        if (accepted) accepted[k] = 0;
+        for (int j = 0; j < 6 && pose_inc; ++j) pose_inc[6 * k + j] = 0.0;
+        if (n_matches) {
+            n_matches[2 * k] = built[k].common_pt;
+            n_matches[2 * k + 1] = built[k].common_ls;
+        }
+    }
+    // the candidates that pass the gate, concatenated for one relative-pose call
+    std::vector<int> passed;
+    std::vector<int32_t> pt_off{0}, ln_off{0};
+    std::vector<double> P, obs, sP, eP, le;
+    for (int k = 0; k < n; ++k) {
+        const LcBuilt &o = built[k];
+        const LcCandidate c = o.candidate(kf_prev_idx[k], kf_curr_idx, mp);
+        int common_pt, common_ls;
+        double rp, rl;
+        if (!inlierRatioGate(c, lc_inlier_ratio, common_pt, common_ls, rp, rl)) continue;
+        passed.push_back(k);
+        P.insert(P.end(), o.pt_P.begin(), o.pt_P.begin() + 3 * common_pt);
+        obs.insert(obs.end(), o.pt_obs.begin(), o.pt_obs.begin() + 2 * common_pt);
+        sP.insert(sP.end(), o.ln_sP.begin(), o.ln_sP.begin() + 3 * common_ls);
+        eP.insert(eP.end(), o.ln_eP.begin(), o.ln_eP.begin() + 3 * common_ls);
+        le.insert(le.end(), o.ln_le.begin(), o.ln_le.begin() + 3 * common_ls);
+        pt_off.push_back(pt_off.back() + common_pt);
+        ln_off.push_back(ln_off.back() + common_ls);
+    }
+    if (passed.empty()) return PLBA_OK;
+    plba_lcpose_batch b{};
+    b.n = (int32_t)passed.size();
+    b.pt_off = pt_off.data(); b.ln_off = ln_off.data();
+    b.pt_P = P.data(); b.pt_obs = obs.data();
+    b.ln_sP = sP.data(); b.ln_eP = eP.data(); b.ln_le = le.data();
+    b.fx = fx_; b.fy = fy_; b.cx = cx_; b.cy = cy_;
+    std::vector<plba_lcpose_out> o(passed.size());
+    std::vector<uint8_t> pin((size_t)pt_off.back() + 1, 0), lin((size_t)ln_off.back() + 1, 0);
+    rc = lcRelativePose(b, o.data(), pin.data(), lin.data());
+    if (rc) return rc;
+    for (size_t j = 0; j < passed.size(); ++j) {
+        if (!o[j].accepted) continue;
+        if (accepted) accepted[passed[j]] = 1;
+        for (int i = 0; i < 6 && pose_inc; ++i) pose_inc[6 * passed[j] + i] = o[j].pose_inc[i];
+    }
+    return PLBA_OK;
+}
+
+// tools/descmatch_bench.py only: the semantics of plba_desc_match (include/plba.h) restated with
+// popcounts, single-threaded. Not a product path.
+int descMatchCpu(const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
+    if (!b || b->n < 0 || b->desc_bytes < 4 || b->desc_bytes > 64 || b->desc_bytes % 4) return PLBA_E_INVALID;
+    const int dw = b->desc_bytes / 4;
+    auto nearest = [&](const uint8_t *q, int nq, const uint8_t *t, int nt, float nnr, std::vector<int32_t> &m) {
+        m.assign((size_t)nq, -1);
+        for (int i = 0; i < nq && nt >= 2; ++i) {
+            int d0 = INT_MAX, d1 = INT_MAX, i0 = -1;
+            for (int j = 0; j < nt; ++j) {
+                int d = 0;
+                for (int c = 0; c < dw; ++c) {
+                    uint32_t x, y;
+                    std::memcpy(&x, q + (size_t)i * b->desc_bytes + 4 * c, 4);
+                    std::memcpy(&y, t + (size_t)j * b->desc_bytes + 4 * c, 4);
+                    d += __builtin_popcount(x ^ y);
+                }
+                if (d < d0) { d1 = d0; d0 = d; i0 = j; }
+                else if (d < d1) d1 = d;
+            }
+            const float lhs = (float)d0, rhs = (float)d1 * nnr;
+            if (lhs < rhs) m[i] = i0;
+        }
+    };
+    std::vector<int32_t> m12, m21;
+    for (int k = 0; k < b->n; ++k) {
+        const int o1 = b->off1[k], n1 = b->off1[k + 1] - o1, o2 = b->off2[k], n2 = b->off2[k + 1] - o2;
+        const uint8_t *a = b->desc1 + (size_t)o1 * b->desc_bytes, *c = b->desc2 + (size_t)o2 * b->desc_bytes;
+        nearest(a, n1, c, n2, b->nnr[k], m12);
+        if (b->best_lr) nearest(c, n2, a, n1, b->nnr[k], m21);
+        int cnt = 0;
+        for (int i1 = 0; i1 < n1; ++i1) {
+            int i2 = m12[i1];
+            if (b->best_lr && i2 >= 0 && m21[i2] != i1) i2 = -1;
+            matches_12[o1 + i1] = i2;
+            cnt += i2 >= 0;
+        }
+        n_matches[k] = cnt;
+    }
     return PLBA_OK;
 }
 

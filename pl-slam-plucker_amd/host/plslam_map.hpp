@@ -59,6 +59,14 @@ using Desc = std::vector<uint8_t>;
 struct StereoFrame {
     std::vector<int> stereo_pt_idx;
     std::vector<int> stereo_ls_idx;
+    // what isLoopClosure reads (src/mapHandler.cpp:4334-4378): the descriptor matrices pdesc_l /
+    // ldesc_l, one row of desc_bytes per feature, and per point feature P and pl, per line feature
+    // sP, eP and le, as flat rows in feature order
+    bool has_features = false;
+    int desc_bytes = 32;
+    std::vector<uint8_t> pdesc_l, ldesc_l;
+    std::vector<double> pt_P, pt_pl;          // [n_pt][3], [n_pt][2]
+    std::vector<double> ls_sP, ls_eP, ls_le;  // [n_ls][3]
 };
 
 // include/keyFrame.h:50-71
@@ -186,6 +194,13 @@ struct PgoStats {
 using LcposeSolveFn = int (*)(void *user, const plba_lcpose_batch *b, const plba_lcpose_params *p, plba_lcpose_out *out,
                               uint8_t *pt_inlier, uint8_t *ln_inlier);
 using Vec4i = std::array<int, 4>;
+using MatchFn = int (*)(void *user, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
+
+// The configuration values isLoopClosure's matching reads (src2/config.cpp:46-47,51,60,68).
+struct MatchParams {
+    float min_ratio_12_p = 0.9f, min_ratio_12_l = 0.9f;
+    bool best_lr = true, has_points = true, has_lines = true;
+};
 
 // What isLoopClosure (src/mapHandler.cpp:4303-4411) has after its descriptor matching: the feature
 // counts of both keyframes and the matched features with their lc_pt_idx / lc_ls_idx rows.
@@ -268,12 +283,21 @@ class MapHandler {
     int lc_state = 0;  // LC_IDLE = 0
     enum { LC_IDLE = 0, LC_ACTIVE = 1, LC_READY = 2 };  // include/mapHandler.h:195-197
 
-    // src/mapHandler.cpp:4053-4116, loopClosure() after lookForLoopCandidates (DBoW2) and the
-    // descriptor matching of isLoopClosure (:4327-4380), both the caller's: the inlier-ratio gate
-    // (:4384-4409), computeRelativePoseRobustGN on the GPU (plba_lc_relative_pose), the lists and
-    // the LC_IDLE / LC_ACTIVE / LC_READY state machine, and on LC_READY the pose graph above.
-    // c == nullptr: lookForLoopCandidates found no candidate.
+    // src/mapHandler.cpp:4053-4116, loopClosure() after lookForLoopCandidates (DBoW2, the caller's)
+    // from a matched candidate: the inlier-ratio gate (:4384-4409), computeRelativePoseRobustGN on
+    // the GPU (plba_lc_relative_pose), the lists and the LC_IDLE / LC_ACTIVE / LC_READY state
+    // machine, and on LC_READY the pose graph above. c == nullptr: no candidate was found.
     int loopClosureStep(const LcCandidate *c, double lc_inlier_ratio, LcStats *stats = nullptr);
+    // The same with isLoopClosure (:4303-4411) whole, from two keyframe indices: the descriptor
+    // matching of :4334 / :4360 in one plba_desc_match call with two pairs (points, lines), then
+    // lc_points / lc_lines / lc_pt_idx / lc_ls_idx in i1 order (:4336-4379) into loopClosureStep.
+    int isLoopClosure(int kf0_idx, int kf1_idx, const MatchParams &mp, double lc_inlier_ratio, LcStats *stats = nullptr);
+    // K candidates for one new keyframe: one match call with 2K pairs, one relative-pose call with
+    // those that pass the gate. No map state is changed. accepted [n], pose_inc [n][6],
+    // n_matches [n][2]; each may be nullptr.
+    int verifyLoopCandidates(int kf_curr_idx, int n, const int32_t *kf_prev_idx, const MatchParams &mp,
+                             double lc_inlier_ratio, int32_t *accepted, double *pose_inc, int32_t *n_matches);
+    void setMatchFn(MatchFn fn, void *user) { match_fn_ = fn; match_user_ = user; }
     std::vector<std::vector<Vec4i>> lc_pt_idxs, lc_ls_idxs;  // inlier-filtered rows, one list per loop (:4078-4079)
     plba_lcpose_params lcpose_params{1e-7, 1.0, 0.01, 0.3, 1.5, 35.0, 5, 10, PLBA_LCPOSE_ROBUST_GN, 0};
     void setLcposeSolver(LcposeSolveFn fn, void *user) { lcpose_fn_ = fn; lcpose_user_ = user; }
@@ -330,6 +354,15 @@ class MapHandler {
     void *pgo_user_ = nullptr;
     LcposeSolveFn lcpose_fn_ = nullptr;
     void *lcpose_user_ = nullptr;
+    MatchFn match_fn_ = nullptr;
+    void *match_user_ = nullptr;
+    // the matched features of kf_prev_idx[0..n) against kf_curr_idx, by one match call
+    struct LcBuilt;
+    int buildLoopCandidates(int kf_curr_idx, int n, const int32_t *kf_prev_idx, const MatchParams &mp,
+                            std::vector<LcBuilt> &out);
+    static bool inlierRatioGate(const LcCandidate &c, double lc_inlier_ratio, int &common_pt, int &common_ls,
+                                double &ratio_pt, double &ratio_ls);
+    int lcRelativePose(const plba_lcpose_batch &b, plba_lcpose_out *out, uint8_t *pin, uint8_t *lin);
     int loopClosurePGO(bool ess, PgoStats *stats);
     std::string err_;
     // per-call scratch reused across LBA calls (capacity kept; see Window::clear)
@@ -346,5 +379,7 @@ Mat4 mul4(const Mat4 &A, const Mat4 &B);  // Matrix4d * Matrix4d
 Mat4 expmap_se3(const Vec6 &x);
 Vec6 logmap_se3(const Mat4 &T);
 int hamming(const Desc &a, const Desc &b);
+// tools/descmatch_bench.py only: plba_desc_match's semantics, single-threaded, on the CPU
+int descMatchCpu(const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
 
 }  // namespace plslam

@@ -331,3 +331,36 @@ def lcpose_out_to_dict(o: PlbaLcposeOut, pt_inlier, ln_inlier) -> dict:
                 x_inc=np.array(o.x_inc[:]), pose_inc=np.array(o.pose_inc[:]),
                 T_inc=np.array(o.T_inc[:]).reshape(3, 4), H=np.array(o.H[:]).reshape(6, 6),
                 pt_inlier=np.array(pt_inlier, np.uint8), ln_inlier=np.array(ln_inlier, np.uint8))
+
+
+# ---- descriptor matching (plba_match_batch / plba_desc_match)
+_fp = C.POINTER(C.c_float)
+
+
+class PlbaMatchBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("off1", _ip), ("off2", _ip), ("desc1", _bp),
+                ("desc2", _bp), ("nnr", _fp), ("best_lr", C.c_int32), ("pad", C.c_int32)]
+
+
+class MatchBatchView:
+    """Concatenates descriptor-set pairs [(desc1 [n1][desc_bytes] uint8, desc2 [n2][desc_bytes]), ...]
+    into contiguous arrays and the PlbaMatchBatch over them. ``nnr``: one ratio, or one per pair."""
+
+    def __init__(self, pairs, nnr, best_lr: bool = True, desc_bytes=None):
+        pairs = [(np.asarray(a, np.uint8), np.asarray(b, np.uint8)) for a, b in pairs]
+        if desc_bytes is None:
+            desc_bytes = next((x.shape[1] for p in pairs for x in p if x.ndim == 2 and x.shape[1]), 32)
+        pairs = [(a.reshape(-1, desc_bytes), b.reshape(-1, desc_bytes)) for a, b in pairs]
+        self.desc_bytes = int(desc_bytes)
+        empty = np.zeros((0, desc_bytes), np.uint8)
+        self.desc1 = np.ascontiguousarray(np.concatenate([a for a, _ in pairs] + [empty]))
+        self.desc2 = np.ascontiguousarray(np.concatenate([b for _, b in pairs] + [empty]))
+        self.off1 = np.zeros(len(pairs) + 1, np.int32)
+        self.off2 = np.zeros(len(pairs) + 1, np.int32)
+        self.off1[1:] = np.cumsum([len(a) for a, _ in pairs], dtype=np.int64)
+        self.off2[1:] = np.cumsum([len(b) for _, b in pairs], dtype=np.int64)
+        self.nnr = np.ascontiguousarray(np.broadcast_to(np.asarray(nnr, np.float32), (len(pairs),)))
+        self.struct = PlbaMatchBatch(
+            n=len(pairs), desc_bytes=self.desc_bytes, off1=_ptr(self.off1, _ip), off2=_ptr(self.off2, _ip),
+            desc1=_ptr(self.desc1, _bp), desc2=_ptr(self.desc2, _bp), nnr=_ptr(self.nnr, _fp),
+            best_lr=int(bool(best_lr)), pad=0)

@@ -31,6 +31,7 @@ EXPORTED = [
     "plba_hlm_default_params", "plba_hlm_lba",
     "plba_pgo_default_params", "plba_pgo_optimize",
     "plba_lcpose_default_params", "plba_lc_relative_pose",
+    "plba_desc_match",
 ]
 
 # int (*plba_host_allreduce_fn)(void *user, double *buf, int64_t n)
@@ -94,6 +95,7 @@ def load(path: Optional[str] = None):
     L.plba_lcpose_default_params.restype = None
     L.plba_lc_relative_pose.argtypes = [vp, C.POINTER(capi.PlbaLcposeBatch), C.POINTER(capi.PlbaLcposeParams),
                                         C.POINTER(capi.PlbaLcposeOut), bp, bp]
+    L.plba_desc_match.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
     for name in EXPORTED:
         f = getattr(L, name)
         if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
@@ -306,6 +308,20 @@ class Solver:
                                                  _p(pin, C.c_uint8), _p(lin, C.c_uint8)), "plba_lc_relative_pose")
         return [capi.lcpose_out_to_dict(out[i], pin[bv.pt_off[i]:bv.pt_off[i + 1]], lin[bv.ln_off[i]:bv.ln_off[i + 1]])
                 for i in range(n)]
+
+    def desc_match(self, pairs, nnr, best_lr: bool = True, desc_bytes=None) -> list:
+        """Descriptor matching (plba_desc_match; StVO::match / matchNNR, src2/matching.cpp:41-91) of a
+        batch of descriptor-set pairs [(desc1, desc2), ...] of uint8 rows, both directions of every
+        pair in one launch. ``nnr``: one ratio or one per pair (taken as float32). One
+        (matches_12, n_matches) per pair: the desc2 row of each desc1 row or -1, and their count.
+        Needs no uploaded window and leaves one intact."""
+        bv = capi.MatchBatchView(pairs, nnr, best_lr, desc_bytes)
+        n = bv.struct.n
+        m12 = np.full(max(int(bv.off1[-1]), 1), -1, np.int32)
+        cnt = np.zeros(max(n, 1), np.int32)
+        self._check(self.L.plba_desc_match(self.ctx, C.byref(bv.struct), _p(m12, C.c_int32), _p(cnt, C.c_int32)),
+                    "plba_desc_match")
+        return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
 
     def trace(self) -> np.ndarray:
         n = C.c_int32(0)

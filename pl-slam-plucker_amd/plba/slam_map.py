@@ -219,6 +219,19 @@ class PlslamHlmStats(C.Structure):
 LCPOSE_SOLVE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaLcposeBatch), C.POINTER(capi.PlbaLcposeParams),
                               C.POINTER(capi.PlbaLcposeOut), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8))
 LC_IDLE, LC_ACTIVE, LC_READY = 0, 1, 2   # include/mapHandler.h:195-197
+MATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaMatchBatch), C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+
+
+class PlslamMatchParams(C.Structure):
+    _fields_ = [("min_ratio_12_p", C.c_float), ("min_ratio_12_l", C.c_float), ("best_lr", C.c_int32),
+                ("has_points", C.c_int32), ("has_lines", C.c_int32), ("pad", C.c_int32)]
+
+
+def match_params(min_ratio_12_p: float = 0.9, min_ratio_12_l: float = 0.9, best_lr: bool = True,
+                 has_points: bool = True, has_lines: bool = True) -> PlslamMatchParams:
+    """src2/config.cpp:46-47,51,60,68."""
+    return PlslamMatchParams(min_ratio_12_p=min_ratio_12_p, min_ratio_12_l=min_ratio_12_l, best_lr=int(best_lr),
+                             has_points=int(has_points), has_lines=int(has_lines), pad=0)
 
 
 class PlslamLcCandidate(C.Structure):
@@ -258,6 +271,8 @@ HOST_EXPORTED = [
     "plslam_set_incremental", "plslam_mark_landmark_changed", "plslam_check_incremental_gather",
     "plslam_set_lcpose_solver", "plslam_set_lcpose_params", "plslam_loop_closure_step", "plslam_get_lc_state",
     "plslam_get_lc_pose_list", "plslam_get_lc_feature_idxs",
+    "plslam_set_keyframe_features", "plslam_set_match_fn", "plslam_loop_closure_step_kf",
+    "plslam_verify_loop_candidates", "plslam_desc_match_cpu",
 ]
 
 
@@ -336,6 +351,14 @@ def load_host(path: Optional[str] = None):
     L.plslam_get_lc_state.argtypes = [vp, ip]
     L.plslam_get_lc_pose_list.argtypes = [vp, dp, C.c_int32, ip]
     L.plslam_get_lc_feature_idxs.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, ip]
+    bp = C.POINTER(C.c_uint8)
+    L.plslam_set_keyframe_features.argtypes = [vp, C.c_int32, C.c_int32, bp, dp, dp, bp, dp, dp, dp]
+    L.plslam_set_match_fn.argtypes = [vp, MATCH_FN, vp]
+    L.plslam_loop_closure_step_kf.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(PlslamMatchParams), C.c_double,
+                                              C.POINTER(PlslamLcStats)]
+    L.plslam_verify_loop_candidates.argtypes = [vp, C.c_int32, C.c_int32, ip, C.POINTER(PlslamMatchParams), C.c_double,
+                                                ip, dp, ip]
+    L.plslam_desc_match_cpu.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
     for n in HOST_EXPORTED:
         if n not in ("plslam_map_last_error", "plslam_pluker_to_orth", "plslam_orth_to_pluker"):
             getattr(L, n).restype = C.c_int
@@ -362,6 +385,7 @@ class HostMap:
         self.h = C.c_void_p()
         self._check(self.L.plslam_map_create(C.byref(self.h), m.fx, m.fy, m.cx, m.cy, C.byref(o)), "create")
         self._cb = None
+        self._kf_feat = {}   # kf_idx -> (point features, line features), as given to plslam_add_keyframe
         self.n_kf = len(m.keyframes)
         self.n_pt = len(m.points)
         self.n_ln = len(m.lines)
@@ -396,6 +420,7 @@ class HostMap:
             li = np.asarray(kf.ls_idx, np.int32)
             self._check(L.plslam_add_keyframe(h, kf.kf_idx, Tp, len(pi), pi.ctypes.data_as(ip), len(li),
                                               li.ctypes.data_as(ip)), "add_keyframe")
+            self._kf_feat[kf.kf_idx] = (len(pi), len(li))
             self._check(L.plslam_set_local(h, 0, kf.kf_idx, int(kf.local)), "set_local")
         bp = C.POINTER(C.c_uint8)
         for kind, lms in ((1, m.points), (2, m.lines)):
@@ -644,6 +669,66 @@ class HostMap:
                               ls_idx=idx[1].ctypes.data_as(ip) if idx[1] is not None else None)
         self._check(self.L.plslam_loop_closure_step(self.h, C.byref(c), lc_inlier_ratio, C.byref(st)), "loop_closure_step")
         return st.as_dict()
+
+    # ---- isLoopClosure from two keyframe indices (src/mapHandler.cpp:4303-4411)
+    def set_keyframe_features(self, kf_idx: int, pdesc, pt_P, pt_pl, ldesc, ls_sP, ls_eP, ls_le, desc_bytes: int = 32):
+        """What isLoopClosure reads of keyframe ``kf_idx``: pdesc_l [n_pt][desc_bytes] uint8 with P
+        [n_pt][3] and pl [n_pt][2]; ldesc_l [n_ls][desc_bytes] with sP, eP and le [n_ls][3]. The
+        counts are those of the keyframe's pt_idx / ls_idx."""
+        bp, dp = C.POINTER(C.c_uint8), C.POINTER(C.c_double)
+        d = [np.ascontiguousarray(np.asarray(a, np.uint8).reshape(-1, desc_bytes)) for a in (pdesc, ldesc)]
+        f = [np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, w))
+             for a, w in ((pt_P, 3), (pt_pl, 2), (ls_sP, 3), (ls_eP, 3), (ls_le, 3))]
+        if not (len(d[0]) == len(f[0]) == len(f[1]) and len(d[1]) == len(f[2]) == len(f[3]) == len(f[4])):
+            raise ValueError("one row per feature in every array of a kind")
+        if self._kf_feat.get(kf_idx, (0, 0)) != (len(d[0]), len(d[1])):
+            raise ValueError(f"keyframe {kf_idx} has {self._kf_feat.get(kf_idx, (0, 0))} features, "
+                             f"not ({len(d[0])}, {len(d[1])})")
+        self._check(self.L.plslam_set_keyframe_features(
+            self.h, kf_idx, desc_bytes, d[0].ctypes.data_as(bp), f[0].ctypes.data_as(dp), f[1].ctypes.data_as(dp),
+            d[1].ctypes.data_as(bp), f[2].ctypes.data_as(dp), f[3].ctypes.data_as(dp), f[4].ctypes.data_as(dp)),
+            "set_keyframe_features")
+
+    def set_match_fn(self, fn: Optional[Callable]):
+        """fn(batch, matches_12, n_matches) -> int, or None for the MI355X backend (plba_desc_match)."""
+        if fn is None:
+            self._mcb = None
+            self._check(self.L.plslam_set_match_fn(self.h, C.cast(None, MATCH_FN), None), "set_match_fn")
+            return
+
+        def tramp(user, bp_, m12, cnt):
+            try:
+                return int(fn(bp_.contents, m12, cnt))
+            except Exception:  # never unwind through C
+                import traceback
+                traceback.print_exc()
+                return -1
+        self._mcb = MATCH_FN(tramp)
+        self._check(self.L.plslam_set_match_fn(self.h, self._mcb, None), "set_match_fn")
+
+    def loop_closure_step_kf(self, kf_prev_idx: int, kf_curr_idx: int, params: Optional[PlslamMatchParams] = None,
+                             lc_inlier_ratio: float = 30.0) -> dict:
+        """loopClosure() with isLoopClosure(kf_prev, kf_curr) whole: descriptor matching, gate,
+        relative pose, lists and state machine."""
+        st = PlslamLcStats()
+        self._check(self.L.plslam_loop_closure_step_kf(self.h, kf_prev_idx, kf_curr_idx,
+                                                       C.byref(params) if params is not None else None,
+                                                       lc_inlier_ratio, C.byref(st)), "loop_closure_step_kf")
+        return st.as_dict()
+
+    def verify_loop_candidates(self, kf_curr_idx: int, kf_prev_idxs, params: Optional[PlslamMatchParams] = None,
+                               lc_inlier_ratio: float = 30.0) -> dict:
+        """K candidates for one new keyframe in one match call and one relative-pose call; no map
+        state is changed. accepted [K], pose_inc [K][6], n_matches [K][2] (points, lines)."""
+        prev = np.ascontiguousarray(np.asarray(kf_prev_idxs, np.int32).reshape(-1))
+        k = len(prev)
+        acc, pose, cnt = np.zeros(max(k, 1), np.int32), np.zeros((max(k, 1), 6)), np.zeros((max(k, 1), 2), np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.L.plslam_verify_loop_candidates(
+            self.h, kf_curr_idx, k, prev.ctypes.data_as(ip), C.byref(params) if params is not None else None,
+            lc_inlier_ratio, acc.ctypes.data_as(ip), pose.ctypes.data_as(C.POINTER(C.c_double)), cnt.ctypes.data_as(ip)),
+            "verify_loop_candidates")
+        return dict(accepted=acc[:k], pose_inc=pose[:k], n_matches=cnt[:k])
 
     def lc_state(self) -> int:
         v = C.c_int32(0)
