@@ -412,6 +412,64 @@ typedef struct plba_match_batch {       /* B descriptor-set pairs, concatenated 
  * nothing and returns PLBA_OK. */
 int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
 
+/* ---- Grid-guided descriptor matching, what the local-mapping associations try first:
+ *   int StVO::matchGrid(points1, desc1, grid, desc2, w, matches_12)               (src2/matching.cpp:111-177)
+ *   int StVO::matchGrid(lines1, desc1, grid, desc2, directions2, w, matches_12)   (:179-258)
+ * called by matchKF2KFPoints / Lines (src/mapHandler.cpp:273, :421) and matchMap2KFPoints / Lines
+ * (:756, :871) when SlamConfig::fastMatching() is set. The train rows (side 2) sit in a cols x rows
+ * grid of cells (GridStructure, 64 x 48 in the reference): a point in one cell, a rasterised line in
+ * several. A query row (side 1) has an integer cell, a line query two (start and end point), already
+ * truncated by the caller (point_2d is pair<int, int>); they may lie outside the grid. A problem has
+ * a kind (0 points, 1 lines), a window half-width ws, a ratio nnr and, for lines, a direction
+ * threshold. Integer work but for two double comparisons: the results are exact.
+ * Candidates: cand(i1, i2) if some cell (cx, cy) of i2 inside [0, cols) x [0, rows) has
+ * max(0, x - ws) <= cx < min(cols, x + ws + 1) and the same in y for the query cell (GridStructure::
+ * get, src2/gridStructure.cpp:65-76); a listed cell outside the grid is ignored (GridStructure::at).
+ * A line query takes the test for either of its two cells and also needs |dot(v1, dir2[i2])| >=
+ * line_sim_th (:221), v1 = the integer difference of its cells divided by its norm, in double. For
+ * two equal cells v1 is NaN, the comparison of :221 is false and the row is kept: the direction
+ * test passes. A train row counts once however many of its cells are in the window.
+ * Cross-check with best_lr: the query rows are taken in increasing i1, and (i1, i2) is seen by row
+ * i1 only if its Hamming distance is strictly below that of every earlier candidate of column i2
+ * (:145-150); matches_21[i2] is the last such i1. Without best_lr every candidate is seen.
+ * Best and second best of a row over its seen pairs in increasing i2: a distance replaces the best
+ * only if strictly smaller, else the second only if strictly smaller (:152-157), so the lowest i2
+ * wins a tie. (The reference iterates an unordered_set there: its order is unspecified.)
+ * Ratio test: (double)best_d < (double)best_d2 * nnr (:160; Config::minRatio12P() is a double), with
+ * INT_MAX for a missing second. Then, with best_lr, matches_12[i1] = i2 survives only if
+ * matches_21[i2] == i1 (:166-174). n_matches[p] is the surviving count, the function's return value.
+ * Defined where the reference is not: a row with candidates but no seen pair has best_d = INT_MAX;
+ * above nnr = 1 the reference counts a match with index -1 there. Here it is -1 and not counted.
+ * A problem has at most 65535 train rows. */
+typedef struct plba_gridmatch_batch {   /* B problems, concatenated */
+    int32_t n;                          /* problems                                             */
+    int32_t desc_bytes;                 /* as in plba_match_batch                               */
+    int32_t cols, rows;                 /* the grid, > 0 (GRID_COLS 64, GRID_ROWS 48)           */
+    int32_t best_lr;                    /* Config::bestLRMatches()                              */
+    int32_t pad;
+    const int32_t *off1, *off2;         /* [n+1] row ranges of problem p: [off[p], off[p+1])    */
+    const uint8_t *desc1, *desc2;       /* [off1[n]][desc_bytes] queries, [off2[n]][desc_bytes] */
+    const int32_t *cell1;               /* [off1[n]][2] (x, y) of a point query, of a line's start */
+    const int32_t *cell1_end;           /* [off1[n]][2] of a line query's end; rows of point
+                                           problems are not read; NULL with no line query       */
+    const int32_t *cell_off2;           /* [off2[n]+1] CSR: cells of train row r are
+                                           cells2[cell_off2[r] .. cell_off2[r+1])               */
+    const int32_t *cells2;              /* [cell_off2[off2[n]]][2] (x, y)                       */
+    const double  *dir2;                /* [off2[n]][2] unit direction of a train line; rows of
+                                           point problems are not read; NULL with no train line */
+    const int32_t *kind;                /* [n] 0 points, 1 lines                                */
+    const int32_t *ws;                  /* [n] window half-width, >= 0 (matchingF2FWs, 3)       */
+    const double  *nnr;                 /* [n] Config::minRatio12P(), for lines too (:241)      */
+    const double  *line_sim_th;         /* [n] Config::lineSimTh(), 0.75; read for lines        */
+} plba_gridmatch_batch;
+/* Runs on the context's stream in a fixed number of launches with one upload and one read-back;
+ * needs no uploaded window and leaves one intact; shares plba_desc_match's device block and pinned
+ * host image. matches_12: [off1[n]], local to the problem; n_matches: [n].
+ * PLBA_E_INVALID for a NULL batch or array where rows exist, n < 0, decreasing or negative offsets
+ * (rows or cells), ws < 0, cols or rows <= 0, a bad desc_bytes, a kind outside {0, 1} or more than
+ * 65535 train rows in a problem; n == 0 does nothing; an empty side gives no match. */
+int plba_grid_match(plba_ctx *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
+
 /* ---- Sharded windows: one context per GPU, one window split over nranks.
  * Landmarks (with all their edges) are partitioned by the keyframe range of their first
  * observation (kf_obs_list[0], the base KF of map_points_kf_idx); poses are replicated.

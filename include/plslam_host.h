@@ -246,6 +246,73 @@ int plslam_verify_loop_candidates(plslam_map *m, int32_t kf_curr_idx, int32_t n,
 /* tools/descmatch_bench.py only, not a product path: a single-threaded popcount restatement of
  * plba_desc_match's semantics on the CPU, with the signature of the matcher hook. */
 int plslam_desc_match_cpu(void *user, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
+/* ---- around the grid-guided matcher (plba_grid_match; StVO::matchGrid, src2/matching.cpp:111-258).
+ * getLineCoords / LineIterator (src2/gridStructure.cpp:33-41, src2/lineIterator.cpp): the cells under
+ * which matchKF2KFLines / matchMap2KFLines (src/mapHandler.cpp:410-413, :860-863) enter a line from
+ * (x1, y1) to (x2, y2), given in grid units (spl * inv_width, ...), in the reference's order: the
+ * cells2 list of that train row. cells [cap][2] is written up to cap entries, *n is their number.
+ * PLBA_E_INVALID for a coordinate that is not finite or beyond 1e6 cells in magnitude. */
+int plslam_line_cells(double x1, double y1, double x2, double y2, int32_t *cells, int32_t cap, int32_t *n);
+/* tools/gridmatch_bench.py and the tests only, not a product path: a single-threaded restatement of
+ * plba_grid_match's semantics on the CPU, the query rows walked in order as the reference does. */
+int plslam_grid_match_cpu(void *user, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
+/* ---- MapHandler::matchMap2KFPoints + matchMap2KFLines (src/mapHandler.cpp:697-921), the map-to-keyframe
+ * association that opens a local-mapping step (lookForCommonMatches, :923), for keyframe kf_idx.
+ * It needs the keyframe's features (plslam_set_keyframe_features), the image endpoints spl / epl of its
+ * line features ([n_ls][2], :857-861, :903) and the camera with the image size (cam->getWidth() /
+ * getHeight(), :716); plslam_set_camera also replaces the intrinsics given to plslam_map_create. */
+int plslam_set_keyframe_line_endpoints(plslam_map *m, int32_t kf_idx, const double *spl, const double *epl);
+int plslam_set_camera(plslam_map *m, double fx, double fy, double cx, double cy, int32_t width, int32_t height);
+/* Grid-matcher hook, in the style of plslam_set_match_fn: NULL = plba_grid_match. */
+typedef int (*plslam_grid_match_fn)(void *user, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
+int plslam_set_grid_match_fn(plslam_map *m, plslam_grid_match_fn fn, void *user);
+typedef struct plslam_mapmatch_params {
+    int32_t fast_matching;                  /* SlamConfig::fastMatching(): false in src/slamConfig.cpp:43, true in
+                                               the shipped config/config/config.yaml:5; the default here is 1    */
+    int32_t ws;                             /* Config::matchingF2FWs(), 3 (src2/config.cpp:92)                  */
+    int32_t min_pt_matches, min_ls_matches; /* SlamConfig::minPointMatches() / minLineMatches(), 10 / 6 (:85-86) */
+    int32_t best_lr;                        /* Config::bestLRMatches(), 1                                       */
+    int32_t has_points, has_lines;          /* SlamConfig::hasPoints() / hasLines(), 1                          */
+    int32_t pad;
+    double  max_kf_epip_p, max_kf_epip_l;   /* SlamConfig::maxKFEpipP() / maxKFEpipL(), 1.0 (:51-52)            */
+    double  line_sim_th;                    /* Config::lineSimTh(), 0.75 (src2/config.cpp:63)                   */
+    double  min_ratio_12_p, min_ratio_12_l; /* Config::minRatio12P() / minRatio12L(), 0.9. matchGrid uses _p for
+                                               lines too (matching.cpp:241); the fallback uses both, as floats  */
+} plslam_mapmatch_params;
+void plslam_mapmatch_default_params(plslam_mapmatch_params *p);
+typedef struct plslam_mapmatch_stats {      /* [0] points, [1] lines */
+    int32_t visible[2];                     /* local landmarks not yet seen by the keyframe, inside the image   */
+    int32_t unmatched[2];                   /* features of the keyframe with idx -1                             */
+    int32_t grid_matches[2];                /* what matchGrid returned                                          */
+    int32_t fallback[2];                    /* 1 if match() ran for the kind (:759-764, :874-879)               */
+    int32_t accepted[2], rejected[2];       /* by the epipolar test (:778, :894)                                */
+    double  match_ms;                       /* the matcher calls                                                */
+} plslam_mapmatch_stats;
+/* The local-landmark scan (pt->local, kf_obs_list.back() != kf, :712 / :813), the projection by Twf
+ * (row-major 4x4, world -> keyframe; NULL = the inverse of the keyframe's T_kf_w) with the strict
+ * in-image test, the cells, the keyframe's features with idx -1 gridded or rasterised; ONE
+ * plba_grid_match call with the point and the line problem; where a kind has more than min_*_matches
+ * visible landmarks and fewer grid matches, one plba_desc_match call through plslam_set_match_fn's
+ * hook (min_ratio_12_p / _l); then per match, in i1 order, points before lines: the epipolar test
+ * (points: the pixel distance < max_kf_epip_p; lines: both signed distances of the projected endpoints
+ * to the feature's line < max_kf_epip_l, signed as the reference has it), the feature's idx,
+ * addMapPointObservation(desc, kf, pl, T_kf_w * normalized(P)) / addMapLineObservation(desc, kf,
+ * (spl, epl)) with the default sigma2 = 1 (include/mapFeatures.h:51,81), and full_graph[kf][obs]++,
+ * full_graph[obs][kf]++ for every earlier observer. The incremental window is told of each landmark.
+ * Lines are projected from line3D, which a Plücker build never sets: the line half is meaningful for
+ * endpoint-line maps or where the caller keeps line3D (plslam_set_line_geometry).
+ * Where the reference's fallback keeps grid matches that match() does not overwrite (match() resizes
+ * matches_12 without clearing it), the fallback's result stands alone here.
+ * params == NULL: the defaults; stats may be NULL. A bad index, a keyframe without features (or without
+ * line endpoints when it has line features), no image size, a keyframe outside full_graph or ws < 0
+ * return PLBA_E_INVALID with the map untouched. */
+int plslam_match_map_to_kf(plslam_map *m, int32_t kf_idx, const double *Twf, const plslam_mapmatch_params *params,
+                           plslam_mapmatch_stats *stats);
+/* lookForCommonMatches' map half, then formLocalMap -> LBA -> culling: plslam_match_map_to_kf(kf_idx,
+ * NULL, params), then plslam_local_mapping_step. */
+int plslam_local_mapping_step_kf(plslam_map *m, int32_t kf_idx, const plslam_mapmatch_params *params,
+                                 plslam_mapmatch_stats *match_stats, plslam_lba_stats *stats, int32_t *n_pt_removed,
+                                 int32_t *n_ln_removed);
 int plslam_get_lc_state(plslam_map *m, int32_t *state);
 /* lc_pose_list [n][6]; the kept index rows of loop `loop` (kind 1 points, 2 lines), [n][4] */
 int plslam_get_lc_pose_list(plslam_map *m, double *out, int32_t cap, int32_t *n);

@@ -30,6 +30,7 @@
 #include "plba_kernels.hpp"
 #include "plba_lcpose.hpp"
 #include "plba_match.hpp"
+#include "plba_gridmatch.hpp"
 #include "plba_plan.hpp"
 
 namespace plba {
@@ -2972,6 +2973,34 @@ int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_
     return PLBA_OK;
 }
 
+// The device block and the pinned host image that plba_desc_match and plba_grid_match share:
+// grow-only, kept across calls.
+static int dm_reserve(plba_ctx *ctx, size_t dev_bytes, size_t host_bytes, const char *what) {
+    if (dev_bytes > ctx->dm_cap) {
+        if (ctx->dm_mem) (void)hipFreeAsync(ctx->dm_mem, ctx->stream);  // stream-ordered, as the relative pose's block
+        ctx->dm_mem = nullptr;
+        ctx->dm_cap = 0;
+        if (hipMallocAsync((void **)&ctx->dm_mem, dev_bytes, ctx->stream) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->set_error("%s: cannot allocate %zu bytes", what, dev_bytes);
+            return PLBA_E_NOMEM;
+        }
+        ctx->dm_cap = dev_bytes;
+    }
+    if (host_bytes > ctx->dm_host_cap) {
+        if (ctx->dm_host) (void)hipHostFree(ctx->dm_host);
+        ctx->dm_host = nullptr;
+        ctx->dm_host_cap = 0;
+        if (hipHostMalloc((void **)&ctx->dm_host, host_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->set_error("%s: cannot allocate %zu bytes of pinned memory", what, host_bytes);
+            return PLBA_E_NOMEM;
+        }
+        ctx->dm_host_cap = host_bytes;
+    }
+    return PLBA_OK;
+}
+
 // ---------------------------------------------------------------- descriptor matching
 // StVO::match / matchNNR (src2/matching.cpp:41-91) for a batch of descriptor-set pairs: one upload,
 // k_desc_nn (both directions of every pair) and k_desc_cross (csrc/plba_match.hpp), one read-back.
@@ -3024,28 +3053,7 @@ int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_1
                  o_d1 = o_nnr + al(sizeof(float) * n), o_d2 = o_d1 + al(db * n1), o_m12 = o_d2 + al(db * n2),
                  o_cnt = o_m12 + al(sizeof(int32_t) * n1), o_nn12 = o_cnt + al(sizeof(int32_t) * n),
                  o_nn21 = o_nn12 + al(sizeof(int32_t) * n1), tot = o_nn21 + al(sizeof(int32_t) * n2);
-    if (tot > ctx->dm_cap) {
-        if (ctx->dm_mem) (void)hipFreeAsync(ctx->dm_mem, ctx->stream);  // stream-ordered, as the relative pose's block
-        ctx->dm_mem = nullptr;
-        ctx->dm_cap = 0;
-        if (hipMallocAsync((void **)&ctx->dm_mem, tot, ctx->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->set_error("descriptor matching: cannot allocate %zu bytes", tot);
-            return PLBA_E_NOMEM;
-        }
-        ctx->dm_cap = tot;
-    }
-    if (o_nn12 > ctx->dm_host_cap) {
-        if (ctx->dm_host) (void)hipHostFree(ctx->dm_host);
-        ctx->dm_host = nullptr;
-        ctx->dm_host_cap = 0;
-        if (hipHostMalloc((void **)&ctx->dm_host, o_nn12) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->set_error("descriptor matching: cannot allocate %zu bytes of pinned memory", o_nn12);
-            return PLBA_E_NOMEM;
-        }
-        ctx->dm_host_cap = o_nn12;
-    }
+    if (const int rc = dm_reserve(ctx, tot, o_nn12, "descriptor matching")) return rc;
     char *h = ctx->dm_host, *dv = ctx->dm_mem;
     memcpy(h + o_off1, b->off1, sizeof(int32_t) * (n + 1));
     memcpy(h + o_off2, b->off2, sizeof(int32_t) * (n + 1));
@@ -3078,6 +3086,159 @@ int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_1
     PLBA_CHECK(hipStreamSynchronize(s));
     if (n1) memcpy(matches_12, h + o_m12, sizeof(int32_t) * n1);
     memcpy(n_matches, h + o_cnt, sizeof(int32_t) * n);
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- grid-guided matching
+// StVO::matchGrid (src2/matching.cpp:111-258) for a batch of point and line problems: one upload, a
+// fill of the key arrays, k_grid_cols twice (best, then second best) and k_grid_rows
+// (csrc/plba_gridmatch.hpp), one read-back.
+int plba_grid_match(plba_ctx *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
+    if (!ctx) return PLBA_E_INVALID;
+    if (!b || b->n < 0) {
+        ctx->set_error("grid matching: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    const int n = b->n;
+    if (n == 0) return PLBA_OK;
+    if (b->desc_bytes < 4 || b->desc_bytes > 64 || b->desc_bytes % 4) {
+        ctx->set_error("grid matching: desc_bytes %d is no multiple of 4 in [4, 64]", b->desc_bytes);
+        return PLBA_E_INVALID;
+    }
+    if (b->cols <= 0 || b->rows <= 0) {
+        ctx->set_error("grid matching: a grid of %d x %d cells", b->cols, b->rows);
+        return PLBA_E_INVALID;
+    }
+    if (!b->off1 || !b->off2 || !b->kind || !b->ws || !b->nnr || !b->line_sim_th || !n_matches) {
+        ctx->set_error("grid matching: NULL off1 / off2 / kind / ws / nnr / line_sim_th / n_matches");
+        return PLBA_E_INVALID;
+    }
+    for (const int32_t *off : {b->off1, b->off2}) {
+        if (off[0] < 0) {
+            ctx->set_error("grid matching: negative row offset");
+            return PLBA_E_INVALID;
+        }
+        for (int k = 0; k < n; ++k)
+            if (off[k + 1] < off[k]) {
+                ctx->set_error("grid matching: row offsets decrease at problem %d", k);
+                return PLBA_E_INVALID;
+            }
+    }
+    int max_train = 0;
+    bool line_q = false, line_t = false;  // a line problem with query rows / with train rows
+    for (int k = 0; k < n; ++k) {
+        if (b->kind[k] != 0 && b->kind[k] != 1) {
+            ctx->set_error("grid matching: kind %d of problem %d", b->kind[k], k);
+            return PLBA_E_INVALID;
+        }
+        if (b->ws[k] < 0) {
+            ctx->set_error("grid matching: window half-width %d of problem %d", b->ws[k], k);
+            return PLBA_E_INVALID;
+        }
+        max_train = std::max(max_train, b->off2[k + 1] - b->off2[k]);
+        line_q = line_q || (b->kind[k] == 1 && b->off1[k + 1] > b->off1[k]);
+        line_t = line_t || (b->kind[k] == 1 && b->off2[k + 1] > b->off2[k]);
+    }
+    if (max_train > kGmMaxTrain) {  // the low 16 bits of a key
+        ctx->set_error("grid matching: %d train rows in a problem are more than %d", max_train, kGmMaxTrain);
+        return PLBA_E_INVALID;
+    }
+    const size_t n1 = (size_t)b->off1[n], n2 = (size_t)b->off2[n], db = (size_t)b->desc_bytes;
+    if ((n1 && (!b->desc1 || !b->cell1 || !matches_12)) || (n2 && (!b->desc2 || !b->cell_off2)) ||
+        (line_q && !b->cell1_end) || (line_t && !b->dir2)) {
+        ctx->set_error("grid matching: NULL desc1 / cell1 / cell1_end / matches_12 / desc2 / cell_off2 / dir2");
+        return PLBA_E_INVALID;
+    }
+    size_t nc = 0;  // the kernels index cells2 through cell_off2: every entry is checked here
+    if (n2) {
+        if (b->cell_off2[0] < 0) {
+            ctx->set_error("grid matching: negative cell offset");
+            return PLBA_E_INVALID;
+        }
+        for (size_t r = 0; r < n2; ++r)
+            if (b->cell_off2[r + 1] < b->cell_off2[r]) {
+                ctx->set_error("grid matching: cell offsets decrease at train row %zu", r);
+                return PLBA_E_INVALID;
+            }
+        nc = (size_t)b->cell_off2[n2];
+        if (nc && !b->cells2) {
+            ctx->set_error("grid matching: NULL cells2");
+            return PLBA_E_INVALID;
+        }
+    }
+    (void)hipSetDevice(ctx->opts.device);
+    // one block, the same layout on the device and in pinned host memory:
+    //   inputs  off1 | off2 | kind | ws | nnr | line_sim_th | desc1 | desc2 | cell1 | cell1_end |
+    //           cell_off2 | cells2 | dir2                  (host -> device)
+    //   outputs matches_12 | n_matches                     (device -> host)
+    //   scratch best | second | matches_21                 (device only)
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t i4 = sizeof(int32_t), f8 = sizeof(double);
+    const size_t o_off1 = 0, o_off2 = o_off1 + al(i4 * (n + 1)), o_kind = o_off2 + al(i4 * (n + 1)), o_ws = o_kind + al(i4 * n),
+                 o_nnr = o_ws + al(i4 * n), o_th = o_nnr + al(f8 * n), o_d1 = o_th + al(f8 * n), o_d2 = o_d1 + al(db * n1),
+                 o_c1 = o_d2 + al(db * n2), o_c1e = o_c1 + al(2 * i4 * n1), o_co2 = o_c1e + al(2 * i4 * n1),
+                 o_cl2 = o_co2 + al(i4 * (n2 + 1)), o_dir = o_cl2 + al(2 * i4 * nc), o_m12 = o_dir + al(2 * f8 * n2),
+                 o_cnt = o_m12 + al(i4 * n1), o_best = o_cnt + al(i4 * n), o_sec = o_best + al(i4 * n1),
+                 o_m21 = o_sec + al(i4 * n1), tot = o_m21 + al(i4 * n2);
+    if (const int rc = dm_reserve(ctx, tot, o_best, "grid matching")) return rc;
+    char *h = ctx->dm_host, *dv = ctx->dm_mem;
+    memcpy(h + o_off1, b->off1, i4 * (n + 1));
+    memcpy(h + o_off2, b->off2, i4 * (n + 1));
+    memcpy(h + o_kind, b->kind, i4 * n);
+    memcpy(h + o_ws, b->ws, i4 * n);
+    memcpy(h + o_nnr, b->nnr, f8 * n);
+    memcpy(h + o_th, b->line_sim_th, f8 * n);
+    if (n1) memcpy(h + o_d1, b->desc1, db * n1);
+    if (n2) memcpy(h + o_d2, b->desc2, db * n2);
+    if (n1) memcpy(h + o_c1, b->cell1, 2 * i4 * n1);
+    if (n1 && b->cell1_end) memcpy(h + o_c1e, b->cell1_end, 2 * i4 * n1);
+    if (n2) memcpy(h + o_co2, b->cell_off2, i4 * (n2 + 1));
+    else memset(h + o_co2, 0, i4);
+    if (nc) memcpy(h + o_cl2, b->cells2, 2 * i4 * nc);
+    if (n2 && b->dir2) memcpy(h + o_dir, b->dir2, 2 * f8 * n2);
+    hipStream_t s = ctx->stream;
+    PLBA_CHECK(hipMemcpyAsync(dv, h, o_m12, hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemsetAsync(dv + o_best, 0xFF, o_m21 - o_best, s));  // kGmNone in every key
+    GmDev D{};
+    D.off1 = (const int32_t *)(dv + o_off1);
+    D.off2 = (const int32_t *)(dv + o_off2);
+    D.kind = (const int32_t *)(dv + o_kind);
+    D.ws = (const int32_t *)(dv + o_ws);
+    D.nnr = (const double *)(dv + o_nnr);
+    D.sim_th = (const double *)(dv + o_th);
+    D.desc1 = (const uint32_t *)(dv + o_d1);
+    D.desc2 = (const uint32_t *)(dv + o_d2);
+    D.cell1 = (const int32_t *)(dv + o_c1);
+    D.cell1e = (const int32_t *)(dv + o_c1e);
+    D.cell_off2 = (const int32_t *)(dv + o_co2);
+    D.cells2 = (const int32_t *)(dv + o_cl2);
+    D.dir2 = (const double *)(dv + o_dir);
+    D.m12 = (int32_t *)(dv + o_m12);
+    D.count = (int32_t *)(dv + o_cnt);
+    D.best = (uint32_t *)(dv + o_best);
+    D.second = (uint32_t *)(dv + o_sec);
+    D.m21 = (int32_t *)(dv + o_m21);
+    D.n = n;
+    D.dwords = b->desc_bytes / 4;
+    D.cols = b->cols;
+    D.rows = b->rows;
+    D.best_lr = b->best_lr != 0;
+    if (max_train > 0) {  // a workgroup past its problem's train rows returns at once
+        const dim3 grid(n, (max_train + kGmNT - 1) / kGmNT);
+        if (D.dwords <= 8) {
+            hipLaunchKernelGGL((k_grid_cols<8, 0>), grid, dim3(kGmNT), 0, s, D);
+            hipLaunchKernelGGL((k_grid_cols<8, 1>), grid, dim3(kGmNT), 0, s, D);
+        } else {
+            hipLaunchKernelGGL((k_grid_cols<16, 0>), grid, dim3(kGmNT), 0, s, D);
+            hipLaunchKernelGGL((k_grid_cols<16, 1>), grid, dim3(kGmNT), 0, s, D);
+        }
+        PLBA_LAUNCHED(ctx, "k_grid_cols");
+    }
+    hipLaunchKernelGGL(k_grid_rows, dim3(n), dim3(kGmRowsNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_grid_rows");
+    PLBA_CHECK(hipMemcpyAsync(h + o_m12, dv + o_m12, o_best - o_m12, hipMemcpyDeviceToHost, s));
+    PLBA_CHECK(hipStreamSynchronize(s));
+    if (n1) memcpy(matches_12, h + o_m12, i4 * n1);
+    memcpy(n_matches, h + o_cnt, i4 * n);
     return PLBA_OK;
 }
 

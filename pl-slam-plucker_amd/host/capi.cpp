@@ -421,6 +421,105 @@ int plslam_desc_match_cpu(void *user, const plba_match_batch *b, int32_t *matche
     return descMatchCpu(b, matches_12, n_matches);
 }
 
+int plslam_line_cells(double x1, double y1, double x2, double y2, int32_t *cells, int32_t cap, int32_t *n) {
+    if (!n || cap < 0 || (cap > 0 && !cells)) return PLBA_E_INVALID;
+    std::vector<std::array<int, 2>> out;
+    const long count = lineCells(x1, y1, x2, y2, out, (size_t)cap);
+    if (count < 0) return PLBA_E_INVALID;
+    *n = (int32_t)count;
+    for (size_t i = 0; i < out.size(); ++i) {
+        cells[2 * i] = out[i][0];
+        cells[2 * i + 1] = out[i][1];
+    }
+    return PLBA_OK;
+}
+
+int plslam_set_keyframe_line_endpoints(plslam_map *m, int32_t kf_idx, const double *spl, const double *epl) {
+    if (!m || !slot_ok(m->mh.map_keyframes, kf_idx)) return PLBA_E_INVALID;
+    StereoFrame &f = m->mh.map_keyframes[kf_idx]->stereo_frame;
+    const size_t nl = f.stereo_ls_idx.size();
+    if (nl && (!spl || !epl)) return PLBA_E_INVALID;
+    f.ls_spl.assign(spl, spl + (nl ? 2 * nl : 0));
+    f.ls_epl.assign(epl, epl + (nl ? 2 * nl : 0));
+    f.has_endpoints = true;
+    return PLBA_OK;
+}
+
+int plslam_set_camera(plslam_map *m, double fx, double fy, double cx, double cy, int32_t width, int32_t height) {
+    if (!m || width <= 0 || height <= 0) return PLBA_E_INVALID;
+    m->mh.setCamera(fx, fy, cx, cy, width, height);
+    return PLBA_OK;
+}
+
+int plslam_set_grid_match_fn(plslam_map *m, plslam_grid_match_fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    m->mh.setGridMatchFn(fn, user);
+    return PLBA_OK;
+}
+
+void plslam_mapmatch_default_params(plslam_mapmatch_params *p) {
+    if (!p) return;
+    const MapMatchParams d;
+    *p = plslam_mapmatch_params{d.fast_matching, d.ws, d.min_pt_matches, d.min_ls_matches, d.best_lr, d.has_points,
+                                d.has_lines, 0, d.max_kf_epip_p, d.max_kf_epip_l, d.line_sim_th, d.min_ratio_12_p,
+                                d.min_ratio_12_l};
+}
+
+namespace {
+MapMatchParams mapmatch_params(const plslam_mapmatch_params *mp) {
+    MapMatchParams p;
+    if (mp) {
+        p.fast_matching = mp->fast_matching != 0; p.best_lr = mp->best_lr != 0;
+        p.has_points = mp->has_points != 0; p.has_lines = mp->has_lines != 0;
+        p.ws = mp->ws; p.min_pt_matches = mp->min_pt_matches; p.min_ls_matches = mp->min_ls_matches;
+        p.max_kf_epip_p = mp->max_kf_epip_p; p.max_kf_epip_l = mp->max_kf_epip_l; p.line_sim_th = mp->line_sim_th;
+        p.min_ratio_12_p = mp->min_ratio_12_p; p.min_ratio_12_l = mp->min_ratio_12_l;
+    }
+    return p;
+}
+void export_mapmatch_stats(const MapMatchStats &s, plslam_mapmatch_stats *o) {
+    if (!o) return;
+    for (int k = 0; k < 2; ++k) {
+        o->visible[k] = s.visible[k]; o->unmatched[k] = s.unmatched[k]; o->grid_matches[k] = s.grid_matches[k];
+        o->fallback[k] = s.fallback[k]; o->accepted[k] = s.accepted[k]; o->rejected[k] = s.rejected[k];
+    }
+    o->match_ms = s.match_ms;
+}
+}  // namespace
+
+int plslam_match_map_to_kf(plslam_map *m, int32_t kf_idx, const double *Twf, const plslam_mapmatch_params *params,
+                           plslam_mapmatch_stats *stats) {
+    if (!m) return PLBA_E_INVALID;
+    Mat4 T;
+    if (Twf) std::memcpy(T.data(), Twf, sizeof(double) * 16);
+    MapMatchStats st;
+    const int rc = m->mh.matchMapToKf(kf_idx, Twf ? &T : nullptr, mapmatch_params(params), &st);
+    if (rc) return rc;
+    export_mapmatch_stats(st, stats);
+    return PLBA_OK;
+}
+
+int plslam_local_mapping_step_kf(plslam_map *m, int32_t kf_idx, const plslam_mapmatch_params *params,
+                                 plslam_mapmatch_stats *match_stats, plslam_lba_stats *stats, int32_t *n_pt_removed,
+                                 int32_t *n_ln_removed) {
+    if (!m) return PLBA_E_INVALID;
+    MapMatchStats ms;
+    LbaStats st;
+    CullStats cs;
+    const int rc = m->mh.localMappingStepKf(kf_idx, mapmatch_params(params), &ms, &st, &cs);
+    if (rc) return rc;
+    export_mapmatch_stats(ms, match_stats);
+    copy_stats(st, stats);
+    if (n_pt_removed) *n_pt_removed = cs.points_removed;
+    if (n_ln_removed) *n_ln_removed = cs.lines_removed;
+    return PLBA_OK;
+}
+
+int plslam_grid_match_cpu(void *user, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
+    (void)user;
+    return gridMatchCpu(b, matches_12, n_matches);
+}
+
 int plslam_get_lc_state(plslam_map *m, int32_t *state) {
     if (!m || !state) return PLBA_E_INVALID;
     *state = m->mh.lc_state;

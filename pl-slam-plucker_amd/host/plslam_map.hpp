@@ -67,6 +67,9 @@ struct StereoFrame {
     std::vector<uint8_t> pdesc_l, ldesc_l;
     std::vector<double> pt_P, pt_pl;          // [n_pt][3], [n_pt][2]
     std::vector<double> ls_sP, ls_eP, ls_le;  // [n_ls][3]
+    // what matchMap2KFLines reads besides (src/mapHandler.cpp:857-861, :903): the image endpoints
+    bool has_endpoints = false;
+    std::vector<double> ls_spl, ls_epl;       // [n_ls][2]
 };
 
 // include/keyFrame.h:50-71
@@ -221,6 +224,23 @@ struct LcStats {
     PgoStats pgo;
 };
 
+using GridMatchFn = int (*)(void *user, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
+
+// What matchMap2KFPoints / Lines read of SlamConfig and Config (src/slamConfig.cpp:43,51-52,85-86;
+// src2/config.cpp:51,60,63,68,92). fast_matching is false in slamConfig.cpp and true in the
+// configuration files the reference ships (config/config/config.yaml:5): true here.
+struct MapMatchParams {
+    bool fast_matching = true, best_lr = true, has_points = true, has_lines = true;
+    int ws = 3, min_pt_matches = 10, min_ls_matches = 6;
+    double max_kf_epip_p = 1.0, max_kf_epip_l = 1.0, line_sim_th = 0.75, min_ratio_12_p = 0.9, min_ratio_12_l = 0.9;
+};
+
+struct MapMatchStats {
+    int visible[2] = {0, 0}, unmatched[2] = {0, 0};  // [points, lines]: landmarks projected into the image, features with idx -1
+    int grid_matches[2] = {0, 0}, fallback[2] = {0, 0}, accepted[2] = {0, 0}, rejected[2] = {0, 0};
+    double match_ms = 0;
+};
+
 struct CullStats {
     int points_removed = 0, lines_removed = 0;
 };
@@ -298,6 +318,20 @@ class MapHandler {
     int verifyLoopCandidates(int kf_curr_idx, int n, const int32_t *kf_prev_idx, const MatchParams &mp,
                              double lc_inlier_ratio, int32_t *accepted, double *pose_inc, int32_t *n_matches);
     void setMatchFn(MatchFn fn, void *user) { match_fn_ = fn; match_user_ = user; }
+    // map_match.cpp. matchMap2KFPoints + matchMap2KFLines (src/mapHandler.cpp:697-921) for keyframe
+    // kf_idx: the local landmarks not yet seen by it that project into the image against its features
+    // with idx -1, by one plba_grid_match call (points and lines) and, where the reference falls back
+    // to match() (:759-764, :874-879), one plba_desc_match call; then the epipolar tests, the feature
+    // idx, addMapPointObservation / addMapLineObservation and full_graph. Twf == nullptr: the inverse
+    // of the keyframe's T_kf_w. Anything invalid returns PLBA_E_INVALID before the map is touched.
+    int matchMapToKf(int kf_idx, const Mat4 *Twf, const MapMatchParams &p, MapMatchStats *stats = nullptr);
+    // matchMapToKf, then localMappingStep
+    int localMappingStepKf(int kf_idx, const MapMatchParams &p, MapMatchStats *ms = nullptr, LbaStats *stats = nullptr,
+                           CullStats *cs = nullptr);
+    void setGridMatchFn(GridMatchFn fn, void *user) { grid_fn_ = fn; grid_user_ = user; }
+    void setCamera(double fx, double fy, double cx, double cy, int width, int height) {
+        fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy; width_ = width; height_ = height;
+    }
     std::vector<std::vector<Vec4i>> lc_pt_idxs, lc_ls_idxs;  // inlier-filtered rows, one list per loop (:4078-4079)
     plba_lcpose_params lcpose_params{1e-7, 1.0, 0.01, 0.3, 1.5, 35.0, 5, 10, PLBA_LCPOSE_ROBUST_GN, 0};
     void setLcposeSolver(LcposeSolveFn fn, void *user) { lcpose_fn_ = fn; lcpose_user_ = user; }
@@ -356,6 +390,9 @@ class MapHandler {
     void *lcpose_user_ = nullptr;
     MatchFn match_fn_ = nullptr;
     void *match_user_ = nullptr;
+    GridMatchFn grid_fn_ = nullptr;
+    void *grid_user_ = nullptr;
+    int width_ = 0, height_ = 0;  // the image size (cam->getWidth() / getHeight()); 0: not set
     // the matched features of kf_prev_idx[0..n) against kf_curr_idx, by one match call
     struct LcBuilt;
     int buildLoopCandidates(int kf_curr_idx, int n, const int32_t *kf_prev_idx, const MatchParams &mp,
@@ -381,5 +418,12 @@ Vec6 logmap_se3(const Mat4 &T);
 int hamming(const Desc &a, const Desc &b);
 // tools/descmatch_bench.py only: plba_desc_match's semantics, single-threaded, on the CPU
 int descMatchCpu(const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
+// map_match.cpp. getLineCoords / LineIterator (src2/gridStructure.cpp:33-41, src2/lineIterator.cpp): the
+// cells a line from (x1, y1) to (x2, y2), in grid units, is entered under in the matching grid
+// Returns the number of cells and writes at most max_out of them; -1 for coordinates that are not
+// finite or beyond +-1e6 cells.
+long lineCells(double x1, double y1, double x2, double y2, std::vector<std::array<int, 2>> &out, size_t max_out);
+// tools/gridmatch_bench.py and the tests only: plba_grid_match's semantics, single-threaded, on the CPU
+int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
 
 }  // namespace plslam

@@ -364,3 +364,65 @@ class MatchBatchView:
             n=len(pairs), desc_bytes=self.desc_bytes, off1=_ptr(self.off1, _ip), off2=_ptr(self.off2, _ip),
             desc1=_ptr(self.desc1, _bp), desc2=_ptr(self.desc2, _bp), nnr=_ptr(self.nnr, _fp),
             best_lr=int(bool(best_lr)), pad=0)
+
+
+# ---- grid-guided matching (plba_gridmatch_batch / plba_grid_match)
+class PlbaGridMatchBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32),
+                ("best_lr", C.c_int32), ("pad", C.c_int32), ("off1", _ip), ("off2", _ip), ("desc1", _bp),
+                ("desc2", _bp), ("cell1", _ip), ("cell1_end", _ip), ("cell_off2", _ip), ("cells2", _ip),
+                ("dir2", _dp), ("kind", _ip), ("ws", _ip), ("nnr", _dp), ("line_sim_th", _dp)]
+
+
+class GridMatchBatchView:
+    """Concatenates matchGrid problems into contiguous arrays and the PlbaGridMatchBatch over them.
+    A problem is a dict: kind (0 points, 1 lines), ws, nnr, line_sim_th (lines), desc1 [n1][desc_bytes]
+    uint8, cell1 [n1][2] int, cell1_end [n1][2] (lines), desc2 [n2][desc_bytes], cells2 (one [k][2] int
+    array per train row) and dir2 [n2][2] (lines)."""
+
+    def __init__(self, problems, cols: int = 64, rows: int = 48, best_lr: bool = True, desc_bytes=None):
+        problems = list(problems)
+        if desc_bytes is None:
+            desc_bytes = next((np.asarray(p[k]).shape[1] for p in problems for k in ("desc1", "desc2")
+                               if np.asarray(p[k]).ndim == 2 and np.asarray(p[k]).shape[1]), 32)
+        self.desc_bytes = db = int(desc_bytes)
+        n = len(problems)
+        d1 = [np.asarray(p["desc1"], np.uint8).reshape(-1, db) for p in problems]
+        d2 = [np.asarray(p["desc2"], np.uint8).reshape(-1, db) for p in problems]
+        self.off1 = np.zeros(n + 1, np.int32)
+        self.off2 = np.zeros(n + 1, np.int32)
+        self.off1[1:] = np.cumsum([len(a) for a in d1], dtype=np.int64)
+        self.off2[1:] = np.cumsum([len(a) for a in d2], dtype=np.int64)
+        self.desc1 = np.ascontiguousarray(np.concatenate(d1 + [np.zeros((0, db), np.uint8)]))
+        self.desc2 = np.ascontiguousarray(np.concatenate(d2 + [np.zeros((0, db), np.uint8)]))
+        n1, n2 = int(self.off1[-1]), int(self.off2[-1])
+        self.cell1 = np.zeros((n1, 2), np.int32)
+        self.cell1_end = np.zeros((n1, 2), np.int32)
+        self.dir2 = np.zeros((n2, 2), np.float64)
+        counts, cells = [], [np.zeros((0, 2), np.int32)]
+        for k, p in enumerate(problems):
+            a, b = self.off1[k], self.off1[k + 1]
+            self.cell1[a:b] = np.asarray(p["cell1"], np.int32).reshape(-1, 2)
+            if p["kind"] == 1:
+                self.cell1_end[a:b] = np.asarray(p["cell1_end"], np.int32).reshape(-1, 2)
+                self.dir2[self.off2[k]:self.off2[k + 1]] = np.asarray(p["dir2"], np.float64).reshape(-1, 2)
+            if len(p["cells2"]) != len(d2[k]):
+                raise ValueError("one cell list per train row")
+            for c in p["cells2"]:
+                c = np.asarray(c, np.int32).reshape(-1, 2)
+                counts.append(len(c))
+                cells.append(c)
+        self.cell_off2 = np.zeros(n2 + 1, np.int32)
+        self.cell_off2[1:] = np.cumsum(counts, dtype=np.int64)
+        self.cells2 = np.ascontiguousarray(np.concatenate(cells))
+        self.kind = np.array([int(p["kind"]) for p in problems], np.int32).reshape(n)
+        self.ws = np.array([int(p["ws"]) for p in problems], np.int32).reshape(n)
+        self.nnr = np.array([float(p["nnr"]) for p in problems], np.float64).reshape(n)
+        self.line_sim_th = np.array([float(p.get("line_sim_th", 0.75)) for p in problems], np.float64).reshape(n)
+        self.struct = PlbaGridMatchBatch(
+            n=n, desc_bytes=db, cols=int(cols), rows=int(rows), best_lr=int(bool(best_lr)), pad=0,
+            off1=_ptr(self.off1, _ip), off2=_ptr(self.off2, _ip), desc1=_ptr(self.desc1, _bp),
+            desc2=_ptr(self.desc2, _bp), cell1=_ptr(self.cell1, _ip), cell1_end=_ptr(self.cell1_end, _ip),
+            cell_off2=_ptr(self.cell_off2, _ip), cells2=_ptr(self.cells2, _ip), dir2=_ptr(self.dir2, _dp),
+            kind=_ptr(self.kind, _ip), ws=_ptr(self.ws, _ip), nnr=_ptr(self.nnr, _dp),
+            line_sim_th=_ptr(self.line_sim_th, _dp))

@@ -31,7 +31,7 @@ EXPORTED = [
     "plba_hlm_default_params", "plba_hlm_lba",
     "plba_pgo_default_params", "plba_pgo_optimize",
     "plba_lcpose_default_params", "plba_lc_relative_pose",
-    "plba_desc_match",
+    "plba_desc_match", "plba_grid_match",
 ]
 
 # int (*plba_host_allreduce_fn)(void *user, double *buf, int64_t n)
@@ -96,6 +96,7 @@ def load(path: Optional[str] = None):
     L.plba_lc_relative_pose.argtypes = [vp, C.POINTER(capi.PlbaLcposeBatch), C.POINTER(capi.PlbaLcposeParams),
                                         C.POINTER(capi.PlbaLcposeOut), bp, bp]
     L.plba_desc_match.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
+    L.plba_grid_match.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
     for name in EXPORTED:
         f = getattr(L, name)
         if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
@@ -321,6 +322,20 @@ class Solver:
         cnt = np.zeros(max(n, 1), np.int32)
         self._check(self.L.plba_desc_match(self.ctx, C.byref(bv.struct), _p(m12, C.c_int32), _p(cnt, C.c_int32)),
                     "plba_desc_match")
+        return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+
+    def grid_match(self, problems, cols: int = 64, rows: int = 48, best_lr: bool = True, desc_bytes=None) -> list:
+        """Grid-guided descriptor matching (plba_grid_match; both StVO::matchGrid overloads,
+        src2/matching.cpp:111-258) of a batch of problems (capi.GridMatchBatchView: point and line
+        problems mixed) over a cols x rows grid, in one call. One (matches_12, n_matches) per problem:
+        the train row of each query row or -1, and their count. Needs no uploaded window and leaves
+        one intact."""
+        bv = capi.GridMatchBatchView(problems, cols, rows, best_lr, desc_bytes)
+        n = bv.struct.n
+        m12 = np.full(max(int(bv.off1[-1]), 1), -1, np.int32)
+        cnt = np.zeros(max(n, 1), np.int32)
+        self._check(self.L.plba_grid_match(self.ctx, C.byref(bv.struct), _p(m12, C.c_int32), _p(cnt, C.c_int32)),
+                    "plba_grid_match")
         return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
 
     def trace(self) -> np.ndarray:

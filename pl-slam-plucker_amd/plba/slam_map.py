@@ -234,6 +234,38 @@ def match_params(min_ratio_12_p: float = 0.9, min_ratio_12_l: float = 0.9, best_
                              has_points=int(has_points), has_lines=int(has_lines), pad=0)
 
 
+GRID_MATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaGridMatchBatch), C.POINTER(C.c_int32),
+                            C.POINTER(C.c_int32))
+
+
+class PlslamMapMatchParams(C.Structure):
+    _fields_ = [("fast_matching", C.c_int32), ("ws", C.c_int32), ("min_pt_matches", C.c_int32),
+                ("min_ls_matches", C.c_int32), ("best_lr", C.c_int32), ("has_points", C.c_int32),
+                ("has_lines", C.c_int32), ("pad", C.c_int32), ("max_kf_epip_p", C.c_double),
+                ("max_kf_epip_l", C.c_double), ("line_sim_th", C.c_double), ("min_ratio_12_p", C.c_double),
+                ("min_ratio_12_l", C.c_double)]
+
+
+class PlslamMapMatchStats(C.Structure):
+    _fields_ = [("visible", C.c_int32 * 2), ("unmatched", C.c_int32 * 2), ("grid_matches", C.c_int32 * 2),
+                ("fallback", C.c_int32 * 2), ("accepted", C.c_int32 * 2), ("rejected", C.c_int32 * 2),
+                ("match_ms", C.c_double)]
+
+    def as_dict(self):
+        return {f: (list(getattr(self, f)) if f != "match_ms" else self.match_ms) for f, _ in self._fields_}
+
+
+def mapmatch_params(**kw) -> PlslamMapMatchParams:
+    """The reference's defaults (plslam_mapmatch_default_params) with ``kw`` over them."""
+    p = PlslamMapMatchParams()
+    load_host().plslam_mapmatch_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(p._fields_):
+            raise TypeError(k)
+        setattr(p, k, v)
+    return p
+
+
 class PlslamLcCandidate(C.Structure):
     _fields_ = [("kf_prev_idx", C.c_int32), ("kf_curr_idx", C.c_int32), ("n_pt_0", C.c_int32), ("n_pt_1", C.c_int32),
                 ("n_ls_0", C.c_int32), ("n_ls_1", C.c_int32), ("has_points", C.c_int32), ("has_lines", C.c_int32),
@@ -273,6 +305,9 @@ HOST_EXPORTED = [
     "plslam_get_lc_pose_list", "plslam_get_lc_feature_idxs",
     "plslam_set_keyframe_features", "plslam_set_match_fn", "plslam_loop_closure_step_kf",
     "plslam_verify_loop_candidates", "plslam_desc_match_cpu",
+    "plslam_line_cells", "plslam_grid_match_cpu",
+    "plslam_set_keyframe_line_endpoints", "plslam_set_camera", "plslam_set_grid_match_fn",
+    "plslam_mapmatch_default_params", "plslam_match_map_to_kf", "plslam_local_mapping_step_kf",
 ]
 
 
@@ -359,11 +394,49 @@ def load_host(path: Optional[str] = None):
     L.plslam_verify_loop_candidates.argtypes = [vp, C.c_int32, C.c_int32, ip, C.POINTER(PlslamMatchParams), C.c_double,
                                                 ip, dp, ip]
     L.plslam_desc_match_cpu.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
+    L.plslam_line_cells.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, ip, C.c_int32, ip]
+    L.plslam_grid_match_cpu.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
+    L.plslam_set_keyframe_line_endpoints.argtypes = [vp, C.c_int32, dp, dp]
+    L.plslam_set_camera.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32]
+    L.plslam_set_grid_match_fn.argtypes = [vp, GRID_MATCH_FN, vp]
+    L.plslam_mapmatch_default_params.argtypes = [C.POINTER(PlslamMapMatchParams)]
+    L.plslam_mapmatch_default_params.restype = None
+    L.plslam_match_map_to_kf.argtypes = [vp, C.c_int32, dp, C.POINTER(PlslamMapMatchParams),
+                                         C.POINTER(PlslamMapMatchStats)]
+    L.plslam_local_mapping_step_kf.argtypes = [vp, C.c_int32, C.POINTER(PlslamMapMatchParams),
+                                               C.POINTER(PlslamMapMatchStats), C.POINTER(PlslamLbaStats), ip, ip]
     for n in HOST_EXPORTED:
-        if n not in ("plslam_map_last_error", "plslam_pluker_to_orth", "plslam_orth_to_pluker"):
+        if n not in ("plslam_map_last_error", "plslam_pluker_to_orth", "plslam_orth_to_pluker",
+                     "plslam_mapmatch_default_params"):
             getattr(L, n).restype = C.c_int
     _hl = L
     return L
+
+
+def line_cells(x1: float, y1: float, x2: float, y2: float) -> np.ndarray:
+    """getLineCoords (src2/gridStructure.cpp:33-41): the grid cells [k][2] of a line given in grid units."""
+    L = load_host()
+    n = C.c_int32(0)
+    ip = C.POINTER(C.c_int32)
+    L.plslam_line_cells(x1, y1, x2, y2, None, 0, C.byref(n))
+    out = np.zeros((max(n.value, 1), 2), np.int32)
+    rc = L.plslam_line_cells(x1, y1, x2, y2, out.ctypes.data_as(ip), n.value, C.byref(n))
+    if rc != 0:
+        raise PlbaError(f"plslam_line_cells failed: {rc}")
+    return out[:n.value]
+
+
+def grid_match_cpu(problems, cols: int = 64, rows: int = 48, best_lr: bool = True, desc_bytes=None) -> list:
+    """plslam_grid_match_cpu on the problems of Solver.grid_match (tests and tools/gridmatch_bench.py)."""
+    bv = capi.GridMatchBatchView(problems, cols, rows, best_lr, desc_bytes)
+    n = bv.struct.n
+    ip = C.POINTER(C.c_int32)
+    m12 = np.full(max(int(bv.off1[-1]), 1), -1, np.int32)
+    cnt = np.zeros(max(n, 1), np.int32)
+    rc = load_host().plslam_grid_match_cpu(None, C.byref(bv.struct), m12.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
+    if rc != 0:
+        raise PlbaError(f"plslam_grid_match_cpu failed: {rc}")
+    return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
 
 
 def _d(a):
@@ -729,6 +802,60 @@ class HostMap:
             lc_inlier_ratio, acc.ctypes.data_as(ip), pose.ctypes.data_as(C.POINTER(C.c_double)), cnt.ctypes.data_as(ip)),
             "verify_loop_candidates")
         return dict(accepted=acc[:k], pose_inc=pose[:k], n_matches=cnt[:k])
+
+    # ---- matchMap2KFPoints / Lines (src/mapHandler.cpp:697-921)
+    def set_keyframe_line_endpoints(self, kf_idx: int, spl, epl):
+        """The image endpoints spl / epl [n_ls][2] of keyframe ``kf_idx``'s line features."""
+        a, b = (np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1, 2)) for x in (spl, epl))
+        if not len(a) == len(b) == self._kf_feat.get(kf_idx, (0, 0))[1]:
+            raise ValueError("one row per line feature")
+        dp = C.POINTER(C.c_double)
+        self._check(self.L.plslam_set_keyframe_line_endpoints(self.h, kf_idx, a.ctypes.data_as(dp), b.ctypes.data_as(dp)),
+                    "set_keyframe_line_endpoints")
+
+    def set_camera(self, fx: float, fy: float, cx: float, cy: float, width: int, height: int):
+        self._check(self.L.plslam_set_camera(self.h, fx, fy, cx, cy, width, height), "set_camera")
+
+    def set_grid_match_fn(self, fn):
+        """fn(batch, matches_12, n_matches) -> int; "cpu" for plslam_grid_match_cpu; None for the
+        MI355X backend (plba_grid_match)."""
+        if fn is None:
+            self._gcb = None
+            self._check(self.L.plslam_set_grid_match_fn(self.h, C.cast(None, GRID_MATCH_FN), None), "set_grid_match_fn")
+            return
+        if fn == "cpu":
+            self._gcb = C.cast(self.L.plslam_grid_match_cpu, GRID_MATCH_FN)
+        else:
+            def tramp(user, bp_, m12, cnt):
+                try:
+                    return int(fn(bp_.contents, m12, cnt))
+                except Exception:  # never unwind through C
+                    import traceback
+                    traceback.print_exc()
+                    return -1
+            self._gcb = GRID_MATCH_FN(tramp)
+        self._check(self.L.plslam_set_grid_match_fn(self.h, self._gcb, None), "set_grid_match_fn")
+
+    def match_map_to_kf(self, kf_idx: int, Twf=None, params: Optional[PlslamMapMatchParams] = None) -> dict:
+        """matchMap2KFPoints + matchMap2KFLines for keyframe ``kf_idx``; ``Twf`` (4, 4) world ->
+        keyframe, None for the inverse of its T_kf_w. Returns the statistics."""
+        st = PlslamMapMatchStats()
+        T = None if Twf is None else np.ascontiguousarray(np.asarray(Twf, np.float64).reshape(16))
+        self._check(self.L.plslam_match_map_to_kf(
+            self.h, kf_idx, T.ctypes.data_as(C.POINTER(C.c_double)) if T is not None else None,
+            C.byref(params) if params is not None else None, C.byref(st)), "match_map_to_kf")
+        return st.as_dict()
+
+    def local_mapping_step_kf(self, kf_idx: int, params: Optional[PlslamMapMatchParams] = None) -> dict:
+        """match_map_to_kf, then local_mapping_step."""
+        ms, st = PlslamMapMatchStats(), PlslamLbaStats()
+        a, b = C.c_int32(), C.c_int32()
+        self._check(self.L.plslam_local_mapping_step_kf(self.h, kf_idx, C.byref(params) if params is not None else None,
+                                                        C.byref(ms), C.byref(st), C.byref(a), C.byref(b)),
+                    "local_mapping_step_kf")
+        d = st.as_dict()
+        d["points_removed"], d["lines_removed"], d["match"] = a.value, b.value, ms.as_dict()
+        return d
 
     def lc_state(self) -> int:
         v = C.c_int32(0)
