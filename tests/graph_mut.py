@@ -59,12 +59,31 @@ def all_fixed(g: Graph) -> Graph:
     return h
 
 
-def add_idle_free_pose(g: Graph) -> Graph:
-    """A free keyframe that no edge observes (inactive in g2o, must stay untouched)."""
+def free_rows(g: Graph) -> np.ndarray:
+    """Array indices of the free keyframes in increasing kf_id: entry r is row r of the reduced
+    camera system as g2o builds it (and as the solver factorises it when no reordering runs)."""
+    free = np.nonzero(g.kf_fixed == 0)[0]
+    return free[np.argsort(g.kf_id[free], kind="stable")]
+
+
+def add_idle_free_pose(g: Graph, row=None) -> Graph:
+    """A free keyframe that no edge observes (inactive in g2o, must stay untouched). It is the
+    last array entry. row: its position among the free poses of the new window in increasing
+    kf_id (negative: from the end); every vertex id at or above the one it takes moves up by one.
+    Default: the id after the largest keyframe id."""
     h = g.copy()
     h.kf_Tcw = np.concatenate([g.kf_Tcw, g.kf_Tcw[-1:]])
     h.kf_fixed = np.concatenate([g.kf_fixed, np.zeros(1, np.uint8)])
-    h.kf_id = np.concatenate([g.kf_id, np.array([g.kf_id.max() + 1], np.int32)])
+    if row is None:
+        h.kf_id = np.concatenate([g.kf_id, np.array([g.kf_id.max() + 1], np.int32)])
+        return h
+    ids = g.kf_id[free_rows(g)]
+    r = row + len(ids) + 1 if row < 0 else row
+    assert 0 <= r <= len(ids), (row, len(ids))
+    new = int(ids[r]) if r < len(ids) else int(ids[-1]) + 1 if len(ids) else int(g.kf_id.max(initial=-1)) + 1
+    h.kf_id = np.concatenate([g.kf_id + (g.kf_id >= new), np.array([new])]).astype(np.int32)
+    h.pt_id = (g.pt_id + (g.pt_id >= new)).astype(np.int32)
+    h.ln_id = (g.ln_id + (g.ln_id >= new)).astype(np.int32)
     return h
 
 
@@ -77,13 +96,15 @@ def fixed_only_landmarks(g: Graph) -> Graph:
     return h
 
 
-def zero_information_keyframe(g: Graph) -> Graph:
+def zero_information_keyframe(g: Graph, row=None) -> Graph:
     """Ω = 0 on every edge of one free keyframe: the vertex stays active (it has edges) but its
     reduced-camera block row is exactly zero, so with λ = 0 the LDLᵀ meets an exact zero pivot
-    in any elimination order (g2o's LinearSolverEigen fails there too)."""
+    in any elimination order (g2o's LinearSolverEigen fails there too). row: the keyframe's
+    position among the free poses in increasing kf_id (negative: from the end). Default: the
+    middle free keyframe in array order."""
     h = g.copy()
     free = np.nonzero(g.kf_fixed == 0)[0]
-    k = free[len(free) // 2]
+    k = free[len(free) // 2] if row is None else free_rows(g)[row]
     h.ept_info = np.where(g.ept_kf == k, 0.0, g.ept_info)
     h.eln_info = np.where(g.eln_kf == k, 0.0, g.eln_info)
     return h
