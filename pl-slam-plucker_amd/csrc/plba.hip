@@ -28,23 +28,10 @@
 #include "../../include/plba.h"
 #include "plba_build.hpp"
 #include "plba_kernels.hpp"
-#include "plba_lcpose.hpp"
-#include "plba_match.hpp"
-#include "plba_gridmatch.hpp"
 #include "plba_plan.hpp"
+#include "plba_scratch.hpp"
 
 namespace plba {
-
-#define PLBA_CHECK(expr)                                                                       \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) {                                                                \
-            (void)hipGetLastError(); /* do not leak into the next launch check */              \
-            ctx->set_error("HIP error %s at %s:%d: %s", hipGetErrorString(_e), __FILE__,       \
-                           __LINE__, #expr);                                                   \
-            return PLBA_E_DEVICE;                                                              \
-        }                                                                                      \
-    } while (0)
 
 enum KernelId {
     K_LINEARIZE, K_REDUCE, K_ITER_INIT, K_ESCHUR, K_MEMSET, K_ASSEMBLE, K_FINALIZE, K_FACTOR,
@@ -62,10 +49,7 @@ static const char *kKernelNames[K_COUNT] = {
 
 using namespace plba;
 
-struct plba_ctx {
-    plba_opts opts;
-    std::string err;
-    hipStream_t stream = nullptr;
+struct plba_ctx : plba::CtxBase {  // (opts, err / set_error, stream and the scratch blocks)
     bool uploaded = false, initialized = false;
     int level = 0;
     int robust = 1;
@@ -144,28 +128,7 @@ struct plba_ctx {
     size_t ev_next = 0;
     double k_ms[K_COUNT] = {0};
     int32_t k_n[K_COUNT] = {0};
-    // loop-closure pose graph (plba_pgo_optimize): its own grow-only device block, independent
-    // of the window arena (a PGO call leaves an uploaded window intact)
-    char *pgo_mem = nullptr;
-    size_t pgo_cap = 0;
-    double *pgo_hout = nullptr;  // pinned [4]
-    // loop-closure relative pose (plba_lc_relative_pose): a grow-only device block and its pinned
-    // host image (inputs up, results and inlier flags down), kept across calls
-    char *lc_mem = nullptr, *lc_host = nullptr;
-    size_t lc_cap = 0, lc_host_cap = 0;
-    // descriptor matching (plba_desc_match): the same, a block of its own
-    char *dm_mem = nullptr, *dm_host = nullptr;
-    size_t dm_cap = 0, dm_host_cap = 0;
 
-    void set_error(const char *fmt, ...) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        if (opts.verbose) fprintf(stderr, "[plba] %s\n", buf);
-    }
     // A new window keeps the instantiated step graphs: the next capture updates them in place
     // (hipGraphExecUpdate, same topology, new kernel arguments and grids) instead of destroying
     // and re-instantiating five executable graphs (capture_step).
@@ -921,20 +884,11 @@ int build_block_pattern(plba_ctx *ctx, WindowStructure &ws, PhaseLog &mark, Bloc
     bp.ch_off.push_back(blk_off[nblk]);
     bp.nch = (int)bp.ch_blk.size();
     // envelope of the lower triangle (per 6-row pose block: first pose block column)
-    const int n = bp.n = 6 * nf, ntiles = bp.ntiles = (n + kTile - 1) / kTile;
-    bp.tile_first.assign(std::max(ntiles, 1), 0);
-    bp.tile_last.assign(std::max(ntiles, 1), 0);
-    for (int I = 0; I < ntiles; ++I) {
-        int f = I;
-        for (int r = I * kTile; r < std::min(n, (I + 1) * kTile); ++r) f = std::min(f, (6 * first_blk[r / 6]) / kTile);
-        bp.tile_first[I] = f;
-    }
-    for (int K = 0; K < ntiles; ++K) {
-        int last = K;
-        for (int I = K; I < ntiles; ++I)
-            if (bp.tile_first[I] <= K) last = I;
-        bp.tile_last[K] = last;
-    }
+    bp.n = 6 * nf;
+    bp.ntiles = (bp.n + kTile - 1) / kTile;
+    TileEnvelope te = tile_envelope(first_blk, bp.n, kTile);
+    bp.tile_first = std::move(te.tile_first);
+    bp.tile_last = std::move(te.tile_last);
     ctx->h_tile_last = bp.tile_last;
     mark("chunks + envelope");
     return PLBA_OK;
@@ -1573,16 +1527,8 @@ int agree_dev_error(plba_ctx *ctx, int mine, int *any) {
 
 // Run a schedule of 1 or 2 optimize() calls entirely on the device: replay the step graph in
 // batches, polling the control block once per batch.
-// every launch outside the step graphs is checked where it is issued (the graph launches are
-// checked by LAUNCH / launch_band)
-#define PLBA_LAUNCHED(ctx_, name_)                                                        \
-    do {                                                                                  \
-        const hipError_t le_ = hipGetLastError();                                         \
-        if (le_ != hipSuccess) {                                                          \
-            (ctx_)->set_error("kernel %s launch failed: %s", name_, hipGetErrorString(le_)); \
-            return PLBA_E_DEVICE;                                                         \
-        }                                                                                 \
-    } while (0)
+// every launch outside the step graphs is checked where it is issued (PLBA_LAUNCHED; the graph
+// launches are checked by LAUNCH / launch_band)
 int run_schedule_once(plba_ctx *ctx, const Ctrl &init, bool &dev_error) {
     dev_error = false;
     Dev &d = ctx->d;
@@ -1793,6 +1739,8 @@ int download_outputs(plba_ctx *ctx, double *kf_Tcw, double *pt_xyz, double *ln_o
 
 }  // namespace
 
+#include "plba_pgo_driver.hpp"
+
 // ==================================================================================== C ABI
 extern "C" {
 
@@ -1977,15 +1925,11 @@ int plba_destroy(plba_ctx *ctx) {
     for (void *p : ctx->retired) (void)hipHostFree(p);
     for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->h_ctrl) (void)hipHostFree(ctx->h_ctrl);
-    if (ctx->pgo_mem) (void)hipFreeAsync(ctx->pgo_mem, ctx->stream);
     ctx->bmemA.release(ctx->stream);
     ctx->bmemB.release(ctx->stream);
+    for (ScratchBlock *sb : {&ctx->pgo, &ctx->lc, &ctx->match}) sb->release(ctx->stream);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->pgo_hout) (void)hipHostFree(ctx->pgo_hout);
-    if (ctx->lc_mem) (void)hipFreeAsync(ctx->lc_mem, ctx->stream);
-    if (ctx->lc_host) (void)hipHostFree(ctx->lc_host);
-    if (ctx->dm_mem) (void)hipFreeAsync(ctx->dm_mem, ctx->stream);
-    if (ctx->dm_host) (void)hipHostFree(ctx->dm_host);
+    for (ScratchBlock *sb : {&ctx->pgo, &ctx->lc, &ctx->match}) sb->release_host();
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
     if (ctx->comm.hbuf) (void)hipHostFree(ctx->comm.hbuf);
     if (ctx->comm.nccl) (void)ncclCommDestroy(ctx->comm.nccl);
@@ -2441,56 +2385,7 @@ int plba_enable_kernel_timing(plba_ctx *ctx, int32_t on) {
 }
 
 // ---------------------------------------------------------------- loop-closure pose graph
-// MapHandler::loopClosureOptimization{EssGraph,CovGraph}G2O (src/mapHandler.cpp:5070-5531):
-// g2o SparseOptimizer::initializeOptimization / computeInitialGuess / optimize over VertexSE3 +
-// EdgeSE3 with OptimizationAlgorithmLevenberg (setUserLambdaInit) — device kernels in
-// csrc/plba_pgo.hpp, Levenberg decisions here.
-namespace {
-#pragma clang fp contract(off)
-struct HIso {
-    double R[9], t[3];
-};
-HIso hiso_load(const double *T) {
-    HIso a;
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) a.R[3 * r + c] = T[4 * r + c];
-        a.t[r] = T[4 * r + 3];
-    }
-    return a;
-}
-void hiso_store(const HIso &a, double *T) {
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) T[4 * r + c] = a.R[3 * r + c];
-        T[4 * r + 3] = a.t[r];
-    }
-}
-HIso hiso_mul(const HIso &a, const HIso &b) {
-    HIso o;
-    for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) {
-            double s = 0.0;
-            for (int k = 0; k < 3; ++k) s = s + a.R[3 * r + k] * b.R[3 * k + c];
-            o.R[3 * r + c] = s;
-        }
-        double s = 0.0;
-        for (int k = 0; k < 3; ++k) s = s + a.R[3 * r + k] * b.t[k];
-        o.t[r] = s + a.t[r];
-    }
-    return o;
-}
-HIso hiso_inv(const HIso &a) {
-    HIso o;
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) o.R[3 * r + c] = a.R[3 * c + r];
-    for (int r = 0; r < 3; ++r) {
-        double s = 0.0;
-        for (int k = 0; k < 3; ++k) s = s + o.R[3 * r + k] * a.t[k];
-        o.t[r] = -s;
-    }
-    return o;
-}
-}  // namespace
-
+// defaults and the forwarder here; the driver is csrc/plba_pgo_driver.hpp
 void plba_pgo_default_params(plba_pgo_params *p) {
     if (!p) return;
     p->user_lambda_init = 1e-10;  // src/mapHandler.cpp:5085
@@ -2501,359 +2396,11 @@ void plba_pgo_default_params(plba_pgo_params *p) {
 }
 
 int plba_pgo_optimize(plba_ctx *ctx, const plba_pgo_graph *g, const plba_pgo_params *pp, plba_pgo_result *res) {
-#pragma clang fp contract(off)
-    if (!ctx || !g || !res || g->n_v < 0 || g->n_e < 0) return PLBA_E_INVALID;
-    if ((g->n_v && (!g->v_id || !g->v_T || !g->v_fixed)) || (g->n_e && (!g->e_v || !g->e_Z))) return PLBA_E_INVALID;
-    plba_pgo_params prm;
-    if (pp) prm = *pp;
-    else plba_pgo_default_params(&prm);
-    if (prm.max_iters < 0 || prm.max_trials < 1) {
-        ctx->set_error("max_iters must be >= 0 and max_trials >= 1");
-        return PLBA_E_INVALID;
-    }
-    const int nv = g->n_v, ne = g->n_e;
-    for (int e = 0; e < 2 * ne; ++e)
-        if (g->e_v[e] < 0 || g->e_v[e] >= nv) {
-            ctx->set_error("pose-graph edge %d references vertex %d (n_v %d)", e / 2, g->e_v[e], nv);
-            return PLBA_E_INVALID;
-        }
-    {
-        std::vector<int32_t> ids(g->v_id, g->v_id + nv);
-        std::sort(ids.begin(), ids.end());
-        if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) {
-            ctx->set_error("duplicate pose-graph vertex id");
-            return PLBA_E_INVALID;
-        }
-    }
-    (void)hipSetDevice(ctx->opts.device);
-    const Tuning tuning = read_tuning();  // (PLBA_NO_RCM, PLBA_SOLVE_LDS_N: sampled per call)
-    const auto t0 = std::chrono::steady_clock::now();
-    // ---- SparseOptimizer::initializeOptimization(): active edges (not all vertices fixed) in
-    //      creation order; Hessian index of the active free vertices in id order
-    std::vector<HIso> X(nv), Z(ne), Zinv(ne);
-    for (int v = 0; v < nv; ++v) X[v] = hiso_load(g->v_T + 12 * (size_t)v);
-    for (int e = 0; e < ne; ++e) {
-        Z[e] = hiso_load(g->e_Z + 12 * (size_t)e);
-        Zinv[e] = hiso_inv(Z[e]);  // EdgeSE3::setMeasurement keeps the inverse
-    }
-    std::vector<int32_t> act;
-    std::vector<uint8_t> is_act(ne, 0);
-    std::vector<int> nact_v(nv, 0);
-    for (int e = 0; e < ne; ++e) {
-        const int a = g->e_v[2 * e], b = g->e_v[2 * e + 1];
-        if (g->v_fixed[a] && g->v_fixed[b]) continue;
-        act.push_back(e);
-        is_act[e] = 1;
-        ++nact_v[a];
-        ++nact_v[b];
-    }
-    std::vector<int> order(nv);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return g->v_id[a] < g->v_id[b]; });
-    std::vector<int32_t> hidx(nv, -1);
-    int nfree = 0;
-    for (int v : order)
-        if (nact_v[v] > 0 && !g->v_fixed[v]) hidx[v] = nfree++;
-    // ---- computeInitialGuess(): EstimatePropagator from the fixed vertices of the active edges
-    //      (std::set<Vertex*>: creation order), unit edge cost, multimap frontier (smallest
-    //      distance first, FIFO among equals), EdgeSE3::initialEstimate on each first reach
-    if (prm.initial_guess) {
-        std::vector<std::vector<int>> vedges(nv);
-        for (int e = 0; e < ne; ++e) {
-            vedges[g->e_v[2 * e]].push_back(e);
-            vedges[g->e_v[2 * e + 1]].push_back(e);
-        }
-        std::vector<int> roots;
-        std::vector<uint8_t> isroot(nv, 0);
-        for (int e : act)
-            for (int sd = 0; sd < 2; ++sd) {
-                const int v = g->e_v[2 * e + sd];
-                if (g->v_fixed[v] && !isroot[v]) { isroot[v] = 1; roots.push_back(v); }
-            }
-        std::sort(roots.begin(), roots.end());
-        const double inf = std::numeric_limits<double>::max();
-        std::vector<double> dist(nv, inf);
-        std::vector<int> level(nv, 0), pedge(nv, -1), parent(nv, -1);
-        std::multimap<double, int> frontier;
-        std::vector<std::multimap<double, int>::iterator> qit(nv);
-        std::vector<uint8_t> inq(nv, 0);
-        auto push = [&](int v) {
-            if (inq[v]) frontier.erase(qit[v]);
-            qit[v] = frontier.insert(frontier.upper_bound(dist[v]), {dist[v], v});
-            inq[v] = 1;
-        };
-        for (int r : roots) { dist[r] = 0.0; push(r); }
-        while (!frontier.empty()) {
-            const auto it = frontier.begin();
-            const int u = it->second;
-            frontier.erase(it);
-            inq[u] = 0;
-            if (level[u] > 0 && !g->v_fixed[u]) {
-                const int e = pedge[u];
-                if (parent[u] == g->e_v[2 * e]) X[u] = hiso_mul(X[g->e_v[2 * e]], Z[e]);
-                else X[u] = hiso_mul(X[g->e_v[2 * e + 1]], hiso_inv(Z[e]));
-            }
-            for (int e : vedges[u]) {
-                if (!is_act[e]) continue;
-                int maxf = -1;
-                for (int sd = 0; sd < 2; ++sd) {
-                    const int z = g->e_v[2 * e + sd];
-                    if (dist[z] != inf) maxf = std::max(maxf, level[z]);
-                }
-                for (int sd = 0; sd < 2; ++sd) {
-                    const int z = g->e_v[2 * e + sd];
-                    if (z == u) continue;
-                    const double zd = dist[u] + 1.0;
-                    if (zd < dist[z]) {
-                        dist[z] = zd;
-                        parent[z] = u;
-                        pedge[z] = e;
-                        level[z] = maxf + 1;
-                        push(z);
-                    }
-                }
-            }
-        }
-    }
-    // ---- Hessian order: Cholmod orders H by AMD before its supernodal factorisation; here the
-    //      free vertices are reordered by reverse Cuthill–McKee when that narrows the band (loop
-    //      edges couple vertices far apart in id order), and the dense factorisation runs over the
-    //      envelope only (tile_first / tile_last). Any symmetric order gives the same exact solve.
-    std::vector<int32_t> first_h(nfree);
-    auto envelope_of = [&](const std::vector<int32_t> &hx, std::vector<int32_t> &fh) {
-        for (int h = 0; h < nfree; ++h) fh[h] = h;
-        for (int e : act) {
-            const int a = hx[g->e_v[2 * e]], b = hx[g->e_v[2 * e + 1]];
-            if (a < 0 || b < 0) continue;
-            fh[std::max(a, b)] = std::min(fh[std::max(a, b)], std::min(a, b));
-        }
-        int w = 0;
-        for (int h = 0; h < nfree; ++h) w = std::max(w, h - fh[h]);
-        return w;
-    };
-    {
-        int bwp = envelope_of(hidx, first_h);
-        if (bwp > 1 && nfree > 2 && !tuning.no_rcm) {
-            std::vector<std::vector<int32_t>> adj(nfree);
-            for (int e : act) {
-                const int a = hidx[g->e_v[2 * e]], b = hidx[g->e_v[2 * e + 1]];
-                if (a < 0 || b < 0 || a == b) continue;
-                adj[a].push_back(b);
-                adj[b].push_back(a);
-            }
-            const std::vector<int32_t> h2 = permute_hidx(hidx, rcm_from_adj(adj));
-            std::vector<int32_t> fh2(nfree);
-            if (envelope_of(h2, fh2) < bwp) {
-                hidx = h2;
-                first_h = fh2;
-            }
-        }
-    }
-    // ---- blocks of H (lower triangle) and their contributions in edge order
-    std::map<std::pair<int, int>, std::vector<int32_t>> blocks;  // (col, row) -> contributions
-    for (int h = 0; h < nfree; ++h) blocks[{h, h}];
-    for (int e : act) {
-        const int hi = hidx[g->e_v[2 * e]], hj = hidx[g->e_v[2 * e + 1]];
-        if (hi >= 0) blocks[{hi, hi}].push_back(e << 2 | 0);
-        if (hj >= 0) blocks[{hj, hj}].push_back(e << 2 | 1);
-        if (hi >= 0 && hj >= 0 && hi != hj) {
-            if (hi > hj) blocks[{hj, hi}].push_back(e << 2 | 2);  // row block = vertex i
-            else blocks[{hi, hj}].push_back(e << 2 | 3);          // row block = vertex j
-        }
-    }
-    std::vector<int32_t> blk_r, blk_c, blk_off{0}, blk_con;
-    for (auto &kv : blocks) {
-        blk_c.push_back(kv.first.first);
-        blk_r.push_back(kv.first.second);
-        for (int32_t c : kv.second) blk_con.push_back(c);
-        blk_off.push_back((int32_t)blk_con.size());
-    }
-    const int n = 6 * nfree, nblk = (int)blk_r.size(), ntiles = (n + kTile - 1) / kTile;
-    const int nact = (int)act.size();
-    // ---- device block (grow-only)
-    struct Slot {
-        void **p;
-        size_t bytes;
-    };
-    PgoDev P{};
-    Dev dd{};
-    double *T0, *T1, *Ad;
-    int32_t *e_v_d, *act_d, *hidx_d, *blk_r_d, *blk_c_d, *blk_off_d, *blk_con_d, *tf_d, *tl_d;
-    double *Zinv_d, *info_d;
-    Ctrl *ctrl_d;
-    std::vector<Slot> slots = {
-        {(void **)&e_v_d, sizeof(int32_t) * 2 * (size_t)ne}, {(void **)&act_d, sizeof(int32_t) * (size_t)nact},
-        {(void **)&hidx_d, sizeof(int32_t) * (size_t)nv}, {(void **)&blk_r_d, sizeof(int32_t) * (size_t)nblk},
-        {(void **)&blk_c_d, sizeof(int32_t) * (size_t)nblk}, {(void **)&blk_off_d, sizeof(int32_t) * (size_t)(nblk + 1)},
-        {(void **)&blk_con_d, sizeof(int32_t) * blk_con.size()}, {(void **)&tf_d, sizeof(int32_t) * (size_t)ntiles},
-        {(void **)&tl_d, sizeof(int32_t) * (size_t)ntiles}, {(void **)&Zinv_d, sizeof(double) * 12 * (size_t)ne},
-        {(void **)&info_d, sizeof(double) * 36 * (size_t)ne}, {(void **)&T0, sizeof(double) * 12 * (size_t)nv},
-        {(void **)&T1, sizeof(double) * 12 * (size_t)nv}, {(void **)&P.eH, sizeof(double) * 144 * (size_t)ne},
-        {(void **)&P.eg, sizeof(double) * 12 * (size_t)ne}, {(void **)&P.echi, sizeof(double) * (size_t)ne},
-        {(void **)&P.Hd, sizeof(double) * (size_t)n * n}, {(void **)&Ad, sizeof(double) * (size_t)n * n},
-        {(void **)&P.b, sizeof(double) * (size_t)n}, {(void **)&P.x, sizeof(double) * (size_t)n},
-        {(void **)&dd.Wbuf, sizeof(double) * (size_t)std::max(n, 1) * (kTile + 1)}, {(void **)&P.out, sizeof(double) * 4},
-        {(void **)&ctrl_d, sizeof(Ctrl)}};
-    size_t tot = 0;
-    for (auto &sl : slots) tot += (std::max(sl.bytes, (size_t)128) + 255) & ~(size_t)255;
-    if (tot > ctx->pgo_cap) {
-        if (ctx->pgo_mem) (void)hipFreeAsync(ctx->pgo_mem, ctx->stream);  // stream-ordered (see commit_plan)
-        ctx->pgo_mem = nullptr;
-        ctx->pgo_cap = 0;
-        if (hipMallocAsync((void **)&ctx->pgo_mem, tot, ctx->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->set_error("pose graph: cannot allocate %zu bytes", tot);
-            return PLBA_E_NOMEM;
-        }
-        ctx->pgo_cap = tot;
-    }
-    if (!ctx->pgo_hout) PLBA_CHECK(hipHostMalloc((void **)&ctx->pgo_hout, sizeof(double) * 4));
-    {
-        size_t off = 0;
-        for (auto &sl : slots) {
-            *sl.p = ctx->pgo_mem + off;
-            off += (std::max(sl.bytes, (size_t)128) + 255) & ~(size_t)255;
-        }
-    }
-    hipStream_t s = ctx->stream;
-    std::vector<double> Tv(12 * (size_t)nv), Zi(12 * (size_t)ne), Om(36 * (size_t)ne);
-    for (int v = 0; v < nv; ++v) hiso_store(X[v], &Tv[12 * (size_t)v]);
-    for (int e = 0; e < ne; ++e) {
-        hiso_store(Zinv[e], &Zi[12 * (size_t)e]);
-        for (int k = 0; k < 36; ++k) Om[36 * (size_t)e + k] = g->e_info ? g->e_info[36 * (size_t)e + k] : (k % 7 == 0 ? 1.0 : 0.0);
-    }
-    std::vector<int32_t> tf(std::max(ntiles, 1), 0), tl(std::max(ntiles, 1), 0);
-    for (int I = 0; I < ntiles; ++I) {
-        int f = I;
-        for (int r = I * kTile; r < std::min(n, (I + 1) * kTile); ++r) f = std::min(f, (6 * first_h[r / 6]) / kTile);
-        tf[I] = f;
-    }
-    for (int K = 0; K < ntiles; ++K) {
-        int last = K;
-        for (int I = K; I < ntiles; ++I)
-            if (tf[I] <= K) last = I;
-        tl[K] = last;
-    }
-    auto up = [&](void *dst, const void *src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    PLBA_CHECK(up(e_v_d, g->e_v, sizeof(int32_t) * 2 * (size_t)ne));
-    PLBA_CHECK(up(act_d, act.data(), sizeof(int32_t) * act.size()));
-    PLBA_CHECK(up(hidx_d, hidx.data(), sizeof(int32_t) * hidx.size()));
-    PLBA_CHECK(up(blk_r_d, blk_r.data(), sizeof(int32_t) * blk_r.size()));
-    PLBA_CHECK(up(blk_c_d, blk_c.data(), sizeof(int32_t) * blk_c.size()));
-    PLBA_CHECK(up(blk_off_d, blk_off.data(), sizeof(int32_t) * blk_off.size()));
-    PLBA_CHECK(up(blk_con_d, blk_con.data(), sizeof(int32_t) * blk_con.size()));
-    PLBA_CHECK(up(tf_d, tf.data(), sizeof(int32_t) * tf.size()));
-    PLBA_CHECK(up(tl_d, tl.data(), sizeof(int32_t) * tl.size()));
-    PLBA_CHECK(up(Zinv_d, Zi.data(), sizeof(double) * Zi.size()));
-    PLBA_CHECK(up(info_d, Om.data(), sizeof(double) * Om.size()));
-    PLBA_CHECK(up(T0, Tv.data(), sizeof(double) * Tv.size()));
-    PLBA_CHECK(hipMemsetAsync(P.x, 0, sizeof(double) * std::max(n, 1), s));  // g2o's _x starts at zero
-    PLBA_CHECK(hipMemsetAsync(ctrl_d, 0, sizeof(Ctrl), s));
-    P.nv = nv; P.ne = ne; P.nact = nact; P.nfree = nfree; P.n = n; P.nblk = nblk;
-    P.e_v = e_v_d; P.act = act_d; P.Zinv = Zinv_d; P.info = info_d; P.hidx = hidx_d;
-    P.T[0] = T0; P.T[1] = T1;
-    P.blk_r = blk_r_d; P.blk_c = blk_c_d; P.blk_off = blk_off_d; P.blk_con = blk_con_d;
-    dd.n = n; dd.ntiles = ntiles; dd.Ad = Ad; dd.bs = P.b; dd.xp = P.x; dd.ctrl = ctrl_d;
-    dd.solve_lds_n = tuning.solve_lds_n;
-    dd.tile_first = tf_d; dd.tile_last = tl_d;
-    double *hout = ctx->pgo_hout;
-    auto fetch = [&]() -> int {
-        PLBA_CHECK(hipMemcpyAsync(hout, P.out, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
-        PLBA_CHECK(hipStreamSynchronize(s));
-        return PLBA_OK;
-    };
-    const int eb = std::max((nact + kPgoNT - 1) / kPgoNT, 1);
-    int cur = 0;
-    // computeActiveErrors() after the initial guess
-    hipLaunchKernelGGL(k_pgo_linearize<false>, dim3(eb), dim3(kPgoNT), 0, s, P, cur); PLBA_LAUNCHED(ctx, "k_pgo_linearize");
-    hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, s, P, (const Ctrl *)ctrl_d, 0, 0.0); PLBA_LAUNCHED(ctx, "k_pgo_sum");
-    PLBA_CHECK(hipGetLastError());
-    if (int rc = fetch()) return rc;
-    res->chi2_initial = hout[0];
-    res->n_free = nfree;
-    res->iterations = res->trials = res->solve_fails = 0;
-    res->n_trace = 0;
-    double lambda = 0.0, ni = 2.0, currentChi = hout[0];
-    for (int it = 0; it < prm.max_iters && nfree > 0; ++it) {
-        // OptimizationAlgorithmLevenberg::solve: computeActiveErrors, buildSystem
-        hipLaunchKernelGGL(k_pgo_linearize<true>, dim3(eb), dim3(kPgoNT), 0, s, P, cur); PLBA_LAUNCHED(ctx, "k_pgo_linearize");
-        hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, s, P, (const Ctrl *)ctrl_d, 0, 0.0); PLBA_LAUNCHED(ctx, "k_pgo_sum");
-        PLBA_CHECK(hipMemsetAsync(P.Hd, 0, sizeof(double) * (size_t)n * n, s));
-        hipLaunchKernelGGL(k_pgo_assemble, dim3((nblk * 42 + kPgoNT - 1) / kPgoNT), dim3(kPgoNT), 0, s, P); PLBA_LAUNCHED(ctx, "k_pgo_assemble");
-        if (it == 0 && prm.user_lambda_init <= 0.0) hipLaunchKernelGGL(k_pgo_maxdiag, dim3(1), dim3(64), 0, s, P); PLBA_LAUNCHED(ctx, "k_pgo_maxdiag");
-        PLBA_CHECK(hipGetLastError());
-        if (int rc = fetch()) return rc;
-        currentChi = hout[0];
-        const double chiStart = currentChi;
-        if (it == 0) {  // computeLambdaInit
-            lambda = prm.user_lambda_init > 0.0 ? prm.user_lambda_init : ctx->opts.tau * hout[2];
-            ni = 2.0;
-        }
-        const double lambdaStart = lambda;
-        double rho = 0.0;
-        int qmax = 0;
-        do {
-            // setLambda + solve (dense LDLᵀ, Cholmod's positive-definite test) + update
-            hipLaunchKernelGGL(k_pgo_damp, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, P, Ad, lambda); PLBA_LAUNCHED(ctx, "k_pgo_damp");
-            for (int K = 0; K < ntiles; ++K) {  // the envelope's row tiles K..tl[K] only
-                const int m = tl[K] - K;
-                hipLaunchKernelGGL(k_dense_panel, dim3((m + 2) / 2), dim3(kDensePanelNT), 0, s, dd, K); PLBA_LAUNCHED(ctx, "k_dense_panel");
-                if (m > 0) hipLaunchKernelGGL(k_dense_update, dim3(m * (m + 1) / 2), dim3(64), 0, s, dd, K); PLBA_LAUNCHED(ctx, "k_dense_update");
-            }
-            hipLaunchKernelGGL(k_pgo_check, dim3(1), dim3(256), 0, s, dd); PLBA_LAUNCHED(ctx, "k_pgo_check");
-            hipLaunchKernelGGL(k_pgo_solve, dim3(1), dim3(kFacThreads),
-                               n <= dd.solve_lds_n ? sizeof(double) * (size_t)n : 0, s, dd); PLBA_LAUNCHED(ctx, "k_pgo_solve");
-            hipLaunchKernelGGL(k_pgo_update, dim3((nv + kPgoNT - 1) / kPgoNT), dim3(kPgoNT), 0, s, P, cur); PLBA_LAUNCHED(ctx, "k_pgo_update");
-            // restoreDiagonal (Hd is untouched), computeActiveErrors at the trial state
-            hipLaunchKernelGGL(k_pgo_linearize<false>, dim3(eb), dim3(kPgoNT), 0, s, P, cur ^ 1); PLBA_LAUNCHED(ctx, "k_pgo_linearize");
-            hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(64), 0, s, P, (const Ctrl *)ctrl_d, 1, lambda); PLBA_LAUNCHED(ctx, "k_pgo_sum");
-            PLBA_CHECK(hipGetLastError());
-            if (int rc = fetch()) return rc;
-            const bool ok = hout[3] != 0.0;
-            double tempChi = hout[1];
-            if (!ok) {
-                tempChi = std::numeric_limits<double>::max();
-                ++res->solve_fails;
-            }
-            const double scale = hout[2] + 1e-3;
-            rho = (currentChi - tempChi) / scale;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                lambda *= std::max(1. / 3., alpha);
-                ni = 2;
-                currentChi = tempChi;
-                cur ^= 1;  // discardTop: the trial state becomes current
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                if (!std::isfinite(lambda)) break;  // (pop: the current state is untouched)
-            }
-            ++qmax;
-            ++res->trials;
-        } while (rho < 0 && qmax < prm.max_trials);
-        const int result = (qmax == prm.max_trials || rho == 0 || !std::isfinite(lambda)) ? 1 : 0;
-        if (res->trace && res->n_trace < res->trace_cap)
-            res->trace[res->n_trace++] = plba_iter_trace{0, it, qmax, result, chiStart, currentChi, lambdaStart, lambda};
-        ++res->iterations;
-        if (result != 0) break;
-    }
-    res->chi2_final = currentChi;
-    res->lambda_final = lambda;
-    if (res->v_T) {
-        PLBA_CHECK(hipMemcpyAsync(res->v_T, P.T[cur], sizeof(double) * 12 * (size_t)nv, hipMemcpyDeviceToHost, s));
-        PLBA_CHECK(hipStreamSynchronize(s));
-    }
-    res->solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return PLBA_OK;
+    return ctx ? pgo_optimize(ctx, g, pp, res) : PLBA_E_INVALID;
 }
 
 // ---------------------------------------------------------------- loop-closure relative pose
-// MapHandler::computeRelativePoseRobustGN / computeRelativePoseGN (src/mapHandler.cpp:4677-5068,
-// :4413-4675) for a batch of candidate pairs: one upload, one launch of k_lcpose
-// (csrc/plba_lcpose.hpp, one workgroup per candidate), one read-back.
+// defaults here; the call itself is plba::lc_relative_pose (csrc/plba_assoc.hip)
 void plba_lcpose_default_params(plba_lcpose_params *p) {
     if (!p) return;
     p->homog_th = 1e-7;       // src2/config.cpp:80
@@ -2870,376 +2417,16 @@ void plba_lcpose_default_params(plba_lcpose_params *p) {
 
 int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
                           uint8_t *pt_inlier, uint8_t *ln_inlier) {
-    if (!ctx) return PLBA_E_INVALID;
-    if (!b || b->n < 0) {
-        ctx->set_error("relative pose: NULL batch or n < 0");
-        return PLBA_E_INVALID;
-    }
-    const int n = b->n;
-    if (n == 0) return PLBA_OK;
-    plba_lcpose_params prm;
-    if (pp) prm = *pp;
-    else plba_lcpose_default_params(&prm);
-    if (!out || !b->pt_off || !b->ln_off) {
-        ctx->set_error("relative pose: NULL out / pt_off / ln_off");
-        return PLBA_E_INVALID;
-    }
-    if ((prm.variant != PLBA_LCPOSE_ROBUST_GN && prm.variant != PLBA_LCPOSE_GN) || prm.max_iters_first < 0 ||
-        prm.max_iters < 0) {
-        ctx->set_error("relative pose: unknown variant %d or a negative iteration cap", prm.variant);
-        return PLBA_E_INVALID;
-    }
-    for (const int32_t *off : {b->pt_off, b->ln_off}) {
-        if (off[0] < 0) {
-            ctx->set_error("relative pose: negative feature offset");
-            return PLBA_E_INVALID;
-        }
-        for (int c = 0; c < n; ++c)
-            if (off[c + 1] < off[c]) {
-                ctx->set_error("relative pose: feature offsets decrease at candidate %d", c);
-                return PLBA_E_INVALID;
-            }
-    }
-    const size_t np = (size_t)b->pt_off[n], nl = (size_t)b->ln_off[n];
-    if ((np && (!b->pt_P || !b->pt_obs)) || (nl && (!b->ln_sP || !b->ln_eP || !b->ln_le))) {
-        ctx->set_error("relative pose: NULL feature array");
-        return PLBA_E_INVALID;
-    }
-    (void)hipSetDevice(ctx->opts.device);
-    // one block, the same layout on the device and in pinned host memory:
-    //   inputs  pt_off | ln_off | pt_P | pt_obs | ln_sP | ln_eP | ln_le      (host -> device)
-    //   outputs out[n] | pt flags | ln flags                                  (device -> host)
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_ptoff = 0, o_lnoff = o_ptoff + al(sizeof(int32_t) * (n + 1)), o_P = o_lnoff + al(sizeof(int32_t) * (n + 1)),
-                 o_obs = o_P + al(sizeof(double) * 3 * np), o_sP = o_obs + al(sizeof(double) * 2 * np),
-                 o_eP = o_sP + al(sizeof(double) * 3 * nl), o_le = o_eP + al(sizeof(double) * 3 * nl),
-                 o_out = o_le + al(sizeof(double) * 3 * nl), o_pin = o_out + al(sizeof(plba_lcpose_out) * (size_t)n),
-                 o_lin = o_pin + al(np), tot = o_lin + al(nl);
-    if (tot > ctx->lc_cap) {
-        if (ctx->lc_mem) (void)hipFreeAsync(ctx->lc_mem, ctx->stream);  // stream-ordered, as the pose graph's block
-        ctx->lc_mem = nullptr;
-        ctx->lc_cap = 0;
-        if (hipMallocAsync((void **)&ctx->lc_mem, tot, ctx->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->set_error("relative pose: cannot allocate %zu bytes", tot);
-            return PLBA_E_NOMEM;
-        }
-        ctx->lc_cap = tot;
-    }
-    if (tot > ctx->lc_host_cap) {
-        if (ctx->lc_host) (void)hipHostFree(ctx->lc_host);
-        ctx->lc_host = nullptr;
-        ctx->lc_host_cap = 0;
-        if (hipHostMalloc((void **)&ctx->lc_host, tot) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->set_error("relative pose: cannot allocate %zu bytes of pinned memory", tot);
-            return PLBA_E_NOMEM;
-        }
-        ctx->lc_host_cap = tot;
-    }
-    char *h = ctx->lc_host, *dv = ctx->lc_mem;
-    memcpy(h + o_ptoff, b->pt_off, sizeof(int32_t) * (n + 1));
-    memcpy(h + o_lnoff, b->ln_off, sizeof(int32_t) * (n + 1));
-    if (np) {
-        memcpy(h + o_P, b->pt_P, sizeof(double) * 3 * np);
-        memcpy(h + o_obs, b->pt_obs, sizeof(double) * 2 * np);
-    }
-    if (nl) {
-        memcpy(h + o_sP, b->ln_sP, sizeof(double) * 3 * nl);
-        memcpy(h + o_eP, b->ln_eP, sizeof(double) * 3 * nl);
-        memcpy(h + o_le, b->ln_le, sizeof(double) * 3 * nl);
-    }
-    hipStream_t s = ctx->stream;
-    PLBA_CHECK(hipMemcpyAsync(dv, h, o_out, hipMemcpyHostToDevice, s));
-    LcDev L{};
-    L.pt_off = (const int32_t *)(dv + o_ptoff);
-    L.ln_off = (const int32_t *)(dv + o_lnoff);
-    L.pt_P = (const double *)(dv + o_P);
-    L.pt_obs = (const double *)(dv + o_obs);
-    L.ln_sP = (const double *)(dv + o_sP);
-    L.ln_eP = (const double *)(dv + o_eP);
-    L.ln_le = (const double *)(dv + o_le);
-    L.out = (plba_lcpose_out *)(dv + o_out);
-    L.pt_in = (uint8_t *)(dv + o_pin);
-    L.ln_in = (uint8_t *)(dv + o_lin);
-    L.cam = Cam{b->fx, b->fy, b->cx, b->cy};
-    L.prm = prm;
-    hipLaunchKernelGGL(k_lcpose, dim3(n), dim3(kLcNT), 0, s, L); PLBA_LAUNCHED(ctx, "k_lcpose");
-    PLBA_CHECK(hipMemcpyAsync(h + o_out, dv + o_out, tot - o_out, hipMemcpyDeviceToHost, s));
-    PLBA_CHECK(hipStreamSynchronize(s));
-    memcpy(out, h + o_out, sizeof(plba_lcpose_out) * (size_t)n);
-    if (pt_inlier && np) memcpy(pt_inlier, h + o_pin, np);
-    if (ln_inlier && nl) memcpy(ln_inlier, h + o_lin, nl);
-    return PLBA_OK;
+    return ctx ? lc_relative_pose(*ctx, b, pp, out, pt_inlier, ln_inlier) : PLBA_E_INVALID;
 }
 
-// The device block and the pinned host image that plba_desc_match and plba_grid_match share:
-// grow-only, kept across calls.
-static int dm_reserve(plba_ctx *ctx, size_t dev_bytes, size_t host_bytes, const char *what) {
-    if (dev_bytes > ctx->dm_cap) {
-        if (ctx->dm_mem) (void)hipFreeAsync(ctx->dm_mem, ctx->stream);  // stream-ordered, as the relative pose's block
-        ctx->dm_mem = nullptr;
-        ctx->dm_cap = 0;
-        if (hipMallocAsync((void **)&ctx->dm_mem, dev_bytes, ctx->stream) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->set_error("%s: cannot allocate %zu bytes", what, dev_bytes);
-            return PLBA_E_NOMEM;
-        }
-        ctx->dm_cap = dev_bytes;
-    }
-    if (host_bytes > ctx->dm_host_cap) {
-        if (ctx->dm_host) (void)hipHostFree(ctx->dm_host);
-        ctx->dm_host = nullptr;
-        ctx->dm_host_cap = 0;
-        if (hipHostMalloc((void **)&ctx->dm_host, host_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->set_error("%s: cannot allocate %zu bytes of pinned memory", what, host_bytes);
-            return PLBA_E_NOMEM;
-        }
-        ctx->dm_host_cap = host_bytes;
-    }
-    return PLBA_OK;
-}
-
-// ---------------------------------------------------------------- descriptor matching
-// StVO::match / matchNNR (src2/matching.cpp:41-91) for a batch of descriptor-set pairs: one upload,
-// k_desc_nn (both directions of every pair) and k_desc_cross (csrc/plba_match.hpp), one read-back.
+// descriptor matching and grid-guided matching (csrc/plba_assoc.hip)
 int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
-    if (!ctx) return PLBA_E_INVALID;
-    if (!b || b->n < 0) {
-        ctx->set_error("descriptor matching: NULL batch or n < 0");
-        return PLBA_E_INVALID;
-    }
-    const int n = b->n;
-    if (n == 0) return PLBA_OK;
-    if (b->desc_bytes < 4 || b->desc_bytes > 64 || b->desc_bytes % 4) {
-        ctx->set_error("descriptor matching: desc_bytes %d is no multiple of 4 in [4, 64]", b->desc_bytes);
-        return PLBA_E_INVALID;
-    }
-    if (!b->off1 || !b->off2 || !b->nnr || !n_matches) {
-        ctx->set_error("descriptor matching: NULL off1 / off2 / nnr / n_matches");
-        return PLBA_E_INVALID;
-    }
-    int max_rows = 0;
-    for (const int32_t *off : {b->off1, b->off2}) {
-        if (off[0] < 0) {
-            ctx->set_error("descriptor matching: negative row offset");
-            return PLBA_E_INVALID;
-        }
-        for (int k = 0; k < n; ++k) {
-            if (off[k + 1] < off[k]) {
-                ctx->set_error("descriptor matching: row offsets decrease at pair %d", k);
-                return PLBA_E_INVALID;
-            }
-            max_rows = std::max(max_rows, off[k + 1] - off[k]);
-        }
-    }
-    if ((max_rows + kDmNT - 1) / kDmNT > 65535) {  // the row tiles are the grid's second dimension
-        ctx->set_error("descriptor matching: a set of %d rows is more than %d", max_rows, 65535 * kDmNT);
-        return PLBA_E_INVALID;
-    }
-    const size_t n1 = (size_t)b->off1[n], n2 = (size_t)b->off2[n], db = (size_t)b->desc_bytes;
-    if ((n1 && (!b->desc1 || !matches_12)) || (n2 && !b->desc2)) {
-        ctx->set_error("descriptor matching: NULL desc1 / desc2 / matches_12");
-        return PLBA_E_INVALID;
-    }
-    (void)hipSetDevice(ctx->opts.device);
-    // one block, the same layout on the device and in pinned host memory:
-    //   inputs  off1 | off2 | nnr | desc1 | desc2        (host -> device)
-    //   outputs matches_12 | n_matches                    (device -> host)
-    //   scratch nn12 | nn21                               (device only)
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_off1 = 0, o_off2 = o_off1 + al(sizeof(int32_t) * (n + 1)), o_nnr = o_off2 + al(sizeof(int32_t) * (n + 1)),
-                 o_d1 = o_nnr + al(sizeof(float) * n), o_d2 = o_d1 + al(db * n1), o_m12 = o_d2 + al(db * n2),
-                 o_cnt = o_m12 + al(sizeof(int32_t) * n1), o_nn12 = o_cnt + al(sizeof(int32_t) * n),
-                 o_nn21 = o_nn12 + al(sizeof(int32_t) * n1), tot = o_nn21 + al(sizeof(int32_t) * n2);
-    if (const int rc = dm_reserve(ctx, tot, o_nn12, "descriptor matching")) return rc;
-    char *h = ctx->dm_host, *dv = ctx->dm_mem;
-    memcpy(h + o_off1, b->off1, sizeof(int32_t) * (n + 1));
-    memcpy(h + o_off2, b->off2, sizeof(int32_t) * (n + 1));
-    memcpy(h + o_nnr, b->nnr, sizeof(float) * n);
-    if (n1) memcpy(h + o_d1, b->desc1, db * n1);
-    if (n2) memcpy(h + o_d2, b->desc2, db * n2);
-    hipStream_t s = ctx->stream;
-    PLBA_CHECK(hipMemcpyAsync(dv, h, o_m12, hipMemcpyHostToDevice, s));
-    DmDev D{};
-    D.off1 = (const int32_t *)(dv + o_off1);
-    D.off2 = (const int32_t *)(dv + o_off2);
-    D.nnr = (const float *)(dv + o_nnr);
-    D.desc1 = (const uint32_t *)(dv + o_d1);
-    D.desc2 = (const uint32_t *)(dv + o_d2);
-    D.m12 = (int32_t *)(dv + o_m12);
-    D.count = (int32_t *)(dv + o_cnt);
-    D.nn12 = (int32_t *)(dv + o_nn12);
-    D.nn21 = (int32_t *)(dv + o_nn21);
-    D.n = n;
-    D.dwords = b->desc_bytes / 4;
-    D.best_lr = b->best_lr != 0;
-    if (max_rows > 0) {  // a workgroup past its pair's rows in its direction returns at once
-        const dim3 grid(n, (max_rows + kDmNT - 1) / kDmNT, 2);
-        if (D.dwords <= 8) hipLaunchKernelGGL(k_desc_nn<8>, grid, dim3(kDmNT), 0, s, D);
-        else hipLaunchKernelGGL(k_desc_nn<16>, grid, dim3(kDmNT), 0, s, D);
-        PLBA_LAUNCHED(ctx, "k_desc_nn");
-    }
-    hipLaunchKernelGGL(k_desc_cross, dim3(n), dim3(kDmNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_desc_cross");
-    PLBA_CHECK(hipMemcpyAsync(h + o_m12, dv + o_m12, o_nn12 - o_m12, hipMemcpyDeviceToHost, s));
-    PLBA_CHECK(hipStreamSynchronize(s));
-    if (n1) memcpy(matches_12, h + o_m12, sizeof(int32_t) * n1);
-    memcpy(n_matches, h + o_cnt, sizeof(int32_t) * n);
-    return PLBA_OK;
+    return ctx ? desc_match(*ctx, b, matches_12, n_matches) : PLBA_E_INVALID;
 }
 
-// ---------------------------------------------------------------- grid-guided matching
-// StVO::matchGrid (src2/matching.cpp:111-258) for a batch of point and line problems: one upload, a
-// fill of the key arrays, k_grid_cols twice (best, then second best) and k_grid_rows
-// (csrc/plba_gridmatch.hpp), one read-back.
 int plba_grid_match(plba_ctx *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
-    if (!ctx) return PLBA_E_INVALID;
-    if (!b || b->n < 0) {
-        ctx->set_error("grid matching: NULL batch or n < 0");
-        return PLBA_E_INVALID;
-    }
-    const int n = b->n;
-    if (n == 0) return PLBA_OK;
-    if (b->desc_bytes < 4 || b->desc_bytes > 64 || b->desc_bytes % 4) {
-        ctx->set_error("grid matching: desc_bytes %d is no multiple of 4 in [4, 64]", b->desc_bytes);
-        return PLBA_E_INVALID;
-    }
-    if (b->cols <= 0 || b->rows <= 0) {
-        ctx->set_error("grid matching: a grid of %d x %d cells", b->cols, b->rows);
-        return PLBA_E_INVALID;
-    }
-    if (!b->off1 || !b->off2 || !b->kind || !b->ws || !b->nnr || !b->line_sim_th || !n_matches) {
-        ctx->set_error("grid matching: NULL off1 / off2 / kind / ws / nnr / line_sim_th / n_matches");
-        return PLBA_E_INVALID;
-    }
-    for (const int32_t *off : {b->off1, b->off2}) {
-        if (off[0] < 0) {
-            ctx->set_error("grid matching: negative row offset");
-            return PLBA_E_INVALID;
-        }
-        for (int k = 0; k < n; ++k)
-            if (off[k + 1] < off[k]) {
-                ctx->set_error("grid matching: row offsets decrease at problem %d", k);
-                return PLBA_E_INVALID;
-            }
-    }
-    int max_train = 0;
-    bool line_q = false, line_t = false;  // a line problem with query rows / with train rows
-    for (int k = 0; k < n; ++k) {
-        if (b->kind[k] != 0 && b->kind[k] != 1) {
-            ctx->set_error("grid matching: kind %d of problem %d", b->kind[k], k);
-            return PLBA_E_INVALID;
-        }
-        if (b->ws[k] < 0) {
-            ctx->set_error("grid matching: window half-width %d of problem %d", b->ws[k], k);
-            return PLBA_E_INVALID;
-        }
-        max_train = std::max(max_train, b->off2[k + 1] - b->off2[k]);
-        line_q = line_q || (b->kind[k] == 1 && b->off1[k + 1] > b->off1[k]);
-        line_t = line_t || (b->kind[k] == 1 && b->off2[k + 1] > b->off2[k]);
-    }
-    if (max_train > kGmMaxTrain) {  // the low 16 bits of a key
-        ctx->set_error("grid matching: %d train rows in a problem are more than %d", max_train, kGmMaxTrain);
-        return PLBA_E_INVALID;
-    }
-    const size_t n1 = (size_t)b->off1[n], n2 = (size_t)b->off2[n], db = (size_t)b->desc_bytes;
-    if ((n1 && (!b->desc1 || !b->cell1 || !matches_12)) || (n2 && (!b->desc2 || !b->cell_off2)) ||
-        (line_q && !b->cell1_end) || (line_t && !b->dir2)) {
-        ctx->set_error("grid matching: NULL desc1 / cell1 / cell1_end / matches_12 / desc2 / cell_off2 / dir2");
-        return PLBA_E_INVALID;
-    }
-    size_t nc = 0;  // the kernels index cells2 through cell_off2: every entry is checked here
-    if (n2) {
-        if (b->cell_off2[0] < 0) {
-            ctx->set_error("grid matching: negative cell offset");
-            return PLBA_E_INVALID;
-        }
-        for (size_t r = 0; r < n2; ++r)
-            if (b->cell_off2[r + 1] < b->cell_off2[r]) {
-                ctx->set_error("grid matching: cell offsets decrease at train row %zu", r);
-                return PLBA_E_INVALID;
-            }
-        nc = (size_t)b->cell_off2[n2];
-        if (nc && !b->cells2) {
-            ctx->set_error("grid matching: NULL cells2");
-            return PLBA_E_INVALID;
-        }
-    }
-    (void)hipSetDevice(ctx->opts.device);
-    // one block, the same layout on the device and in pinned host memory:
-    //   inputs  off1 | off2 | kind | ws | nnr | line_sim_th | desc1 | desc2 | cell1 | cell1_end |
-    //           cell_off2 | cells2 | dir2                  (host -> device)
-    //   outputs matches_12 | n_matches                     (device -> host)
-    //   scratch best | second | matches_21                 (device only)
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t i4 = sizeof(int32_t), f8 = sizeof(double);
-    const size_t o_off1 = 0, o_off2 = o_off1 + al(i4 * (n + 1)), o_kind = o_off2 + al(i4 * (n + 1)), o_ws = o_kind + al(i4 * n),
-                 o_nnr = o_ws + al(i4 * n), o_th = o_nnr + al(f8 * n), o_d1 = o_th + al(f8 * n), o_d2 = o_d1 + al(db * n1),
-                 o_c1 = o_d2 + al(db * n2), o_c1e = o_c1 + al(2 * i4 * n1), o_co2 = o_c1e + al(2 * i4 * n1),
-                 o_cl2 = o_co2 + al(i4 * (n2 + 1)), o_dir = o_cl2 + al(2 * i4 * nc), o_m12 = o_dir + al(2 * f8 * n2),
-                 o_cnt = o_m12 + al(i4 * n1), o_best = o_cnt + al(i4 * n), o_sec = o_best + al(i4 * n1),
-                 o_m21 = o_sec + al(i4 * n1), tot = o_m21 + al(i4 * n2);
-    if (const int rc = dm_reserve(ctx, tot, o_best, "grid matching")) return rc;
-    char *h = ctx->dm_host, *dv = ctx->dm_mem;
-    memcpy(h + o_off1, b->off1, i4 * (n + 1));
-    memcpy(h + o_off2, b->off2, i4 * (n + 1));
-    memcpy(h + o_kind, b->kind, i4 * n);
-    memcpy(h + o_ws, b->ws, i4 * n);
-    memcpy(h + o_nnr, b->nnr, f8 * n);
-    memcpy(h + o_th, b->line_sim_th, f8 * n);
-    if (n1) memcpy(h + o_d1, b->desc1, db * n1);
-    if (n2) memcpy(h + o_d2, b->desc2, db * n2);
-    if (n1) memcpy(h + o_c1, b->cell1, 2 * i4 * n1);
-    if (n1 && b->cell1_end) memcpy(h + o_c1e, b->cell1_end, 2 * i4 * n1);
-    if (n2) memcpy(h + o_co2, b->cell_off2, i4 * (n2 + 1));
-    else memset(h + o_co2, 0, i4);
-    if (nc) memcpy(h + o_cl2, b->cells2, 2 * i4 * nc);
-    if (n2 && b->dir2) memcpy(h + o_dir, b->dir2, 2 * f8 * n2);
-    hipStream_t s = ctx->stream;
-    PLBA_CHECK(hipMemcpyAsync(dv, h, o_m12, hipMemcpyHostToDevice, s));
-    PLBA_CHECK(hipMemsetAsync(dv + o_best, 0xFF, o_m21 - o_best, s));  // kGmNone in every key
-    GmDev D{};
-    D.off1 = (const int32_t *)(dv + o_off1);
-    D.off2 = (const int32_t *)(dv + o_off2);
-    D.kind = (const int32_t *)(dv + o_kind);
-    D.ws = (const int32_t *)(dv + o_ws);
-    D.nnr = (const double *)(dv + o_nnr);
-    D.sim_th = (const double *)(dv + o_th);
-    D.desc1 = (const uint32_t *)(dv + o_d1);
-    D.desc2 = (const uint32_t *)(dv + o_d2);
-    D.cell1 = (const int32_t *)(dv + o_c1);
-    D.cell1e = (const int32_t *)(dv + o_c1e);
-    D.cell_off2 = (const int32_t *)(dv + o_co2);
-    D.cells2 = (const int32_t *)(dv + o_cl2);
-    D.dir2 = (const double *)(dv + o_dir);
-    D.m12 = (int32_t *)(dv + o_m12);
-    D.count = (int32_t *)(dv + o_cnt);
-    D.best = (uint32_t *)(dv + o_best);
-    D.second = (uint32_t *)(dv + o_sec);
-    D.m21 = (int32_t *)(dv + o_m21);
-    D.n = n;
-    D.dwords = b->desc_bytes / 4;
-    D.cols = b->cols;
-    D.rows = b->rows;
-    D.best_lr = b->best_lr != 0;
-    if (max_train > 0) {  // a workgroup past its problem's train rows returns at once
-        const dim3 grid(n, (max_train + kGmNT - 1) / kGmNT);
-        if (D.dwords <= 8) {
-            hipLaunchKernelGGL((k_grid_cols<8, 0>), grid, dim3(kGmNT), 0, s, D);
-            hipLaunchKernelGGL((k_grid_cols<8, 1>), grid, dim3(kGmNT), 0, s, D);
-        } else {
-            hipLaunchKernelGGL((k_grid_cols<16, 0>), grid, dim3(kGmNT), 0, s, D);
-            hipLaunchKernelGGL((k_grid_cols<16, 1>), grid, dim3(kGmNT), 0, s, D);
-        }
-        PLBA_LAUNCHED(ctx, "k_grid_cols");
-    }
-    hipLaunchKernelGGL(k_grid_rows, dim3(n), dim3(kGmRowsNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_grid_rows");
-    PLBA_CHECK(hipMemcpyAsync(h + o_m12, dv + o_m12, o_best - o_m12, hipMemcpyDeviceToHost, s));
-    PLBA_CHECK(hipStreamSynchronize(s));
-    if (n1) memcpy(matches_12, h + o_m12, i4 * n1);
-    memcpy(n_matches, h + o_cnt, i4 * n);
-    return PLBA_OK;
+    return ctx ? grid_match(*ctx, b, matches_12, n_matches) : PLBA_E_INVALID;
 }
 
 }  // extern "C"
