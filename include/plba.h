@@ -470,6 +470,63 @@ typedef struct plba_gridmatch_batch {   /* B problems, concatenated */
  * 65535 train rows in a problem; n == 0 does nothing; an empty side gives no match. */
 int plba_grid_match(plba_ctx *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
 
+/* ---- Place recognition, the step of loopClosure() that decides whether to look for a loop at all:
+ *   DBoW2 TemplatedVocabulary<FORB>::transform(features, v)   (TemplatedVocabulary.h:1046-1084, :1198-1239)
+ *   BowVector::addWeight / normalize(L1)                       (BowVector.cpp:34-84)
+ *   L1Scoring::score(v1, v2)                                   (ScoringObject.cpp:23-68)
+ * as insertKFBowVectorP / L / PL call them for every keyframe (src/mapHandler.cpp:4118-4239) on
+ * dbow_voc_p and dbow_voc_l. Only TF-IDF weighting with L1 scoring is supported: the only combination
+ * the reference's vocabularies use. A slot (0 points, 1 lines) holds one vocabulary and one database
+ * of BoW vectors, both resident on the device; the slots are independent.
+ * The vocabulary is a flat tree. Node 0 is the root; its descriptor and weight are not read. The
+ * children of node i are children[child_off[i] .. child_off[i+1]), in the order of the vocabulary
+ * file (TemplatedVocabulary.h:1458-1471). A node without children is a leaf (a word).
+ * Arithmetic, equal to the reference's bit for bit:
+ * Descent: from the root, the child with the smallest Hamming distance over desc_bytes
+ * (FORB.cpp:78-100); a child replaces the best only if strictly nearer, so the first child wins a
+ * tie; until a node has no children. Leaves may sit at different depths.
+ * Accumulation: a descriptor whose leaf weight is not > 0 is dropped; otherwise v[word] += weight,
+ * once per descriptor: the repeated sum, not count * weight.
+ * Normalisation: norm = sum |v_i| added in increasing word id; if norm > 0 every value is divided by
+ * it (a division, not a product with the reciprocal).
+ * Score: over the words common to both vectors in increasing word id, s += |a - b| - |a| - |b| with a
+ * of the first argument (the new vector); the score is -s / 2.0, which is -0.0 with no common word. */
+typedef struct plba_bow_vocab {
+    int32_t n_nodes;                    /* nodes, the root included: >= 2                        */
+    int32_t n_words;                    /* words: word ids are 0 .. n_words-1                    */
+    int32_t desc_bytes;                 /* as in plba_match_batch                                */
+    int32_t pad;
+    const int32_t *child_off;           /* [n_nodes+1]                                           */
+    const int32_t *children;            /* [child_off[n_nodes]] node indices in 1 .. n_nodes-1   */
+    const uint8_t *node_desc;           /* [n_nodes][desc_bytes]                                 */
+    const int32_t *word_id;             /* [n_nodes] the word of a leaf, -1 on inner nodes       */
+    const double  *weight;              /* [n_nodes] the idf of a leaf (Node::weight)            */
+} plba_bow_vocab;
+/* Uploads the vocabulary of a slot, once; it stays resident. Clears the slot's database.
+ * PLBA_E_INVALID, with the slot left as it was, for a slot outside {0, 1}, a NULL array, n_nodes < 2,
+ * a root without children, offsets that do not start at 0 or decrease, a child index out of range or
+ * not greater than 0, a node reached twice (which covers cycles) or never, a leaf without a word_id in
+ * [0, n_words) or with one that another leaf has, an inner node with a word_id >= 0, a weight that is
+ * not finite, or a bad desc_bytes. The validated depth bounds the descent loop on the device. */
+int plba_bow_set_vocab(plba_ctx *ctx, int32_t slot, const plba_bow_vocab *v);
+/* Transforms desc [n_desc][desc_bytes] into a BoW vector, stores it under kf_id, and scores it against
+ * every live stored vector of the slot and, last, against itself: *n = live vectors + 1 entries,
+ * ids[j] in increasing kf_id (the last is kf_id itself), scores[j] = score(new, ids[j]). At most cap
+ * entries are written; the vector is stored whatever cap is. A fixed number of launches (three), one
+ * upload and one read-back; runs on the context's stream, needs no uploaded window and leaves one
+ * intact. PLBA_E_INVALID, with nothing stored, for a bad slot, no vocabulary in the slot, kf_id < 0 or
+ * already used in the slot (a removed vector keeps its id), n_desc < 0 or above 65535, desc == NULL
+ * with n_desc > 0, scores or ids == NULL with cap > 0, cap < 0 or n == NULL. */
+int plba_bow_insert(plba_ctx *ctx, int32_t slot, int32_t kf_id, const uint8_t *desc, int32_t n_desc,
+                    double *scores, int32_t *ids, int32_t cap, int32_t *n);
+/* Marks the vector of kf_id dead (the reference skips map_keyframes[i] == NULL): it is never scored
+ * again. PLBA_E_INVALID if the slot has no live vector of that id. */
+int plba_bow_remove(plba_ctx *ctx, int32_t slot, int32_t kf_id);
+/* Reads the live vector of kf_id back (KeyFrame::descDBoW_P / _L): *n = its length, word_ids and
+ * values in increasing word id, at most cap entries written (both may be NULL with cap == 0). */
+int plba_bow_get(plba_ctx *ctx, int32_t slot, int32_t kf_id, int32_t *word_ids, double *values, int32_t cap,
+                 int32_t *n);
+
 /* ---- Sharded windows: one context per GPU, one window split over nranks.
  * Landmarks (with all their edges) are partitioned by the keyframe range of their first
  * observation (kf_obs_list[0], the base KF of map_points_kf_idx); poses are replicated.

@@ -176,8 +176,9 @@ typedef struct plslam_pgo_stats {
     double  chi2_initial, chi2_final, solve_ms;
 } plslam_pgo_stats;
 int plslam_loop_closure_optimization(plslam_map *m, int32_t ess, plslam_pgo_stats *stats);
-/* ---- MapHandler::loopClosure() (src/mapHandler.cpp:4053-4116) after lookForLoopCandidates (DBoW2),
- * which stays the caller's: the descriptor matching of isLoopClosure (:4327-4380, through
+/* ---- MapHandler::loopClosure() (src/mapHandler.cpp:4053-4116) after lookForLoopCandidates (which
+ * plslam_loop_closure_kf below runs first; these entry points take its candidate from the caller):
+ * the descriptor matching of isLoopClosure (:4327-4380, through
  * plba_desc_match or the hook, in plslam_loop_closure_step_kf below; plslam_loop_closure_step takes
  * the matched candidate from a caller that keeps its own matcher), the
  * inlier-ratio gate (:4384-4409; a zero feature count makes the ratio NaN or 0, so false),
@@ -243,6 +244,78 @@ int plslam_loop_closure_step_kf(plslam_map *m, int32_t kf_prev_idx, int32_t kf_c
 int plslam_verify_loop_candidates(plslam_map *m, int32_t kf_curr_idx, int32_t n, const int32_t *kf_prev_idx,
                                   const plslam_match_params *mp, double lc_inlier_ratio, int32_t *accepted,
                                   double *pose_inc, int32_t *n_matches);
+/* ---- place recognition: insertKFBowVectorP / L / PL (src/mapHandler.cpp:4118-4239), lookForLoopCandidates
+ * (:4241-4301) and with them loopClosure() (:4053-4116) whole, from a keyframe's descriptors. The BoW
+ * vectors (KeyFrame::descDBoW_P / _L) live in the place-recognition database of plba.h, slot 0 for
+ * points and slot 1 for lines; the map keeps conf_matrix.
+ * The hook, in the style of plslam_set_match_fn: every database operation goes through one call
+ * record. NULL = the device path (plba_bow_set_vocab / _insert / _remove / _get). */
+#define PLSLAM_BOW_SET_VOCAB 0          /* slot, vocab                                             */
+#define PLSLAM_BOW_INSERT    1          /* slot, kf_id, desc, n_desc, scores, ids, cap -> n        */
+#define PLSLAM_BOW_REMOVE    2          /* slot, kf_id                                             */
+#define PLSLAM_BOW_GET       3          /* slot, kf_id, word_ids, values, cap -> n                 */
+typedef struct plslam_bow_call {
+    int32_t op, slot, kf_id, n_desc, cap;
+    int32_t n;                          /* out, as *n of plba_bow_insert / plba_bow_get            */
+    const plba_bow_vocab *vocab;
+    const uint8_t *desc;
+    double  *scores;
+    int32_t *ids;
+    int32_t *word_ids;
+    double  *values;
+} plslam_bow_call;
+typedef int (*plslam_bow_fn)(void *user, plslam_bow_call *c);
+int plslam_set_bow_fn(plslam_map *m, plslam_bow_fn fn, void *user);
+/* The tests and tools/bow_bench.py only, not a product path: a single-threaded C++ restatement of
+ * plba_bow_*'s semantics (sorted arrays, popcounts) with the hook's signature. user: a database made
+ * by plslam_bow_cpu_new, which holds both slots. */
+void *plslam_bow_cpu_new(void);
+void  plslam_bow_cpu_free(void *db);
+int   plslam_bow_cpu(void *user, plslam_bow_call *c);
+/* dbow_voc_p (slot 0) / dbow_voc_l (slot 1): forwards to the hook or the device; clears the slot. */
+int plslam_set_vocabulary(plslam_map *m, int32_t slot, const plba_bow_vocab *v);
+/* map_keyframes[kf_idx] = NULL (a culled keyframe). Its BoW vectors leave the database at the next
+ * plslam_insert_kf_bow; its row and column of conf_matrix stay as they are. */
+int plslam_remove_keyframe(plslam_map *m, int32_t kf_idx);
+/* insertKFBowVectorPL (both kinds), ...P or ...L (one kind); PLBA_E_INVALID with neither. Reads the
+ * descriptors given by plslam_set_keyframe_features and, for PL, the point pixels pl and the line
+ * midpoints (spl + epl) * 0.5 (plslam_set_keyframe_line_endpoints) for vector_stdv
+ * (src2/auxiliar.cpp:504-513: mean and squared sum sequential, sqrt(1.0 / n * e)). The PL score is
+ * :4226-4228 in that order in double, without contraction; n_pl == 0 or std_pl == 0 divides by zero as
+ * the reference does and the NaN is stored. conf_matrix is vector<vector<float>>
+ * (include/mapHandler.h:153): every score is rounded to float when stored, for row and column alike,
+ * and the matrix grows with zeros to kf_idx + 1 (expandGraphs, :1000-1002). Keyframes that are NULL
+ * are skipped. PLBA_E_INVALID, with the map and the database untouched, for a keyframe that does not
+ * exist, has no features (or, for PL with line features, no endpoints), was inserted before, a slot
+ * without vocabulary, or for PL when the two slots do not hold the same keyframes. */
+int plslam_insert_kf_bow(plslam_map *m, int32_t kf_idx, int32_t has_points, int32_t has_lines);
+/* conf_matrix: row kf_idx, *n = its length, at most cap floats written; the whole n x n matrix set */
+int plslam_get_conf_matrix_row(plslam_map *m, int32_t kf_idx, float *out, int32_t cap, int32_t *n);
+int plslam_set_conf_matrix(plslam_map *m, int32_t n, const float *c);
+typedef struct plslam_lc_search_params {
+    int32_t lc_kf_dist;                 /* SlamConfig::lcKFDist()      50 (src/slamConfig.cpp:80)  */
+    int32_t lc_kf_max_dist;             /* SlamConfig::lcKFMaxDist()   50 (:81)                    */
+    int32_t lc_nkf_closest;             /* SlamConfig::lcNKFClosest()   4 (:82)                    */
+    int32_t min_lm_cov_graph;           /* SlamConfig::minLMCovGraph() 75 (:61)                    */
+    int32_t min_kf_local_map;           /* SlamConfig::minKFLocalMap()  3 (:62)                    */
+    int32_t pad;
+} plslam_lc_search_params;
+void plslam_lc_search_default_params(plslam_lc_search_params *p);
+/* lookForLoopCandidates (:4241-4301): the live keyframes i < kf_curr_idx - lc_kf_dist with
+ * conf_matrix[i][kf_curr_idx]; more than lc_kf_max_dist of them, else no candidate; sorted by score,
+ * descending, ties by increasing index, NaN last (the reference's std::sort leaves ties open);
+ * lc_min_score, from 1.0, the smallest score > 0.001 over the keyframes i < kf_curr_idx with
+ * full_graph[i][kf_curr_idx] >= min_lm_cov_graph or kf_curr_idx - i <= min_kf_local_map + 3; the best
+ * must be >= lc_min_score; then the ranks >= 1 with |idx - idx_max| <= lc_kf_max_dist and score >=
+ * lc_min_score * 0.8 are counted, and lc_nkf_closest of them make idx_max the candidate.
+ * *kf_prev_idx is -1 without one. p == NULL: the defaults. PLBA_E_INVALID for a negative parameter (the
+ * reference compares a size_t with it), or a kf_curr_idx outside conf_matrix or full_graph. */
+int plslam_look_for_loop_candidates(plslam_map *m, int32_t kf_curr_idx, const plslam_lc_search_params *p,
+                                    int32_t *is_candidate, int32_t *kf_prev_idx);
+/* loopClosure() whole: the search above, then plslam_loop_closure_step_kf with the candidate, or the
+ * c == NULL branch of plslam_loop_closure_step without one. */
+int plslam_loop_closure_kf(plslam_map *m, int32_t kf_curr_idx, const plslam_lc_search_params *sp,
+                           const plslam_match_params *mp, double lc_inlier_ratio, plslam_lc_stats *st);
 /* tools/descmatch_bench.py only, not a product path: a single-threaded popcount restatement of
  * plba_desc_match's semantics on the CPU, with the signature of the matcher hook. */
 int plslam_desc_match_cpu(void *user, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);

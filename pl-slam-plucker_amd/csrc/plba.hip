@@ -1927,9 +1927,11 @@ int plba_destroy(plba_ctx *ctx) {
     if (ctx->h_ctrl) (void)hipHostFree(ctx->h_ctrl);
     ctx->bmemA.release(ctx->stream);
     ctx->bmemB.release(ctx->stream);
-    for (ScratchBlock *sb : {&ctx->pgo, &ctx->lc, &ctx->match}) sb->release(ctx->stream);
+    std::vector<ScratchBlock *> blocks{&ctx->pgo, &ctx->lc, &ctx->match, &ctx->bow_io};
+    for (BowSlot &b : ctx->bow) blocks.insert(blocks.end(), {&b.voc, &b.db_word, &b.db_val});
+    for (ScratchBlock *sb : blocks) sb->release(ctx->stream);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (ScratchBlock *sb : {&ctx->pgo, &ctx->lc, &ctx->match}) sb->release_host();
+    for (ScratchBlock *sb : blocks) sb->release_host();
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
     if (ctx->comm.hbuf) (void)hipHostFree(ctx->comm.hbuf);
     if (ctx->comm.nccl) (void)ncclCommDestroy(ctx->comm.nccl);
@@ -2427,6 +2429,25 @@ int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_1
 
 int plba_grid_match(plba_ctx *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
     return ctx ? grid_match(*ctx, b, matches_12, n_matches) : PLBA_E_INVALID;
+}
+
+// place recognition (csrc/plba_assoc.hip, csrc/plba_bow.hpp)
+int plba_bow_set_vocab(plba_ctx *ctx, int32_t slot, const plba_bow_vocab *v) {
+    return ctx ? bow_set_vocab(*ctx, slot, v) : PLBA_E_INVALID;
+}
+
+int plba_bow_insert(plba_ctx *ctx, int32_t slot, int32_t kf_id, const uint8_t *desc, int32_t n_desc, double *scores,
+                    int32_t *ids, int32_t cap, int32_t *n) {
+    return ctx ? bow_insert(*ctx, slot, kf_id, desc, n_desc, scores, ids, cap, n) : PLBA_E_INVALID;
+}
+
+int plba_bow_remove(plba_ctx *ctx, int32_t slot, int32_t kf_id) {
+    return ctx ? bow_remove(*ctx, slot, kf_id) : PLBA_E_INVALID;
+}
+
+int plba_bow_get(plba_ctx *ctx, int32_t slot, int32_t kf_id, int32_t *word_ids, double *values, int32_t cap,
+                 int32_t *n) {
+    return ctx ? bow_get(*ctx, slot, kf_id, word_ids, values, cap, n) : PLBA_E_INVALID;
 }
 
 }  // extern "C"

@@ -1,16 +1,19 @@
-// plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose
-// and the two descriptor matchers. They share nothing with the solver (no Dev, no step graph, no
-// window arena), so they are a translation unit of their own: an edit to a matcher does not
-// rebuild the factorisation kernels. Each call is one upload, its kernels and one read-back through
-// a ScratchBlock laid out by a Layout; the extern "C" symbols are forwarders in plba.hip.
+// plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose,
+// the two descriptor matchers and place recognition. They share nothing with the solver (no Dev, no
+// step graph, no window arena), so they are a translation unit of their own: an edit to a matcher
+// does not rebuild the factorisation kernels. Each call is one upload, its kernels and one read-back
+// through a ScratchBlock laid out by a Layout; the extern "C" symbols are forwarders in plba.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "plba_lcpose.hpp"
 #include "plba_match.hpp"
 #include "plba_gridmatch.hpp"
+#include "plba_bow.hpp"
 #include "plba_scratch.hpp"
 
 namespace plba {
@@ -331,6 +334,300 @@ int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, 
     PLBA_CHECK(hipStreamSynchronize(s));
     if (n1) memcpy(matches_12, h + o_m12, sizeof(int32_t) * n1);
     memcpy(n_matches, h + o_cnt, sizeof(int32_t) * n);
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- place recognition
+// DBoW2's transform and L1 score as insertKFBowVectorP / L / PL use them (src/mapHandler.cpp:
+// 4118-4239); the kernels and the arithmetic are in csrc/plba_bow.hpp.
+namespace {
+
+BowSlot *bow_slot(CtxBase *ctx, const char *op, int slot, bool need_vocab) {
+    if (slot != 0 && slot != 1) {
+        ctx->set_error("%s: slot %d is neither 0 (points) nor 1 (lines)", op, slot);
+        return nullptr;
+    }
+    if (need_vocab && ctx->bow[slot].n_nodes == 0) {
+        ctx->set_error("%s: slot %d has no vocabulary", op, slot);
+        return nullptr;
+    }
+    return &ctx->bow[slot];
+}
+
+// A database array that keeps its contents when it grows (ScratchBlock::reserve does not): at
+// least doubled, the used part copied on the stream.
+int bow_grow(CtxBase *ctx, ScratchBlock &b, size_t need, size_t used) {
+    if (need <= b.dev_cap) return PLBA_OK;
+    const size_t cap = std::max(need, 2 * b.dev_cap);
+    char *nd = nullptr;
+    if (hipMallocAsync((void **)&nd, cap, ctx->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->set_error("place recognition: cannot allocate %zu bytes for the database", cap);
+        return PLBA_E_NOMEM;
+    }
+    if (used) {
+        const hipError_t e = hipMemcpyAsync(nd, b.dev, used, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFreeAsync(nd, ctx->stream);  // the old array stays
+            ctx->set_error("place recognition: HIP error %s while the database grew", hipGetErrorString(e));
+            return PLBA_E_DEVICE;
+        }
+    }
+    b.release(ctx->stream);
+    b.dev = nd;
+    b.dev_cap = cap;
+    return PLBA_OK;
+}
+
+std::vector<BowSlot::Row>::iterator bow_find(BowSlot &S, int kf_id) {
+    return std::lower_bound(S.rows.begin(), S.rows.end(), kf_id,
+                            [](const BowSlot::Row &r, int id) { return r.kf_id < id; });
+}
+
+}  // namespace
+
+int bow_set_vocab(CtxBase &cb, int slot, const plba_bow_vocab *v) {
+    CtxBase *const ctx = &cb;
+    const char *const op = "vocabulary";
+    BowSlot *S = bow_slot(ctx, op, slot, false);
+    if (!S) return PLBA_E_INVALID;
+    if (!v || !v->child_off || !v->children || !v->node_desc || !v->word_id || !v->weight) {
+        ctx->set_error("vocabulary: NULL vocabulary or array");
+        return PLBA_E_INVALID;
+    }
+    if (const int rc = check_desc_bytes(ctx, op, v->desc_bytes)) return rc;
+    const int nn = v->n_nodes;
+    if (nn < 2 || v->n_words < 1 || v->n_words > nn) {
+        ctx->set_error("vocabulary: %d nodes and %d words", nn, v->n_words);
+        return PLBA_E_INVALID;
+    }
+    if (v->child_off[0] != 0) {
+        ctx->set_error("vocabulary: the child offsets do not start at 0");
+        return PLBA_E_INVALID;
+    }
+    int max_children = 0;
+    if (const int rc = check_offsets(ctx, op, "child", "node", v->child_off, nn, &max_children)) return rc;
+    if (v->child_off[nn] != nn - 1 || v->child_off[1] == 0) {
+        // a tree in which every node but the root is reached once has n_nodes - 1 child entries
+        ctx->set_error("vocabulary: %d child entries for %d nodes, or a root without children", v->child_off[nn], nn);
+        return PLBA_E_INVALID;
+    }
+    // breadth first from the root: every child index in range, every node reached exactly once
+    std::vector<int32_t> level(nn, -1), queue{0};
+    queue.reserve(nn);
+    level[0] = 0;
+    int depth = 0;
+    for (size_t head = 0; head < queue.size(); ++head) {
+        const int node = queue[head];
+        for (int e = v->child_off[node]; e < v->child_off[node + 1]; ++e) {
+            const int c = v->children[e];
+            if (c <= 0 || c >= nn) {
+                ctx->set_error("vocabulary: child %d of node %d is outside 1 .. %d", c, node, nn - 1);
+                return PLBA_E_INVALID;
+            }
+            if (level[c] >= 0) {
+                ctx->set_error("vocabulary: node %d is reached twice", c);
+                return PLBA_E_INVALID;
+            }
+            level[c] = level[node] + 1;
+            depth = std::max(depth, level[c]);
+            queue.push_back(c);
+        }
+    }
+    if ((int)queue.size() != nn) {
+        ctx->set_error("vocabulary: %d of %d nodes are not reached from the root", nn - (int)queue.size(), nn);
+        return PLBA_E_INVALID;
+    }
+    std::vector<double> word_weight(v->n_words, 0.0);
+    std::vector<uint8_t> word_seen(v->n_words, 0);
+    for (int i = 0; i < nn; ++i) {
+        if (!std::isfinite(v->weight[i])) {
+            ctx->set_error("vocabulary: the weight of node %d is not finite", i);
+            return PLBA_E_INVALID;
+        }
+        const int w = v->word_id[i];
+        if (v->child_off[i + 1] > v->child_off[i]) {
+            if (w >= 0) {
+                ctx->set_error("vocabulary: inner node %d has word id %d", i, w);
+                return PLBA_E_INVALID;
+            }
+            continue;
+        }
+        if (w < 0 || w >= v->n_words || word_seen[w]) {
+            ctx->set_error("vocabulary: leaf %d has word id %d, outside 0 .. %d or used twice", i, w, v->n_words - 1);
+            return PLBA_E_INVALID;
+        }
+        word_seen[w] = 1;
+        word_weight[w] = v->weight[i];
+    }
+    (void)hipSetDevice(ctx->opts.device);
+    const size_t db = (size_t)v->desc_bytes;
+    Layout L;
+    const size_t o_co = L.add<int32_t>(nn + 1), o_ch = L.add<int32_t>(nn - 1), o_d = L.add(db * nn),
+                 o_w = L.add<int32_t>(nn), o_ww = L.add<double>(v->n_words);
+    S->n_nodes = 0;  // the slot is empty until the upload is through
+    S->rows.clear();
+    S->used = 0;
+    if (const int rc = S->voc.reserve(cb, L.total, 0, op)) return rc;
+    hipStream_t s = ctx->stream;
+    char *dv = S->voc.dev;
+    PLBA_CHECK(hipMemcpyAsync(dv + o_co, v->child_off, sizeof(int32_t) * (nn + 1), hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(dv + o_ch, v->children, sizeof(int32_t) * (nn - 1), hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(dv + o_d, v->node_desc, db * nn, hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(dv + o_w, v->word_id, sizeof(int32_t) * nn, hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(dv + o_ww, word_weight.data(), sizeof(double) * v->n_words, hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipStreamSynchronize(s));  // the caller's arrays and word_weight are free again
+    S->o_child_off = o_co; S->o_children = o_ch; S->o_desc = o_d; S->o_word = o_w; S->o_weight = o_ww;
+    S->n_words = v->n_words;
+    S->dwords = v->desc_bytes / 4;
+    S->depth = depth;
+    S->max_children = max_children;
+    S->n_nodes = nn;
+    return PLBA_OK;
+}
+
+int bow_insert(CtxBase &cb, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,
+               int32_t *n_out) {
+    CtxBase *const ctx = &cb;
+    const char *const op = "place recognition";
+    BowSlot *S = bow_slot(ctx, op, slot, true);
+    if (!S) return PLBA_E_INVALID;
+    if (kf_id < 0 || n_desc < 0 || n_desc > kBowMaxDesc || cap < 0 || !n_out) {
+        ctx->set_error("place recognition: kf_id %d, %d descriptors (at most %d), cap %d or n == NULL", kf_id, n_desc,
+                       kBowMaxDesc, cap);
+        return PLBA_E_INVALID;
+    }
+    if ((n_desc && !desc) || (cap && (!scores || !ids))) {
+        ctx->set_error("place recognition: NULL desc / scores / ids");
+        return PLBA_E_INVALID;
+    }
+    auto pos = bow_find(*S, kf_id);
+    if (pos != S->rows.end() && pos->kf_id == kf_id) {
+        ctx->set_error("place recognition: keyframe %d is already in slot %d", kf_id, slot);
+        return PLBA_E_INVALID;
+    }
+    if (S->used + (size_t)n_desc > (size_t)INT32_MAX) {
+        ctx->set_error("place recognition: the database of slot %d is full", slot);
+        return PLBA_E_NOMEM;
+    }
+    (void)hipSetDevice(ctx->opts.device);
+    int n_live = 0;
+    for (const BowSlot::Row &r : S->rows) n_live += r.live;
+    int npad = 1;
+    while (npad < n_desc) npad <<= 1;
+    const size_t db = 4 * (size_t)S->dwords;
+    Layout L;
+    const size_t o_desc = L.add(db * n_desc), o_ent = L.add<int32_t>(2 * (size_t)n_live);
+    const size_t inputs_end = L.mark();  // host -> device
+    const size_t o_scores = L.add<double>((size_t)n_live + 1), o_nnew = L.add<int32_t>(1);
+    const size_t outputs_end = L.mark();  // device -> host
+    const size_t o_keys = L.add<uint32_t>(n_desc), o_sort = L.add<uint32_t>(npad > kBowLdsKeys ? npad : 0),
+                 o_run = L.add<int32_t>(n_desc);  // device only
+    if (const int rc = ctx->bow_io.reserve(cb, L.total, outputs_end, op)) return rc;
+    // the new row has at most n_desc words
+    if (const int rc = bow_grow(ctx, S->db_word, sizeof(int32_t) * (S->used + n_desc + 32), sizeof(int32_t) * S->used))
+        return rc;
+    if (const int rc = bow_grow(ctx, S->db_val, sizeof(double) * (S->used + n_desc + 32), sizeof(double) * S->used))
+        return rc;
+    char *h = ctx->bow_io.host, *dv = ctx->bow_io.dev;
+    if (n_desc) put(h, o_desc, desc, db * n_desc);
+    int32_t *ent = at<int32_t>(h, o_ent);
+    int j = 0;
+    for (const BowSlot::Row &r : S->rows) {
+        if (!r.live) continue;
+        ent[2 * j] = r.off;
+        ent[2 * j + 1] = r.len;
+        if (j < cap) ids[j] = r.kf_id;
+        ++j;
+    }
+    hipStream_t s = ctx->stream;
+    PLBA_CHECK(hipMemcpyAsync(dv, h, inputs_end, hipMemcpyHostToDevice, s));
+    BowDev D{};
+    const char *vd = S->voc.dev;
+    D.child_off = at<const int32_t>(const_cast<char *>(vd), S->o_child_off);
+    D.children = at<const int32_t>(const_cast<char *>(vd), S->o_children);
+    D.node_desc = at<const uint32_t>(const_cast<char *>(vd), S->o_desc);
+    D.word_id = at<const int32_t>(const_cast<char *>(vd), S->o_word);
+    D.word_weight = at<const double>(const_cast<char *>(vd), S->o_weight);
+    D.dwords = S->dwords;
+    D.depth = S->depth;
+    D.max_children = S->max_children;
+    D.desc = at<const uint32_t>(dv, o_desc);
+    D.keys = at<uint32_t>(dv, o_keys);
+    D.sortbuf = at<uint32_t>(dv, o_sort);
+    D.run_start = at<int32_t>(dv, o_run);
+    D.n_desc = n_desc;
+    D.npad = npad;
+    D.db_word = at<int32_t>(S->db_word.dev, 0);
+    D.db_val = at<double>(S->db_val.dev, 0);
+    D.ent = at<const int32_t>(dv, o_ent);
+    D.new_off = (int32_t)S->used;
+    D.n_live = n_live;
+    D.n_new = at<int32_t>(dv, o_nnew);
+    D.scores = at<double>(dv, o_scores);
+    constexpr int per_wg = kBowDescNT / kBowGroup, waves_per_wg = kBowScoreNT / 64;
+    hipLaunchKernelGGL(k_bow_descend, dim3(std::max(1, (n_desc + per_wg - 1) / per_wg)), dim3(kBowDescNT), 0, s, D);
+    PLBA_LAUNCHED(ctx, "k_bow_descend");
+    hipLaunchKernelGGL(k_bow_vector, dim3(1), dim3(kBowVecNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_bow_vector");
+    hipLaunchKernelGGL(k_bow_score, dim3((n_live + 1 + waves_per_wg - 1) / waves_per_wg), dim3(kBowScoreNT), 0, s, D);
+    PLBA_LAUNCHED(ctx, "k_bow_score");
+    PLBA_CHECK(hipMemcpyAsync(h + inputs_end, dv + inputs_end, outputs_end - inputs_end, hipMemcpyDeviceToHost, s));
+    PLBA_CHECK(hipStreamSynchronize(s));
+    const int32_t len = *at<int32_t>(h, o_nnew);
+    if (len < 0 || len > n_desc) {
+        ctx->set_error("place recognition: the device returned a vector of %d words for %d descriptors", len, n_desc);
+        return PLBA_E_DEVICE;
+    }
+    S->rows.insert(bow_find(*S, kf_id), BowSlot::Row{kf_id, (int32_t)S->used, len, true});
+    S->used += (size_t)len;
+    const double *sc = at<double>(h, o_scores);
+    for (int k = 0; k < std::min(cap, n_live); ++k) scores[k] = sc[k];
+    if (n_live < cap) {
+        scores[n_live] = sc[n_live];
+        ids[n_live] = kf_id;
+    }
+    *n_out = n_live + 1;
+    return PLBA_OK;
+}
+
+int bow_remove(CtxBase &cb, int slot, int kf_id) {
+    CtxBase *const ctx = &cb;
+    BowSlot *S = bow_slot(ctx, "place recognition", slot, false);
+    if (!S) return PLBA_E_INVALID;
+    auto pos = bow_find(*S, kf_id);
+    if (pos == S->rows.end() || pos->kf_id != kf_id || !pos->live) {
+        ctx->set_error("place recognition: slot %d has no live vector of keyframe %d", slot, kf_id);
+        return PLBA_E_INVALID;
+    }
+    pos->live = false;
+    return PLBA_OK;
+}
+
+int bow_get(CtxBase &cb, int slot, int kf_id, int32_t *word_ids, double *values, int cap, int32_t *n_out) {
+    CtxBase *const ctx = &cb;
+    BowSlot *S = bow_slot(ctx, "place recognition", slot, false);
+    if (!S) return PLBA_E_INVALID;
+    auto pos = bow_find(*S, kf_id);
+    if (pos == S->rows.end() || pos->kf_id != kf_id || !pos->live) {
+        ctx->set_error("place recognition: slot %d has no live vector of keyframe %d", slot, kf_id);
+        return PLBA_E_INVALID;
+    }
+    if (cap < 0 || !n_out || (cap && (!word_ids || !values))) {
+        ctx->set_error("place recognition: cap %d, NULL word_ids / values / n", cap);
+        return PLBA_E_INVALID;
+    }
+    *n_out = pos->len;
+    const size_t cnt = (size_t)std::min(cap, pos->len);
+    if (cnt) {
+        (void)hipSetDevice(ctx->opts.device);
+        hipStream_t s = ctx->stream;
+        PLBA_CHECK(hipMemcpyAsync(word_ids, S->db_word.dev + sizeof(int32_t) * (size_t)pos->off, sizeof(int32_t) * cnt,
+                                  hipMemcpyDeviceToHost, s));
+        PLBA_CHECK(hipMemcpyAsync(values, S->db_val.dev + sizeof(double) * (size_t)pos->off, sizeof(double) * cnt,
+                                  hipMemcpyDeviceToHost, s));
+        PLBA_CHECK(hipStreamSynchronize(s));
+    }
     return PLBA_OK;
 }
 

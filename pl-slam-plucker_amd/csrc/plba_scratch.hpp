@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 #include "../../include/plba.h"
 #include "plba_layout.hpp"
@@ -38,6 +39,21 @@ struct ScratchBlock {
     }
 };
 
+// One place-recognition slot (plba_bow_*; 0 points, 1 lines): the resident vocabulary and the
+// database of BoW vectors as CSR rows. The rows' bookkeeping stays on the host.
+struct BowSlot {
+    ScratchBlock voc;              // child_off, children, node_desc, word_id, word_weight
+    ScratchBlock db_word, db_val;  // int32 word ids and double values of every row, appended
+    size_t o_child_off = 0, o_children = 0, o_desc = 0, o_word = 0, o_weight = 0;  // offsets into voc
+    int n_nodes = 0, n_words = 0, dwords = 0, depth = 0, max_children = 0;  // n_nodes == 0: no vocabulary
+    struct Row {
+        int32_t kf_id, off, len;
+        bool live;
+    };
+    std::vector<Row> rows;         // in increasing kf_id; a removed row keeps its id and its space
+    size_t used = 0;               // elements of db_word / db_val in use
+};
+
 struct CtxBase {
     plba_opts opts;
     std::string err;
@@ -46,6 +62,8 @@ struct CtxBase {
     ScratchBlock pgo;    // pose graph (plba_pgo_optimize); host image: the four doubles read back per trial
     ScratchBlock lc;     // relative pose (plba_lc_relative_pose): inputs up, results and inlier flags down
     ScratchBlock match;  // descriptor and grid-guided matching share one
+    BowSlot bow[2];      // place recognition: the vocabulary and the database of each slot
+    ScratchBlock bow_io; // descriptors and the live rows up, scores down, the sort's scratch
 
     void set_error(const char *fmt, ...) {
         char buf[512];
@@ -105,10 +123,16 @@ inline int ScratchBlock::reserve(CtxBase &ctx, size_t dev_bytes, size_t host_byt
         }                                                                                 \
     } while (0)
 
-// plba_assoc.hip: the bodies of plba_lc_relative_pose, plba_desc_match and plba_grid_match
+// plba_assoc.hip: the bodies of plba_lc_relative_pose, plba_desc_match and plba_grid_match,
 int lc_relative_pose(CtxBase &cb, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
                      uint8_t *pt_inlier, uint8_t *ln_inlier);
 int desc_match(CtxBase &cb, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
 int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
+// and of plba_bow_set_vocab / _insert / _remove / _get
+int bow_set_vocab(CtxBase &cb, int slot, const plba_bow_vocab *v);
+int bow_insert(CtxBase &cb, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,
+               int32_t *n);
+int bow_remove(CtxBase &cb, int slot, int kf_id);
+int bow_get(CtxBase &cb, int slot, int kf_id, int32_t *word_ids, double *values, int cap, int32_t *n);
 
 }  // namespace plba

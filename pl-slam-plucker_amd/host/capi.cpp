@@ -416,6 +416,86 @@ int plslam_verify_loop_candidates(plslam_map *m, int32_t kf_curr_idx, int32_t n,
                                       n_matches);
 }
 
+// ---- place recognition (bow.cpp)
+static_assert(sizeof(plslam_bow_call) == sizeof(BowCall), "plslam_bow_call and BowCall share one layout");
+
+int plslam_set_bow_fn(plslam_map *m, plslam_bow_fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    m->mh.setBowFn(reinterpret_cast<BowFn>(fn), user);
+    return PLBA_OK;
+}
+
+void *plslam_bow_cpu_new(void) { return bowCpuNew(); }
+void plslam_bow_cpu_free(void *db) { bowCpuFree(static_cast<BowCpuDb *>(db)); }
+int plslam_bow_cpu(void *user, plslam_bow_call *c) {
+    return bowCpu(static_cast<BowCpuDb *>(user), reinterpret_cast<BowCall *>(c));
+}
+
+int plslam_set_vocabulary(plslam_map *m, int32_t slot, const plba_bow_vocab *v) {
+    return m ? m->mh.setVocabulary(slot, v) : PLBA_E_INVALID;
+}
+
+int plslam_remove_keyframe(plslam_map *m, int32_t kf_idx) { return m ? m->mh.removeKeyframe(kf_idx) : PLBA_E_INVALID; }
+
+int plslam_insert_kf_bow(plslam_map *m, int32_t kf_idx, int32_t has_points, int32_t has_lines) {
+    return m ? m->mh.insertKfBow(kf_idx, has_points != 0, has_lines != 0) : PLBA_E_INVALID;
+}
+
+int plslam_get_conf_matrix_row(plslam_map *m, int32_t kf_idx, float *out, int32_t cap, int32_t *n) {
+    if (!m || !n || cap < 0 || (cap && !out) || kf_idx < 0 || kf_idx >= (int)m->mh.conf_matrix.size()) return PLBA_E_INVALID;
+    const std::vector<float> &row = m->mh.conf_matrix[kf_idx];
+    *n = (int32_t)row.size();
+    for (int i = 0; i < std::min<int>(cap, *n); ++i) out[i] = row[i];
+    return PLBA_OK;
+}
+
+int plslam_set_conf_matrix(plslam_map *m, int32_t n, const float *c) {
+    if (!m || n < 0 || (n && !c)) return PLBA_E_INVALID;
+    m->mh.conf_matrix.assign((size_t)n, std::vector<float>((size_t)n, 0.0f));
+    for (int i = 0; i < n; ++i) std::memcpy(m->mh.conf_matrix[i].data(), c + (size_t)i * n, sizeof(float) * (size_t)n);
+    return PLBA_OK;
+}
+
+void plslam_lc_search_default_params(plslam_lc_search_params *p) {
+    if (!p) return;
+    const LcSearchParams d;
+    p->lc_kf_dist = d.lc_kf_dist; p->lc_kf_max_dist = d.lc_kf_max_dist; p->lc_nkf_closest = d.lc_nkf_closest;
+    p->min_lm_cov_graph = d.min_lm_cov_graph; p->min_kf_local_map = d.min_kf_local_map; p->pad = 0;
+}
+
+namespace {
+LcSearchParams search_params(const plslam_lc_search_params *sp) {
+    LcSearchParams p;
+    if (sp) {
+        p.lc_kf_dist = sp->lc_kf_dist; p.lc_kf_max_dist = sp->lc_kf_max_dist; p.lc_nkf_closest = sp->lc_nkf_closest;
+        p.min_lm_cov_graph = sp->min_lm_cov_graph; p.min_kf_local_map = sp->min_kf_local_map;
+    }
+    return p;
+}
+}  // namespace
+
+int plslam_look_for_loop_candidates(plslam_map *m, int32_t kf_curr_idx, const plslam_lc_search_params *p,
+                                    int32_t *is_candidate, int32_t *kf_prev_idx) {
+    if (!m || !is_candidate || !kf_prev_idx) return PLBA_E_INVALID;
+    bool cand = false;
+    int prev = -1;
+    const int rc = m->mh.lookForLoopCandidates(kf_curr_idx, search_params(p), cand, prev);
+    if (rc) return rc;
+    *is_candidate = cand ? 1 : 0;
+    *kf_prev_idx = prev;
+    return PLBA_OK;
+}
+
+int plslam_loop_closure_kf(plslam_map *m, int32_t kf_curr_idx, const plslam_lc_search_params *sp,
+                           const plslam_match_params *mp, double lc_inlier_ratio, plslam_lc_stats *stats) {
+    if (!m) return PLBA_E_INVALID;
+    LcStats st;
+    const int rc = m->mh.loopClosureKf(kf_curr_idx, search_params(sp), match_params(mp), lc_inlier_ratio, &st);
+    if (rc) return rc;
+    if (stats) export_lc_stats(st, stats);
+    return PLBA_OK;
+}
+
 int plslam_desc_match_cpu(void *user, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
     (void)user;
     return descMatchCpu(b, matches_12, n_matches);

@@ -226,6 +226,30 @@ struct LcStats {
 
 using GridMatchFn = int (*)(void *user, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
 
+// One place-recognition database operation (plslam_bow_call of plslam_host.h, the same layout) and
+// the hook that takes it.
+struct BowCall {
+    int32_t op, slot, kf_id, n_desc, cap, n;
+    const plba_bow_vocab *vocab;
+    const uint8_t *desc;
+    double *scores;
+    int32_t *ids;
+    int32_t *word_ids;
+    double *values;
+};
+enum { BOW_SET_VOCAB = 0, BOW_INSERT = 1, BOW_REMOVE = 2, BOW_GET = 3 };
+using BowFn = int (*)(void *user, BowCall *c);
+// the tests and tools/bow_bench.py only: plba_bow_*'s semantics, single-threaded, on the CPU
+struct BowCpuDb;
+BowCpuDb *bowCpuNew();
+void bowCpuFree(BowCpuDb *db);
+int bowCpu(BowCpuDb *db, BowCall *c);
+
+// SlamConfig values of lookForLoopCandidates (src/slamConfig.cpp:61-62,80-82)
+struct LcSearchParams {
+    int lc_kf_dist = 50, lc_kf_max_dist = 50, lc_nkf_closest = 4, min_lm_cov_graph = 75, min_kf_local_map = 3;
+};
+
 // What matchMap2KFPoints / Lines read of SlamConfig and Config (src/slamConfig.cpp:43,51-52,85-86;
 // src2/config.cpp:51,60,63,68,92). fast_matching is false in slamConfig.cpp and true in the
 // configuration files the reference ships (config/config/config.yaml:5): true here.
@@ -318,6 +342,17 @@ class MapHandler {
     int verifyLoopCandidates(int kf_curr_idx, int n, const int32_t *kf_prev_idx, const MatchParams &mp,
                              double lc_inlier_ratio, int32_t *accepted, double *pose_inc, int32_t *n_matches);
     void setMatchFn(MatchFn fn, void *user) { match_fn_ = fn; match_user_ = user; }
+    // bow.cpp. Place recognition: insertKFBowVectorP / L / PL (src/mapHandler.cpp:4118-4239) over the
+    // database of plba_bow_* (or the hook), the float conf_matrix (include/mapHandler.h:153),
+    // lookForLoopCandidates (:4241-4301) and loopClosure() whole (:4053-4116).
+    std::vector<std::vector<float>> conf_matrix;
+    void setBowFn(BowFn fn, void *user) { bow_fn_ = fn; bow_user_ = user; }
+    int setVocabulary(int slot, const plba_bow_vocab *v);
+    int removeKeyframe(int kf_idx);
+    int insertKfBow(int kf_idx, bool has_points, bool has_lines);
+    int lookForLoopCandidates(int kf_curr_idx, const LcSearchParams &p, bool &is_candidate, int &kf_prev_idx);
+    int loopClosureKf(int kf_curr_idx, const LcSearchParams &sp, const MatchParams &mp, double lc_inlier_ratio,
+                      LcStats *stats = nullptr);
     // map_match.cpp. matchMap2KFPoints + matchMap2KFLines (src/mapHandler.cpp:697-921) for keyframe
     // kf_idx: the local landmarks not yet seen by it that project into the image against its features
     // with idx -1, by one plba_grid_match call (points and lines) and, where the reference falls back
@@ -392,6 +427,12 @@ class MapHandler {
     void *match_user_ = nullptr;
     GridMatchFn grid_fn_ = nullptr;
     void *grid_user_ = nullptr;
+    BowFn bow_fn_ = nullptr;
+    void *bow_user_ = nullptr;
+    int bowCall(BowCall &c);                 // the hook, or plba_bow_* on the map's context
+    bool bow_vocab_[2] = {false, false};
+    std::vector<uint8_t> bow_in_db_[2];      // [kf_idx] the keyframe has a live vector in the slot
+    std::vector<uint8_t> bow_inserted_;      // [kf_idx] insertKfBow ran for it
     int width_ = 0, height_ = 0;  // the image size (cam->getWidth() / getHeight()); 0: not set
     // the matched features of kf_prev_idx[0..n) against kf_curr_idx, by one match call
     struct LcBuilt;

@@ -366,6 +366,35 @@ class MatchBatchView:
             best_lr=int(bool(best_lr)), pad=0)
 
 
+# ---- place recognition (plba_bow_vocab / plba_bow_*)
+class PlbaBowVocab(C.Structure):
+    _fields_ = [("n_nodes", C.c_int32), ("n_words", C.c_int32), ("desc_bytes", C.c_int32), ("pad", C.c_int32),
+                ("child_off", _ip), ("children", _ip), ("node_desc", _bp), ("word_id", _ip), ("weight", _dp)]
+
+
+class BowVocabView:
+    """Contiguous copies of a flat vocabulary tree and the PlbaBowVocab over them. ``voc``: a dict (or
+    an object) with child_off [n_nodes+1], children, node_desc [n_nodes][desc_bytes] uint8, word_id
+    [n_nodes] (-1 on inner nodes), weight [n_nodes] and n_words."""
+
+    def __init__(self, voc):
+        get = voc.__getitem__ if isinstance(voc, dict) else (lambda k: getattr(voc, k))
+        self.child_off = np.ascontiguousarray(get("child_off"), dtype=np.int32)
+        self.children = np.ascontiguousarray(get("children"), dtype=np.int32)
+        self.node_desc = np.ascontiguousarray(get("node_desc"), dtype=np.uint8)
+        self.word_id = np.ascontiguousarray(get("word_id"), dtype=np.int32)
+        self.weight = np.ascontiguousarray(get("weight"), dtype=np.float64)
+        n_nodes = len(self.word_id)
+        try:
+            self.desc_bytes = int(get("desc_bytes"))
+        except (KeyError, AttributeError):
+            self.desc_bytes = int(self.node_desc.shape[1])
+        self.struct = PlbaBowVocab(
+            n_nodes=n_nodes, n_words=int(get("n_words")), desc_bytes=self.desc_bytes, pad=0,
+            child_off=_ptr(self.child_off, _ip), children=_ptr(self.children, _ip),
+            node_desc=_ptr(self.node_desc, _bp), word_id=_ptr(self.word_id, _ip), weight=_ptr(self.weight, _dp))
+
+
 # ---- grid-guided matching (plba_gridmatch_batch / plba_grid_match)
 class PlbaGridMatchBatch(C.Structure):
     _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32),

@@ -32,6 +32,7 @@ EXPORTED = [
     "plba_pgo_default_params", "plba_pgo_optimize",
     "plba_lcpose_default_params", "plba_lc_relative_pose",
     "plba_desc_match", "plba_grid_match",
+    "plba_bow_set_vocab", "plba_bow_insert", "plba_bow_remove", "plba_bow_get",
 ]
 
 # int (*plba_host_allreduce_fn)(void *user, double *buf, int64_t n)
@@ -97,6 +98,10 @@ def load(path: Optional[str] = None):
                                         C.POINTER(capi.PlbaLcposeOut), bp, bp]
     L.plba_desc_match.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
     L.plba_grid_match.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
+    L.plba_bow_set_vocab.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaBowVocab)]
+    L.plba_bow_insert.argtypes = [vp, C.c_int32, C.c_int32, bp, C.c_int32, dp, ip, C.c_int32, ip]
+    L.plba_bow_remove.argtypes = [vp, C.c_int32, C.c_int32]
+    L.plba_bow_get.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, C.c_int32, ip]
     for name in EXPORTED:
         f = getattr(L, name)
         if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
@@ -151,6 +156,7 @@ class Solver:
         if rc != 0:
             raise PlbaError(f"plba_create failed: {PLBA_ERRORS.get(rc, rc)} (no usable HIP device?)")
         self.graph: Optional[Graph] = None
+        self._bow_live = {0: 0, 1: 0}   # live vectors per place-recognition slot: sizes bow_insert's outputs
         if kernel_timing:
             self._check(self.L.plba_enable_kernel_timing(self.ctx, 1), "plba_enable_kernel_timing")
 
@@ -337,6 +343,43 @@ class Solver:
         self._check(self.L.plba_grid_match(self.ctx, C.byref(bv.struct), _p(m12, C.c_int32), _p(cnt, C.c_int32)),
                     "plba_grid_match")
         return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+
+    def bow_set_vocab(self, slot: int, voc):
+        """Uploads the vocabulary of a place-recognition slot (plba_bow_set_vocab; 0 points, 1 lines)
+        from a flat tree (capi.BowVocabView) and clears the slot's database."""
+        vv = voc if isinstance(voc, capi.BowVocabView) else capi.BowVocabView(voc)
+        self._check(self.L.plba_bow_set_vocab(self.ctx, slot, C.byref(vv.struct)), "plba_bow_set_vocab")
+        self._bow_live[slot] = 0
+
+    def bow_insert(self, slot: int, kf_id: int, desc):
+        """plba_bow_insert: the BoW vector of the uint8 rows ``desc`` (DBoW2 transform, TF-IDF / L1) is
+        stored under kf_id and scored against every live stored vector and, last, itself.
+        Returns (ids int32, scores float64) in increasing kf_id. Needs no uploaded window and leaves
+        one intact."""
+        desc = np.ascontiguousarray(desc, dtype=np.uint8)
+        n_desc = int(desc.shape[0]) if desc.ndim == 2 else 0
+        cap = self._bow_live.get(slot, 0) + 1
+        scores, ids, n = np.zeros(cap), np.zeros(cap, np.int32), C.c_int32(0)
+        self._check(self.L.plba_bow_insert(self.ctx, slot, kf_id, _p(desc, C.c_uint8) if n_desc else None, n_desc,
+                                           _p(scores), _p(ids, C.c_int32), cap, C.byref(n)), "plba_bow_insert")
+        if n.value != cap:
+            raise PlbaError(f"plba_bow_insert returned {n.value} scores for {cap} live vectors")
+        self._bow_live[slot] = cap
+        return ids, scores
+
+    def bow_remove(self, slot: int, kf_id: int):
+        """plba_bow_remove: the vector of kf_id is never scored again."""
+        self._check(self.L.plba_bow_remove(self.ctx, slot, kf_id), "plba_bow_remove")
+        self._bow_live[slot] -= 1
+
+    def bow_get(self, slot: int, kf_id: int):
+        """plba_bow_get: (word_ids int32, values float64) of a stored vector, in increasing word id."""
+        n = C.c_int32(0)
+        self._check(self.L.plba_bow_get(self.ctx, slot, kf_id, None, None, 0, C.byref(n)), "plba_bow_get")
+        w, v = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1))
+        self._check(self.L.plba_bow_get(self.ctx, slot, kf_id, _p(w, C.c_int32), _p(v), n.value, C.byref(n)),
+                    "plba_bow_get")
+        return w[:n.value].copy(), v[:n.value].copy()
 
     def trace(self) -> np.ndarray:
         n = C.c_int32(0)

@@ -308,7 +308,91 @@ HOST_EXPORTED = [
     "plslam_line_cells", "plslam_grid_match_cpu",
     "plslam_set_keyframe_line_endpoints", "plslam_set_camera", "plslam_set_grid_match_fn",
     "plslam_mapmatch_default_params", "plslam_match_map_to_kf", "plslam_local_mapping_step_kf",
+    "plslam_set_bow_fn", "plslam_bow_cpu", "plslam_set_vocabulary", "plslam_remove_keyframe", "plslam_insert_kf_bow",
+    "plslam_get_conf_matrix_row", "plslam_set_conf_matrix", "plslam_look_for_loop_candidates", "plslam_loop_closure_kf",
+    "plslam_bow_cpu_new", "plslam_bow_cpu_free", "plslam_lc_search_default_params",
 ]
+
+
+# ---- place recognition (plslam_bow_call / plslam_set_bow_fn / plslam_lc_search_params)
+BOW_SET_VOCAB, BOW_INSERT, BOW_REMOVE, BOW_GET = 0, 1, 2, 3
+
+
+class PlslamBowCall(C.Structure):
+    _fields_ = [("op", C.c_int32), ("slot", C.c_int32), ("kf_id", C.c_int32), ("n_desc", C.c_int32), ("cap", C.c_int32),
+                ("n", C.c_int32), ("vocab", C.POINTER(capi.PlbaBowVocab)), ("desc", C.POINTER(C.c_uint8)),
+                ("scores", C.POINTER(C.c_double)), ("ids", C.POINTER(C.c_int32)), ("word_ids", C.POINTER(C.c_int32)),
+                ("values", C.POINTER(C.c_double))]
+
+
+BOW_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(PlslamBowCall))
+
+
+class PlslamLcSearchParams(C.Structure):
+    _fields_ = [("lc_kf_dist", C.c_int32), ("lc_kf_max_dist", C.c_int32), ("lc_nkf_closest", C.c_int32),
+                ("min_lm_cov_graph", C.c_int32), ("min_kf_local_map", C.c_int32), ("pad", C.c_int32)]
+
+
+def lc_search_params(lc_kf_dist: int = 50, lc_kf_max_dist: int = 50, lc_nkf_closest: int = 4,
+                     min_lm_cov_graph: int = 75, min_kf_local_map: int = 3) -> PlslamLcSearchParams:
+    """src/slamConfig.cpp:61-62,80-82."""
+    return PlslamLcSearchParams(lc_kf_dist, lc_kf_max_dist, lc_nkf_closest, min_lm_cov_graph, min_kf_local_map, 0)
+
+
+class BowCpu:
+    """The single-threaded CPU restatement of plba_bow_* (plslam_bow_cpu) with a database of its own:
+    the hook of the CPU tests and the baseline of tools/bow_bench.py. Not a product path."""
+
+    def __init__(self):
+        self.L = load_host()
+        self.db = C.c_void_p(self.L.plslam_bow_cpu_new())
+
+    def close(self):
+        if self.db:
+            self.L.plslam_bow_cpu_free(self.db)
+            self.db = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, c: PlslamBowCall):
+        rc = self.L.plslam_bow_cpu(self.db, C.byref(c))
+        if rc != 0:
+            raise PlbaError(f"plslam_bow_cpu op {c.op} failed: {PLBA_ERRORS.get(rc, rc)}")
+
+    def set_vocab(self, slot: int, voc):
+        vv = voc if isinstance(voc, capi.BowVocabView) else capi.BowVocabView(voc)
+        self._call(PlslamBowCall(op=BOW_SET_VOCAB, slot=slot, vocab=C.pointer(vv.struct)))
+        self._live = getattr(self, "_live", {})
+        self._live[slot] = 0
+
+    def insert(self, slot: int, kf_id: int, desc):
+        desc = np.ascontiguousarray(desc, dtype=np.uint8)
+        n_desc = int(desc.shape[0]) if desc.ndim == 2 else 0
+        cap = self._live[slot] + 1
+        scores, ids = np.zeros(cap), np.zeros(cap, np.int32)
+        c = PlslamBowCall(op=BOW_INSERT, slot=slot, kf_id=kf_id, n_desc=n_desc, cap=cap,
+                          desc=desc.ctypes.data_as(C.POINTER(C.c_uint8)) if n_desc else None,
+                          scores=scores.ctypes.data_as(C.POINTER(C.c_double)), ids=ids.ctypes.data_as(C.POINTER(C.c_int32)))
+        self._call(c)
+        assert c.n == cap
+        self._live[slot] = cap
+        return ids, scores
+
+    def remove(self, slot: int, kf_id: int):
+        self._call(PlslamBowCall(op=BOW_REMOVE, slot=slot, kf_id=kf_id))
+        self._live[slot] -= 1
+
+    def get(self, slot: int, kf_id: int):
+        c = PlslamBowCall(op=BOW_GET, slot=slot, kf_id=kf_id)
+        self._call(c)
+        w, v = np.zeros(max(c.n, 1), np.int32), np.zeros(max(c.n, 1))
+        c.cap, c.word_ids, c.values = c.n, w.ctypes.data_as(C.POINTER(C.c_int32)), v.ctypes.data_as(C.POINTER(C.c_double))
+        self._call(c)
+        return w[:c.n].copy(), v[:c.n].copy()
 
 
 @dataclasses.dataclass
@@ -405,9 +489,27 @@ def load_host(path: Optional[str] = None):
                                          C.POINTER(PlslamMapMatchStats)]
     L.plslam_local_mapping_step_kf.argtypes = [vp, C.c_int32, C.POINTER(PlslamMapMatchParams),
                                                C.POINTER(PlslamMapMatchStats), C.POINTER(PlslamLbaStats), ip, ip]
+    fp = C.POINTER(C.c_float)
+    L.plslam_set_bow_fn.argtypes = [vp, vp, vp]    # the hook as an address: plslam_bow_cpu itself can be passed
+    L.plslam_bow_cpu_new.argtypes = []
+    L.plslam_bow_cpu_new.restype = vp
+    L.plslam_bow_cpu_free.argtypes = [vp]
+    L.plslam_bow_cpu_free.restype = None
+    L.plslam_bow_cpu.argtypes = [vp, C.POINTER(PlslamBowCall)]
+    L.plslam_set_vocabulary.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaBowVocab)]
+    L.plslam_remove_keyframe.argtypes = [vp, C.c_int32]
+    L.plslam_insert_kf_bow.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.plslam_get_conf_matrix_row.argtypes = [vp, C.c_int32, fp, C.c_int32, ip]
+    L.plslam_set_conf_matrix.argtypes = [vp, C.c_int32, fp]
+    L.plslam_look_for_loop_candidates.argtypes = [vp, C.c_int32, C.POINTER(PlslamLcSearchParams), ip, ip]
+    L.plslam_loop_closure_kf.argtypes = [vp, C.c_int32, C.POINTER(PlslamLcSearchParams), C.POINTER(PlslamMatchParams),
+                                         C.c_double, C.POINTER(PlslamLcStats)]
+    L.plslam_lc_search_default_params.argtypes = [C.POINTER(PlslamLcSearchParams)]
+    L.plslam_lc_search_default_params.restype = None
     for n in HOST_EXPORTED:
         if n not in ("plslam_map_last_error", "plslam_pluker_to_orth", "plslam_orth_to_pluker",
-                     "plslam_mapmatch_default_params"):
+                     "plslam_mapmatch_default_params", "plslam_bow_cpu_new", "plslam_bow_cpu_free",
+                     "plslam_lc_search_default_params"):
             getattr(L, n).restype = C.c_int
     _hl = L
     return L
@@ -778,6 +880,74 @@ class HostMap:
                 return -1
         self._mcb = MATCH_FN(tramp)
         self._check(self.L.plslam_set_match_fn(self.h, self._mcb, None), "set_match_fn")
+
+    # ---- place recognition: insertKFBowVector*, lookForLoopCandidates, loopClosure() whole
+    def set_bow_cpu(self, bow_cpu: Optional["BowCpu"]):
+        """Routes the place-recognition database through plslam_bow_cpu with ``bow_cpu``'s database (CPU
+        tests), or, with None, back to the MI355X backend (plba_bow_*)."""
+        self._bow_cpu = bow_cpu
+        if bow_cpu is None:
+            self._check(self.L.plslam_set_bow_fn(self.h, None, None), "set_bow_fn")
+            return
+        fn = C.cast(self.L.plslam_bow_cpu, C.c_void_p)
+        self._check(self.L.plslam_set_bow_fn(self.h, fn, bow_cpu.db), "set_bow_fn")
+
+    def set_bow_fn(self, fn: Optional[Callable]):
+        """fn(call: PlslamBowCall) -> int, or None for the MI355X backend."""
+        if fn is None:
+            return self.set_bow_cpu(None)
+
+        def tramp(user, cp):
+            try:
+                return int(fn(cp.contents))
+            except Exception:  # never unwind through C
+                import traceback
+                traceback.print_exc()
+                return -1
+        self._bcb = BOW_FN(tramp)
+        self._check(self.L.plslam_set_bow_fn(self.h, C.cast(self._bcb, C.c_void_p), None), "set_bow_fn")
+
+    def set_vocabulary(self, slot: int, voc):
+        vv = voc if isinstance(voc, capi.BowVocabView) else capi.BowVocabView(voc)
+        self._check(self.L.plslam_set_vocabulary(self.h, slot, C.byref(vv.struct)), "set_vocabulary")
+
+    def remove_keyframe(self, kf_idx: int):
+        self._check(self.L.plslam_remove_keyframe(self.h, kf_idx), "remove_keyframe")
+
+    def insert_kf_bow(self, kf_idx: int, has_points: bool = True, has_lines: bool = True):
+        """insertKFBowVectorPL / P / L for keyframe ``kf_idx`` (its features given before)."""
+        self._check(self.L.plslam_insert_kf_bow(self.h, kf_idx, int(has_points), int(has_lines)), "insert_kf_bow")
+
+    def conf_matrix(self) -> np.ndarray:
+        n = C.c_int32(0)
+        fp = C.POINTER(C.c_float)
+        if self.L.plslam_get_conf_matrix_row(self.h, 0, None, 0, C.byref(n)) != 0:
+            return np.zeros((0, 0), np.float32)
+        out = np.zeros((n.value, n.value), np.float32)
+        for i in range(n.value):
+            self._check(self.L.plslam_get_conf_matrix_row(self.h, i, out[i].ctypes.data_as(fp), n.value, C.byref(n)),
+                        "get_conf_matrix_row")
+        return out
+
+    def set_conf_matrix(self, c):
+        c = np.ascontiguousarray(c, np.float32)
+        self._check(self.L.plslam_set_conf_matrix(self.h, len(c), c.ctypes.data_as(C.POINTER(C.c_float))), "set_conf_matrix")
+
+    def look_for_loop_candidates(self, kf_curr_idx: int, params: Optional[PlslamLcSearchParams] = None):
+        """lookForLoopCandidates: (is_candidate, kf_prev_idx)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        self._check(self.L.plslam_look_for_loop_candidates(self.h, kf_curr_idx, C.byref(params) if params is not None else None,
+                                                           C.byref(a), C.byref(b)), "look_for_loop_candidates")
+        return bool(a.value), b.value
+
+    def loop_closure_kf(self, kf_curr_idx: int, search: Optional[PlslamLcSearchParams] = None,
+                        params: Optional[PlslamMatchParams] = None, lc_inlier_ratio: float = 30.0) -> dict:
+        """loopClosure() whole: the candidate search, then isLoopClosure and the state machine."""
+        st = PlslamLcStats()
+        self._check(self.L.plslam_loop_closure_kf(self.h, kf_curr_idx, C.byref(search) if search is not None else None,
+                                                  C.byref(params) if params is not None else None, lc_inlier_ratio,
+                                                  C.byref(st)), "loop_closure_kf")
+        return st.as_dict()
 
     def loop_closure_step_kf(self, kf_prev_idx: int, kf_curr_idx: int, params: Optional[PlslamMatchParams] = None,
                              lc_inlier_ratio: float = 30.0) -> dict:
