@@ -470,6 +470,115 @@ typedef struct plba_gridmatch_batch {   /* B problems, concatenated */
  * 65535 train rows in a problem; n == 0 does nothing; an empty side gives no match. */
 int plba_grid_match(plba_ctx *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
 
+/* ---- Stereo association of a frame's features, what makes stereo_pt / stereo_ls of every frame:
+ *   StereoFrame::matchStereoPoints(points_l, points_r, pdesc_l, pdesc_r, initial)   (src2/stereoFrame.cpp:121-174)
+ *   StereoFrame::matchStereoLines(lines_l, lines_r, ldesc_l, ldesc_r, initial)      (:310-435)
+ * from the detector output of the left and the right image (cv::KeyPoint::pt; KeyLine::startPointX,
+ * startPointY, endPointX, endPointY: all float). A call takes a batch of frames, each with its point
+ * and its line problem. Detection, octave, angle and the idx that `initial` assigns stay the caller's:
+ * pt_src / ls_src give the left row of every survivor.
+ * Cells. inv_width = cols / (double)width, inv_height = rows / (double)height (:47-48). A left
+ * feature's query cell is ((int)(x * inv_width), (int)(y * inv_height)): the float promoted to double,
+ * one double product, truncated toward zero (:133, :322-323: point_2d is pair<int, int>); a line has
+ * the cell of its start and of its end. A right point is entered in its one cell (:139). A right line
+ * is entered in the cells of getLineCoords over its endpoints in grid units (:336; the walk of
+ * plslam_line_cells), and its direction is normalize(((ex - sx) * inv_width, (ey - sy) * inv_height))
+ * with the differences taken in float first (:333).
+ * Window. w.width = (matching_s_ws, 0), w.height = (0, 0) (:142-144): the candidates of a query cell
+ * (x, y) are the right rows with an in-grid cell (cx, cy), max(0, x - matching_s_ws) <= cx <
+ * min(cols, x + 1) and max(0, y) <= cy < min(rows, y + 1) (GridStructure::get, src2/gridStructure.cpp:
+ * 65-76). Everything else is matchGrid exactly as plba_grid_match defines it above: candidate order,
+ * the prefix-minimum cross-check with best_lr, the direction test against line_sim_th, the ratio test
+ * in double with min_ratio_12_p for points and lines alike.
+ * Point gates, for a match i1 -> i2 (:158-161): (double)|yl - yr| <= max_dist_epip with the
+ * difference and its absolute value in float; disp = (double)(xl - xr), the difference in float;
+ * disp >= min_disp. Then pl = (xl, yl) and P = backProjection(xl, yl, disp) (src2/pinholeStereoCamera.
+ * cpp:225-233): bd = b / disp, P = (bd * (u - cx), bd * (v - cy), bd * fx).
+ * Line part (:357-397), every float promoted first. sp_l = (sx, sy, 1), ep_l = (ex, ey, 1), le = sp_l x
+ * ep_l divided, component by component, by sqrt(le0 * le0 + le1 * le1). overlap =
+ * lineSegmentOverlapStereo(sy_l, ey_l, sy_r, ey_r) (:510-545) on the right line's own endpoints: 1 if
+ * |ey_l - sy_l| <= line_horiz_th; else with sln / eln the smaller / larger left y and spn / epn of the
+ * right, length = eln - spn; 0 if epn < sln or spn > eln, eln - sln if epn > eln and spn < sln, else
+ * min(eln, epn) - max(sln, spn); divided by length if length > (double)0.01f, else 0; at most 1.
+ * Then :367 overwrites sp_r and :368 reads what it wrote:
+ *   X  = (sx_r * (sy_l - ey_r) + ex_r * (sy_r - sy_l)) / (sy_r - ey_r),     sp_r = (X, sy_l)
+ *   Xe = (X * (ey_l - ey_r) + ex_r * (sy_l - ey_l)) / (sy_l - ey_r),        ep_r = (Xe, ey_l)
+ * sdisp = sx_l - X, edisp = ex_l - Xe; if min(sdisp, edisp) / max(sdisp, edisp) < ls_min_disp_ratio
+ * both become -1 (:442-452; std::min(a, b) = b < a ? b : a, std::max(a, b) = a < b ? b : a). The five
+ * gates (:372-375): sdisp >= min_disp, edisp >= min_disp, |sy_l - ey_l| > line_horiz_th, |sp_r(1) -
+ * ep_r(1)| > line_horiz_th, which after the overwrite is the same |sy_l - ey_l| again, and overlap >
+ * stereo_overlap_th. sP = backProjection(sx_l, sy_l, sdisp), eP = backProjection(ex_l, ey_l, edisp).
+ * With pluker (a USE_LINE_PLUKER build, :383-397, :870-883): unit(u, v) = ((u - cx) / fx, (v - cy) / fy,
+ * 1); a = unit(sp_l), c = unit(ep_l), a2 = unit(sp_r) + (b, 0, 0), c2 = unit(ep_r) + (b, 0, 0) with the
+ * overwritten sp_r / ep_r, o1 = 0, o2 = (b, 0, 0); pi_from_ppp(x1, x2, x3) = ((x1 - x3) x (x2 - x3),
+ * -(x3 . (x1 x x2))), the dot product summed as t0 + (t1 + t2) (Eigen's unrolled reduction of three);
+ * pi1 = pi_from_ppp(a, c, o1), pi2 = pi_from_ppp(a2, c2, o2); dp(i, j) = pi1[i] * pi2[j] - pi2[i] *
+ * pi1[j]; NDc = (dp03, dp13, dp23, -dp12, dp02, -dp01). A cross product is (a1 b2 - a2 b1, a2 b0 -
+ * a0 b2, a0 b1 - a1 b0).
+ * Arithmetic: every double operation is rounded once (no fused multiply-add); only + - * / sqrt occur,
+ * so the doubles are bit for bit those of a host evaluation in this order.
+ * Defined where the reference is not: a frame side with no rows gives no survivor and does not
+ * disturb the batch; NaN (0 / 0 in X for sy_r == ey_r, say) compares false in every gate, as in C++.
+ * A coordinate must be finite and at most one image size outside the image: -width <= x <= 2 * width,
+ * -height <= y <= 2 * height. That bounds the walk of a right line: it advances one cell per step along
+ * the axis of larger extent from (int)first to (int)last (src2/lineIterator.cpp:53-76), and both lie in
+ * [-size, 2 * size] grid units, so a line has at most 3 * max(cols, rows) + 1 cells. Their coordinates
+ * along that axis are distinct, so at most max(cols, rows) of them lie inside the grid. */
+typedef struct plba_stereo_params {
+    int32_t cols, rows;                 /* GRID_COLS 64, GRID_ROWS 48 (include2/stereoFrame.h)   */
+    int32_t width, height;              /* the image size, > 0                                   */
+    int32_t matching_s_ws;              /* Config::matchingSWs()        10 (src2/config.cpp:91)  */
+    int32_t best_lr;                    /* Config::bestLRMatches()       1 (:51)                 */
+    int32_t pluker;                     /* 1: a USE_LINE_PLUKER build, NDc is computed           */
+    int32_t pad;
+    double  min_ratio_12_p;             /* Config::minRatio12P()       0.9 (:60)                 */
+    double  line_sim_th;                /* Config::lineSimTh()        0.75 (:63)                 */
+    double  max_dist_epip;              /* Config::maxDistEpip()       1.0 (:58)                 */
+    double  min_disp;                   /* Config::minDisp()           1.0 (:59)                 */
+    double  ls_min_disp_ratio;          /* Config::lsMinDispRatio()    0.7 (:69)                 */
+    double  line_horiz_th;              /* Config::lineHorizTh()       0.1 (:67)                 */
+    double  stereo_overlap_th;          /* Config::stereoOverlapTh()  0.75 (:64)                 */
+    double  fx, fy, cx, cy, b;          /* PinholeStereoCamera                                   */
+} plba_stereo_params;
+typedef struct plba_stereo_batch {      /* n frames, concatenated */
+    int32_t n;                          /* frames                                                */
+    int32_t desc_bytes;                 /* as in plba_match_batch                                */
+    const int32_t *pt_off_l, *pt_off_r; /* [n+1] point rows of frame f: [off[f], off[f+1])       */
+    const int32_t *ls_off_l, *ls_off_r; /* [n+1] line rows                                       */
+    const float   *pt_l, *pt_r;         /* [.][2] (x, y) of the left / right keypoints           */
+    const uint8_t *pdesc_l, *pdesc_r;   /* [.][desc_bytes]                                       */
+    const float   *ls_l, *ls_r;         /* [.][4] (sx, sy, ex, ey) of the left / right segments  */
+    const uint8_t *ldesc_l, *ldesc_r;   /* [.][desc_bytes]                                       */
+} plba_stereo_batch;
+/* The survivors of frame f, compacted in increasing left index (the order the reference pushes
+ * them): n_pt[f] rows from row pt_off_l[f] of every point array, n_ls[f] rows from row ls_off_l[f] of
+ * every line array. Rows past the count are not written. n_pt and n_ls are required; any other array
+ * may be NULL and is then skipped. ls_NDc is written only with params.pluker. */
+typedef struct plba_stereo_out {
+    int32_t *n_pt, *n_ls;               /* [n]                                                   */
+    int32_t *pt_src;                    /* [pt_off_l[n]] the left row i1, local to the frame     */
+    double  *pt_pl, *pt_disp, *pt_P;    /* [.][2], [.], [.][3]                                   */
+    uint8_t *pdesc;                     /* [.][desc_bytes] the filtered pdesc_l                  */
+    int32_t *ls_src;                    /* [ls_off_l[n]]                                         */
+    double  *ls_spl, *ls_epl;           /* [.][2]                                                */
+    double  *ls_sdisp, *ls_edisp;       /* [.]                                                   */
+    double  *ls_sP, *ls_eP, *ls_le;     /* [.][3]                                                */
+    double  *ls_NDc;                    /* [.][6]                                                */
+    uint8_t *ldesc;                     /* [.][desc_bytes] the filtered ldesc_l                  */
+} plba_stereo_out;
+/* The defaults of src2/config.cpp:51-91 with the grid of include2/stereoFrame.h; width, height, the
+ * camera and pluker are zero and must be set. */
+void plba_stereo_default_params(plba_stereo_params *p);
+/* Runs on the context's stream in a fixed number of launches (the cells, the matcher's three, the
+ * gates) with one upload and one read-back; needs no uploaded window and leaves one intact; shares
+ * plba_desc_match's device block and pinned host image. PLBA_E_INVALID, checked on the host before
+ * anything is launched, for a NULL batch, params, out, n_pt, n_ls or offset array, a NULL input array
+ * where rows exist, n < 0, decreasing or negative offsets, a bad desc_bytes, cols, rows, width or
+ * height <= 0, matching_s_ws < 0, more than 65535 right rows in a problem, or a coordinate that is not
+ * finite or outside the bound above; n == 0 does nothing and returns PLBA_OK. */
+int plba_stereo_associate(plba_ctx *ctx, const plba_stereo_batch *b, const plba_stereo_params *p,
+                          const plba_stereo_out *out);
+
 /* ---- Place recognition, the step of loopClosure() that decides whether to look for a loop at all:
  *   DBoW2 TemplatedVocabulary<FORB>::transform(features, v)   (TemplatedVocabulary.h:1046-1084, :1198-1239)
  *   BowVector::addWeight / normalize(L1)                       (BowVector.cpp:34-84)

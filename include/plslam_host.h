@@ -386,6 +386,40 @@ int plslam_match_map_to_kf(plslam_map *m, int32_t kf_idx, const double *Twf, con
 int plslam_local_mapping_step_kf(plslam_map *m, int32_t kf_idx, const plslam_mapmatch_params *params,
                                  plslam_mapmatch_stats *match_stats, plslam_lba_stats *stats, int32_t *n_pt_removed,
                                  int32_t *n_ln_removed);
+/* ---- StereoFrame::matchStereoPoints + matchStereoLines (src2/stereoFrame.cpp:121-174, :310-435): the
+ * features of keyframe kf_idx from the detector output of its two images, with no StVO on the caller's
+ * side. One plba_stereo_associate call (or the hook) with the one frame; the survivors are stored as
+ * plslam_set_keyframe_features + plslam_set_keyframe_line_endpoints would store them (pdesc, P, pl,
+ * ldesc, sP, eP, le, spl, epl). plslam_add_keyframe fixes a kind's feature count when it is given that
+ * kind's idx list: the count must then equal the survivors'. A keyframe added without the list (NULL
+ * or n = 0) is sized here with every idx -1, the reference's frames after the first (:168, :411).
+ * pt_src [n_pt_l] / ls_src [n_ls_l] (may be NULL) receive the left row of each stored feature, for the
+ * octave and whatever else the caller keeps per detection; stats (may be NULL) the counts. params is
+ * required (the baseline b and the image size are in it). Anything invalid returns PLBA_E_INVALID with
+ * the keyframe untouched. */
+typedef struct plslam_stereo_frame {
+    int32_t desc_bytes;                     /* as in plba_match_batch                                           */
+    int32_t n_pt_l, n_pt_r, n_ls_l, n_ls_r; /* detections of the left / right image                             */
+    int32_t pad;
+    const float   *pt_l, *pt_r;             /* [n][2] cv::KeyPoint::pt                                          */
+    const uint8_t *pdesc_l, *pdesc_r;       /* [n][desc_bytes]                                                  */
+    const float   *ls_l, *ls_r;             /* [n][4] KeyLine startPointX, startPointY, endPointX, endPointY    */
+    const uint8_t *ldesc_l, *ldesc_r;       /* [n][desc_bytes]                                                  */
+} plslam_stereo_frame;
+typedef struct plslam_stereo_stats {
+    int32_t n_pt, n_ls;                     /* stereo_pt.size(), stereo_ls.size()                               */
+    double  ms;                             /* the association call                                             */
+} plslam_stereo_stats;
+int plslam_set_keyframe_stereo(plslam_map *m, int32_t kf_idx, const plslam_stereo_frame *frame,
+                               const plba_stereo_params *params, int32_t *pt_src, int32_t *ls_src,
+                               plslam_stereo_stats *stats);
+/* Stereo hook, in the style of plslam_set_grid_match_fn: NULL = plba_stereo_associate. */
+typedef int (*plslam_stereo_fn)(void *user, const plba_stereo_batch *b, const plba_stereo_params *p,
+                                const plba_stereo_out *out);
+int plslam_set_stereo_fn(plslam_map *m, plslam_stereo_fn fn, void *user);
+/* tools/stereo_bench.py and the tests only, not a product path: a single-threaded restatement of
+ * plba_stereo_associate's semantics on the CPU, with the hook's signature. */
+int plslam_stereo_cpu(void *user, const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
 int plslam_get_lc_state(plslam_map *m, int32_t *state);
 /* lc_pose_list [n][6]; the kept index rows of loop `loop` (kind 1 points, 2 lines), [n][4] */
 int plslam_get_lc_pose_list(plslam_map *m, double *out, int32_t cap, int32_t *n);

@@ -2431,6 +2431,28 @@ int plba_grid_match(plba_ctx *ctx, const plba_gridmatch_batch *b, int32_t *match
     return ctx ? grid_match(*ctx, b, matches_12, n_matches) : PLBA_E_INVALID;
 }
 
+// stereo association (csrc/plba_assoc.hip, csrc/plba_stereo.hpp)
+void plba_stereo_default_params(plba_stereo_params *p) {
+    if (!p) return;
+    *p = plba_stereo_params{};
+    p->cols = 64;                  // GRID_COLS / GRID_ROWS (include2/stereoFrame.h:51-52)
+    p->rows = 48;
+    p->matching_s_ws = 10;         // src2/config.cpp:91
+    p->best_lr = 1;                // :51
+    p->min_ratio_12_p = 0.9;       // :60
+    p->line_sim_th = 0.75;         // :63
+    p->max_dist_epip = 1.0;        // :58
+    p->min_disp = 1.0;             // :59
+    p->ls_min_disp_ratio = 0.7;    // :69
+    p->line_horiz_th = 0.1;        // :67
+    p->stereo_overlap_th = 0.75;   // :64
+}
+
+int plba_stereo_associate(plba_ctx *ctx, const plba_stereo_batch *b, const plba_stereo_params *p,
+                          const plba_stereo_out *out) {
+    return ctx ? stereo_associate(*ctx, b, p, out) : PLBA_E_INVALID;
+}
+
 // place recognition (csrc/plba_assoc.hip, csrc/plba_bow.hpp)
 int plba_bow_set_vocab(plba_ctx *ctx, int32_t slot, const plba_bow_vocab *v) {
     return ctx ? bow_set_vocab(*ctx, slot, v) : PLBA_E_INVALID;

@@ -1,8 +1,9 @@
 // plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose,
-// the two descriptor matchers and place recognition. They share nothing with the solver (no Dev, no
-// step graph, no window arena), so they are a translation unit of their own: an edit to a matcher
-// does not rebuild the factorisation kernels. Each call is one upload, its kernels and one read-back
-// through a ScratchBlock laid out by a Layout; the extern "C" symbols are forwarders in plba.hip.
+// the two descriptor matchers, the stereo association and place recognition. They share nothing
+// with the solver (no Dev, no step graph, no window arena), so they are a translation unit of their
+// own: an edit to a matcher does not rebuild the factorisation kernels. Each call is one upload, its
+// kernels and one read-back through a ScratchBlock laid out by a Layout; the extern "C" symbols are
+// forwarders in plba.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include "plba_lcpose.hpp"
 #include "plba_match.hpp"
 #include "plba_gridmatch.hpp"
+#include "plba_stereo.hpp"
 #include "plba_bow.hpp"
 #include "plba_scratch.hpp"
 
@@ -266,7 +268,7 @@ int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, 
     // one block; the pinned host image holds its inputs and outputs
     Layout L;
     const size_t o_off1 = L.add<int32_t>(n + 1), o_off2 = L.add<int32_t>(n + 1), o_kind = L.add<int32_t>(n),
-                 o_ws = L.add<int32_t>(n), o_nnr = L.add<double>(n), o_th = L.add<double>(n), o_d1 = L.add(db * n1),
+                 o_ws = L.add<int32_t>(4 * (size_t)n), o_nnr = L.add<double>(n), o_th = L.add<double>(n), o_d1 = L.add(db * n1),
                  o_d2 = L.add(db * n2), o_c1 = L.add<int32_t>(2 * n1), o_c1e = L.add<int32_t>(2 * n1),
                  o_co2 = L.add<int32_t>(n2 + 1), o_cl2 = L.add<int32_t>(2 * nc), o_dir = L.add<double>(2 * n2);
     const size_t inputs_end = L.mark();  // host -> device
@@ -280,7 +282,8 @@ int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, 
     put(h, o_off1, b->off1, n + 1);
     put(h, o_off2, b->off2, n + 1);
     put(h, o_kind, b->kind, n);
-    put(h, o_ws, b->ws, n);
+    for (int k = 0; k < n; ++k)  // the symmetric window of matchGrid's callers: ws to the left, right, up and down
+        for (int e = 0; e < 4; ++e) at<int32_t>(h, o_ws)[4 * k + e] = b->ws[k];
     put(h, o_nnr, b->nnr, n);
     put(h, o_th, b->line_sim_th, n);
     put(h, o_d1, b->desc1, db * n1);
@@ -334,6 +337,234 @@ int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, 
     PLBA_CHECK(hipStreamSynchronize(s));
     if (n1) memcpy(matches_12, h + o_m12, sizeof(int32_t) * n1);
     memcpy(n_matches, h + o_cnt, sizeof(int32_t) * n);
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- stereo association
+// StereoFrame::matchStereoPoints / matchStereoLines (src2/stereoFrame.cpp:121-174, :310-435) for a batch
+// of frames: one upload, k_stereo_cells, the matcher's three launches with the window
+// (matching_s_ws, 0, 0, 0), k_stereo_gate (csrc/plba_stereo.hpp), one read-back. Frame f is the
+// matcher's problems 2 f (points) and 2 f + 1 (lines).
+int stereo_associate(CtxBase &cb, const plba_stereo_batch *b, const plba_stereo_params *pp, const plba_stereo_out *out) {
+    CtxBase *const ctx = &cb;
+    const char *const op = "stereo association";
+    if (!b || b->n < 0) {
+        ctx->set_error("stereo association: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    const int n = b->n;
+    if (n == 0) return PLBA_OK;
+    if (n > (INT32_MAX - 1) / 2) {
+        ctx->set_error("stereo association: %d frames", n);
+        return PLBA_E_INVALID;
+    }
+    if (const int rc = check_desc_bytes(ctx, op, b->desc_bytes)) return rc;
+    if (!pp || !out || !out->n_pt || !out->n_ls || !b->pt_off_l || !b->pt_off_r || !b->ls_off_l || !b->ls_off_r) {
+        ctx->set_error("stereo association: NULL params / out / n_pt / n_ls / offsets");
+        return PLBA_E_INVALID;
+    }
+    const plba_stereo_params &prm = *pp;
+    if (prm.cols <= 0 || prm.rows <= 0 || prm.width <= 0 || prm.height <= 0 || prm.matching_s_ws < 0) {
+        ctx->set_error("stereo association: a grid of %d x %d cells, an image of %d x %d or a window of %d", prm.cols,
+                       prm.rows, prm.width, prm.height, prm.matching_s_ws);
+        return PLBA_E_INVALID;
+    }
+    for (const int32_t *off : {b->pt_off_l, b->pt_off_r, b->ls_off_l, b->ls_off_r})
+        if (const int rc = check_offsets(ctx, op, "row", "frame", off, n)) return rc;
+    // the rows of each side, counted from the first frame's offset
+    const int32_t *const offs[2][2] = {{b->pt_off_l, b->pt_off_r}, {b->ls_off_l, b->ls_off_r}};
+    size_t cnt[2][2];
+    for (int kd = 0; kd < 2; ++kd)
+        for (int sd = 0; sd < 2; ++sd) cnt[kd][sd] = (size_t)(offs[kd][sd][n] - offs[kd][sd][0]);
+    const size_t N1 = cnt[0][0] + cnt[1][0], N2 = cnt[0][1] + cnt[1][1], db = (size_t)b->desc_bytes;
+    const int stride = std::max(prm.cols, prm.rows);
+    const size_t nc = cnt[0][1] + cnt[1][1] * (size_t)stride;
+    if (N1 > (size_t)INT32_MAX || N2 > (size_t)INT32_MAX || nc > (size_t)INT32_MAX) {
+        ctx->set_error("stereo association: %zu left rows, %zu right rows or %zu cells are more than %d", N1, N2, nc, INT32_MAX);
+        return PLBA_E_INVALID;
+    }
+    if ((cnt[0][0] && (!b->pt_l || !b->pdesc_l)) || (cnt[0][1] && (!b->pt_r || !b->pdesc_r)) ||
+        (cnt[1][0] && (!b->ls_l || !b->ldesc_l)) || (cnt[1][1] && (!b->ls_r || !b->ldesc_r))) {
+        ctx->set_error("stereo association: NULL coordinate or descriptor array");
+        return PLBA_E_INVALID;
+    }
+    int max_rows = 0, max_train = 0;
+    for (int f = 0; f < n; ++f)
+        for (int kd = 0; kd < 2; ++kd) {
+            const int r1 = offs[kd][0][f + 1] - offs[kd][0][f], r2 = offs[kd][1][f + 1] - offs[kd][1][f];
+            max_rows = std::max(max_rows, std::max(r1, r2));
+            max_train = std::max(max_train, r2);
+        }
+    if (max_train > kGmMaxTrain) {  // the low 16 bits of a key
+        ctx->set_error("stereo association: %d right rows in a problem are more than %d", max_train, kGmMaxTrain);
+        return PLBA_E_INVALID;
+    }
+    // a coordinate at most one image size outside the image: the bound of a right line's walk
+    const float *const coords[2][2] = {{b->pt_l, b->pt_r}, {b->ls_l, b->ls_r}};
+    for (int kd = 0; kd < 2; ++kd)
+        for (int sd = 0; sd < 2; ++sd) {
+            if (!cnt[kd][sd]) continue;
+            const int per = kd ? 4 : 2;
+            const float *c = coords[kd][sd] + (size_t)per * offs[kd][sd][0];
+            for (size_t e = 0; e < cnt[kd][sd] * per; ++e) {
+                const double v = c[e], size = (e & 1) ? prm.height : prm.width;
+                if (!(v >= -size && v <= 2.0 * size)) {  // false for NaN
+                    ctx->set_error("stereo association: coordinate %g of %s %s row %zu is not finite or outside [%g, %g]", v,
+                                   sd ? "right" : "left", kd ? "line" : "point", e / per, -size, 2.0 * size);
+                    return PLBA_E_INVALID;
+                }
+            }
+        }
+    (void)hipSetDevice(ctx->opts.device);
+    const int np = 2 * n;
+    const size_t P = (size_t)np;
+    Layout L;
+    const size_t o_off1 = L.add<int32_t>(P + 1), o_off2 = L.add<int32_t>(P + 1), o_kind = L.add<int32_t>(P),
+                 o_kbase = L.add<int32_t>(P), o_cbase = L.add<int32_t>(P + 1), o_ws = L.add<int32_t>(4 * P),
+                 o_nnr = L.add<double>(P), o_th = L.add<double>(P), o_d1 = L.add(db * N1), o_d2 = L.add(db * N2),
+                 o_co1 = L.add<float>(4 * N1), o_co2 = L.add<float>(4 * N2);
+    const size_t inputs_end = L.mark();  // host -> device
+    const size_t o_cnt = L.add<int32_t>(P), o_src = L.add<int32_t>(N1), o_od = L.add(db * N1),
+                 o_ptd = L.add<double>(kStPtDoubles * cnt[0][0]), o_lsd = L.add<double>(kStLsDoubles * cnt[1][0]);
+    const size_t outputs_end = L.mark();  // device -> host
+    const size_t o_best = L.add<uint32_t>(N1), o_sec = L.add<uint32_t>(N1);
+    const size_t keys_end = L.mark();  // the key arrays start as kGmNone
+    const size_t o_m12 = L.add<int32_t>(N1), o_m21 = L.add<int32_t>(N2), o_gcnt = L.add<int32_t>(P),
+                 o_c1 = L.add<int32_t>(2 * N1), o_c1e = L.add<int32_t>(2 * N1), o_co = L.add<int32_t>(N2 + 1),
+                 o_cl = L.add<int32_t>(2 * nc), o_dir = L.add<double>(2 * N2);  // device only
+    if (const int rc = ctx->match.reserve(cb, L.total, outputs_end, op)) return rc;
+    char *h = ctx->match.host, *dv = ctx->match.dev;
+    int32_t *off1 = at<int32_t>(h, o_off1), *off2 = at<int32_t>(h, o_off2), *kind = at<int32_t>(h, o_kind),
+            *kbase = at<int32_t>(h, o_kbase), *cbase = at<int32_t>(h, o_cbase), *ws = at<int32_t>(h, o_ws);
+    const uint8_t *const descs[2][2] = {{b->pdesc_l, b->pdesc_r}, {b->ldesc_l, b->ldesc_r}};
+    off1[0] = off2[0] = cbase[0] = 0;
+    for (int p = 0; p < np; ++p) {
+        const int f = p / 2, kd = p % 2, per = kd ? 4 : 2;
+        const int a1 = offs[kd][0][f], r1 = offs[kd][0][f + 1] - a1, a2 = offs[kd][1][f], r2 = offs[kd][1][f + 1] - a2;
+        kind[p] = kd;
+        kbase[p] = a1 - offs[kd][0][0];
+        off1[p + 1] = off1[p] + r1;
+        off2[p + 1] = off2[p] + r2;
+        cbase[p + 1] = cbase[p] + r2 * (kd ? stride : 1);
+        ws[4 * p] = prm.matching_s_ws;  // w.width = (matchingSWs, 0), w.height = (0, 0) (:142-144)
+        ws[4 * p + 1] = ws[4 * p + 2] = ws[4 * p + 3] = 0;
+        at<double>(h, o_nnr)[p] = prm.min_ratio_12_p;  // matching.cpp:160, :241: for lines too
+        at<double>(h, o_th)[p] = prm.line_sim_th;
+        if (r1) memcpy(h + o_d1 + db * off1[p], descs[kd][0] + db * a1, db * r1);
+        if (r2) memcpy(h + o_d2 + db * off2[p], descs[kd][1] + db * a2, db * r2);
+        for (int sd = 0; sd < 2; ++sd) {
+            const int a = sd ? a2 : a1, r = sd ? r2 : r1;
+            float *dst = at<float>(h, sd ? o_co2 : o_co1) + 4 * (size_t)(sd ? off2[p] : off1[p]);
+            const float *src = coords[kd][sd];
+            for (int i = 0; i < r; ++i)
+                for (int e = 0; e < 4; ++e) dst[4 * i + e] = e < per ? src[(size_t)per * (a + i) + e] : 0.0f;
+        }
+    }
+    hipStream_t s = ctx->stream;
+    PLBA_CHECK(hipMemcpyAsync(dv, h, inputs_end, hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemsetAsync(dv + o_best, 0xFF, keys_end - o_best, s));  // kGmNone in every key
+    StDev S{};
+    S.off1 = at<const int32_t>(dv, o_off1);
+    S.off2 = at<const int32_t>(dv, o_off2);
+    S.kind = at<const int32_t>(dv, o_kind);
+    S.kbase = at<const int32_t>(dv, o_kbase);
+    S.cbase = at<const int32_t>(dv, o_cbase);
+    S.co1 = at<const float>(dv, o_co1);
+    S.co2 = at<const float>(dv, o_co2);
+    S.desc1 = at<const uint32_t>(dv, o_d1);
+    S.cell1 = at<int32_t>(dv, o_c1);
+    S.cell1e = at<int32_t>(dv, o_c1e);
+    S.cell_off2 = at<int32_t>(dv, o_co);
+    S.cells2 = at<int32_t>(dv, o_cl);
+    S.dir2 = at<double>(dv, o_dir);
+    S.m12 = at<const int32_t>(dv, o_m12);
+    S.count = at<int32_t>(dv, o_cnt);
+    S.src = at<int32_t>(dv, o_src);
+    S.odesc = at<uint32_t>(dv, o_od);
+    S.ptd = at<double>(dv, o_ptd);
+    S.lsd = at<double>(dv, o_lsd);
+    S.inv_w = prm.cols / (double)prm.width;   // :47-48
+    S.inv_h = prm.rows / (double)prm.height;
+    S.dwords = b->desc_bytes / 4;
+    S.stride = stride;
+    S.prm = prm;
+    GmDev D{};
+    D.off1 = S.off1;
+    D.off2 = S.off2;
+    D.kind = S.kind;
+    D.ws = at<const int32_t>(dv, o_ws);
+    D.nnr = at<const double>(dv, o_nnr);
+    D.sim_th = at<const double>(dv, o_th);
+    D.desc1 = S.desc1;
+    D.desc2 = at<const uint32_t>(dv, o_d2);
+    D.cell1 = S.cell1;
+    D.cell1e = S.cell1e;
+    D.cell_off2 = S.cell_off2;
+    D.cells2 = S.cells2;
+    D.dir2 = S.dir2;
+    D.m12 = at<int32_t>(dv, o_m12);
+    D.count = at<int32_t>(dv, o_gcnt);
+    D.best = at<uint32_t>(dv, o_best);
+    D.second = at<uint32_t>(dv, o_sec);
+    D.m21 = at<int32_t>(dv, o_m21);
+    D.n = np;
+    D.dwords = S.dwords;
+    D.cols = prm.cols;
+    D.rows = prm.rows;
+    D.best_lr = prm.best_lr != 0;
+    if (max_rows > 0) {  // a thread past its problem's rows does nothing
+        hipLaunchKernelGGL(k_stereo_cells, dim3(np, (max_rows + kStNT - 1) / kStNT), dim3(kStNT), 0, s, S);
+        PLBA_LAUNCHED(ctx, "k_stereo_cells");
+    }
+    if (max_train > 0) {  // a workgroup past its problem's right rows returns at once
+        const dim3 grid(np, (max_train + kGmNT - 1) / kGmNT);
+        if (D.dwords <= 8) {
+            hipLaunchKernelGGL((k_grid_cols<8, 0>), grid, dim3(kGmNT), 0, s, D);
+            hipLaunchKernelGGL((k_grid_cols<8, 1>), grid, dim3(kGmNT), 0, s, D);
+        } else {
+            hipLaunchKernelGGL((k_grid_cols<16, 0>), grid, dim3(kGmNT), 0, s, D);
+            hipLaunchKernelGGL((k_grid_cols<16, 1>), grid, dim3(kGmNT), 0, s, D);
+        }
+        PLBA_LAUNCHED(ctx, "k_grid_cols");
+    }
+    hipLaunchKernelGGL(k_grid_rows, dim3(np), dim3(kGmRowsNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_grid_rows");
+    hipLaunchKernelGGL(k_stereo_gate, dim3(np), dim3(kStNT), 0, s, S); PLBA_LAUNCHED(ctx, "k_stereo_gate");
+    PLBA_CHECK(hipMemcpyAsync(h + inputs_end, dv + inputs_end, outputs_end - inputs_end, hipMemcpyDeviceToHost, s));
+    PLBA_CHECK(hipStreamSynchronize(s));
+    // the first count[p] rows of each problem, to the frame's left offset in the caller's arrays
+    const int32_t *count = at<int32_t>(h, o_cnt), *src = at<int32_t>(h, o_src);
+    const double *ptd = at<double>(h, o_ptd), *lsd = at<double>(h, o_lsd);
+    for (int p = 0; p < np; ++p) {
+        const int f = p / 2, kd = p % 2, k = count[p], a1 = offs[kd][0][f];
+        if (k < 0 || k > off1[p + 1] - off1[p]) {
+            ctx->set_error("stereo association: the device returned %d survivors for %d rows", k, off1[p + 1] - off1[p]);
+            return PLBA_E_DEVICE;
+        }
+        (kd ? out->n_ls : out->n_pt)[f] = k;
+        int32_t *osrc = kd ? out->ls_src : out->pt_src;
+        uint8_t *odesc = kd ? out->ldesc : out->pdesc;
+        if (osrc && k) memcpy(osrc + a1, src + off1[p], sizeof(int32_t) * k);
+        if (odesc && k) memcpy(odesc + db * a1, h + o_od + db * off1[p], db * k);
+        auto cols_out = [&](double *dst, const double *rec, int nd, int first, int width) {
+            if (!dst) return;
+            for (int i = 0; i < k; ++i)
+                for (int e = 0; e < width; ++e) dst[(size_t)width * (a1 + i) + e] = rec[(size_t)nd * (kbase[p] + i) + first + e];
+        };
+        if (!kd) {
+            cols_out(out->pt_pl, ptd, kStPtDoubles, 0, 2);
+            cols_out(out->pt_disp, ptd, kStPtDoubles, 2, 1);
+            cols_out(out->pt_P, ptd, kStPtDoubles, 3, 3);
+        } else {
+            cols_out(out->ls_spl, lsd, kStLsDoubles, 0, 2);
+            cols_out(out->ls_epl, lsd, kStLsDoubles, 2, 2);
+            cols_out(out->ls_sdisp, lsd, kStLsDoubles, 4, 1);
+            cols_out(out->ls_edisp, lsd, kStLsDoubles, 5, 1);
+            cols_out(out->ls_sP, lsd, kStLsDoubles, 6, 3);
+            cols_out(out->ls_eP, lsd, kStLsDoubles, 9, 3);
+            cols_out(out->ls_le, lsd, kStLsDoubles, 12, 3);
+            if (prm.pluker) cols_out(out->ls_NDc, lsd, kStLsDoubles, 15, 6);
+        }
+    }
     return PLBA_OK;
 }
 

@@ -54,7 +54,8 @@ struct GmDev {
     const int32_t *cell_off2;        // [off2[n]+1] CSR over the train rows
     const int32_t *cells2;           // [.][2]
     const double *dir2;              // [off2[n]][2]
-    const int32_t *kind, *ws;        // [n]
+    const int32_t *kind;             // [n]
+    const int32_t *ws;               // [n][4] window half-widths: left, right (x), up, down (y)
     const double *nnr, *sim_th;      // [n]
     uint32_t *best, *second;         // [off1[n]] smallest and second-smallest seen key of a row
     int32_t *m21;                    // [off2[n]] matches_21 (best_lr)
@@ -63,10 +64,11 @@ struct GmDev {
     int32_t n, dwords, cols, rows, best_lr;
 };
 
-// GridStructure::get's bounds (src2/gridStructure.cpp:67-71) for one axis, [lo, hi) kept inside
-// [0, size] so that an empty range stays empty whatever the query cell is
-__device__ inline int2 gm_window(int x, int ws, int size) {
-    const long long lo = max(0LL, (long long)x - ws), hi = min((long long)size, (long long)x + ws + 1);
+// GridStructure::get's bounds (src2/gridStructure.cpp:67-71) for one axis with the two half-widths of
+// a GridWindow pair (w.width or w.height: below, above), [lo, hi) kept inside [0, size] so that an
+// empty range stays empty whatever the query cell is
+__device__ inline int2 gm_window(int x, int ws_lo, int ws_hi, int size) {
+    const long long lo = max(0LL, (long long)x - ws_lo), hi = min((long long)size, (long long)x + ws_hi + 1);
     return make_int2((int)min(lo, (long long)size), (int)max(hi, 0LL));
 }
 
@@ -101,7 +103,8 @@ __global__ __launch_bounds__(kGmNT) void k_grid_cols(GmDev D) {
     if ((int)blockIdx.y * kGmNT >= n2) return;  // the whole workgroup, before any barrier
     const int i2 = blockIdx.y * kGmNT + tid;
     const bool owner = i2 < n2;
-    const int dw = D.dwords, ws = D.ws[p], cols = D.cols, rows = D.rows;
+    const int dw = D.dwords, cols = D.cols, rows = D.rows;
+    const int wl = D.ws[4 * p], wr = D.ws[4 * p + 1], wu = D.ws[4 * p + 2], wd = D.ws[4 * p + 3];
     const bool line = D.kind[p] != 0;
     const double th = D.sim_th[p];
 
@@ -163,11 +166,11 @@ __global__ __launch_bounds__(kGmNT) void k_grid_cols(GmDev D) {
         for (int r = tid; r < nrow; r += kGmNT) {
             const size_t g = (size_t)(o1 + base + r);
             const int sx = D.cell1[2 * g], sy = D.cell1[2 * g + 1];
-            const int2 wx = gm_window(sx, ws, cols), wy = gm_window(sy, ws, rows);
+            const int2 wx = gm_window(sx, wl, wr, cols), wy = gm_window(sy, wu, wd, rows);
             win0[r] = make_int4(wx.x, wx.y, wy.x, wy.y);
             if (line) {
                 const int ex = D.cell1e[2 * g], ey = D.cell1e[2 * g + 1];
-                const int2 vx = gm_window(ex, ws, cols), vy = gm_window(ey, ws, rows);
+                const int2 vx = gm_window(ex, wl, wr, cols), vy = gm_window(ey, wu, wd, rows);
                 win1[r] = make_int4(vx.x, vx.y, vy.x, vy.y);
                 // matching.cpp:210-211: the integer difference, normalised; a zero vector gives NaN
                 const double ux = (double)((long long)ex - sx), uy = (double)((long long)ey - sy);

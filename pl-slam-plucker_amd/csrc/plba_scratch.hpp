@@ -61,7 +61,7 @@ struct CtxBase {
     // Blocks independent of the window arena (these calls leave an uploaded window intact):
     ScratchBlock pgo;    // pose graph (plba_pgo_optimize); host image: the four doubles read back per trial
     ScratchBlock lc;     // relative pose (plba_lc_relative_pose): inputs up, results and inlier flags down
-    ScratchBlock match;  // descriptor and grid-guided matching share one
+    ScratchBlock match;  // descriptor matching, grid-guided matching and stereo association share one
     BowSlot bow[2];      // place recognition: the vocabulary and the database of each slot
     ScratchBlock bow_io; // descriptors and the live rows up, scores down, the sort's scratch
 
@@ -123,11 +123,14 @@ inline int ScratchBlock::reserve(CtxBase &ctx, size_t dev_bytes, size_t host_byt
         }                                                                                 \
     } while (0)
 
-// plba_assoc.hip: the bodies of plba_lc_relative_pose, plba_desc_match and plba_grid_match,
+// plba_assoc.hip: the bodies of plba_lc_relative_pose, plba_desc_match, plba_grid_match and
+// plba_stereo_associate,
 int lc_relative_pose(CtxBase &cb, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
                      uint8_t *pt_inlier, uint8_t *ln_inlier);
 int desc_match(CtxBase &cb, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
 int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
+int stereo_associate(CtxBase &cb, const plba_stereo_batch *b, const plba_stereo_params *pp,
+                     const plba_stereo_out *out);
 // and of plba_bow_set_vocab / _insert / _remove / _get
 int bow_set_vocab(CtxBase &cb, int slot, const plba_bow_vocab *v);
 int bow_insert(CtxBase &cb, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,

@@ -600,6 +600,31 @@ int plslam_grid_match_cpu(void *user, const plba_gridmatch_batch *b, int32_t *ma
     return gridMatchCpu(b, matches_12, n_matches);
 }
 
+int plslam_set_keyframe_stereo(plslam_map *m, int32_t kf_idx, const plslam_stereo_frame *frame,
+                               const plba_stereo_params *params, int32_t *pt_src, int32_t *ls_src,
+                               plslam_stereo_stats *stats) {
+    if (!m || !frame || !params) return PLBA_E_INVALID;
+    const StereoInput in{frame->desc_bytes, frame->n_pt_l, frame->n_pt_r, frame->n_ls_l, frame->n_ls_r, 0,
+                         frame->pt_l, frame->pt_r, frame->pdesc_l, frame->pdesc_r,
+                         frame->ls_l, frame->ls_r, frame->ldesc_l, frame->ldesc_r};
+    StereoStats st;
+    const int rc = m->mh.setKeyframeStereo(kf_idx, in, *params, pt_src, ls_src, &st);
+    if (rc) return rc;
+    if (stats) *stats = plslam_stereo_stats{st.n_pt, st.n_ls, st.ms};
+    return PLBA_OK;
+}
+
+int plslam_set_stereo_fn(plslam_map *m, plslam_stereo_fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    m->mh.setStereoFn(fn, user);
+    return PLBA_OK;
+}
+
+int plslam_stereo_cpu(void *user, const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out) {
+    (void)user;
+    return stereoCpu(b, p, out);
+}
+
 int plslam_get_lc_state(plslam_map *m, int32_t *state) {
     if (!m || !state) return PLBA_E_INVALID;
     *state = m->mh.lc_state;

@@ -48,17 +48,18 @@ long lineCells(double ax, double ay, double bx, double by, std::vector<std::arra
 
 // plba_grid_match's semantics (include/plba.h) restated as the reference runs them: the query rows
 // in order, the running `distances` / `matches_21` of the columns, the candidates of a row in
-// increasing train index.
-int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
+// increasing train index. win: [n][4] half-widths of the window to the left, right, up and down (the stereo
+// association's w.width / w.height pairs); nullptr: b->ws on all four sides.
+int gridMatchCpuWin(const plba_gridmatch_batch *b, const int32_t *win, int32_t *matches_12, int32_t *n_matches) {
     if (!b || b->n < 0) return PLBA_E_INVALID;
     if (b->n == 0) return PLBA_OK;
     // what plba_grid_match refuses is refused here
     if (b->desc_bytes < 4 || b->desc_bytes > 64 || b->desc_bytes % 4 || b->cols <= 0 || b->rows <= 0) return PLBA_E_INVALID;
-    if (!b->off1 || !b->off2 || !b->kind || !b->ws || !b->nnr || !b->line_sim_th || !n_matches) return PLBA_E_INVALID;
+    if (!b->off1 || !b->off2 || !b->kind || (!win && !b->ws) || !b->nnr || !b->line_sim_th || !n_matches) return PLBA_E_INVALID;
     if (b->off1[0] < 0 || b->off2[0] < 0) return PLBA_E_INVALID;
     bool line_q = false, line_t = false;
     for (int k = 0; k < b->n; ++k) {
-        if (b->off1[k + 1] < b->off1[k] || b->off2[k + 1] < b->off2[k] || b->ws[k] < 0 || (b->kind[k] != 0 && b->kind[k] != 1) ||
+        if (b->off1[k + 1] < b->off1[k] || b->off2[k + 1] < b->off2[k] || (!win && b->ws[k] < 0) || (b->kind[k] != 0 && b->kind[k] != 1) ||
             b->off2[k + 1] - b->off2[k] > 65535)
             return PLBA_E_INVALID;
         line_q = line_q || (b->kind[k] == 1 && b->off1[k + 1] > b->off1[k]);
@@ -79,7 +80,10 @@ int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_
     for (int k = 0; k < b->n; ++k) {
         const int o1 = b->off1[k], n1 = b->off1[k + 1] - o1, o2 = b->off2[k], n2 = b->off2[k + 1] - o2;
         const bool line = b->kind[k] == 1;
-        const int ws = b->ws[k];
+        int wl, wr, wu, wd;
+        if (win) { wl = win[4 * k]; wr = win[4 * k + 1]; wu = win[4 * k + 2]; wd = win[4 * k + 3]; }
+        else wl = wr = wu = wd = b->ws[k];
+        if (wl < 0 || wr < 0 || wu < 0 || wd < 0) return PLBA_E_INVALID;
         distances.assign((size_t)n2, INT_MAX);
         matches_21.assign((size_t)n2, -1);
         // the bounding box of each train row's in-grid cells, to skip most rows without reading their cells
@@ -98,8 +102,8 @@ int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_
             long long w[2][4];
             int nw = 1;
             auto window = [&](const int32_t *c, long long *o) {
-                o[0] = std::max(0LL, (long long)c[0] - ws); o[1] = std::min((long long)b->cols, (long long)c[0] + ws + 1);
-                o[2] = std::max(0LL, (long long)c[1] - ws); o[3] = std::min((long long)b->rows, (long long)c[1] + ws + 1);
+                o[0] = std::max(0LL, (long long)c[0] - wl); o[1] = std::min((long long)b->cols, (long long)c[0] + wr + 1);
+                o[2] = std::max(0LL, (long long)c[1] - wu); o[3] = std::min((long long)b->rows, (long long)c[1] + wd + 1);
             };
             window(q, w[0]);
             double vx = 0, vy = 0;
@@ -170,6 +174,10 @@ int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_
         n_matches[k] = matches;
     }
     return PLBA_OK;
+}
+
+int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
+    return gridMatchCpuWin(b, nullptr, matches_12, n_matches);
 }
 
 namespace {

@@ -265,6 +265,21 @@ struct MapMatchStats {
     double match_ms = 0;
 };
 
+// The detector output of one stereo frame (plslam_stereo_frame of plslam_host.h, the same layout), what
+// setKeyframeStereo reports, and the hook that takes the association.
+struct StereoInput {
+    int32_t desc_bytes, n_pt_l, n_pt_r, n_ls_l, n_ls_r, pad;
+    const float *pt_l, *pt_r;
+    const uint8_t *pdesc_l, *pdesc_r;
+    const float *ls_l, *ls_r;
+    const uint8_t *ldesc_l, *ldesc_r;
+};
+struct StereoStats {
+    int n_pt = 0, n_ls = 0;
+    double ms = 0;
+};
+using StereoFn = int (*)(void *user, const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
+
 struct CullStats {
     int points_removed = 0, lines_removed = 0;
 };
@@ -364,6 +379,15 @@ class MapHandler {
     int localMappingStepKf(int kf_idx, const MapMatchParams &p, MapMatchStats *ms = nullptr, LbaStats *stats = nullptr,
                            CullStats *cs = nullptr);
     void setGridMatchFn(GridMatchFn fn, void *user) { grid_fn_ = fn; grid_user_ = user; }
+    // stereo.cpp. StereoFrame::matchStereoPoints + matchStereoLines (src2/stereoFrame.cpp:121-174, :310-435)
+    // for keyframe kf_idx from the detector output of its two images: one plba_stereo_associate call (or the
+    // hook), stored as plslam_set_keyframe_features + plslam_set_keyframe_line_endpoints would store it.
+    // A keyframe added with idx lists must have been added with the surviving counts; one added without
+    // is sized here, every idx -1. pt_src / ls_src (may be nullptr) receive the left row of each feature.
+    // Anything invalid returns before the keyframe is touched.
+    int setKeyframeStereo(int kf_idx, const StereoInput &in, const plba_stereo_params &prm, int32_t *pt_src, int32_t *ls_src,
+                          StereoStats *stats = nullptr);
+    void setStereoFn(StereoFn fn, void *user) { stereo_fn_ = fn; stereo_user_ = user; }
     void setCamera(double fx, double fy, double cx, double cy, int width, int height) {
         fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy; width_ = width; height_ = height;
     }
@@ -427,6 +451,8 @@ class MapHandler {
     void *match_user_ = nullptr;
     GridMatchFn grid_fn_ = nullptr;
     void *grid_user_ = nullptr;
+    StereoFn stereo_fn_ = nullptr;
+    void *stereo_user_ = nullptr;
     BowFn bow_fn_ = nullptr;
     void *bow_user_ = nullptr;
     int bowCall(BowCall &c);                 // the hook, or plba_bow_* on the map's context
@@ -466,5 +492,9 @@ int descMatchCpu(const plba_match_batch *b, int32_t *matches_12, int32_t *n_matc
 long lineCells(double x1, double y1, double x2, double y2, std::vector<std::array<int, 2>> &out, size_t max_out);
 // tools/gridmatch_bench.py and the tests only: plba_grid_match's semantics, single-threaded, on the CPU
 int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
+// the same with a window of four half-widths per problem (win [n][4]: left, right, up, down; b->ws is not read)
+int gridMatchCpuWin(const plba_gridmatch_batch *b, const int32_t *win, int32_t *matches_12, int32_t *n_matches);
+// stereo.cpp. tools/stereo_bench.py and the tests only: plba_stereo_associate's semantics, single-threaded, on the CPU
+int stereoCpu(const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
 
 }  // namespace plslam

@@ -455,3 +455,102 @@ class GridMatchBatchView:
             cell_off2=_ptr(self.cell_off2, _ip), cells2=_ptr(self.cells2, _ip), dir2=_ptr(self.dir2, _dp),
             kind=_ptr(self.kind, _ip), ws=_ptr(self.ws, _ip), nnr=_ptr(self.nnr, _dp),
             line_sim_th=_ptr(self.line_sim_th, _dp))
+
+
+# ---- stereo association (plba_stereo_params / plba_stereo_batch / plba_stereo_out / plba_stereo_associate)
+class PlbaStereoParams(C.Structure):
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("matching_s_ws", C.c_int32), ("best_lr", C.c_int32), ("pluker", C.c_int32), ("pad", C.c_int32),
+                ("min_ratio_12_p", C.c_double), ("line_sim_th", C.c_double), ("max_dist_epip", C.c_double),
+                ("min_disp", C.c_double), ("ls_min_disp_ratio", C.c_double), ("line_horiz_th", C.c_double),
+                ("stereo_overlap_th", C.c_double), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("b", C.c_double)]
+
+
+class PlbaStereoBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("pt_off_l", _ip), ("pt_off_r", _ip), ("ls_off_l", _ip),
+                ("ls_off_r", _ip), ("pt_l", _fp), ("pt_r", _fp), ("pdesc_l", _bp), ("pdesc_r", _bp), ("ls_l", _fp),
+                ("ls_r", _fp), ("ldesc_l", _bp), ("ldesc_r", _bp)]
+
+
+class PlbaStereoOut(C.Structure):
+    _fields_ = [("n_pt", _ip), ("n_ls", _ip), ("pt_src", _ip), ("pt_pl", _dp), ("pt_disp", _dp), ("pt_P", _dp),
+                ("pdesc", _bp), ("ls_src", _ip), ("ls_spl", _dp), ("ls_epl", _dp), ("ls_sdisp", _dp), ("ls_edisp", _dp),
+                ("ls_sP", _dp), ("ls_eP", _dp), ("ls_le", _dp), ("ls_NDc", _dp), ("ldesc", _bp)]
+
+
+def stereo_params(params=None) -> PlbaStereoParams:
+    """PlbaStereoParams from a dict: plba_stereo_default_params, then the dict's entries (width, height,
+    fx, fy, cx, cy and b have no default)."""
+    if isinstance(params, PlbaStereoParams):
+        return params
+    from . import lib   # lib imports this module
+    p = PlbaStereoParams()
+    lib.load().plba_stereo_default_params(C.byref(p))
+    for k, v in dict(params or {}).items():
+        if k not in dict(PlbaStereoParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+class StereoBatchView:
+    """Concatenates stereo frames into contiguous arrays, the PlbaStereoBatch over them and the output
+    arrays of a call. A frame is a dict: pt_l [n][2] / pt_r float32, pdesc_l / pdesc_r [n][desc_bytes] uint8,
+    ls_l / ls_r [n][4] float32 (sx, sy, ex, ey), ldesc_l / ldesc_r; a missing key is an empty side."""
+
+    KEYS = (("pt_l", 2), ("pt_r", 2), ("ls_l", 4), ("ls_r", 4))
+    DESC = {"pt_l": "pdesc_l", "pt_r": "pdesc_r", "ls_l": "ldesc_l", "ls_r": "ldesc_r"}
+
+    def __init__(self, frames, desc_bytes=None):
+        frames = list(frames)
+        if desc_bytes is None:
+            desc_bytes = next((np.asarray(f[k]).shape[1] for f in frames for k in self.DESC.values()
+                               if k in f and np.asarray(f[k]).ndim == 2 and np.asarray(f[k]).shape[1]), 32)
+        self.desc_bytes = db = int(desc_bytes)
+        self.n = n = len(frames)
+        self.off, self.co, self.desc = {}, {}, {}
+        for key, per in self.KEYS:
+            co = [np.asarray(f.get(key, np.zeros((0, per))), np.float32).reshape(-1, per) for f in frames]
+            de = [np.asarray(f.get(self.DESC[key], np.zeros((0, db))), np.uint8).reshape(-1, db) for f in frames]
+            if any(len(a) != len(d) for a, d in zip(co, de)):
+                raise ValueError("one descriptor row per feature")
+            off = np.zeros(n + 1, np.int32)
+            off[1:] = np.cumsum([len(a) for a in co], dtype=np.int64)
+            self.off[key] = off
+            self.co[key] = np.ascontiguousarray(np.concatenate(co + [np.zeros((0, per), np.float32)]))
+            self.desc[key] = np.ascontiguousarray(np.concatenate(de + [np.zeros((0, db), np.uint8)]))
+        self.struct = PlbaStereoBatch(
+            n=n, desc_bytes=db, pt_off_l=_ptr(self.off["pt_l"], _ip), pt_off_r=_ptr(self.off["pt_r"], _ip),
+            ls_off_l=_ptr(self.off["ls_l"], _ip), ls_off_r=_ptr(self.off["ls_r"], _ip),
+            pt_l=_ptr(self.co["pt_l"], _fp), pt_r=_ptr(self.co["pt_r"], _fp), pdesc_l=_ptr(self.desc["pt_l"], _bp),
+            pdesc_r=_ptr(self.desc["pt_r"], _bp), ls_l=_ptr(self.co["ls_l"], _fp), ls_r=_ptr(self.co["ls_r"], _fp),
+            ldesc_l=_ptr(self.desc["ls_l"], _bp), ldesc_r=_ptr(self.desc["ls_r"], _bp))
+        npt, nls = max(int(self.off["pt_l"][-1]), 1), max(int(self.off["ls_l"][-1]), 1)
+        # rows past a frame's count are never written: a fill that no result can equal shows it
+        self.o = dict(
+            n_pt=np.zeros(max(n, 1), np.int32), n_ls=np.zeros(max(n, 1), np.int32),
+            pt_src=np.full(npt, -7, np.int32), pt_pl=np.full((npt, 2), np.nan), pt_disp=np.full(npt, np.nan),
+            pt_P=np.full((npt, 3), np.nan), pdesc=np.zeros((npt, db), np.uint8),
+            ls_src=np.full(nls, -7, np.int32), ls_spl=np.full((nls, 2), np.nan), ls_epl=np.full((nls, 2), np.nan),
+            ls_sdisp=np.full(nls, np.nan), ls_edisp=np.full(nls, np.nan), ls_sP=np.full((nls, 3), np.nan),
+            ls_eP=np.full((nls, 3), np.nan), ls_le=np.full((nls, 3), np.nan), ls_NDc=np.full((nls, 6), np.nan),
+            ldesc=np.zeros((nls, db), np.uint8))
+        kinds = {np.dtype(np.int32): _ip, np.dtype(np.float64): _dp, np.dtype(np.uint8): _bp}
+        self.out = PlbaStereoOut(**{k: v.ctypes.data_as(kinds[v.dtype]) for k, v in self.o.items()})
+
+    PT = ("pt_src", "pt_pl", "pt_disp", "pt_P", "pdesc")
+    LS = ("ls_src", "ls_spl", "ls_epl", "ls_sdisp", "ls_edisp", "ls_sP", "ls_eP", "ls_le", "ls_NDc", "ldesc")
+
+    def results(self, pluker: bool) -> list:
+        """One dict per frame: n_pt, n_ls and the first n_pt / n_ls rows of every output array (ls_NDc only
+        with pluker), copied."""
+        res = []
+        for f in range(self.n):
+            kp, kl = int(self.o["n_pt"][f]), int(self.o["n_ls"][f])
+            a, b = int(self.off["pt_l"][f]), int(self.off["ls_l"][f])
+            r = dict(n_pt=kp, n_ls=kl)
+            r.update({k: self.o[k][a:a + kp].copy() for k in self.PT})
+            r.update({k: self.o[k][b:b + kl].copy() for k in self.LS if pluker or k != "ls_NDc"})
+            res.append(r)
+        return res

@@ -31,7 +31,7 @@ EXPORTED = [
     "plba_hlm_default_params", "plba_hlm_lba",
     "plba_pgo_default_params", "plba_pgo_optimize",
     "plba_lcpose_default_params", "plba_lc_relative_pose",
-    "plba_desc_match", "plba_grid_match",
+    "plba_desc_match", "plba_grid_match", "plba_stereo_default_params", "plba_stereo_associate",
     "plba_bow_set_vocab", "plba_bow_insert", "plba_bow_remove", "plba_bow_get",
 ]
 
@@ -98,6 +98,10 @@ def load(path: Optional[str] = None):
                                         C.POINTER(capi.PlbaLcposeOut), bp, bp]
     L.plba_desc_match.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
     L.plba_grid_match.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
+    L.plba_stereo_default_params.argtypes = [C.POINTER(capi.PlbaStereoParams)]
+    L.plba_stereo_default_params.restype = None
+    L.plba_stereo_associate.argtypes = [vp, C.POINTER(capi.PlbaStereoBatch), C.POINTER(capi.PlbaStereoParams),
+                                        C.POINTER(capi.PlbaStereoOut)]
     L.plba_bow_set_vocab.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaBowVocab)]
     L.plba_bow_insert.argtypes = [vp, C.c_int32, C.c_int32, bp, C.c_int32, dp, ip, C.c_int32, ip]
     L.plba_bow_remove.argtypes = [vp, C.c_int32, C.c_int32]
@@ -105,7 +109,7 @@ def load(path: Optional[str] = None):
     for name in EXPORTED:
         f = getattr(L, name)
         if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
-                        "plba_lcpose_default_params"):
+                        "plba_lcpose_default_params", "plba_stereo_default_params"):
             f.restype = C.c_int
     _lib = L
     return L
@@ -343,6 +347,19 @@ class Solver:
         self._check(self.L.plba_grid_match(self.ctx, C.byref(bv.struct), _p(m12, C.c_int32), _p(cnt, C.c_int32)),
                     "plba_grid_match")
         return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+
+    def stereo_associate(self, frames, params, desc_bytes=None) -> list:
+        """Stereo association (plba_stereo_associate; StereoFrame::matchStereoPoints / matchStereoLines,
+        src2/stereoFrame.cpp:121-174, :310-435) of a batch of frames (capi.StereoBatchView) in one call.
+        params: a dict over plba_stereo_default_params with width, height, fx, fy, cx, cy, b (or a
+        capi.PlbaStereoParams). One dict per frame: n_pt, n_ls and the survivors' rows in increasing left
+        index (pt_src, pt_pl, pt_disp, pt_P, pdesc; ls_src, ls_spl, ls_epl, ls_sdisp, ls_edisp, ls_sP, ls_eP,
+        ls_le, ls_NDc with pluker, ldesc). Needs no uploaded window and leaves one intact."""
+        bv = frames if isinstance(frames, capi.StereoBatchView) else capi.StereoBatchView(frames, desc_bytes)
+        prm = capi.stereo_params(params)
+        self._check(self.L.plba_stereo_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
+                    "plba_stereo_associate")
+        return bv.results(bool(prm.pluker))
 
     def bow_set_vocab(self, slot: int, voc):
         """Uploads the vocabulary of a place-recognition slot (plba_bow_set_vocab; 0 points, 1 lines)

@@ -234,6 +234,21 @@ def match_params(min_ratio_12_p: float = 0.9, min_ratio_12_l: float = 0.9, best_
                              has_points=int(has_points), has_lines=int(has_lines), pad=0)
 
 
+STEREO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaStereoBatch), C.POINTER(capi.PlbaStereoParams),
+                        C.POINTER(capi.PlbaStereoOut))
+
+
+class PlslamStereoFrame(C.Structure):
+    _fields_ = [("desc_bytes", C.c_int32), ("n_pt_l", C.c_int32), ("n_pt_r", C.c_int32), ("n_ls_l", C.c_int32),
+                ("n_ls_r", C.c_int32), ("pad", C.c_int32), ("pt_l", C.POINTER(C.c_float)), ("pt_r", C.POINTER(C.c_float)),
+                ("pdesc_l", C.POINTER(C.c_uint8)), ("pdesc_r", C.POINTER(C.c_uint8)), ("ls_l", C.POINTER(C.c_float)),
+                ("ls_r", C.POINTER(C.c_float)), ("ldesc_l", C.POINTER(C.c_uint8)), ("ldesc_r", C.POINTER(C.c_uint8))]
+
+
+class PlslamStereoStats(C.Structure):
+    _fields_ = [("n_pt", C.c_int32), ("n_ls", C.c_int32), ("ms", C.c_double)]
+
+
 GRID_MATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaGridMatchBatch), C.POINTER(C.c_int32),
                             C.POINTER(C.c_int32))
 
@@ -306,6 +321,7 @@ HOST_EXPORTED = [
     "plslam_set_keyframe_features", "plslam_set_match_fn", "plslam_loop_closure_step_kf",
     "plslam_verify_loop_candidates", "plslam_desc_match_cpu",
     "plslam_line_cells", "plslam_grid_match_cpu",
+    "plslam_set_keyframe_stereo", "plslam_set_stereo_fn", "plslam_stereo_cpu",
     "plslam_set_keyframe_line_endpoints", "plslam_set_camera", "plslam_set_grid_match_fn",
     "plslam_mapmatch_default_params", "plslam_match_map_to_kf", "plslam_local_mapping_step_kf",
     "plslam_set_bow_fn", "plslam_bow_cpu", "plslam_set_vocabulary", "plslam_remove_keyframe", "plslam_insert_kf_bow",
@@ -480,6 +496,11 @@ def load_host(path: Optional[str] = None):
     L.plslam_desc_match_cpu.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
     L.plslam_line_cells.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, ip, C.c_int32, ip]
     L.plslam_grid_match_cpu.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
+    L.plslam_set_keyframe_stereo.argtypes = [vp, C.c_int32, C.POINTER(PlslamStereoFrame), C.POINTER(capi.PlbaStereoParams),
+                                             ip, ip, C.POINTER(PlslamStereoStats)]
+    L.plslam_set_stereo_fn.argtypes = [vp, STEREO_FN, vp]
+    L.plslam_stereo_cpu.argtypes = [vp, C.POINTER(capi.PlbaStereoBatch), C.POINTER(capi.PlbaStereoParams),
+                                    C.POINTER(capi.PlbaStereoOut)]
     L.plslam_set_keyframe_line_endpoints.argtypes = [vp, C.c_int32, dp, dp]
     L.plslam_set_camera.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32]
     L.plslam_set_grid_match_fn.argtypes = [vp, GRID_MATCH_FN, vp]
@@ -539,6 +560,16 @@ def grid_match_cpu(problems, cols: int = 64, rows: int = 48, best_lr: bool = Tru
     if rc != 0:
         raise PlbaError(f"plslam_grid_match_cpu failed: {rc}")
     return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+
+
+def stereo_cpu(frames, params, desc_bytes=None) -> list:
+    """plslam_stereo_cpu on the frames of Solver.stereo_associate (tests and tools/stereo_bench.py)."""
+    bv = frames if isinstance(frames, capi.StereoBatchView) else capi.StereoBatchView(frames, desc_bytes)
+    prm = capi.stereo_params(params)
+    rc = load_host().plslam_stereo_cpu(None, C.byref(bv.struct), C.byref(prm), C.byref(bv.out))
+    if rc != 0:
+        raise PlbaError(f"plslam_stereo_cpu failed: {rc}")
+    return bv.results(bool(prm.pluker))
 
 
 def _d(a):
@@ -982,6 +1013,49 @@ class HostMap:
         dp = C.POINTER(C.c_double)
         self._check(self.L.plslam_set_keyframe_line_endpoints(self.h, kf_idx, a.ctypes.data_as(dp), b.ctypes.data_as(dp)),
                     "set_keyframe_line_endpoints")
+
+    def set_stereo_fn(self, fn):
+        """fn(batch, params, out) -> int; "cpu" for plslam_stereo_cpu; None for the MI355X backend
+        (plba_stereo_associate)."""
+        if fn is None:
+            self._scb = None
+            self._check(self.L.plslam_set_stereo_fn(self.h, C.cast(None, STEREO_FN), None), "set_stereo_fn")
+            return
+        if fn == "cpu":
+            self._scb = C.cast(self.L.plslam_stereo_cpu, STEREO_FN)
+        else:
+            def tramp(user, bp_, pp, op):
+                try:
+                    return int(fn(bp_.contents, pp.contents, op.contents))
+                except Exception:  # never unwind through C
+                    import traceback
+                    traceback.print_exc()
+                    return -1
+            self._scb = STEREO_FN(tramp)
+        self._check(self.L.plslam_set_stereo_fn(self.h, self._scb, None), "set_stereo_fn")
+
+    def set_keyframe_stereo(self, kf_idx: int, frame: dict, params, desc_bytes=None) -> dict:
+        """The features of keyframe ``kf_idx`` from the detector output of its two images (``frame``: a
+        dict as in capi.StereoBatchView): matchStereoPoints + matchStereoLines through
+        plba_stereo_associate or the hook, stored as set_keyframe_features + set_keyframe_line_endpoints
+        would store them. Returns n_pt, n_ls, pt_src, ls_src (the left row of each feature) and ms."""
+        bv = capi.StereoBatchView([frame], desc_bytes)
+        fp, bp = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+        n = {k: len(bv.co[k]) for k in bv.co}
+        fr = PlslamStereoFrame(
+            desc_bytes=bv.desc_bytes, n_pt_l=n["pt_l"], n_pt_r=n["pt_r"], n_ls_l=n["ls_l"], n_ls_r=n["ls_r"], pad=0,
+            pt_l=bv.co["pt_l"].ctypes.data_as(fp), pt_r=bv.co["pt_r"].ctypes.data_as(fp),
+            pdesc_l=bv.desc["pt_l"].ctypes.data_as(bp), pdesc_r=bv.desc["pt_r"].ctypes.data_as(bp),
+            ls_l=bv.co["ls_l"].ctypes.data_as(fp), ls_r=bv.co["ls_r"].ctypes.data_as(fp),
+            ldesc_l=bv.desc["ls_l"].ctypes.data_as(bp), ldesc_r=bv.desc["ls_r"].ctypes.data_as(bp))
+        prm = capi.stereo_params(params)
+        ip = C.POINTER(C.c_int32)
+        psrc, lsrc = np.full(n["pt_l"] + 1, -1, np.int32), np.full(n["ls_l"] + 1, -1, np.int32)
+        st = PlslamStereoStats()
+        self._check(self.L.plslam_set_keyframe_stereo(self.h, kf_idx, C.byref(fr), C.byref(prm), psrc.ctypes.data_as(ip),
+                                                      lsrc.ctypes.data_as(ip), C.byref(st)), "set_keyframe_stereo")
+        self._kf_feat[kf_idx] = (st.n_pt, st.n_ls)
+        return dict(n_pt=st.n_pt, n_ls=st.n_ls, pt_src=psrc[:st.n_pt].copy(), ls_src=lsrc[:st.n_ls].copy(), ms=st.ms)
 
     def set_camera(self, fx: float, fy: float, cx: float, cy: float, width: int, height: int):
         self._check(self.L.plslam_set_camera(self.h, fx, fy, cx, cy, width, height), "set_camera")
