@@ -45,6 +45,9 @@ static const char *kKernelNames[K_COUNT] = {
     "k_rcs_chunk", "k_rcs_finalize", "k_rcs_factor", "k_pose_update", "k_lm_solve", "k_edge_eval", "k_decide",
     "k_dense_panel", "k_dense_update", "k_shard_pack", "collectives"};
 
+// the pinned host copy of Ctrl, rounded up so that the trace copy behind it starts aligned
+constexpr size_t kCtrlBlock = (sizeof(Ctrl) + 255) & ~(size_t)255;
+
 }  // namespace plba
 
 using namespace plba;
@@ -78,7 +81,8 @@ struct plba_ctx : plba::CtxBase {  // (opts, err / set_error, stream and the scr
     BuildMem bmemA, bmemB;   // device window build scratch (plba_build.hip), grow-only
     char *arena = nullptr, *staging = nullptr;
     size_t arena_cap = 0, staging_cap = 0;
-    Ctrl *h_ctrl = nullptr;  // pinned
+    Ctrl *h_ctrl = nullptr;  // pinned, one block with h_trace
+    plba_iter_trace *h_trace = nullptr;  // [kTraceCap] pinned copy of Dev::trace, read with h_ctrl
     uint8_t *d_depth = nullptr;  // [Ep] isDepthPositive flags
     double *d_outd = nullptr;    // download staging, caller order: Tcw | pt_xyz | ln_orth | χ² (points,
                                  // lines) | bytes: depth flags [Ep] | levels (points, lines)
@@ -1479,8 +1483,11 @@ int launch_steps_graph(plba_ctx *ctx, int n) {
     return PLBA_OK;
 }
 
+// One poll of a schedule: the control block and the per-iteration trace (all kTraceCap records:
+// how many are valid is in the control block the same poll reads) into the pinned block, one wait.
 int read_ctrl(plba_ctx *ctx) {
     PLBA_CHECK(hipMemcpyAsync(ctx->h_ctrl, ctx->d.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost, ctx->stream));
+    PLBA_CHECK(hipMemcpyAsync(ctx->h_trace, ctx->d.trace, sizeof(plba_iter_trace) * kTraceCap, hipMemcpyDeviceToHost, ctx->stream));
     PLBA_CHECK(hipStreamSynchronize(ctx->stream));
     return PLBA_OK;
 }
@@ -1525,11 +1532,25 @@ int agree_dev_error(plba_ctx *ctx, int mine, int *any) {
     return PLBA_OK;
 }
 
+// computeError() on the edges of `level` at the device's current state. when_done: queued as a
+// schedule's epilogue before the control block is polled (k_refresh does nothing then unless the
+// schedule has finished).
+int launch_refresh(plba_ctx *ctx, int level, bool when_done) {
+    if (ctx->d.E > 0) hipLaunchKernelGGL(k_refresh, dim3(blocks_for(ctx->d.E)), dim3(kBlock), 0, ctx->stream, ctx->d, level, when_done ? 1 : 0); PLBA_LAUNCHED(ctx, "k_refresh");
+    PLBA_CHECK(hipGetLastError());
+    return PLBA_OK;
+}
+
 // Run a schedule of 1 or 2 optimize() calls entirely on the device: replay the step graph in
 // batches, polling the control block once per batch.
+// refresh_level >= 0: the caller's epilogue, computeError() on that level's edges at the final
+// state. It is queued behind every batch, before the poll (k_refresh's when_done: it reads the
+// current buffers from the device control block and does nothing until the schedule has finished),
+// so the batch that finishes the schedule needs no wait of its own for it: one host wait per solve
+// when the first batch was long enough.
 // every launch outside the step graphs is checked where it is issued (PLBA_LAUNCHED; the graph
 // launches are checked by LAUNCH / launch_band)
-int run_schedule_once(plba_ctx *ctx, const Ctrl &init, bool &dev_error) {
+int run_schedule_once(plba_ctx *ctx, const Ctrl &init, int refresh_level, bool &dev_error) {
     dev_error = false;
     Dev &d = ctx->d;
     *ctx->h_ctrl = init;
@@ -1578,8 +1599,9 @@ int run_schedule_once(plba_ctx *ctx, const Ctrl &init, bool &dev_error) {
                 if (int rc = capture_now()) return rc;
         }
         launched += batch;
-        int rc = read_ctrl(ctx);
+        int rc = refresh_level >= 0 ? launch_refresh(ctx, refresh_level, true) : PLBA_OK;
         if (rc) return rc;
+        if ((rc = read_ctrl(ctx))) return rc;
         if (tlog) {
             const auto tb1 = std::chrono::steady_clock::now();
             fprintf(stderr, "[plba schedule] batch of %3d steps (%3d so far, device step %3d) %8.3f ms\n", batch, launched,
@@ -1606,11 +1628,9 @@ int run_schedule_once(plba_ctx *ctx, const Ctrl &init, bool &dev_error) {
     ctx->cur = ctx->h_ctrl->cur;
     ctx->last_ok = ctx->h_ctrl->last_ok;
     ctx->chi_src = ctx->h_ctrl->chi_src;
-    // per-iteration trace written by k_decide
+    // per-iteration trace written by k_decide (read by the poll that saw the schedule finish)
     const int nt = std::min(ctx->h_ctrl->ntrace, kTraceCap);
-    std::vector<plba_iter_trace> tr(nt);
-    if (nt) PLBA_CHECK(d2h(ctx, tr.data(), d.trace, sizeof(plba_iter_trace) * nt));
-    ctx->trace.insert(ctx->trace.end(), tr.begin(), tr.end());
+    ctx->trace.insert(ctx->trace.end(), ctx->h_trace, ctx->h_trace + nt);
     return PLBA_OK;
 }
 
@@ -1619,12 +1639,12 @@ int run_schedule_once(plba_ctx *ctx, const Ctrl &init, bool &dev_error) {
 // back, the window is switched to the column-lane factorisation for the rest of this context's
 // life (its arrays were allocated with the BCR ones) and the same schedule runs again, in this
 // process. Sharded windows agree on the error first, so every rank falls back together.
-int run_schedule(plba_ctx *ctx, const Ctrl &init) {
+int run_schedule(plba_ctx *ctx, const Ctrl &init, int refresh_level = -1) {
     Dev &d = ctx->d;
     int rc;
     if (d.bcr && (rc = bcr_state_copy(ctx, true))) return rc;
     bool dev_error = false;
-    rc = run_schedule_once(ctx, init, dev_error);
+    rc = run_schedule_once(ctx, init, refresh_level, dev_error);
     if (!rc || !dev_error || !d.bcr) return rc;
     PLBA_CHECK(hipStreamSynchronize(ctx->stream));
     if ((rc = bcr_state_copy(ctx, false))) return rc;
@@ -1635,7 +1655,7 @@ int run_schedule(plba_ctx *ctx, const Ctrl &init) {
     ctx->no_bcr = true;
     ++ctx->bcr_fallbacks;
     ctx->err.clear();
-    rc = run_schedule_once(ctx, init, dev_error);
+    rc = run_schedule_once(ctx, init, refresh_level, dev_error);
     return rc;
 }
 
@@ -1668,12 +1688,6 @@ int do_optimize(plba_ctx *ctx, int iterations, int32_t *iters_done, double *fina
     if (rc) return rc;
     if (iters_done) *iters_done = ctx->h_ctrl->iters_done[0];
     if (final_chi2) *final_chi2 = ctx->h_ctrl->chi2_final[0];
-    return PLBA_OK;
-}
-
-int launch_edges(plba_ctx *ctx, void (*k)(Dev, int), int arg) {
-    if (ctx->d.E > 0) hipLaunchKernelGGL(k, dim3(blocks_for(ctx->d.E)), dim3(kBlock), 0, ctx->stream, ctx->d, arg); PLBA_LAUNCHED(ctx, "edge kernel");
-    PLBA_CHECK(hipGetLastError());
     return PLBA_OK;
 }
 
@@ -1883,11 +1897,12 @@ int plba_create(plba_ctx **out, const plba_opts *opts) {
     }
     if (ctx->opts.device < 0 || ctx->opts.device >= ndev || hipSetDevice(ctx->opts.device) != hipSuccess ||
         hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void **)&ctx->h_ctrl, sizeof(Ctrl), hipHostMallocDefault) != hipSuccess) {
+        hipHostMalloc((void **)&ctx->h_ctrl, kCtrlBlock + sizeof(plba_iter_trace) * kTraceCap, hipHostMallocDefault) != hipSuccess) {
         delete ctx;
         return PLBA_E_DEVICE;
     }
-    std::memset(ctx->h_ctrl, 0, sizeof(Ctrl));
+    std::memset(ctx->h_ctrl, 0, kCtrlBlock + sizeof(plba_iter_trace) * kTraceCap);
+    ctx->h_trace = reinterpret_cast<plba_iter_trace *>(reinterpret_cast<char *>(ctx->h_ctrl) + kCtrlBlock);
     *out = ctx;
     // Pre-warm (PLBA_NO_PREWARM=1 skips it): the first window of a process otherwise pays the
     // code-object load, the first rocPRIM sorts of the device window build and the first pinned
@@ -1955,16 +1970,12 @@ int plba_reset_estimates(plba_ctx *ctx) {
     if (!ctx || !ctx->uploaded) return ctx ? PLBA_E_STATE : PLBA_E_INVALID;
     Dev &d = ctx->d;
     ctx->cur = ctx->last_ok = ctx->chi_src = 0;
-    PLBA_CHECK(hipMemcpyAsync(d.Tb[0], d.T_init, sizeof(double) * (size_t)d.n_kf * 12, hipMemcpyDeviceToDevice, ctx->stream));
-    PLBA_CHECK(hipMemcpyAsync(d.Xb[0], d.X_init, sizeof(double) * (size_t)d.n_lm * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    PLBA_CHECK(hipMemsetAsync(&d.ctrl->cur, 0, sizeof(int32_t), ctx->stream));
-    PLBA_CHECK(hipMemsetAsync(&d.ctrl->last_ok, 0, 2 * sizeof(int32_t), ctx->stream));  // last_ok, chi_src
-    PLBA_CHECK(hipMemsetAsync(d.e_level, 0, std::max(d.E, 1), ctx->stream));
-    for (int b = 0; b < d.nbx; ++b) {
-        PLBA_CHECK(hipMemsetAsync(d.xpb[b], 0, sizeof(double) * std::max(d.n, 1), ctx->stream));
-        PLBA_CHECK(hipMemsetAsync(d.xlb[b], 0, sizeof(double) * std::max((size_t)d.n_lm * 4, (size_t)1), ctx->stream));
-        PLBA_CHECK(hipMemsetAsync(d.chi2b[b], 0, sizeof(double) * std::max(d.E, 1), ctx->stream));
-    }
+    // one launch for every array (k_reset_estimates): sized by the longest range, capped — the
+    // kernel strides
+    const size_t longest = std::max({(size_t)d.n_kf * 12, (size_t)d.n_lm * 4, (size_t)d.E, (size_t)d.n, (size_t)1});
+    const int blocks = (int)std::min((longest + kBlock - 1) / kBlock, (size_t)2048);
+    hipLaunchKernelGGL(k_reset_estimates, dim3(blocks), dim3(kBlock), 0, ctx->stream, d); PLBA_LAUNCHED(ctx, "k_reset_estimates");
+    PLBA_CHECK(hipGetLastError());
     std::fill(ctx->h_level.begin(), ctx->h_level.end(), 0);
     ctx->robust = 1;
     ctx->initialized = false;
@@ -1983,7 +1994,7 @@ int plba_set_edge_levels(plba_ctx *ctx, const uint8_t *ept_level, const uint8_t 
         lv[e] = is_pt ? (ept_level ? ept_level[o] : 0) : (eln_level ? eln_level[o] : 0);
     }
     ctx->h_level = lv;
-    // on the solver stream (ordered after a pending plba_reset_estimates memset), then wait:
+    // on the solver stream (ordered after a pending plba_reset_estimates launch), then wait:
     // lv is a local buffer
     if (E) {
         PLBA_CHECK(hipMemcpyAsync(ctx->d.e_level, lv.data(), E, hipMemcpyHostToDevice, ctx->stream));
@@ -2018,7 +2029,7 @@ int plba_optimize(plba_ctx *ctx, int32_t iterations, int32_t *iters_done, double
 int plba_refresh_edge_errors(plba_ctx *ctx, int32_t level) {
     if (!ctx) return PLBA_E_INVALID;
     if (!ctx->uploaded) return PLBA_E_STATE;
-    return launch_edges(ctx, k_refresh, level);
+    return launch_refresh(ctx, level, false);
 }
 
 int plba_get_edge_chi2(plba_ctx *ctx, double *ept_chi2, uint8_t *ept_depth_ok, double *eln_chi2) {
@@ -2080,10 +2091,9 @@ int plba_lba_plucker(plba_ctx *ctx, plba_result *res) {
     c.stage_level[1] = 0;
     c.stage_classify[0] = 0;
     c.stage_classify[1] = 1;
-    if ((rc = run_schedule(ctx, c))) return rc;
-    // computeError() on the level-1 edges at the final state
-    if ((rc = launch_edges(ctx, k_refresh, 1))) return rc;
-    PLBA_CHECK(hipStreamSynchronize(ctx->stream));
+    // the schedule, with computeError() on the level-1 edges at the final state as its epilogue
+    // (done when the schedule's last poll returns)
+    if ((rc = run_schedule(ctx, c, 1))) return rc;
     auto t1 = std::chrono::steady_clock::now();
     if ((rc = collect_timing(ctx))) return rc;
     ctx->robust = 0;

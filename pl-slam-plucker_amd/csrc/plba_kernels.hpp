@@ -1424,9 +1424,44 @@ __global__ void k_line_pluker(Dev d) {
     for (int k = 0; k < 6; ++k) o[k] = L[k];
 }
 
+// plba_reset_estimates in one launch: the initial estimates into state buffer 0, zeros into every
+// solve / χ² buffer and the edge levels, and the three buffer indices of the control block back to
+// 0. One grid-stride loop per range; the extents are the ones the arrays are allocated with
+// (an empty array still owns one record, plba_layout.hpp).
+__global__ __launch_bounds__(kBlock) void k_reset_estimates(Dev d) {
+    const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x, nt = (size_t)gridDim.x * kBlock;
+    auto copy = [&](double *dst, const double *src, size_t n) {
+        for (size_t i = t; i < n; i += nt) dst[i] = src[i];
+    };
+    auto zero = [&](double *dst, size_t n) {
+        for (size_t i = t; i < (n > 0 ? n : 1); i += nt) dst[i] = 0.0;
+    };
+    copy(d.Tb[0], d.T_init, (size_t)d.n_kf * 12);
+    copy(d.Xb[0], d.X_init, (size_t)d.n_lm * 4);
+    for (int b = 0; b < d.nbx; ++b) {
+        zero(d.xpb[b], (size_t)d.n);
+        zero(d.xlb[b], (size_t)d.n_lm * 4);
+        zero(d.chi2b[b], (size_t)d.E);
+    }
+    // levels are bytes: whole words first (the array is 256-byte aligned), then the tail
+    const size_t lb = d.E > 0 ? (size_t)d.E : 1, lw = lb / 4;
+    uint32_t *lv = reinterpret_cast<uint32_t *>(d.e_level);
+    for (size_t i = t; i < lw; i += nt) lv[i] = 0u;
+    for (size_t i = lw * 4 + t; i < lb; i += nt) d.e_level[i] = 0;
+    if (t == 0) {
+        d.ctrl->cur = 0;
+        d.ctrl->last_ok = 0;
+        d.ctrl->chi_src = 0;
+    }
+}
+
 // ---------------------------------------------------------------- outlier pass helpers
-// computeError() at the current state for edges of `level`
-__global__ void k_refresh(Dev d, int level) {
+// computeError() at the current state for edges of `level`. The current state buffer and the χ²
+// buffer are the control block's, so the launch may be queued behind the steps that decide them.
+// when_done: the epilogue of a schedule, queued before the host has polled the control block —
+// nothing happens unless the schedule finished (and no hand-off wait timed out).
+__global__ void k_refresh(Dev d, int level, int when_done) {
+    if (when_done && (!d.ctrl->all_done || d.ctrl->dev_error)) return;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= d.E || d.e_level[e] != level) return;
     const double *T = Tcur(d) + (size_t)d.e_kf[e] * 12;
