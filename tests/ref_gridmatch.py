@@ -8,6 +8,17 @@ Pinned where the reference leaves it open or undefined:
   * normalize() of a zero vector gives NaN, `abs(dot) < th` is then false and the candidate is kept;
   * a row with candidates but no seen pair (best_d = INT_MAX) is unmatched whatever nnr is (above
     nnr = 1 the reference counts a match with index -1).
+Each of the three is confirmed on the compiled reference (tests/test_refpin.py, test_divergence_*): the set's
+order shows only where two seen candidates tie at a row's minimum above nnr = 1; the reference keeps the
+NaN candidate too; and it does return a count that includes rows left at -1.
+
+Pinned to the reference's own code (oracle/refpin compiles src2/lineIterator.cpp, gridStructure.cpp and
+matching.cpp in place; tests/golden/refpin.npz records their outputs; tests/test_refpin.py compares, for
+equality): line_cells against getLineCoords; Grid.get and candidates_and_distances against
+GridStructure::get under symmetric windows and, through ref_stereo.WindowGrid, the stereo window;
+hamming_row against distance; match_grid against both matchGrid overloads at 32-byte descriptors (distance
+reads eight 32-bit words whatever the width, so no other width can be pinned). Still a restatement with
+no reference run behind it: match / matchNNR (tests/ref_descmatch.py; they need OpenCV's BFMatcher).
 
 A problem is a dict: kind (0 points, 1 lines), ws, nnr, line_sim_th, desc1 [n1][B] uint8, cell1 [n1][2],
 cell1_end [n1][2] (lines), desc2 [n2][B], cells2 (a list of [k][2] int arrays, one per train row),
