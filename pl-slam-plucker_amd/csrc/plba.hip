@@ -2429,16 +2429,16 @@ void plba_lcpose_default_params(plba_lcpose_params *p) {
 
 int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
                           uint8_t *pt_inlier, uint8_t *ln_inlier) {
-    return ctx ? lc_relative_pose(*ctx, b, pp, out, pt_inlier, ln_inlier) : PLBA_E_INVALID;
+    return ctx ? lc_relative_pose(ctx, b, pp, out, pt_inlier, ln_inlier) : PLBA_E_INVALID;
 }
 
 // descriptor matching and grid-guided matching (csrc/plba_assoc.hip)
 int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
-    return ctx ? desc_match(*ctx, b, matches_12, n_matches) : PLBA_E_INVALID;
+    return ctx ? desc_match(ctx, b, matches_12, n_matches) : PLBA_E_INVALID;
 }
 
 int plba_grid_match(plba_ctx *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
-    return ctx ? grid_match(*ctx, b, matches_12, n_matches) : PLBA_E_INVALID;
+    return ctx ? grid_match(ctx, b, matches_12, n_matches) : PLBA_E_INVALID;
 }
 
 // stereo association (csrc/plba_assoc.hip, csrc/plba_stereo.hpp)
@@ -2460,26 +2460,26 @@ void plba_stereo_default_params(plba_stereo_params *p) {
 
 int plba_stereo_associate(plba_ctx *ctx, const plba_stereo_batch *b, const plba_stereo_params *p,
                           const plba_stereo_out *out) {
-    return ctx ? stereo_associate(*ctx, b, p, out) : PLBA_E_INVALID;
+    return ctx ? stereo_associate(ctx, b, p, out) : PLBA_E_INVALID;
 }
 
 // place recognition (csrc/plba_assoc.hip, csrc/plba_bow.hpp)
 int plba_bow_set_vocab(plba_ctx *ctx, int32_t slot, const plba_bow_vocab *v) {
-    return ctx ? bow_set_vocab(*ctx, slot, v) : PLBA_E_INVALID;
+    return ctx ? bow_set_vocab(ctx, slot, v) : PLBA_E_INVALID;
 }
 
 int plba_bow_insert(plba_ctx *ctx, int32_t slot, int32_t kf_id, const uint8_t *desc, int32_t n_desc, double *scores,
                     int32_t *ids, int32_t cap, int32_t *n) {
-    return ctx ? bow_insert(*ctx, slot, kf_id, desc, n_desc, scores, ids, cap, n) : PLBA_E_INVALID;
+    return ctx ? bow_insert(ctx, slot, kf_id, desc, n_desc, scores, ids, cap, n) : PLBA_E_INVALID;
 }
 
 int plba_bow_remove(plba_ctx *ctx, int32_t slot, int32_t kf_id) {
-    return ctx ? bow_remove(*ctx, slot, kf_id) : PLBA_E_INVALID;
+    return ctx ? bow_remove(ctx, slot, kf_id) : PLBA_E_INVALID;
 }
 
 int plba_bow_get(plba_ctx *ctx, int32_t slot, int32_t kf_id, int32_t *word_ids, double *values, int32_t cap,
                  int32_t *n) {
-    return ctx ? bow_get(*ctx, slot, kf_id, word_ids, values, cap, n) : PLBA_E_INVALID;
+    return ctx ? bow_get(ctx, slot, kf_id, word_ids, values, cap, n) : PLBA_E_INVALID;
 }
 
 }  // extern "C"

@@ -2,8 +2,10 @@
 // the two descriptor matchers, the stereo association and place recognition. They share nothing
 // with the solver (no Dev, no step graph, no window arena), so they are a translation unit of their
 // own: an edit to a matcher does not rebuild the factorisation kernels. Each call is one upload, its
-// kernels and one read-back through a ScratchBlock laid out by a Layout; the extern "C" symbols are
-// forwarders in plba.hip.
+// kernels and one read-back through a ScratchBlock. A Staged (csrc/plba_layout.hpp) lays the block
+// out: the call declares each array once, by its kernel-struct field, role, count and host source or
+// destination; stage() then fills the pinned image and the fields, fetch() delivers the outputs.
+// The extern "C" symbols are forwarders in plba.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,10 +51,50 @@ int check_offsets(CtxBase *ctx, const char *op, const char *kind, const char *un
     return PLBA_OK;
 }
 
-// copies count T into the host image at `off` (nothing for an absent or empty array)
-template <typename T>
-void put(char *h, size_t off, const T *src, size_t count) {
-    if (src && count) memcpy(h + off, src, sizeof(T) * count);
+// the one upload of a call: the inputs of the pinned image to the device
+int upload(CtxBase *ctx, const ScratchBlock &k, const Staged &B) {
+    PLBA_CHECK(hipMemcpyAsync(k.dev, k.host, B.inputs_end(), hipMemcpyHostToDevice, ctx->stream));
+    return PLBA_OK;
+}
+
+// the one read-back of a call: the outputs into the pinned image, and the wait for them
+int read_back(CtxBase *ctx, const ScratchBlock &k, const Staged &B) {
+    const size_t from = B.inputs_end();
+    PLBA_CHECK(hipMemcpyAsync(k.host + from, k.dev + from, B.outputs_end() - from, hipMemcpyDeviceToHost, ctx->stream));
+    PLBA_CHECK(hipStreamSynchronize(ctx->stream));
+    return PLBA_OK;
+}
+
+// The grid matcher's device side on a GmDev whose arrays are bound, in two steps so that the stereo
+// path can launch k_stereo_cells between them. First its scalars and kGmNone in every key (best
+// and second are one range of key_bytes):
+int grid_prepare(CtxBase *ctx, GmDev &D, int n, int desc_bytes, int cols, int rows, int best_lr, size_t key_bytes) {
+    PLBA_CHECK(hipMemsetAsync(D.best, 0xFF, key_bytes, ctx->stream));
+    D.n = n;
+    D.dwords = desc_bytes / 4;
+    D.cols = cols;
+    D.rows = rows;
+    D.best_lr = best_lr != 0;
+    return PLBA_OK;
+}
+
+// then k_grid_cols for the best and for the second-best key, and k_grid_rows
+int grid_launch(CtxBase *ctx, const GmDev &D, int max_train) {
+    hipStream_t s = ctx->stream;
+    const int n = D.n;
+    if (max_train > 0) {  // a workgroup past its problem's train rows returns at once
+        const dim3 grid(n, (max_train + kGmNT - 1) / kGmNT);
+        if (D.dwords <= 8) {
+            hipLaunchKernelGGL((k_grid_cols<8, 0>), grid, dim3(kGmNT), 0, s, D);
+            hipLaunchKernelGGL((k_grid_cols<8, 1>), grid, dim3(kGmNT), 0, s, D);
+        } else {
+            hipLaunchKernelGGL((k_grid_cols<16, 0>), grid, dim3(kGmNT), 0, s, D);
+            hipLaunchKernelGGL((k_grid_cols<16, 1>), grid, dim3(kGmNT), 0, s, D);
+        }
+        PLBA_LAUNCHED(ctx, "k_grid_cols");
+    }
+    hipLaunchKernelGGL(k_grid_rows, dim3(n), dim3(kGmRowsNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_grid_rows");
+    return PLBA_OK;
 }
 
 }  // namespace
@@ -61,9 +103,8 @@ void put(char *h, size_t off, const T *src, size_t count) {
 // MapHandler::computeRelativePoseRobustGN / computeRelativePoseGN (src/mapHandler.cpp:4677-5068,
 // :4413-4675) for a batch of candidate pairs: one upload, one launch of k_lcpose
 // (csrc/plba_lcpose.hpp, one workgroup per candidate), one read-back.
-int lc_relative_pose(CtxBase &cb, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
+int lc_relative_pose(CtxBase *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
                      uint8_t *pt_inlier, uint8_t *ln_inlier) {
-    CtxBase *const ctx = &cb;
     const char *const op = "relative pose";
     if (!b || b->n < 0) {
         ctx->set_error("relative pose: NULL batch or n < 0");
@@ -92,51 +133,33 @@ int lc_relative_pose(CtxBase &cb, const plba_lcpose_batch *b, const plba_lcpose_
     }
     (void)hipSetDevice(ctx->opts.device);
     // one block, the same layout on the device and in pinned host memory
-    Layout L;
-    const size_t o_ptoff = L.add<int32_t>(n + 1), o_lnoff = L.add<int32_t>(n + 1), o_P = L.add<double>(3 * np),
-                 o_obs = L.add<double>(2 * np), o_sP = L.add<double>(3 * nl), o_eP = L.add<double>(3 * nl),
-                 o_le = L.add<double>(3 * nl);
-    const size_t inputs_end = L.mark();  // host -> device
-    const size_t o_out = L.add<plba_lcpose_out>(n), o_pin = L.add(np), o_lin = L.add(nl);
-    const size_t outputs_end = L.mark();  // device -> host
-    if (const int rc = ctx->lc.reserve(cb, outputs_end, outputs_end, op)) return rc;
-    char *h = ctx->lc.host, *dv = ctx->lc.dev;
-    put(h, o_ptoff, b->pt_off, n + 1);
-    put(h, o_lnoff, b->ln_off, n + 1);
-    put(h, o_P, b->pt_P, 3 * np);
-    put(h, o_obs, b->pt_obs, 2 * np);
-    put(h, o_sP, b->ln_sP, 3 * nl);
-    put(h, o_eP, b->ln_eP, 3 * nl);
-    put(h, o_le, b->ln_le, 3 * nl);
-    hipStream_t s = ctx->stream;
-    PLBA_CHECK(hipMemcpyAsync(dv, h, inputs_end, hipMemcpyHostToDevice, s));
     LcDev D{};
-    D.pt_off = at<const int32_t>(dv, o_ptoff);
-    D.ln_off = at<const int32_t>(dv, o_lnoff);
-    D.pt_P = at<const double>(dv, o_P);
-    D.pt_obs = at<const double>(dv, o_obs);
-    D.ln_sP = at<const double>(dv, o_sP);
-    D.ln_eP = at<const double>(dv, o_eP);
-    D.ln_le = at<const double>(dv, o_le);
-    D.out = at<plba_lcpose_out>(dv, o_out);
-    D.pt_in = at<uint8_t>(dv, o_pin);
-    D.ln_in = at<uint8_t>(dv, o_lin);
+    Staged B;
+    B.in(D.pt_off, n + 1, b->pt_off);
+    B.in(D.ln_off, n + 1, b->ln_off);
+    B.in(D.pt_P, 3 * np, b->pt_P);
+    B.in(D.pt_obs, 2 * np, b->pt_obs);
+    B.in(D.ln_sP, 3 * nl, b->ln_sP);
+    B.in(D.ln_eP, 3 * nl, b->ln_eP);
+    B.in(D.ln_le, 3 * nl, b->ln_le);
+    B.out(D.out, n, out);
+    B.out(D.pt_in, np, pt_inlier);
+    B.out(D.ln_in, nl, ln_inlier);
+    if (const int rc = ctx->lc.reserve(*ctx, B.outputs_end(), B.outputs_end(), op)) return rc;
+    B.stage(ctx->lc.host, ctx->lc.dev);
+    if (const int rc = upload(ctx, ctx->lc, B)) return rc;
     D.cam = Cam{b->fx, b->fy, b->cx, b->cy};
     D.prm = prm;
-    hipLaunchKernelGGL(k_lcpose, dim3(n), dim3(kLcNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_lcpose");
-    PLBA_CHECK(hipMemcpyAsync(h + inputs_end, dv + inputs_end, outputs_end - inputs_end, hipMemcpyDeviceToHost, s));
-    PLBA_CHECK(hipStreamSynchronize(s));
-    memcpy(out, h + o_out, sizeof(plba_lcpose_out) * (size_t)n);
-    if (pt_inlier && np) memcpy(pt_inlier, h + o_pin, np);
-    if (ln_inlier && nl) memcpy(ln_inlier, h + o_lin, nl);
+    hipLaunchKernelGGL(k_lcpose, dim3(n), dim3(kLcNT), 0, ctx->stream, D); PLBA_LAUNCHED(ctx, "k_lcpose");
+    if (const int rc = read_back(ctx, ctx->lc, B)) return rc;
+    B.fetch();
     return PLBA_OK;
 }
 
 // ---------------------------------------------------------------- descriptor matching
 // StVO::match / matchNNR (src2/matching.cpp:41-91) for a batch of descriptor-set pairs: one upload,
 // k_desc_nn (both directions of every pair) and k_desc_cross (csrc/plba_match.hpp), one read-back.
-int desc_match(CtxBase &cb, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
-    CtxBase *const ctx = &cb;
+int desc_match(CtxBase *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
     const char *const op = "descriptor matching";
     if (!b || b->n < 0) {
         ctx->set_error("descriptor matching: NULL batch or n < 0");
@@ -156,39 +179,27 @@ int desc_match(CtxBase &cb, const plba_match_batch *b, int32_t *matches_12, int3
         ctx->set_error("descriptor matching: a set of %d rows is more than %d", max_rows, 65535 * kDmNT);
         return PLBA_E_INVALID;
     }
-    const size_t n1 = (size_t)b->off1[n], n2 = (size_t)b->off2[n], db = (size_t)b->desc_bytes;
+    const size_t n1 = (size_t)b->off1[n], n2 = (size_t)b->off2[n], dw = (size_t)b->desc_bytes / 4;
     if ((n1 && (!b->desc1 || !matches_12)) || (n2 && !b->desc2)) {
         ctx->set_error("descriptor matching: NULL desc1 / desc2 / matches_12");
         return PLBA_E_INVALID;
     }
     (void)hipSetDevice(ctx->opts.device);
-    // one block; the pinned host image holds its inputs and outputs
-    Layout L;
-    const size_t o_off1 = L.add<int32_t>(n + 1), o_off2 = L.add<int32_t>(n + 1), o_nnr = L.add<float>(n),
-                 o_d1 = L.add(db * n1), o_d2 = L.add(db * n2);
-    const size_t inputs_end = L.mark();  // host -> device
-    const size_t o_m12 = L.add<int32_t>(n1), o_cnt = L.add<int32_t>(n);
-    const size_t outputs_end = L.mark();  // device -> host
-    const size_t o_nn12 = L.add<int32_t>(n1), o_nn21 = L.add<int32_t>(n2);  // device only
-    if (const int rc = ctx->match.reserve(cb, L.total, outputs_end, op)) return rc;
-    char *h = ctx->match.host, *dv = ctx->match.dev;
-    put(h, o_off1, b->off1, n + 1);
-    put(h, o_off2, b->off2, n + 1);
-    put(h, o_nnr, b->nnr, n);
-    put(h, o_d1, b->desc1, db * n1);
-    put(h, o_d2, b->desc2, db * n2);
-    hipStream_t s = ctx->stream;
-    PLBA_CHECK(hipMemcpyAsync(dv, h, inputs_end, hipMemcpyHostToDevice, s));
     DmDev D{};
-    D.off1 = at<const int32_t>(dv, o_off1);
-    D.off2 = at<const int32_t>(dv, o_off2);
-    D.nnr = at<const float>(dv, o_nnr);
-    D.desc1 = at<const uint32_t>(dv, o_d1);
-    D.desc2 = at<const uint32_t>(dv, o_d2);
-    D.m12 = at<int32_t>(dv, o_m12);
-    D.count = at<int32_t>(dv, o_cnt);
-    D.nn12 = at<int32_t>(dv, o_nn12);
-    D.nn21 = at<int32_t>(dv, o_nn21);
+    Staged B;
+    B.in(D.off1, n + 1, b->off1);
+    B.in(D.off2, n + 1, b->off2);
+    B.in(D.nnr, n, b->nnr);
+    B.in(D.desc1, dw * n1, b->desc1);
+    B.in(D.desc2, dw * n2, b->desc2);
+    B.out(D.m12, n1, matches_12);
+    B.out(D.count, n, n_matches);
+    B.dev(D.nn12, n1);
+    B.dev(D.nn21, n2);
+    if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
+    B.stage(ctx->match.host, ctx->match.dev);
+    if (const int rc = upload(ctx, ctx->match, B)) return rc;
+    hipStream_t s = ctx->stream;
     D.n = n;
     D.dwords = b->desc_bytes / 4;
     D.best_lr = b->best_lr != 0;
@@ -199,10 +210,8 @@ int desc_match(CtxBase &cb, const plba_match_batch *b, int32_t *matches_12, int3
         PLBA_LAUNCHED(ctx, "k_desc_nn");
     }
     hipLaunchKernelGGL(k_desc_cross, dim3(n), dim3(kDmNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_desc_cross");
-    PLBA_CHECK(hipMemcpyAsync(h + inputs_end, dv + inputs_end, outputs_end - inputs_end, hipMemcpyDeviceToHost, s));
-    PLBA_CHECK(hipStreamSynchronize(s));
-    if (n1) memcpy(matches_12, h + o_m12, sizeof(int32_t) * n1);
-    memcpy(n_matches, h + o_cnt, sizeof(int32_t) * n);
+    if (const int rc = read_back(ctx, ctx->match, B)) return rc;
+    B.fetch();
     return PLBA_OK;
 }
 
@@ -210,8 +219,7 @@ int desc_match(CtxBase &cb, const plba_match_batch *b, int32_t *matches_12, int3
 // StVO::matchGrid (src2/matching.cpp:111-258) for a batch of point and line problems: one upload, a
 // fill of the key arrays, k_grid_cols twice (best, then second best) and k_grid_rows
 // (csrc/plba_gridmatch.hpp), one read-back.
-int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
-    CtxBase *const ctx = &cb;
+int grid_match(CtxBase *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
     const char *const op = "grid matching";
     if (!b || b->n < 0) {
         ctx->set_error("grid matching: NULL batch or n < 0");
@@ -249,7 +257,7 @@ int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, 
         ctx->set_error("grid matching: %d train rows in a problem are more than %d", max_train, kGmMaxTrain);
         return PLBA_E_INVALID;
     }
-    const size_t n1 = (size_t)b->off1[n], n2 = (size_t)b->off2[n], db = (size_t)b->desc_bytes;
+    const size_t n1 = (size_t)b->off1[n], n2 = (size_t)b->off2[n], dw = (size_t)b->desc_bytes / 4;
     if ((n1 && (!b->desc1 || !b->cell1 || !matches_12)) || (n2 && (!b->desc2 || !b->cell_off2)) ||
         (line_q && !b->cell1_end) || (line_t && !b->dir2)) {
         ctx->set_error("grid matching: NULL desc1 / cell1 / cell1_end / matches_12 / desc2 / cell_off2 / dir2");
@@ -265,78 +273,38 @@ int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, 
         }
     }
     (void)hipSetDevice(ctx->opts.device);
-    // one block; the pinned host image holds its inputs and outputs
-    Layout L;
-    const size_t o_off1 = L.add<int32_t>(n + 1), o_off2 = L.add<int32_t>(n + 1), o_kind = L.add<int32_t>(n),
-                 o_ws = L.add<int32_t>(4 * (size_t)n), o_nnr = L.add<double>(n), o_th = L.add<double>(n), o_d1 = L.add(db * n1),
-                 o_d2 = L.add(db * n2), o_c1 = L.add<int32_t>(2 * n1), o_c1e = L.add<int32_t>(2 * n1),
-                 o_co2 = L.add<int32_t>(n2 + 1), o_cl2 = L.add<int32_t>(2 * nc), o_dir = L.add<double>(2 * n2);
-    const size_t inputs_end = L.mark();  // host -> device
-    const size_t o_m12 = L.add<int32_t>(n1), o_cnt = L.add<int32_t>(n);
-    const size_t outputs_end = L.mark();  // device -> host
-    const size_t o_best = L.add<uint32_t>(n1), o_sec = L.add<uint32_t>(n1);
-    const size_t keys_end = L.mark();  // the key arrays start as kGmNone
-    const size_t o_m21 = L.add<int32_t>(n2);  // device only, as the keys
-    if (const int rc = ctx->match.reserve(cb, L.total, outputs_end, op)) return rc;
-    char *h = ctx->match.host, *dv = ctx->match.dev;
-    put(h, o_off1, b->off1, n + 1);
-    put(h, o_off2, b->off2, n + 1);
-    put(h, o_kind, b->kind, n);
-    for (int k = 0; k < n; ++k)  // the symmetric window of matchGrid's callers: ws to the left, right, up and down
-        for (int e = 0; e < 4; ++e) at<int32_t>(h, o_ws)[4 * k + e] = b->ws[k];
-    put(h, o_nnr, b->nnr, n);
-    put(h, o_th, b->line_sim_th, n);
-    put(h, o_d1, b->desc1, db * n1);
-    put(h, o_d2, b->desc2, db * n2);
-    put(h, o_c1, b->cell1, 2 * n1);
-    put(h, o_c1e, b->cell1_end, 2 * n1);
-    if (n2) put(h, o_co2, b->cell_off2, n2 + 1);
-    else memset(h + o_co2, 0, sizeof(int32_t));
-    put(h, o_cl2, b->cells2, 2 * nc);
-    put(h, o_dir, b->dir2, 2 * n2);
-    hipStream_t s = ctx->stream;
-    PLBA_CHECK(hipMemcpyAsync(dv, h, inputs_end, hipMemcpyHostToDevice, s));
-    PLBA_CHECK(hipMemsetAsync(dv + o_best, 0xFF, keys_end - o_best, s));  // kGmNone in every key
     GmDev D{};
-    D.off1 = at<const int32_t>(dv, o_off1);
-    D.off2 = at<const int32_t>(dv, o_off2);
-    D.kind = at<const int32_t>(dv, o_kind);
-    D.ws = at<const int32_t>(dv, o_ws);
-    D.nnr = at<const double>(dv, o_nnr);
-    D.sim_th = at<const double>(dv, o_th);
-    D.desc1 = at<const uint32_t>(dv, o_d1);
-    D.desc2 = at<const uint32_t>(dv, o_d2);
-    D.cell1 = at<const int32_t>(dv, o_c1);
-    D.cell1e = at<const int32_t>(dv, o_c1e);
-    D.cell_off2 = at<const int32_t>(dv, o_co2);
-    D.cells2 = at<const int32_t>(dv, o_cl2);
-    D.dir2 = at<const double>(dv, o_dir);
-    D.m12 = at<int32_t>(dv, o_m12);
-    D.count = at<int32_t>(dv, o_cnt);
-    D.best = at<uint32_t>(dv, o_best);
-    D.second = at<uint32_t>(dv, o_sec);
-    D.m21 = at<int32_t>(dv, o_m21);
-    D.n = n;
-    D.dwords = b->desc_bytes / 4;
-    D.cols = b->cols;
-    D.rows = b->rows;
-    D.best_lr = b->best_lr != 0;
-    if (max_train > 0) {  // a workgroup past its problem's train rows returns at once
-        const dim3 grid(n, (max_train + kGmNT - 1) / kGmNT);
-        if (D.dwords <= 8) {
-            hipLaunchKernelGGL((k_grid_cols<8, 0>), grid, dim3(kGmNT), 0, s, D);
-            hipLaunchKernelGGL((k_grid_cols<8, 1>), grid, dim3(kGmNT), 0, s, D);
-        } else {
-            hipLaunchKernelGGL((k_grid_cols<16, 0>), grid, dim3(kGmNT), 0, s, D);
-            hipLaunchKernelGGL((k_grid_cols<16, 1>), grid, dim3(kGmNT), 0, s, D);
-        }
-        PLBA_LAUNCHED(ctx, "k_grid_cols");
-    }
-    hipLaunchKernelGGL(k_grid_rows, dim3(n), dim3(kGmRowsNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_grid_rows");
-    PLBA_CHECK(hipMemcpyAsync(h + inputs_end, dv + inputs_end, outputs_end - inputs_end, hipMemcpyDeviceToHost, s));
-    PLBA_CHECK(hipStreamSynchronize(s));
-    if (n1) memcpy(matches_12, h + o_m12, sizeof(int32_t) * n1);
-    memcpy(n_matches, h + o_cnt, sizeof(int32_t) * n);
+    Staged B;
+    B.in(D.off1, n + 1, b->off1);
+    B.in(D.off2, n + 1, b->off2);
+    B.in(D.kind, n, b->kind);
+    B.in(D.ws, 4 * (size_t)n);  // filled below
+    B.in(D.nnr, n, b->nnr);
+    B.in(D.sim_th, n, b->line_sim_th);
+    B.in(D.desc1, dw * n1, b->desc1);
+    B.in(D.desc2, dw * n2, b->desc2);
+    B.in(D.cell1, 2 * n1, b->cell1);
+    B.in(D.cell1e, 2 * n1, b->cell1_end);
+    B.in(D.cell_off2, n2 + 1, n2 ? b->cell_off2 : nullptr);  // without train rows: one zero, below
+    B.in(D.cells2, 2 * nc, b->cells2);
+    B.in(D.dir2, 2 * n2, b->dir2);
+    B.out(D.m12, n1, matches_12);
+    B.out(D.count, n, n_matches);
+    const size_t o_best = B.dev(D.best, n1);
+    B.dev(D.second, n1);
+    const size_t key_bytes = B.mark() - o_best;  // the two key arrays start as kGmNone
+    B.dev(D.m21, n2);
+    if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
+    B.stage(ctx->match.host, ctx->match.dev);
+    int32_t *const ws = B.host(D.ws);
+    for (int k = 0; k < n; ++k)  // the symmetric window of matchGrid's callers: ws to the left, right, up and down
+        for (int e = 0; e < 4; ++e) ws[4 * k + e] = b->ws[k];
+    if (!n2) B.host(D.cell_off2)[0] = 0;
+    if (const int rc = upload(ctx, ctx->match, B)) return rc;
+    if (const int rc = grid_prepare(ctx, D, n, b->desc_bytes, b->cols, b->rows, b->best_lr, key_bytes)) return rc;
+    if (const int rc = grid_launch(ctx, D, max_train)) return rc;
+    if (const int rc = read_back(ctx, ctx->match, B)) return rc;
+    B.fetch();
     return PLBA_OK;
 }
 
@@ -345,8 +313,7 @@ int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, 
 // of frames: one upload, k_stereo_cells, the matcher's three launches with the window
 // (matching_s_ws, 0, 0, 0), k_stereo_gate (csrc/plba_stereo.hpp), one read-back. Frame f is the
 // matcher's problems 2 f (points) and 2 f + 1 (lines).
-int stereo_associate(CtxBase &cb, const plba_stereo_batch *b, const plba_stereo_params *pp, const plba_stereo_out *out) {
-    CtxBase *const ctx = &cb;
+int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp, const plba_stereo_out *out) {
     const char *const op = "stereo association";
     if (!b || b->n < 0) {
         ctx->set_error("stereo association: NULL batch or n < 0");
@@ -376,7 +343,7 @@ int stereo_associate(CtxBase &cb, const plba_stereo_batch *b, const plba_stereo_
     size_t cnt[2][2];
     for (int kd = 0; kd < 2; ++kd)
         for (int sd = 0; sd < 2; ++sd) cnt[kd][sd] = (size_t)(offs[kd][sd][n] - offs[kd][sd][0]);
-    const size_t N1 = cnt[0][0] + cnt[1][0], N2 = cnt[0][1] + cnt[1][1], db = (size_t)b->desc_bytes;
+    const size_t N1 = cnt[0][0] + cnt[1][0], N2 = cnt[0][1] + cnt[1][1], db = (size_t)b->desc_bytes, dw = db / 4;
     const int stride = std::max(prm.cols, prm.rows);
     const size_t nc = cnt[0][1] + cnt[1][1] * (size_t)stride;
     if (N1 > (size_t)INT32_MAX || N2 > (size_t)INT32_MAX || nc > (size_t)INT32_MAX) {
@@ -418,24 +385,46 @@ int stereo_associate(CtxBase &cb, const plba_stereo_batch *b, const plba_stereo_
     (void)hipSetDevice(ctx->opts.device);
     const int np = 2 * n;
     const size_t P = (size_t)np;
-    Layout L;
-    const size_t o_off1 = L.add<int32_t>(P + 1), o_off2 = L.add<int32_t>(P + 1), o_kind = L.add<int32_t>(P),
-                 o_kbase = L.add<int32_t>(P), o_cbase = L.add<int32_t>(P + 1), o_ws = L.add<int32_t>(4 * P),
-                 o_nnr = L.add<double>(P), o_th = L.add<double>(P), o_d1 = L.add(db * N1), o_d2 = L.add(db * N2),
-                 o_co1 = L.add<float>(4 * N1), o_co2 = L.add<float>(4 * N2);
-    const size_t inputs_end = L.mark();  // host -> device
-    const size_t o_cnt = L.add<int32_t>(P), o_src = L.add<int32_t>(N1), o_od = L.add(db * N1),
-                 o_ptd = L.add<double>(kStPtDoubles * cnt[0][0]), o_lsd = L.add<double>(kStLsDoubles * cnt[1][0]);
-    const size_t outputs_end = L.mark();  // device -> host
-    const size_t o_best = L.add<uint32_t>(N1), o_sec = L.add<uint32_t>(N1);
-    const size_t keys_end = L.mark();  // the key arrays start as kGmNone
-    const size_t o_m12 = L.add<int32_t>(N1), o_m21 = L.add<int32_t>(N2), o_gcnt = L.add<int32_t>(P),
-                 o_c1 = L.add<int32_t>(2 * N1), o_c1e = L.add<int32_t>(2 * N1), o_co = L.add<int32_t>(N2 + 1),
-                 o_cl = L.add<int32_t>(2 * nc), o_dir = L.add<double>(2 * N2);  // device only
-    if (const int rc = ctx->match.reserve(cb, L.total, outputs_end, op)) return rc;
-    char *h = ctx->match.host, *dv = ctx->match.dev;
-    int32_t *off1 = at<int32_t>(h, o_off1), *off2 = at<int32_t>(h, o_off2), *kind = at<int32_t>(h, o_kind),
-            *kbase = at<int32_t>(h, o_kbase), *cbase = at<int32_t>(h, o_cbase), *ws = at<int32_t>(h, o_ws);
+    // the matcher's arrays are bound in S where the stereo kernels use them too, and handed to D below;
+    // the inputs are all filled here, problem by problem
+    StDev S{};
+    GmDev D{};
+    Staged B;
+    B.in(S.off1, P + 1);
+    B.in(S.off2, P + 1);
+    B.in(S.kind, P);
+    B.in(S.kbase, P);
+    B.in(S.cbase, P + 1);
+    B.in(D.ws, 4 * P);
+    B.in(D.nnr, P);
+    B.in(D.sim_th, P);
+    B.in(S.desc1, dw * N1);
+    B.in(D.desc2, dw * N2);
+    B.in(S.co1, 4 * N1);
+    B.in(S.co2, 4 * N2);
+    B.out(S.count, P);  // the outputs are scattered to the caller's arrays below
+    B.out(S.src, N1);
+    B.out(S.odesc, dw * N1);
+    B.out(S.ptd, kStPtDoubles * cnt[0][0]);
+    B.out(S.lsd, kStLsDoubles * cnt[1][0]);
+    const size_t o_best = B.dev(D.best, N1);
+    B.dev(D.second, N1);
+    const size_t key_bytes = B.mark() - o_best;  // the two key arrays start as kGmNone
+    B.dev(D.m12, N1);
+    B.dev(D.m21, N2);
+    B.dev(D.count, P);
+    B.dev(S.cell1, 2 * N1);
+    B.dev(S.cell1e, 2 * N1);
+    B.dev(S.cell_off2, N2 + 1);
+    B.dev(S.cells2, 2 * nc);
+    B.dev(S.dir2, 2 * N2);
+    if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
+    B.stage(ctx->match.host, ctx->match.dev);
+    int32_t *off1 = B.host(S.off1), *off2 = B.host(S.off2), *kind = B.host(S.kind), *kbase = B.host(S.kbase),
+            *cbase = B.host(S.cbase), *ws = B.host(D.ws);
+    double *nnr = B.host(D.nnr), *sim_th = B.host(D.sim_th);
+    uint8_t *const desc_h[2] = {(uint8_t *)B.host(S.desc1), (uint8_t *)B.host(D.desc2)};
+    float *const co_h[2] = {B.host(S.co1), B.host(S.co2)};
     const uint8_t *const descs[2][2] = {{b->pdesc_l, b->pdesc_r}, {b->ldesc_l, b->ldesc_r}};
     off1[0] = off2[0] = cbase[0] = 0;
     for (int p = 0; p < np; ++p) {
@@ -448,92 +437,40 @@ int stereo_associate(CtxBase &cb, const plba_stereo_batch *b, const plba_stereo_
         cbase[p + 1] = cbase[p] + r2 * (kd ? stride : 1);
         ws[4 * p] = prm.matching_s_ws;  // w.width = (matchingSWs, 0), w.height = (0, 0) (:142-144)
         ws[4 * p + 1] = ws[4 * p + 2] = ws[4 * p + 3] = 0;
-        at<double>(h, o_nnr)[p] = prm.min_ratio_12_p;  // matching.cpp:160, :241: for lines too
-        at<double>(h, o_th)[p] = prm.line_sim_th;
-        if (r1) memcpy(h + o_d1 + db * off1[p], descs[kd][0] + db * a1, db * r1);
-        if (r2) memcpy(h + o_d2 + db * off2[p], descs[kd][1] + db * a2, db * r2);
+        nnr[p] = prm.min_ratio_12_p;  // matching.cpp:160, :241: for lines too
+        sim_th[p] = prm.line_sim_th;
+        if (r1) memcpy(desc_h[0] + db * off1[p], descs[kd][0] + db * a1, db * r1);
+        if (r2) memcpy(desc_h[1] + db * off2[p], descs[kd][1] + db * a2, db * r2);
         for (int sd = 0; sd < 2; ++sd) {
             const int a = sd ? a2 : a1, r = sd ? r2 : r1;
-            float *dst = at<float>(h, sd ? o_co2 : o_co1) + 4 * (size_t)(sd ? off2[p] : off1[p]);
+            float *dst = co_h[sd] + 4 * (size_t)(sd ? off2[p] : off1[p]);
             const float *src = coords[kd][sd];
             for (int i = 0; i < r; ++i)
                 for (int e = 0; e < 4; ++e) dst[4 * i + e] = e < per ? src[(size_t)per * (a + i) + e] : 0.0f;
         }
     }
+    if (const int rc = upload(ctx, ctx->match, B)) return rc;
     hipStream_t s = ctx->stream;
-    PLBA_CHECK(hipMemcpyAsync(dv, h, inputs_end, hipMemcpyHostToDevice, s));
-    PLBA_CHECK(hipMemsetAsync(dv + o_best, 0xFF, keys_end - o_best, s));  // kGmNone in every key
-    StDev S{};
-    S.off1 = at<const int32_t>(dv, o_off1);
-    S.off2 = at<const int32_t>(dv, o_off2);
-    S.kind = at<const int32_t>(dv, o_kind);
-    S.kbase = at<const int32_t>(dv, o_kbase);
-    S.cbase = at<const int32_t>(dv, o_cbase);
-    S.co1 = at<const float>(dv, o_co1);
-    S.co2 = at<const float>(dv, o_co2);
-    S.desc1 = at<const uint32_t>(dv, o_d1);
-    S.cell1 = at<int32_t>(dv, o_c1);
-    S.cell1e = at<int32_t>(dv, o_c1e);
-    S.cell_off2 = at<int32_t>(dv, o_co);
-    S.cells2 = at<int32_t>(dv, o_cl);
-    S.dir2 = at<double>(dv, o_dir);
-    S.m12 = at<const int32_t>(dv, o_m12);
-    S.count = at<int32_t>(dv, o_cnt);
-    S.src = at<int32_t>(dv, o_src);
-    S.odesc = at<uint32_t>(dv, o_od);
-    S.ptd = at<double>(dv, o_ptd);
-    S.lsd = at<double>(dv, o_lsd);
+    S.m12 = D.m12;
     S.inv_w = prm.cols / (double)prm.width;   // :47-48
     S.inv_h = prm.rows / (double)prm.height;
     S.dwords = b->desc_bytes / 4;
     S.stride = stride;
     S.prm = prm;
-    GmDev D{};
-    D.off1 = S.off1;
-    D.off2 = S.off2;
-    D.kind = S.kind;
-    D.ws = at<const int32_t>(dv, o_ws);
-    D.nnr = at<const double>(dv, o_nnr);
-    D.sim_th = at<const double>(dv, o_th);
-    D.desc1 = S.desc1;
-    D.desc2 = at<const uint32_t>(dv, o_d2);
-    D.cell1 = S.cell1;
-    D.cell1e = S.cell1e;
-    D.cell_off2 = S.cell_off2;
-    D.cells2 = S.cells2;
-    D.dir2 = S.dir2;
-    D.m12 = at<int32_t>(dv, o_m12);
-    D.count = at<int32_t>(dv, o_gcnt);
-    D.best = at<uint32_t>(dv, o_best);
-    D.second = at<uint32_t>(dv, o_sec);
-    D.m21 = at<int32_t>(dv, o_m21);
-    D.n = np;
-    D.dwords = S.dwords;
-    D.cols = prm.cols;
-    D.rows = prm.rows;
-    D.best_lr = prm.best_lr != 0;
+    D.off1 = S.off1; D.off2 = S.off2; D.kind = S.kind; D.desc1 = S.desc1;
+    D.cell1 = S.cell1; D.cell1e = S.cell1e; D.cell_off2 = S.cell_off2; D.cells2 = S.cells2; D.dir2 = S.dir2;
+    if (const int rc = grid_prepare(ctx, D, np, b->desc_bytes, prm.cols, prm.rows, prm.best_lr, key_bytes)) return rc;
     if (max_rows > 0) {  // a thread past its problem's rows does nothing
         hipLaunchKernelGGL(k_stereo_cells, dim3(np, (max_rows + kStNT - 1) / kStNT), dim3(kStNT), 0, s, S);
         PLBA_LAUNCHED(ctx, "k_stereo_cells");
     }
-    if (max_train > 0) {  // a workgroup past its problem's right rows returns at once
-        const dim3 grid(np, (max_train + kGmNT - 1) / kGmNT);
-        if (D.dwords <= 8) {
-            hipLaunchKernelGGL((k_grid_cols<8, 0>), grid, dim3(kGmNT), 0, s, D);
-            hipLaunchKernelGGL((k_grid_cols<8, 1>), grid, dim3(kGmNT), 0, s, D);
-        } else {
-            hipLaunchKernelGGL((k_grid_cols<16, 0>), grid, dim3(kGmNT), 0, s, D);
-            hipLaunchKernelGGL((k_grid_cols<16, 1>), grid, dim3(kGmNT), 0, s, D);
-        }
-        PLBA_LAUNCHED(ctx, "k_grid_cols");
-    }
-    hipLaunchKernelGGL(k_grid_rows, dim3(np), dim3(kGmRowsNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_grid_rows");
+    if (const int rc = grid_launch(ctx, D, max_train)) return rc;
     hipLaunchKernelGGL(k_stereo_gate, dim3(np), dim3(kStNT), 0, s, S); PLBA_LAUNCHED(ctx, "k_stereo_gate");
-    PLBA_CHECK(hipMemcpyAsync(h + inputs_end, dv + inputs_end, outputs_end - inputs_end, hipMemcpyDeviceToHost, s));
-    PLBA_CHECK(hipStreamSynchronize(s));
+    if (const int rc = read_back(ctx, ctx->match, B)) return rc;
     // the first count[p] rows of each problem, to the frame's left offset in the caller's arrays
-    const int32_t *count = at<int32_t>(h, o_cnt), *src = at<int32_t>(h, o_src);
-    const double *ptd = at<double>(h, o_ptd), *lsd = at<double>(h, o_lsd);
+    const int32_t *count = B.host(S.count), *src = B.host(S.src);
+    const double *ptd = B.host(S.ptd), *lsd = B.host(S.lsd);
+    const uint8_t *odesc_h = (const uint8_t *)B.host(S.odesc);
     for (int p = 0; p < np; ++p) {
         const int f = p / 2, kd = p % 2, k = count[p], a1 = offs[kd][0][f];
         if (k < 0 || k > off1[p + 1] - off1[p]) {
@@ -544,7 +481,7 @@ int stereo_associate(CtxBase &cb, const plba_stereo_batch *b, const plba_stereo_
         int32_t *osrc = kd ? out->ls_src : out->pt_src;
         uint8_t *odesc = kd ? out->ldesc : out->pdesc;
         if (osrc && k) memcpy(osrc + a1, src + off1[p], sizeof(int32_t) * k);
-        if (odesc && k) memcpy(odesc + db * a1, h + o_od + db * off1[p], db * k);
+        if (odesc && k) memcpy(odesc + db * a1, odesc_h + db * off1[p], db * k);
         auto cols_out = [&](double *dst, const double *rec, int nd, int first, int width) {
             if (!dst) return;
             for (int i = 0; i < k; ++i)
@@ -618,8 +555,7 @@ std::vector<BowSlot::Row>::iterator bow_find(BowSlot &S, int kf_id) {
 
 }  // namespace
 
-int bow_set_vocab(CtxBase &cb, int slot, const plba_bow_vocab *v) {
-    CtxBase *const ctx = &cb;
+int bow_set_vocab(CtxBase *ctx, int slot, const plba_bow_vocab *v) {
     const char *const op = "vocabulary";
     BowSlot *S = bow_slot(ctx, op, slot, false);
     if (!S) return PLBA_E_INVALID;
@@ -694,22 +630,28 @@ int bow_set_vocab(CtxBase &cb, int slot, const plba_bow_vocab *v) {
     }
     (void)hipSetDevice(ctx->opts.device);
     const size_t db = (size_t)v->desc_bytes;
-    Layout L;
-    const size_t o_co = L.add<int32_t>(nn + 1), o_ch = L.add<int32_t>(nn - 1), o_d = L.add(db * nn),
-                 o_w = L.add<int32_t>(nn), o_ww = L.add<double>(v->n_words);
     S->n_nodes = 0;  // the slot is empty until the upload is through
     S->rows.clear();
     S->used = 0;
-    if (const int rc = S->voc.reserve(cb, L.total, 0, op)) return rc;
+    int32_t *child_off, *children, *word_id;
+    uint32_t *node_desc;
+    double *weight;
+    Staged B;  // for the offsets alone: no host image, five copies from the caller's arrays
+    B.dev(child_off, nn + 1);
+    B.dev(children, nn - 1);
+    B.dev(node_desc, db / 4 * nn);
+    B.dev(word_id, nn);
+    B.dev(weight, v->n_words);
+    if (const int rc = S->voc.reserve(*ctx, B.total(), 0, op)) return rc;
+    B.stage(nullptr, S->voc.dev);
     hipStream_t s = ctx->stream;
-    char *dv = S->voc.dev;
-    PLBA_CHECK(hipMemcpyAsync(dv + o_co, v->child_off, sizeof(int32_t) * (nn + 1), hipMemcpyHostToDevice, s));
-    PLBA_CHECK(hipMemcpyAsync(dv + o_ch, v->children, sizeof(int32_t) * (nn - 1), hipMemcpyHostToDevice, s));
-    PLBA_CHECK(hipMemcpyAsync(dv + o_d, v->node_desc, db * nn, hipMemcpyHostToDevice, s));
-    PLBA_CHECK(hipMemcpyAsync(dv + o_w, v->word_id, sizeof(int32_t) * nn, hipMemcpyHostToDevice, s));
-    PLBA_CHECK(hipMemcpyAsync(dv + o_ww, word_weight.data(), sizeof(double) * v->n_words, hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(child_off, v->child_off, sizeof(int32_t) * (nn + 1), hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(children, v->children, sizeof(int32_t) * (nn - 1), hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(node_desc, v->node_desc, db * nn, hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(word_id, v->word_id, sizeof(int32_t) * nn, hipMemcpyHostToDevice, s));
+    PLBA_CHECK(hipMemcpyAsync(weight, word_weight.data(), sizeof(double) * v->n_words, hipMemcpyHostToDevice, s));
     PLBA_CHECK(hipStreamSynchronize(s));  // the caller's arrays and word_weight are free again
-    S->o_child_off = o_co; S->o_children = o_ch; S->o_desc = o_d; S->o_word = o_w; S->o_weight = o_ww;
+    S->child_off = child_off; S->children = children; S->node_desc = node_desc; S->word_id = word_id; S->word_weight = weight;
     S->n_words = v->n_words;
     S->dwords = v->desc_bytes / 4;
     S->depth = depth;
@@ -718,9 +660,8 @@ int bow_set_vocab(CtxBase &cb, int slot, const plba_bow_vocab *v) {
     return PLBA_OK;
 }
 
-int bow_insert(CtxBase &cb, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,
+int bow_insert(CtxBase *ctx, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,
                int32_t *n_out) {
-    CtxBase *const ctx = &cb;
     const char *const op = "place recognition";
     BowSlot *S = bow_slot(ctx, op, slot, true);
     if (!S) return PLBA_E_INVALID;
@@ -747,23 +688,23 @@ int bow_insert(CtxBase &cb, int slot, int kf_id, const uint8_t *desc, int n_desc
     for (const BowSlot::Row &r : S->rows) n_live += r.live;
     int npad = 1;
     while (npad < n_desc) npad <<= 1;
-    const size_t db = 4 * (size_t)S->dwords;
-    Layout L;
-    const size_t o_desc = L.add(db * n_desc), o_ent = L.add<int32_t>(2 * (size_t)n_live);
-    const size_t inputs_end = L.mark();  // host -> device
-    const size_t o_scores = L.add<double>((size_t)n_live + 1), o_nnew = L.add<int32_t>(1);
-    const size_t outputs_end = L.mark();  // device -> host
-    const size_t o_keys = L.add<uint32_t>(n_desc), o_sort = L.add<uint32_t>(npad > kBowLdsKeys ? npad : 0),
-                 o_run = L.add<int32_t>(n_desc);  // device only
-    if (const int rc = ctx->bow_io.reserve(cb, L.total, outputs_end, op)) return rc;
+    BowDev D{};
+    Staged B;
+    B.in(D.desc, (size_t)S->dwords * n_desc, desc);
+    B.in(D.ent, 2 * (size_t)n_live);  // filled below
+    B.out(D.scores, (size_t)n_live + 1);  // delivered below, up to the caller's cap
+    B.out(D.n_new, 1);
+    B.dev(D.keys, n_desc);
+    B.dev(D.sortbuf, npad > kBowLdsKeys ? npad : 0);
+    B.dev(D.run_start, n_desc);
+    if (const int rc = ctx->bow_io.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
     // the new row has at most n_desc words
     if (const int rc = bow_grow(ctx, S->db_word, sizeof(int32_t) * (S->used + n_desc + 32), sizeof(int32_t) * S->used))
         return rc;
     if (const int rc = bow_grow(ctx, S->db_val, sizeof(double) * (S->used + n_desc + 32), sizeof(double) * S->used))
         return rc;
-    char *h = ctx->bow_io.host, *dv = ctx->bow_io.dev;
-    if (n_desc) put(h, o_desc, desc, db * n_desc);
-    int32_t *ent = at<int32_t>(h, o_ent);
+    B.stage(ctx->bow_io.host, ctx->bow_io.dev);
+    int32_t *ent = B.host(D.ent);
     int j = 0;
     for (const BowSlot::Row &r : S->rows) {
         if (!r.live) continue;
@@ -772,47 +713,37 @@ int bow_insert(CtxBase &cb, int slot, int kf_id, const uint8_t *desc, int n_desc
         if (j < cap) ids[j] = r.kf_id;
         ++j;
     }
+    if (const int rc = upload(ctx, ctx->bow_io, B)) return rc;
     hipStream_t s = ctx->stream;
-    PLBA_CHECK(hipMemcpyAsync(dv, h, inputs_end, hipMemcpyHostToDevice, s));
-    BowDev D{};
-    const char *vd = S->voc.dev;
-    D.child_off = at<const int32_t>(const_cast<char *>(vd), S->o_child_off);
-    D.children = at<const int32_t>(const_cast<char *>(vd), S->o_children);
-    D.node_desc = at<const uint32_t>(const_cast<char *>(vd), S->o_desc);
-    D.word_id = at<const int32_t>(const_cast<char *>(vd), S->o_word);
-    D.word_weight = at<const double>(const_cast<char *>(vd), S->o_weight);
+    D.child_off = S->child_off;
+    D.children = S->children;
+    D.node_desc = S->node_desc;
+    D.word_id = S->word_id;
+    D.word_weight = S->word_weight;
     D.dwords = S->dwords;
     D.depth = S->depth;
     D.max_children = S->max_children;
-    D.desc = at<const uint32_t>(dv, o_desc);
-    D.keys = at<uint32_t>(dv, o_keys);
-    D.sortbuf = at<uint32_t>(dv, o_sort);
-    D.run_start = at<int32_t>(dv, o_run);
     D.n_desc = n_desc;
     D.npad = npad;
-    D.db_word = at<int32_t>(S->db_word.dev, 0);
-    D.db_val = at<double>(S->db_val.dev, 0);
-    D.ent = at<const int32_t>(dv, o_ent);
+    D.db_word = reinterpret_cast<int32_t *>(S->db_word.dev);
+    D.db_val = reinterpret_cast<double *>(S->db_val.dev);
     D.new_off = (int32_t)S->used;
     D.n_live = n_live;
-    D.n_new = at<int32_t>(dv, o_nnew);
-    D.scores = at<double>(dv, o_scores);
     constexpr int per_wg = kBowDescNT / kBowGroup, waves_per_wg = kBowScoreNT / 64;
     hipLaunchKernelGGL(k_bow_descend, dim3(std::max(1, (n_desc + per_wg - 1) / per_wg)), dim3(kBowDescNT), 0, s, D);
     PLBA_LAUNCHED(ctx, "k_bow_descend");
     hipLaunchKernelGGL(k_bow_vector, dim3(1), dim3(kBowVecNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_bow_vector");
     hipLaunchKernelGGL(k_bow_score, dim3((n_live + 1 + waves_per_wg - 1) / waves_per_wg), dim3(kBowScoreNT), 0, s, D);
     PLBA_LAUNCHED(ctx, "k_bow_score");
-    PLBA_CHECK(hipMemcpyAsync(h + inputs_end, dv + inputs_end, outputs_end - inputs_end, hipMemcpyDeviceToHost, s));
-    PLBA_CHECK(hipStreamSynchronize(s));
-    const int32_t len = *at<int32_t>(h, o_nnew);
+    if (const int rc = read_back(ctx, ctx->bow_io, B)) return rc;
+    const int32_t len = *B.host(D.n_new);
     if (len < 0 || len > n_desc) {
         ctx->set_error("place recognition: the device returned a vector of %d words for %d descriptors", len, n_desc);
         return PLBA_E_DEVICE;
     }
     S->rows.insert(bow_find(*S, kf_id), BowSlot::Row{kf_id, (int32_t)S->used, len, true});
     S->used += (size_t)len;
-    const double *sc = at<double>(h, o_scores);
+    const double *sc = B.host(D.scores);
     for (int k = 0; k < std::min(cap, n_live); ++k) scores[k] = sc[k];
     if (n_live < cap) {
         scores[n_live] = sc[n_live];
@@ -822,8 +753,7 @@ int bow_insert(CtxBase &cb, int slot, int kf_id, const uint8_t *desc, int n_desc
     return PLBA_OK;
 }
 
-int bow_remove(CtxBase &cb, int slot, int kf_id) {
-    CtxBase *const ctx = &cb;
+int bow_remove(CtxBase *ctx, int slot, int kf_id) {
     BowSlot *S = bow_slot(ctx, "place recognition", slot, false);
     if (!S) return PLBA_E_INVALID;
     auto pos = bow_find(*S, kf_id);
@@ -835,8 +765,7 @@ int bow_remove(CtxBase &cb, int slot, int kf_id) {
     return PLBA_OK;
 }
 
-int bow_get(CtxBase &cb, int slot, int kf_id, int32_t *word_ids, double *values, int cap, int32_t *n_out) {
-    CtxBase *const ctx = &cb;
+int bow_get(CtxBase *ctx, int slot, int kf_id, int32_t *word_ids, double *values, int cap, int32_t *n_out) {
     BowSlot *S = bow_slot(ctx, "place recognition", slot, false);
     if (!S) return PLBA_E_INVALID;
     auto pos = bow_find(*S, kf_id);

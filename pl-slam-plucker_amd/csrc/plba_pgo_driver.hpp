@@ -277,20 +277,21 @@ void pgo_block_pattern(PgoProblem &pb) {
 }
 
 // the device block (grow-only), its uploads and the kernels' views of it
-int pgo_stage(CtxBase *ctx, const PgoProblem &pb, PgoDev &P, Dev &dd) {
+int pgo_stage(CtxBase *ctx, const PgoProblem &pb, PgoDev &P_out, Dev &dd_out) {
     const plba_pgo_graph *g = pb.g;
     const size_t nv = pb.nv, ne = pb.ne, n = pb.n, nblk = pb.nblk, nt = pb.ntiles;
-    Layout L;
-    const size_t o_ev = L.add<int32_t>(2 * ne), o_act = L.add<int32_t>(pb.act.size()), o_hidx = L.add<int32_t>(nv),
-                 o_br = L.add<int32_t>(nblk), o_bc = L.add<int32_t>(nblk), o_boff = L.add<int32_t>(nblk + 1),
-                 o_bcon = L.add<int32_t>(pb.blk_con.size()), o_tf = L.add<int32_t>(nt), o_tl = L.add<int32_t>(nt),
-                 o_Zinv = L.add<double>(12 * ne), o_info = L.add<double>(36 * ne), o_T0 = L.add<double>(12 * nv),
-                 o_T1 = L.add<double>(12 * nv), o_eH = L.add<double>(144 * ne), o_eg = L.add<double>(12 * ne),
-                 o_echi = L.add<double>(ne), o_Hd = L.add<double>(n * n), o_Ad = L.add<double>(n * n),
-                 o_b = L.add<double>(n), o_x = L.add<double>(n), o_W = L.add<double>(std::max(n, (size_t)1) * (kTile + 1)),
-                 o_out = L.add<double>(4), o_ctrl = L.add<Ctrl>(1);
-    if (const int rc = ctx->pgo.reserve(*ctx, L.total, sizeof(double) * 4, "pose graph")) return rc;
-    char *m = ctx->pgo.dev;
+    PgoDev P{};  // the caller's are written once everything is issued
+    Dev dd{};
+    Staged B;  // device only: the uploads below are copies from pageable memory, array by array
+    B.dev(P.e_v, 2 * ne); B.dev(P.act, pb.act.size()); B.dev(P.hidx, nv);
+    B.dev(P.blk_r, nblk); B.dev(P.blk_c, nblk); B.dev(P.blk_off, nblk + 1); B.dev(P.blk_con, pb.blk_con.size());
+    B.dev(dd.tile_first, nt); B.dev(dd.tile_last, nt);
+    B.dev(P.Zinv, 12 * ne); B.dev(P.info, 36 * ne); B.dev(P.T[0], 12 * nv); B.dev(P.T[1], 12 * nv);
+    B.dev(P.eH, 144 * ne); B.dev(P.eg, 12 * ne); B.dev(P.echi, ne);
+    B.dev(P.Hd, n * n); B.dev(dd.Ad, n * n); B.dev(P.b, n); B.dev(P.x, n);
+    B.dev(dd.Wbuf, std::max(n, (size_t)1) * (kTile + 1)); B.dev(P.out, 4); B.dev(dd.ctrl, 1);
+    if (const int rc = ctx->pgo.reserve(*ctx, B.total(), sizeof(double) * 4, "pose graph")) return rc;
+    B.stage(nullptr, ctx->pgo.dev);
     hipStream_t s = ctx->stream;
     std::vector<double> Tv(12 * nv), Zi(12 * ne), Om(36 * ne);
     for (size_t v = 0; v < nv; ++v) hiso_store(pb.X[v], &Tv[12 * v]);
@@ -298,38 +299,29 @@ int pgo_stage(CtxBase *ctx, const PgoProblem &pb, PgoDev &P, Dev &dd) {
         hiso_store(pb.Zinv[e], &Zi[12 * e]);
         for (int k = 0; k < 36; ++k) Om[36 * e + k] = g->e_info ? g->e_info[36 * e + k] : (k % 7 == 0 ? 1.0 : 0.0);
     }
-    auto up = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(m + off, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    auto up = [&](const void *dst, const void *src, size_t bytes) -> hipError_t {
+        return bytes ? hipMemcpyAsync(const_cast<void *>(dst), src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
     };
-    auto upv = [&](size_t off, const auto &v) { return up(off, v.data(), sizeof(v[0]) * v.size()); };
-    PLBA_CHECK(up(o_ev, g->e_v, sizeof(int32_t) * 2 * ne));
-    PLBA_CHECK(upv(o_act, pb.act));
-    PLBA_CHECK(upv(o_hidx, pb.hidx));
-    PLBA_CHECK(upv(o_br, pb.blk_r));
-    PLBA_CHECK(upv(o_bc, pb.blk_c));
-    PLBA_CHECK(upv(o_boff, pb.blk_off));
-    PLBA_CHECK(upv(o_bcon, pb.blk_con));
-    PLBA_CHECK(upv(o_tf, pb.env.tile_first));
-    PLBA_CHECK(upv(o_tl, pb.env.tile_last));
-    PLBA_CHECK(upv(o_Zinv, Zi));
-    PLBA_CHECK(upv(o_info, Om));
-    PLBA_CHECK(upv(o_T0, Tv));
-    PLBA_CHECK(hipMemsetAsync(m + o_x, 0, sizeof(double) * std::max(n, (size_t)1), s));  // g2o's _x starts at zero
-    PLBA_CHECK(hipMemsetAsync(m + o_ctrl, 0, sizeof(Ctrl), s));
-    P = PgoDev{};
+    auto upv = [&](const void *dst, const auto &v) { return up(dst, v.data(), sizeof(v[0]) * v.size()); };
+    PLBA_CHECK(up(P.e_v, g->e_v, sizeof(int32_t) * 2 * ne));
+    PLBA_CHECK(upv(P.act, pb.act));
+    PLBA_CHECK(upv(P.hidx, pb.hidx));
+    PLBA_CHECK(upv(P.blk_r, pb.blk_r));
+    PLBA_CHECK(upv(P.blk_c, pb.blk_c));
+    PLBA_CHECK(upv(P.blk_off, pb.blk_off));
+    PLBA_CHECK(upv(P.blk_con, pb.blk_con));
+    PLBA_CHECK(upv(dd.tile_first, pb.env.tile_first));
+    PLBA_CHECK(upv(dd.tile_last, pb.env.tile_last));
+    PLBA_CHECK(upv(P.Zinv, Zi));
+    PLBA_CHECK(upv(P.info, Om));
+    PLBA_CHECK(upv(P.T[0], Tv));
+    PLBA_CHECK(hipMemsetAsync(P.x, 0, sizeof(double) * std::max(n, (size_t)1), s));  // g2o's _x starts at zero
+    PLBA_CHECK(hipMemsetAsync(dd.ctrl, 0, sizeof(Ctrl), s));
     P.nv = pb.nv; P.ne = pb.ne; P.nact = (int)pb.act.size(); P.nfree = pb.nfree; P.n = pb.n; P.nblk = pb.nblk;
-    P.e_v = at<int32_t>(m, o_ev); P.act = at<int32_t>(m, o_act); P.hidx = at<int32_t>(m, o_hidx);
-    P.Zinv = at<double>(m, o_Zinv); P.info = at<double>(m, o_info);
-    P.T[0] = at<double>(m, o_T0); P.T[1] = at<double>(m, o_T1);
-    P.blk_r = at<int32_t>(m, o_br); P.blk_c = at<int32_t>(m, o_bc);
-    P.blk_off = at<int32_t>(m, o_boff); P.blk_con = at<int32_t>(m, o_bcon);
-    P.eH = at<double>(m, o_eH); P.eg = at<double>(m, o_eg); P.echi = at<double>(m, o_echi);
-    P.Hd = at<double>(m, o_Hd); P.b = at<double>(m, o_b); P.x = at<double>(m, o_x); P.out = at<double>(m, o_out);
-    dd = Dev{};
-    dd.n = pb.n; dd.ntiles = pb.ntiles; dd.Ad = at<double>(m, o_Ad); dd.bs = P.b; dd.xp = P.x;
-    dd.Wbuf = at<double>(m, o_W); dd.ctrl = at<Ctrl>(m, o_ctrl);
+    dd.n = pb.n; dd.ntiles = pb.ntiles; dd.bs = P.b; dd.xp = P.x;
     dd.solve_lds_n = pb.tuning.solve_lds_n;
-    dd.tile_first = at<int32_t>(m, o_tf); dd.tile_last = at<int32_t>(m, o_tl);
+    P_out = P;
+    dd_out = dd;
     return PLBA_OK;
 }
 

@@ -44,7 +44,9 @@ struct ScratchBlock {
 struct BowSlot {
     ScratchBlock voc;              // child_off, children, node_desc, word_id, word_weight
     ScratchBlock db_word, db_val;  // int32 word ids and double values of every row, appended
-    size_t o_child_off = 0, o_children = 0, o_desc = 0, o_word = 0, o_weight = 0;  // offsets into voc
+    int32_t *child_off = nullptr, *children = nullptr, *word_id = nullptr;  // the arrays of voc (BowDev's names)
+    uint32_t *node_desc = nullptr;
+    double *word_weight = nullptr;
     int n_nodes = 0, n_words = 0, dwords = 0, depth = 0, max_children = 0;  // n_nodes == 0: no vocabulary
     struct Row {
         int32_t kf_id, off, len;
@@ -125,17 +127,17 @@ inline int ScratchBlock::reserve(CtxBase &ctx, size_t dev_bytes, size_t host_byt
 
 // plba_assoc.hip: the bodies of plba_lc_relative_pose, plba_desc_match, plba_grid_match and
 // plba_stereo_associate,
-int lc_relative_pose(CtxBase &cb, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
+int lc_relative_pose(CtxBase *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
                      uint8_t *pt_inlier, uint8_t *ln_inlier);
-int desc_match(CtxBase &cb, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
-int grid_match(CtxBase &cb, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
-int stereo_associate(CtxBase &cb, const plba_stereo_batch *b, const plba_stereo_params *pp,
+int desc_match(CtxBase *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
+int grid_match(CtxBase *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
+int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp,
                      const plba_stereo_out *out);
 // and of plba_bow_set_vocab / _insert / _remove / _get
-int bow_set_vocab(CtxBase &cb, int slot, const plba_bow_vocab *v);
-int bow_insert(CtxBase &cb, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,
+int bow_set_vocab(CtxBase *ctx, int slot, const plba_bow_vocab *v);
+int bow_insert(CtxBase *ctx, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,
                int32_t *n);
-int bow_remove(CtxBase &cb, int slot, int kf_id);
-int bow_get(CtxBase &cb, int slot, int kf_id, int32_t *word_ids, double *values, int cap, int32_t *n);
+int bow_remove(CtxBase *ctx, int slot, int kf_id);
+int bow_get(CtxBase *ctx, int slot, int kf_id, int32_t *word_ids, double *values, int cap, int32_t *n);
 
 }  // namespace plba
