@@ -116,18 +116,23 @@ def sharded_hlm_worker(rank, world, port, outdir, cfg, params):
     dist.destroy_process_group()
 
 
-def sharded_gpu_worker(rank, world, port, outdir, cfg, transport, host_build=False, own_device=False):
+def sharded_gpu_worker(rank, world, port, outdir, cfg, transport, host_build=False, own_device=False, behind=None):
     """GPU rank (all ranks may share one GPU with the host transport): full sharded LBA.
     host_build: PLBA_HOST_BUILD=1 (the host window build and its shard_plan) instead of the device
     build's own ownership kernel (k_b_owner). own_device: rank r on GPU r (one process per GPU,
-    the RCCL transport's deployment)."""
+    the RCCL transport's deployment). behind: a variant of depth_cases.VARIANTS instead of cfg (the
+    window with points behind cameras)."""
     if host_build:
         os.environ["PLBA_HOST_BUILD"] = "1"
     dist = init_gloo(rank, world, port)
     from plba import synth
     from plba.dist import sharded_solver
     from plba.lib import shard_plan
-    g = synth.generate(cfg)
+    if behind is not None:
+        import depth_cases
+        g = depth_cases.window(behind)
+    else:
+        g = synth.generate(cfg)
     po, lo = shard_plan(g, world)  # the documented plan (plba_shard_plan)
     plan_lm = int((po == rank).sum() + (lo == rank).sum())
     plan_e = int((po[g.ept_lm] == rank).sum() + (lo[g.eln_lm] == rank).sum())

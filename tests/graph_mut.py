@@ -96,6 +96,41 @@ def fixed_only_landmarks(g: Graph) -> Graph:
     return h
 
 
+def camera_centres(g: Graph) -> np.ndarray:
+    """C_k = −Rᵀt of every keyframe estimate, (n_kf, 3)."""
+    return -np.einsum("kji,kj->ki", g.kf_Tcw[:, :, :3], g.kf_Tcw[:, :, 3])
+
+
+def point_depths(kf_Tcw, pt_xyz, ept_kf, ept_lm) -> np.ndarray:
+    """Camera-frame depth Pc[2] = R₂·P + t₂ of every point edge at the given estimates."""
+    T = np.asarray(kf_Tcw)[ept_kf]
+    return np.einsum("ej,ej->e", T[:, 2, :3], np.asarray(pt_xyz)[ept_lm]) + T[:, 2, 3]
+
+
+def points_behind_cameras(g: Graph, every=7, count=20, through="first") -> Graph:
+    """Reflect some point landmarks through a camera centre: P_j <- 2·C − P_j. The landmarks are
+    every `every`-th one, `count` at the most; C is the centre of the first keyframe (in edge
+    order) that observes the landmark ("first"), or the mean of its observing centres ("mean").
+    "short" takes its landmarks among those with at most 3 observations only, and reflects through
+    the first observer. A reflection through a camera's centre keeps that camera's projection and
+    makes its depth negative: the window stays finite, with a small χ² in that view and large ones
+    in the others. The chosen landmarks are left in `_behind`."""
+    assert through in ("first", "mean", "short"), through
+    h = g.copy()
+    nobs = np.bincount(g.ept_lm, minlength=g.n_pt)
+    cand = np.nonzero(nobs > 0)[0]
+    if through == "short":
+        cand = cand[nobs[cand] <= 3]
+    sel = cand[::every][:count]
+    C = camera_centres(g)
+    for j in sel:
+        kfs = g.ept_kf[g.ept_lm == j]
+        c = C[kfs].mean(axis=0) if through == "mean" else C[kfs[0]]
+        h.pt_xyz[j] = 2.0 * c - g.pt_xyz[j]
+    h._behind = sel
+    return h
+
+
 def zero_information_keyframe(g: Graph, row=None) -> Graph:
     """Ω = 0 on every edge of one free keyframe: the vertex stays active (it has edges) but its
     reduced-camera block row is exactly zero, so with λ = 0 the LDLᵀ meets an exact zero pivot

@@ -47,6 +47,31 @@ def test_two_ranks_host_transport_match_oracle(tmp_path, cfg):
     _check(r[0], oa.lba_plucker(g))
 
 
+def test_two_ranks_gather_depth_flags_of_points_behind_cameras(tmp_path):
+    """k_depth + k_gather on a window where isDepthPositive has both outcomes (depth_cases, the
+    "first" variant; no depth within 1e-6 of zero): each rank scatters the flags of its own edges to
+    their whole-window positions and the sum over ranks must be the unsharded run's flags and the
+    checker's, on every rank."""
+    import torch.multiprocessing as mp
+    import depth_cases as dc
+    from plba.lib import Solver
+    world = 2
+    mp.spawn(dw.sharded_gpu_worker, args=(world, dw.free_port(), str(tmp_path), "C1L", "host", False, False, "first"),
+             nprocs=world, join=True)
+    r = [dict(np.load(tmp_path / f"rank{i}.npz")) for i in range(world)]
+    g, ref = dc.window("first"), dc.oracle("first")
+    assert all(0 < int(x["local_edges"]) < g.n_ept + g.n_eln for x in r)
+    with Solver() as s:
+        s.upload(g)
+        one = s.lba_plucker()
+    assert 20 <= int((one["ept_depth_ok"] == 0).sum()) <= g.n_ept - 20
+    for x in r:
+        for k in ("ept_depth_ok", "ept_level", "eln_level"):
+            np.testing.assert_array_equal(x[k], one[k], err_msg=k)
+            np.testing.assert_array_equal(x[k], ref[k], err_msg=k)
+    _check(r[0], ref)
+
+
 def test_two_ranks_allreduce_exchange_matches_oracle(tmp_path, monkeypatch):
     """PLBA_SHARD_XCHG=allreduce: the reduced camera system summed by one all-reduce of the whole
     system (the round-3 exchange) instead of the all-gather of each rank's block-row runs."""
