@@ -579,6 +579,115 @@ void plba_stereo_default_params(plba_stereo_params *p);
 int plba_stereo_associate(plba_ctx *ctx, const plba_stereo_batch *b, const plba_stereo_params *p,
                           const plba_stereo_out *out);
 
+/* ---- Keyframe-to-keyframe association, the first half of lookForCommonMatches and the only place
+ * where map landmarks are created:
+ *   MapHandler::matchKF2KFPoints(prev_kf, curr_kf)    (src/mapHandler.cpp:237-366)
+ *   MapHandler::matchKF2KFLines(prev_kf, curr_kf)     (:368-695, the USE_LINE_PLUKER branch :433-590)
+ * up to, and without, the sequential part that builds the landmarks: the matches of every previous row
+ * and the geometry a new or extended landmark needs, indexed by previous row. A call takes a batch of
+ * keyframe pairs; pair f is the matcher's problems 2 f (points) and 2 f + 1 (lines). The previous
+ * keyframe's rows are the query side (1), the current keyframe's the train side (2).
+ * Sums. A sum of three terms t0, t1, t2 is t0 + (t1 + t2) (Eigen's unrolled reduction of three, as in the
+ * stereo block). R x + t for a pose T = (R, t) is (R_i0 x0 + (R_i1 x1 + R_i2 x2)) + t_i, and the norm of
+ * x is sqrt(x0 x0 + (x1 x1 + x2 x2)). A cross product is (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0).
+ * Query cells. inv_width = cols / (double)width, inv_height = rows / (double)height. A previous point
+ * projects as Q = DT.R P + DT.t, u = cx + fx * Q0 / Q2 (the product first, then the quotient), v = cy +
+ * fy * Q1 / Q2 (src2/pinholeStereoCamera.cpp:235-241); there is no depth check (:258). Its cell is
+ * ((int)(u * inv_width), (int)(v * inv_height)) (:259). A previous line's two cells are the truncated
+ * pixel coordinates ((int)u, (int)v) of its projected sP and eP: :395-396 does not scale them, unlike
+ * :823-824. With line_query_in_grid_units they are scaled like a point's. Converting a double that is
+ * not finite or out of range to int is undefined in the reference; here, if a cell's coordinate g (after
+ * the scaling, if any) has !(fabs(g) < 2^30) in x or in y, the cell is (-2^30, -2^30): its clipped window
+ * is empty, so the grid stage has no match for that row.
+ * Train side. A current point is entered in the cell ((int)(pl0 * inv_width), (int)(pl1 * inv_height))
+ * (:266). A current line is entered in the cells of getLineCoords over (spl * inv, epl * inv) (:410-411,
+ * the walk of plslam_line_cells), with the direction normalize(((epl0 - spl0) * inv_width, (epl1 - spl1)
+ * * inv_height)) (:407-408): mag = sqrt(x x + y y), then two divisions. A current coordinate must be
+ * finite and at most one image size outside the image, as in the stereo block: that bounds the walk.
+ * Matching. With fast_matching, matchGrid as plba_grid_match defines it, window (ws, ws, ws, ws), ratio
+ * min_ratio_12_p for points and lines alike (matching.cpp:160, :241). Without it the grid count is 0.
+ * The brute-force fallback (:277-281, :424-429) replaces a problem's matches when n2 > min and n1 > min
+ * and grid count < min, min = min_pt_matches or min_ls_matches; it is match() as plba_desc_match defines
+ * it with the ratio (float)min_ratio_12_p or (float)min_ratio_12_l. The fallback's result stands alone:
+ * the reference's match() resizes matches_12 without clearing it, so a grid match that the brute-force
+ * ratio test does not replace can survive there; here it does not. The decision is taken on the device.
+ * Point record [9], for a row with a match i1 -> i2 (:299-318, :339-341): P3d = T_prev.R P1 + T_prev.t;
+ * dir_prev = P3d / |P3d|; dir_curr = Pc / |Pc| with Pc = T_curr.R P2 + T_curr.t, each component divided.
+ * Line record [8] (:450-494, :546-562). TransformForPluker(T, (N, D)) (include/mapHandler.h:232-240) is
+ * head = (R_i . N) + (M_i . D), tail = R_i . D, with column j of M the cross product t x R_col_j and the
+ * structural zeros of the 6 x 6 skipped. For a row with ls_new (the feature's idx is -1): L =
+ * TransformForPluker(T_prev, NDc), d = |L.head| / |L.tail|, new_pluker_lw = ((L.head_i / |L.head|) * d,
+ * L.tail_i / |L.tail|). The error of a world line W seen from Tcw against the image segment (s, e):
+ * h = head of TransformForPluker(Tcw, W); lx = fy * h0, ly = fx * h1, lz = (-fy * cx) h0 + ((-fx * cy) h1
+ * + (fx * fy) h2) (getPlukerK, src2/pinholeStereoCamera.cpp:123-125); f = sqrt(lx lx + ly ly); e0 = ((s0 lx
+ * + s1 ly) + lz) / f, e1 the same with e; the norm sqrt(e0 e0 + e1 e1). err_prev (new rows only) is that
+ * of new_pluker_lw from Tcw_prev against the previous row's (spl, epl); err_curr against the current
+ * row's, of new_pluker_lw from Tcw_curr for a new row, of ls_lm_NDw for a row that carries a landmark.
+ * ls_rejected = err_curr > sqrt(5.991) (:489, :557); NaN compares false. The record is new_pluker_lw[6],
+ * err_prev, err_curr; what a row does not compute is 0, and a row without a match has a zero record.
+ * Tcw_prev / Tcw_curr are the caller's T.inverse() (Eigen's general inverse): the device does not invert.
+ * Arithmetic: doubles, only + - * / sqrt, one rounding per operation, as in the stereo block. */
+typedef struct plba_kfassoc_params {
+    int32_t cols, rows;                 /* GRID_COLS 64, GRID_ROWS 48                            */
+    int32_t width, height;              /* the image size, > 0                                   */
+    int32_t fast_matching;              /* SlamConfig::fastMatching(): 1 as the shipped yaml has */
+    int32_t ws;                         /* Config::matchingF2FWs()     3 (src2/config.cpp:92)  */
+    int32_t best_lr;                    /* Config::bestLRMatches()       1 (src2/config.cpp:51)  */
+    int32_t min_pt_matches;             /* SlamConfig::minPointMatches() 10                      */
+    int32_t min_ls_matches;             /* SlamConfig::minLineMatches()   6                      */
+    int32_t line_query_in_grid_units;   /* 0: the reference's pixel-unit line query (:395-396)   */
+    double  min_ratio_12_p;             /* Config::minRatio12P()       0.9 (:60)                 */
+    double  min_ratio_12_l;             /* Config::minRatio12L()       0.9 (:68)                 */
+    double  line_sim_th;                /* Config::lineSimTh()        0.75 (:63)                 */
+    double  fx, fy, cx, cy;             /* PinholeStereoCamera                                   */
+} plba_kfassoc_params;
+typedef struct plba_kfassoc_batch {     /* n keyframe pairs, concatenated; _p previous, _c current */
+    int32_t n;
+    int32_t desc_bytes;                 /* as in plba_match_batch                                */
+    const int32_t *pt_off_p, *pt_off_c; /* [n+1] point rows of pair f: [off[f], off[f+1])        */
+    const int32_t *ls_off_p, *ls_off_c; /* [n+1] line rows                                       */
+    const double  *DT;                  /* [n][12] 3 x 4, row-major                              */
+    const double  *T_prev, *T_curr;     /* [n][16] T_kf_w of the two keyframes, row-major        */
+    const double  *Tcw_prev, *Tcw_curr; /* [n][16] their inverses                                */
+    const double  *pt_P_p;              /* [.][3]                                                */
+    const uint8_t *pdesc_p;             /* [.][desc_bytes]                                       */
+    const double  *ls_sP_p, *ls_eP_p;   /* [.][3]                                                */
+    const double  *ls_NDc_p;            /* [.][6]                                                */
+    const double  *ls_spl_p, *ls_epl_p; /* [.][2]                                                */
+    const uint8_t *ldesc_p;
+    const double  *ls_lm_NDw;           /* [.][6] the map line's NDw where ls_new is 0, else 0   */
+    const uint8_t *ls_new;              /* [.] 1 where the feature's idx is -1                   */
+    const double  *pt_pl_c;             /* [.][2]                                                */
+    const double  *pt_P_c;              /* [.][3]                                                */
+    const uint8_t *pdesc_c;
+    const double  *ls_spl_c, *ls_epl_c; /* [.][2]                                                */
+    const uint8_t *ldesc_c;
+} plba_kfassoc_batch;
+/* Indexed by previous row, not compacted: the sequential part needs them in row order. n_grid,
+ * n_matches and fallback are required; any other array may be NULL and is then skipped. */
+typedef struct plba_kfassoc_out {
+    int32_t *n_grid, *n_matches, *fallback; /* [2n] per problem: 2 f points, 2 f + 1 lines       */
+    int32_t *pt_m12;                    /* [pt_off_p[n]] the current row, local to the pair, or -1 */
+    int32_t *ls_m12;                    /* [ls_off_p[n]]                                         */
+    double  *pt_rec;                    /* [.][9] P3d, dir_prev, dir_curr                        */
+    double  *ls_rec;                    /* [.][8] new_pluker_lw, |err_prev|, |err_curr|          */
+    uint8_t *ls_rejected;               /* [.]                                                   */
+} plba_kfassoc_out;
+/* src/slamConfig.cpp and src2/config.cpp, fast_matching as the shipped configuration files have it;
+ * width, height and the camera are zero and must be set. */
+void plba_kfassoc_default_params(plba_kfassoc_params *p);
+/* Runs on the context's stream in a fixed number of launches (the cells, the matcher's three, the
+ * brute-force matcher's two, which return at once where a problem does not fall back, and the geometry)
+ * with one upload and one read-back; needs no uploaded window and leaves one intact; shares
+ * plba_desc_match's device block and pinned host image. PLBA_E_INVALID, checked on the host before
+ * anything is launched, for a NULL batch, params, out, n_grid, n_matches, fallback or offset array, a
+ * NULL input array where rows exist, n < 0, decreasing or negative offsets, a bad desc_bytes, cols, rows,
+ * width or height <= 0, ws < 0 or ws >= 2^30, more than 65535 current rows in a problem, a DT, T or Tcw
+ * that is not finite, or a current coordinate that is not finite or outside the bound above; n == 0 does
+ * nothing and returns PLBA_OK. */
+int plba_kf_associate(plba_ctx *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *p,
+                      const plba_kfassoc_out *out);
+
 /* ---- Place recognition, the step of loopClosure() that decides whether to look for a loop at all:
  *   DBoW2 TemplatedVocabulary<FORB>::transform(features, v)   (TemplatedVocabulary.h:1046-1084, :1198-1239)
  *   BowVector::addWeight / normalize(L1)                       (BowVector.cpp:34-84)

@@ -420,6 +420,49 @@ int plslam_set_stereo_fn(plslam_map *m, plslam_stereo_fn fn, void *user);
 /* tools/stereo_bench.py and the tests only, not a product path: a single-threaded restatement of
  * plba_stereo_associate's semantics on the CPU, with the hook's signature. */
 int plslam_stereo_cpu(void *user, const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
+/* ---- MapHandler::matchKF2KFPoints + matchKF2KFLines (src/mapHandler.cpp:237-366, :368-590, the
+ * USE_LINE_PLUKER branch), the only place where map landmarks are created, between two keyframes that have
+ * their features (plslam_set_keyframe_stereo with params.pluker, or plslam_set_keyframe_features +
+ * plslam_set_keyframe_line_endpoints + plslam_set_keyframe_line_pluker). One plba_kf_associate call (or the
+ * hook) with the one pair, then the rows of the previous keyframe in order as :283-363 and :434-589 walk them.
+ * New landmark (the previous feature's idx is -1): its index is the size of the map's point / line list (the
+ * reference's max_pt_idx / max_ls_idx always equal it); both features get it; the landmark is built from the
+ * previous keyframe's observation, listed under that keyframe in map_points_kf_idx / map_lines_kf_idx, given
+ * the current keyframe's observation (sigma2 1), and full_graph is bumped both ways. Existing landmark: a
+ * deleted (NULL) one skips the row; otherwise the current feature takes the idx, the landmark the observation,
+ * and full_graph is bumped against every earlier observer. Rejected line (|error2| > sqrt(5.991)): both idx
+ * become -1 for a new landmark, the current one for an existing. Two previous rows matching one current row
+ * (without best_lr) both go through, and the later one overwrites the idx, as in the reference.
+ * DT: 4 x 4 row-major, NULL = expmap(logmap(inverse(T_curr) * T_prev)) (:143-145). params NULL = the defaults;
+ * params->width == 0 and height == 0: the image size and the camera of plslam_set_camera. The pose refinement
+ * of :937-977 (has_refinement, default false) is not part of it: the accepted pairs are returned for a caller
+ * that runs its own. Anything invalid returns PLBA_E_INVALID before the map is touched. */
+typedef struct plslam_kfmatch_stats {
+    int32_t grid_matches[2], fallback[2], matches[2];   /* [points, lines]                                  */
+    int32_t created[2], extended[2], rejected[2];
+    int32_t n_pairs[2];                     /* accepted rows: created + extended                            */
+    int32_t pt_cap, ls_cap;                 /* in: the pairs that pt_pairs / ls_pairs hold                  */
+    int32_t *pt_pairs, *ls_pairs;           /* in: [cap][2] or NULL; out: the first min(n, cap) accepted
+                                               (i1, i2) in row order (matched_pt / matched_ls)              */
+    double  match_ms;
+} plslam_kfmatch_stats;
+int plslam_match_kf_to_kf(plslam_map *m, int32_t kf_prev_idx, int32_t kf_curr_idx, const double *DT,
+                          const plba_kfassoc_params *params, plslam_kfmatch_stats *stats);
+/* lookForCommonMatches (:923-990) without the refinement block: plslam_match_kf_to_kf with DT NULL, then
+ * plslam_match_map_to_kf of the current keyframe with Twf NULL. */
+int plslam_look_for_common_matches(plslam_map *m, int32_t kf_prev_idx, int32_t kf_curr_idx,
+                                   const plba_kfassoc_params *kf_params, const plslam_mapmatch_params *map_params,
+                                   plslam_kfmatch_stats *kf_stats, plslam_mapmatch_stats *map_stats);
+/* NDc [n_ls][6] of keyframe kf_idx's line features, for callers on the plslam_set_keyframe_features route
+ * (plslam_set_keyframe_stereo stores it with params.pluker). */
+int plslam_set_keyframe_line_pluker(plslam_map *m, int32_t kf_idx, const double *NDc);
+/* Association hook, in the style of plslam_set_stereo_fn: NULL = plba_kf_associate. */
+typedef int (*plslam_kfassoc_fn)(void *user, const plba_kfassoc_batch *b, const plba_kfassoc_params *p,
+                                 const plba_kfassoc_out *out);
+int plslam_set_kfassoc_fn(plslam_map *m, plslam_kfassoc_fn fn, void *user);
+/* tools/kfassoc_bench.py and the tests only, not a product path: a single-threaded restatement of
+ * plba_kf_associate's semantics (matchKF2KFPoints / Lines up to the sequential part) on the CPU. */
+int plslam_kf_assoc_cpu(void *user, const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out);
 int plslam_get_lc_state(plslam_map *m, int32_t *state);
 /* lc_pose_list [n][6]; the kept index rows of loop `loop` (kind 1 points, 2 lines), [n][4] */
 int plslam_get_lc_pose_list(plslam_map *m, double *out, int32_t cap, int32_t *n);

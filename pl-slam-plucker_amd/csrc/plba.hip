@@ -2463,6 +2463,27 @@ int plba_stereo_associate(plba_ctx *ctx, const plba_stereo_batch *b, const plba_
     return ctx ? stereo_associate(ctx, b, p, out) : PLBA_E_INVALID;
 }
 
+// keyframe-to-keyframe association (csrc/plba_assoc.hip, csrc/plba_kfassoc.hpp)
+void plba_kfassoc_default_params(plba_kfassoc_params *p) {
+    if (!p) return;
+    *p = plba_kfassoc_params{};
+    p->cols = 64;                  // GRID_COLS / GRID_ROWS (include2/stereoFrame.h:51-52)
+    p->rows = 48;
+    p->fast_matching = 1;          // config/config/config.yaml:5 (src/slamConfig.cpp:43 has false)
+    p->ws = 3;                     // src2/config.cpp:92
+    p->best_lr = 1;                // :51
+    p->min_pt_matches = 10;        // src/slamConfig.cpp:51-52
+    p->min_ls_matches = 6;
+    p->min_ratio_12_p = 0.9;       // src2/config.cpp:60
+    p->min_ratio_12_l = 0.9;       // :68
+    p->line_sim_th = 0.75;         // :63
+}
+
+int plba_kf_associate(plba_ctx *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *p,
+                      const plba_kfassoc_out *out) {
+    return ctx ? kf_associate(ctx, b, p, out) : PLBA_E_INVALID;
+}
+
 // place recognition (csrc/plba_assoc.hip, csrc/plba_bow.hpp)
 int plba_bow_set_vocab(plba_ctx *ctx, int32_t slot, const plba_bow_vocab *v) {
     return ctx ? bow_set_vocab(ctx, slot, v) : PLBA_E_INVALID;

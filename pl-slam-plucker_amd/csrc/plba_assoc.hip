@@ -1,5 +1,5 @@
 // plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose,
-// the two descriptor matchers, the stereo association and place recognition. They share nothing
+// the two descriptor matchers, the stereo and the keyframe association and place recognition. They share nothing
 // with the solver (no Dev, no step graph, no window arena), so they are a translation unit of their
 // own: an edit to a matcher does not rebuild the factorisation kernels. Each call is one upload, its
 // kernels and one read-back through a ScratchBlock. A Staged (csrc/plba_layout.hpp) lays the block
@@ -17,6 +17,7 @@
 #include "plba_match.hpp"
 #include "plba_gridmatch.hpp"
 #include "plba_stereo.hpp"
+#include "plba_kfassoc.hpp"
 #include "plba_bow.hpp"
 #include "plba_scratch.hpp"
 
@@ -500,6 +501,259 @@ int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo
             cols_out(out->ls_eP, lsd, kStLsDoubles, 9, 3);
             cols_out(out->ls_le, lsd, kStLsDoubles, 12, 3);
             if (prm.pluker) cols_out(out->ls_NDc, lsd, kStLsDoubles, 15, 6);
+        }
+    }
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- keyframe-to-keyframe association
+// MapHandler::matchKF2KFPoints / matchKF2KFLines (src/mapHandler.cpp:237-366, :368-590) up to the
+// sequential part, for a batch of keyframe pairs: one upload, k_kf_cells, the grid matcher's three
+// launches with the window (ws, ws, ws, ws), the brute-force matcher's two, gated per problem on the
+// device by the grid count, k_kf_geom (csrc/plba_kfassoc.hpp), one read-back. Pair f is the matcher's
+// problems 2 f (points) and 2 f + 1 (lines).
+int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *pp, const plba_kfassoc_out *out) {
+    const char *const op = "keyframe association";
+    if (!b || b->n < 0) {
+        ctx->set_error("keyframe association: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    const int n = b->n;
+    if (n == 0) return PLBA_OK;
+    if (n > (INT32_MAX - 1) / 2) {
+        ctx->set_error("keyframe association: %d pairs", n);
+        return PLBA_E_INVALID;
+    }
+    if (const int rc = check_desc_bytes(ctx, op, b->desc_bytes)) return rc;
+    if (!pp || !out || !out->n_grid || !out->n_matches || !out->fallback || !b->pt_off_p || !b->pt_off_c || !b->ls_off_p ||
+        !b->ls_off_c || !b->DT || !b->T_prev || !b->T_curr || !b->Tcw_prev || !b->Tcw_curr) {
+        ctx->set_error("keyframe association: NULL params / out / n_grid / n_matches / fallback / offsets / poses");
+        return PLBA_E_INVALID;
+    }
+    const plba_kfassoc_params &prm = *pp;
+    if (prm.cols <= 0 || prm.rows <= 0 || prm.width <= 0 || prm.height <= 0 || prm.ws < 0 || prm.ws >= (1 << 30)) {
+        ctx->set_error("keyframe association: a grid of %d x %d cells, an image of %d x %d or a window of %d", prm.cols,
+                       prm.rows, prm.width, prm.height, prm.ws);
+        return PLBA_E_INVALID;
+    }
+    for (const int32_t *off : {b->pt_off_p, b->pt_off_c, b->ls_off_p, b->ls_off_c})
+        if (const int rc = check_offsets(ctx, op, "row", "pair", off, n)) return rc;
+    // the rows of each side, counted from the first pair's offset
+    const int32_t *const offs[2][2] = {{b->pt_off_p, b->pt_off_c}, {b->ls_off_p, b->ls_off_c}};
+    size_t cnt[2][2];
+    for (int kd = 0; kd < 2; ++kd)
+        for (int sd = 0; sd < 2; ++sd) cnt[kd][sd] = (size_t)(offs[kd][sd][n] - offs[kd][sd][0]);
+    const size_t N1 = cnt[0][0] + cnt[1][0], N2 = cnt[0][1] + cnt[1][1], db = (size_t)b->desc_bytes, dw = db / 4;
+    const int stride = std::max(prm.cols, prm.rows);
+    const size_t nc = cnt[0][1] + cnt[1][1] * (size_t)stride;
+    if (N1 > (size_t)INT32_MAX || N2 > (size_t)INT32_MAX || nc > (size_t)INT32_MAX) {
+        ctx->set_error("keyframe association: %zu previous rows, %zu current rows or %zu cells are more than %d", N1, N2, nc,
+                       INT32_MAX);
+        return PLBA_E_INVALID;
+    }
+    if ((cnt[0][0] && (!b->pt_P_p || !b->pdesc_p)) || (cnt[0][1] && (!b->pt_pl_c || !b->pt_P_c || !b->pdesc_c)) ||
+        (cnt[1][0] && (!b->ls_sP_p || !b->ls_eP_p || !b->ls_NDc_p || !b->ls_spl_p || !b->ls_epl_p || !b->ldesc_p ||
+                       !b->ls_lm_NDw || !b->ls_new)) ||
+        (cnt[1][1] && (!b->ls_spl_c || !b->ls_epl_c || !b->ldesc_c))) {
+        ctx->set_error("keyframe association: NULL feature or descriptor array");
+        return PLBA_E_INVALID;
+    }
+    int max_rows = 0, max_prev = 0, max_train = 0;
+    for (int f = 0; f < n; ++f)
+        for (int kd = 0; kd < 2; ++kd) {
+            const int r1 = offs[kd][0][f + 1] - offs[kd][0][f], r2 = offs[kd][1][f + 1] - offs[kd][1][f];
+            max_rows = std::max(max_rows, std::max(r1, r2));
+            max_prev = std::max(max_prev, r1);
+            max_train = std::max(max_train, r2);
+        }
+    if (max_train > kGmMaxTrain) {  // the low 16 bits of a key
+        ctx->set_error("keyframe association: %d current rows in a problem are more than %d", max_train, kGmMaxTrain);
+        return PLBA_E_INVALID;
+    }
+    const double *const poses[5] = {b->DT, b->T_prev, b->T_curr, b->Tcw_prev, b->Tcw_curr};
+    for (int k = 0; k < 5; ++k)
+        for (size_t e = 0; e < (size_t)n * (k ? 16 : 12); ++e)
+            if (!std::isfinite(poses[k][e])) {
+                ctx->set_error("keyframe association: %s of pair %zu is not finite",
+                               k == 0 ? "DT" : k == 1 ? "T_prev" : k == 2 ? "T_curr" : k == 3 ? "Tcw_prev" : "Tcw_curr",
+                               e / (k ? 16 : 12));
+                return PLBA_E_INVALID;
+            }
+    // a current coordinate at most one image size outside the image: the bound of a line's walk
+    const double *const ccoords[3] = {b->pt_pl_c, b->ls_spl_c, b->ls_epl_c};
+    for (int k = 0; k < 3; ++k) {
+        const int kd = k ? 1 : 0;
+        if (!cnt[kd][1]) continue;
+        const double *c = ccoords[k] + 2 * (size_t)offs[kd][1][0];
+        for (size_t e = 0; e < 2 * cnt[kd][1]; ++e) {
+            const double v = c[e], size = (e & 1) ? prm.height : prm.width;
+            if (!(v >= -size && v <= 2.0 * size)) {  // false for NaN
+                ctx->set_error("keyframe association: coordinate %g of current %s row %zu is not finite or outside [%g, %g]", v,
+                               kd ? "line" : "point", e / 2, -size, 2.0 * size);
+                return PLBA_E_INVALID;
+            }
+        }
+    }
+    (void)hipSetDevice(ctx->opts.device);
+    const int np = 2 * n;
+    const size_t P = (size_t)np;
+    // the arrays that several kernels use are bound in K and handed to the matchers' structs below; the
+    // inputs are all filled here, problem by problem
+    KfDev K{};
+    GmDev D{};
+    DmDev M{};
+    Staged B;
+    B.in(K.off1, P + 1);
+    B.in(K.off2, P + 1);
+    B.in(K.kind, P);
+    B.in(K.kbase1, P);
+    B.in(K.kbase2, P);
+    B.in(K.cbase, P + 1);
+    B.in(K.gate_min, P);
+    B.in(D.ws, 4 * P);
+    B.in(D.nnr, P);
+    B.in(D.sim_th, P);
+    B.in(M.nnr, P);
+    B.in(K.pose, (size_t)kKfPoseDoubles * n);
+    B.in(D.desc1, dw * N1);
+    B.in(D.desc2, dw * N2);
+    B.in(K.q_pt, 3 * cnt[0][0]);
+    B.in(K.q_ls, kKfQLsDoubles * cnt[1][0]);
+    B.in(K.ls_new, cnt[1][0]);
+    B.in(K.t_pt, kKfTPtDoubles * cnt[0][1]);
+    B.in(K.t_ls, kKfTLsDoubles * cnt[1][1]);
+    B.out(K.res, 3 * P);  // the outputs are scattered to the caller's arrays below
+    B.out(K.m12, N1);
+    B.out(K.ptd, kKfPtDoubles * cnt[0][0]);
+    B.out(K.lsd, kKfLsDoubles * cnt[1][0]);
+    B.out(K.rej, cnt[1][0]);
+    const size_t o_best = B.dev(D.best, N1);
+    B.dev(D.second, N1);
+    const size_t key_bytes = B.mark() - o_best;  // the two key arrays start as kGmNone
+    B.dev(D.m12, N1);
+    B.dev(D.m21, N2);
+    B.dev(D.count, P);
+    B.dev(K.cell1, 2 * N1);
+    B.dev(K.cell1e, 2 * N1);
+    B.dev(K.cell_off2, N2 + 1);
+    B.dev(K.cells2, 2 * nc);
+    B.dev(K.dir2, 2 * N2);
+    B.dev(M.nn12, N1);
+    B.dev(M.nn21, N2);
+    B.dev(M.m12, N1);
+    B.dev(M.count, P);
+    if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
+    B.stage(ctx->match.host, ctx->match.dev);
+    int32_t *off1 = B.host(K.off1), *off2 = B.host(K.off2), *kind = B.host(K.kind), *kbase1 = B.host(K.kbase1),
+            *kbase2 = B.host(K.kbase2), *cbase = B.host(K.cbase), *gate_min = B.host(K.gate_min), *ws = B.host(D.ws);
+    double *nnr = B.host(D.nnr), *sim_th = B.host(D.sim_th), *pose = B.host(K.pose);
+    float *fnnr = B.host(M.nnr);
+    uint8_t *const desc_h[2] = {(uint8_t *)B.host(D.desc1), (uint8_t *)B.host(D.desc2)};
+    const uint8_t *const descs[2][2] = {{b->pdesc_p, b->pdesc_c}, {b->ldesc_p, b->ldesc_c}};
+    for (int f = 0; f < n; ++f) {
+        double *q = pose + (size_t)kKfPoseDoubles * f;
+        memcpy(q, b->DT + 12 * (size_t)f, 12 * sizeof(double));
+        for (int k = 1; k < 5; ++k) memcpy(q + 12 + 16 * (k - 1), poses[k] + 16 * (size_t)f, 16 * sizeof(double));
+    }
+    off1[0] = off2[0] = cbase[0] = 0;
+    for (int p = 0; p < np; ++p) {
+        const int f = p / 2, kd = p % 2;
+        const int a1 = offs[kd][0][f], r1 = offs[kd][0][f + 1] - a1, a2 = offs[kd][1][f], r2 = offs[kd][1][f + 1] - a2;
+        const int min_matches = kd ? prm.min_ls_matches : prm.min_pt_matches;
+        kind[p] = kd;
+        kbase1[p] = a1 - offs[kd][0][0];
+        kbase2[p] = a2 - offs[kd][1][0];
+        off1[p + 1] = off1[p] + r1;
+        off2[p + 1] = off2[p] + r2;
+        cbase[p + 1] = cbase[p] + r2 * (kd ? stride : 1);
+        gate_min[p] = (r2 > min_matches && r1 > min_matches) ? min_matches : INT32_MIN;  // :277-279, :424-426
+        for (int e = 0; e < 4; ++e) ws[4 * p + e] = prm.ws;  // :269-272, :416-419
+        nnr[p] = prm.min_ratio_12_p;  // matching.cpp:160, :241: for lines too
+        sim_th[p] = prm.line_sim_th;
+        fnnr[p] = (float)(kd ? prm.min_ratio_12_l : prm.min_ratio_12_p);  // :280, :427
+        if (r1) memcpy(desc_h[0] + db * off1[p], descs[kd][0] + db * a1, db * r1);
+        if (r2) memcpy(desc_h[1] + db * off2[p], descs[kd][1] + db * a2, db * r2);
+    }
+    {  // the rows of each kind keep the caller's order from the first pair's offset
+        const size_t ap = (size_t)offs[0][0][0], al = (size_t)offs[1][0][0], cp = (size_t)offs[0][1][0], cl = (size_t)offs[1][1][0];
+        if (cnt[0][0]) memcpy(B.host(K.q_pt), b->pt_P_p + 3 * ap, 3 * cnt[0][0] * sizeof(double));
+        double *q = B.host(K.q_ls);
+        for (size_t i = 0; i < cnt[1][0]; ++i, q += kKfQLsDoubles) {
+            const size_t r = al + i;
+            memcpy(q, b->ls_sP_p + 3 * r, 3 * sizeof(double));
+            memcpy(q + 3, b->ls_eP_p + 3 * r, 3 * sizeof(double));
+            memcpy(q + 6, b->ls_NDc_p + 6 * r, 6 * sizeof(double));
+            memcpy(q + 12, b->ls_spl_p + 2 * r, 2 * sizeof(double));
+            memcpy(q + 14, b->ls_epl_p + 2 * r, 2 * sizeof(double));
+            memcpy(q + 16, b->ls_lm_NDw + 6 * r, 6 * sizeof(double));
+        }
+        if (cnt[1][0]) memcpy(B.host(K.ls_new), b->ls_new + al, cnt[1][0]);
+        double *t = B.host(K.t_pt);
+        for (size_t i = 0; i < cnt[0][1]; ++i, t += kKfTPtDoubles) {
+            memcpy(t, b->pt_pl_c + 2 * (cp + i), 2 * sizeof(double));
+            memcpy(t + 2, b->pt_P_c + 3 * (cp + i), 3 * sizeof(double));
+        }
+        t = B.host(K.t_ls);
+        for (size_t i = 0; i < cnt[1][1]; ++i, t += kKfTLsDoubles) {
+            memcpy(t, b->ls_spl_c + 2 * (cl + i), 2 * sizeof(double));
+            memcpy(t + 2, b->ls_epl_c + 2 * (cl + i), 2 * sizeof(double));
+        }
+    }
+    if (const int rc = upload(ctx, ctx->match, B)) return rc;
+    hipStream_t s = ctx->stream;
+    K.gm12 = D.m12; K.gcount = D.count; K.fm12 = M.m12; K.fcount = M.count;
+    K.inv_w = prm.cols / (double)prm.width;
+    K.inv_h = prm.rows / (double)prm.height;
+    K.stride = stride;
+    K.prm = prm;
+    D.off1 = K.off1; D.off2 = K.off2; D.kind = K.kind;
+    D.cell1 = K.cell1; D.cell1e = K.cell1e; D.cell_off2 = K.cell_off2; D.cells2 = K.cells2; D.dir2 = K.dir2;
+    M.off1 = K.off1; M.off2 = K.off2; M.desc1 = D.desc1; M.desc2 = D.desc2;
+    M.n = np;
+    M.dwords = b->desc_bytes / 4;
+    M.best_lr = prm.best_lr != 0;
+    M.gate_count = D.count;
+    M.gate_min = K.gate_min;
+    if (prm.fast_matching) {
+        if (const int rc = grid_prepare(ctx, D, np, b->desc_bytes, prm.cols, prm.rows, prm.best_lr, key_bytes)) return rc;
+        if (max_rows > 0) {  // a thread past its problem's rows does nothing
+            hipLaunchKernelGGL(k_kf_cells, dim3(np, (max_rows + kKfNT - 1) / kKfNT), dim3(kKfNT), 0, s, K);
+            PLBA_LAUNCHED(ctx, "k_kf_cells");
+        }
+        if (const int rc = grid_launch(ctx, D, max_train)) return rc;
+    } else {  // the grid count is 0 (:249)
+        PLBA_CHECK(hipMemsetAsync(D.count, 0, sizeof(int32_t) * P, s));
+    }
+    if (max_rows > 0) {  // a workgroup past its problem's rows in its direction, or of a problem that keeps its grid matches, returns at once
+        const dim3 grid(np, (max_rows + kDmNT - 1) / kDmNT, 2);
+        if (M.dwords <= 8) hipLaunchKernelGGL(k_desc_nn<8>, grid, dim3(kDmNT), 0, s, M);
+        else hipLaunchKernelGGL(k_desc_nn<16>, grid, dim3(kDmNT), 0, s, M);
+        PLBA_LAUNCHED(ctx, "k_desc_nn");
+    }
+    hipLaunchKernelGGL(k_desc_cross, dim3(np), dim3(kDmNT), 0, s, M); PLBA_LAUNCHED(ctx, "k_desc_cross");
+    hipLaunchKernelGGL(k_kf_geom, dim3(np, std::max(1, (max_prev + kKfNT - 1) / kKfNT)), dim3(kKfNT), 0, s, K);
+    PLBA_LAUNCHED(ctx, "k_kf_geom");
+    if (const int rc = read_back(ctx, ctx->match, B)) return rc;
+    const int32_t *res = B.host(K.res), *m12 = B.host(K.m12);
+    const double *ptd = B.host(K.ptd), *lsd = B.host(K.lsd);
+    const uint8_t *rej = B.host(K.rej);
+    for (int p = 0; p < np; ++p) {
+        const int f = p / 2, kd = p % 2, a1 = offs[kd][0][f], r1 = off1[p + 1] - off1[p];
+        if (res[3 * p + 1] < 0 || res[3 * p + 1] > r1) {
+            ctx->set_error("keyframe association: the device returned %d matches for %d rows", res[3 * p + 1], r1);
+            return PLBA_E_DEVICE;
+        }
+        out->n_grid[p] = res[3 * p];
+        out->n_matches[p] = res[3 * p + 1];
+        out->fallback[p] = res[3 * p + 2];
+        if (!r1) continue;
+        int32_t *om = kd ? out->ls_m12 : out->pt_m12;
+        if (om) memcpy(om + a1, m12 + off1[p], sizeof(int32_t) * r1);
+        if (!kd) {
+            if (out->pt_rec) memcpy(out->pt_rec + (size_t)kKfPtDoubles * a1, ptd + (size_t)kKfPtDoubles * kbase1[p], sizeof(double) * kKfPtDoubles * r1);
+        } else {
+            if (out->ls_rec) memcpy(out->ls_rec + (size_t)kKfLsDoubles * a1, lsd + (size_t)kKfLsDoubles * kbase1[p], sizeof(double) * kKfLsDoubles * r1);
+            if (out->ls_rejected) memcpy(out->ls_rejected + a1, rej + kbase1[p], r1);
         }
     }
     return PLBA_OK;

@@ -19,6 +19,8 @@
 //                 per thread, then over the wave and over the four waves in a fixed order.
 // Every element is written by the one thread that owns its index, with ordinary vector stores, so
 // the result does not depend on the launch geometry.
+// plba_kf_associate launches both kernels over every problem with a gate (DmDev::gate_count): a
+// workgroup of a problem that does not fall back returns at once and writes nothing.
 // Defined where the reference is not: fewer than 2 train rows give no match in that direction (the
 // reference reads matches_[idx][1] out of range).
 #pragma once
@@ -40,7 +42,14 @@ struct DmDev {
     int32_t *m12;                 // [off1[n]] matches_12
     int32_t *count;               // [n]
     int32_t n, dwords, best_lr;
+    // plba_kf_associate's fallback: a pair runs only if gate_count[pair] < gate_min[pair]; NULL: every pair
+    const int32_t *gate_count, *gate_min;
 };
+
+// uniform over the workgroup: the pair is switched off by its gate
+__device__ inline bool dm_gated_off(const DmDev &D, int pair) {
+    return D.gate_count && !(D.gate_count[pair] < D.gate_min[pair]);
+}
 
 // W: dwords of a row in registers and in LDS (8 or 16), dwords <= W
 template <int W>
@@ -51,7 +60,7 @@ __global__ __launch_bounds__(kDmNT) void k_desc_nn(DmDev D) {
     const int q0 = qoff[pair], nq = qoff[pair + 1] - q0;
     const int t0 = toff[pair], nt = toff[pair + 1] - t0;
     const int row = blockIdx.y * kDmNT + tid;
-    if ((int)blockIdx.y * kDmNT >= nq) return;  // the whole workgroup, before any barrier
+    if ((int)blockIdx.y * kDmNT >= nq || dm_gated_off(D, pair)) return;  // the whole workgroup, before any barrier
     const int dw = D.dwords;
     const uint32_t *qd = dir ? D.desc2 : D.desc1, *td = dir ? D.desc1 : D.desc2;
     const bool owner = row < nq;
@@ -118,6 +127,7 @@ __global__ __launch_bounds__(kDmNT) void k_desc_nn(DmDev D) {
 __global__ __launch_bounds__(kDmNT) void k_desc_cross(DmDev D) {
     __shared__ int wsum[kDmNT / 64];
     const int pair = blockIdx.x, tid = threadIdx.x;
+    if (dm_gated_off(D, pair)) return;  // the whole workgroup, before the barrier
     const int o1 = D.off1[pair], n1 = D.off1[pair + 1] - o1, o2 = D.off2[pair];
     int cnt = 0;
     for (int i1 = tid; i1 < n1; i1 += kDmNT) {

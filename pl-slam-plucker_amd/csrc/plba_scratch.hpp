@@ -133,6 +133,7 @@ int desc_match(CtxBase *ctx, const plba_match_batch *b, int32_t *matches_12, int
 int grid_match(CtxBase *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
 int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp,
                      const plba_stereo_out *out);
+int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *pp, const plba_kfassoc_out *out);
 // and of plba_bow_set_vocab / _insert / _remove / _get
 int bow_set_vocab(CtxBase *ctx, int slot, const plba_bow_vocab *v);
 int bow_insert(CtxBase *ctx, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,

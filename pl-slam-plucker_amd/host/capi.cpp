@@ -625,6 +625,78 @@ int plslam_stereo_cpu(void *user, const plba_stereo_batch *b, const plba_stereo_
     return stereoCpu(b, p, out);
 }
 
+int plslam_set_keyframe_line_pluker(plslam_map *m, int32_t kf_idx, const double *NDc) {
+    if (!m || !slot_ok(m->mh.map_keyframes, kf_idx)) return PLBA_E_INVALID;
+    StereoFrame &f = m->mh.map_keyframes[kf_idx]->stereo_frame;
+    const size_t nl = f.stereo_ls_idx.size();
+    if (nl && !NDc) return PLBA_E_INVALID;
+    f.ls_NDc.assign(NDc, NDc + (nl ? 6 * nl : 0));
+    f.has_pluker = true;
+    return PLBA_OK;
+}
+
+namespace {
+void export_kfmatch_stats(const KfMatchStats &s, plslam_kfmatch_stats *o) {
+    if (!o) return;
+    for (int k = 0; k < 2; ++k) {
+        o->grid_matches[k] = s.grid_matches[k]; o->fallback[k] = s.fallback[k]; o->matches[k] = s.matches[k];
+        o->created[k] = s.created[k]; o->extended[k] = s.extended[k]; o->rejected[k] = s.rejected[k];
+    }
+    o->n_pairs[0] = (int32_t)s.pt_pairs.size();
+    o->n_pairs[1] = (int32_t)s.ls_pairs.size();
+    for (int i = 0; o->pt_pairs && i < o->pt_cap && i < o->n_pairs[0]; ++i) {
+        o->pt_pairs[2 * i] = s.pt_pairs[i][0];
+        o->pt_pairs[2 * i + 1] = s.pt_pairs[i][1];
+    }
+    for (int i = 0; o->ls_pairs && i < o->ls_cap && i < o->n_pairs[1]; ++i) {
+        o->ls_pairs[2 * i] = s.ls_pairs[i][0];
+        o->ls_pairs[2 * i + 1] = s.ls_pairs[i][1];
+    }
+    o->match_ms = s.match_ms;
+}
+plba_kfassoc_params kfassoc_params(const plba_kfassoc_params *p) {
+    plba_kfassoc_params d;
+    plba_kfassoc_default_params(&d);
+    return p ? *p : d;
+}
+}  // namespace
+
+int plslam_match_kf_to_kf(plslam_map *m, int32_t kf_prev_idx, int32_t kf_curr_idx, const double *DT,
+                          const plba_kfassoc_params *params, plslam_kfmatch_stats *stats) {
+    if (!m) return PLBA_E_INVALID;
+    Mat4 T;
+    if (DT) std::memcpy(T.data(), DT, sizeof(double) * 16);
+    KfMatchStats st;
+    const int rc = m->mh.matchKfToKf(kf_prev_idx, kf_curr_idx, DT ? &T : nullptr, kfassoc_params(params), &st);
+    if (rc) return rc;
+    export_kfmatch_stats(st, stats);
+    return PLBA_OK;
+}
+
+int plslam_look_for_common_matches(plslam_map *m, int32_t kf_prev_idx, int32_t kf_curr_idx,
+                                   const plba_kfassoc_params *kf_params, const plslam_mapmatch_params *map_params,
+                                   plslam_kfmatch_stats *kf_stats, plslam_mapmatch_stats *map_stats) {
+    if (!m) return PLBA_E_INVALID;
+    KfMatchStats ks;
+    MapMatchStats ms;
+    const int rc = m->mh.lookForCommonMatches(kf_prev_idx, kf_curr_idx, kfassoc_params(kf_params), mapmatch_params(map_params), &ks, &ms);
+    if (rc) return rc;
+    export_kfmatch_stats(ks, kf_stats);
+    export_mapmatch_stats(ms, map_stats);
+    return PLBA_OK;
+}
+
+int plslam_set_kfassoc_fn(plslam_map *m, plslam_kfassoc_fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    m->mh.setKfAssocFn(fn, user);
+    return PLBA_OK;
+}
+
+int plslam_kf_assoc_cpu(void *user, const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out) {
+    (void)user;
+    return kfAssocCpu(b, p, out);
+}
+
 int plslam_get_lc_state(plslam_map *m, int32_t *state) {
     if (!m || !state) return PLBA_E_INVALID;
     *state = m->mh.lc_state;

@@ -70,6 +70,9 @@ struct StereoFrame {
     // what matchMap2KFLines reads besides (src/mapHandler.cpp:857-861, :903): the image endpoints
     bool has_endpoints = false;
     std::vector<double> ls_spl, ls_epl;       // [n_ls][2]
+    // what matchKF2KFLines reads besides (src/mapHandler.cpp:451): the Plücker line in the camera frame
+    bool has_pluker = false;
+    std::vector<double> ls_NDc;               // [n_ls][6]
 };
 
 // include/keyFrame.h:50-71
@@ -280,6 +283,16 @@ struct StereoStats {
 };
 using StereoFn = int (*)(void *user, const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
 
+// What matchKfToKf reports, per kind [points, lines]; pt_pairs / ls_pairs are the accepted (i1, i2) in row
+// order, the reference's matched_pt / matched_ls for a caller that runs its own refinement.
+struct KfMatchStats {
+    int grid_matches[2] = {0, 0}, fallback[2] = {0, 0}, matches[2] = {0, 0};
+    int created[2] = {0, 0}, extended[2] = {0, 0}, rejected[2] = {0, 0};
+    double match_ms = 0;
+    std::vector<std::array<int, 2>> pt_pairs, ls_pairs;
+};
+using KfAssocFn = int (*)(void *user, const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out);
+
 struct CullStats {
     int points_removed = 0, lines_removed = 0;
 };
@@ -388,6 +401,22 @@ class MapHandler {
     int setKeyframeStereo(int kf_idx, const StereoInput &in, const plba_stereo_params &prm, int32_t *pt_src, int32_t *ls_src,
                           StereoStats *stats = nullptr);
     void setStereoFn(StereoFn fn, void *user) { stereo_fn_ = fn; stereo_user_ = user; }
+    // kf_match.cpp. matchKF2KFPoints + matchKF2KFLines (src/mapHandler.cpp:237-366, :368-590, the
+    // USE_LINE_PLUKER branch) between two keyframes with features: one plba_kf_associate call (or the hook),
+    // then the rows in order as :283-363 and :434-589 walk them: a new landmark takes the index
+    // map_points.size() / map_lines.size() (the reference's max_pt_idx / max_ls_idx always equal it, :67-68,
+    // :320-321, :519-520), is built by the constructors and adopted by the registry, pushed to
+    // map_*_kf_idx of the previous keyframe, and full_graph is bumped both ways; an existing landmark gets
+    // the observation and full_graph against every earlier observer (a NULL landmark skips the row); a
+    // rejected line resets the idx (both for a new landmark, the current one for an existing). DT == nullptr:
+    // expmap(logmap(inverse(T_curr) * T_prev)) (:143-145). p.width == 0: the image size and the camera of
+    // setCamera. Anything invalid returns PLBA_E_INVALID before the map is touched. The pose refinement of
+    // :937-977 (has_refinement) is not part of it.
+    int matchKfToKf(int kf_prev_idx, int kf_curr_idx, const Mat4 *DT, const plba_kfassoc_params &p, KfMatchStats *stats = nullptr);
+    // matchKfToKf, then matchMapToKf of the current keyframe: lookForCommonMatches (:923-990) without the refinement
+    int lookForCommonMatches(int kf_prev_idx, int kf_curr_idx, const plba_kfassoc_params &kp, const MapMatchParams &mp,
+                             KfMatchStats *ks = nullptr, MapMatchStats *ms = nullptr);
+    void setKfAssocFn(KfAssocFn fn, void *user) { kfassoc_fn_ = fn; kfassoc_user_ = user; }
     void setCamera(double fx, double fy, double cx, double cy, int width, int height) {
         fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy; width_ = width; height_ = height;
     }
@@ -453,6 +482,8 @@ class MapHandler {
     void *grid_user_ = nullptr;
     StereoFn stereo_fn_ = nullptr;
     void *stereo_user_ = nullptr;
+    KfAssocFn kfassoc_fn_ = nullptr;
+    void *kfassoc_user_ = nullptr;
     BowFn bow_fn_ = nullptr;
     void *bow_user_ = nullptr;
     int bowCall(BowCall &c);                 // the hook, or plba_bow_* on the map's context
@@ -496,5 +527,7 @@ int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_
 int gridMatchCpuWin(const plba_gridmatch_batch *b, const int32_t *win, int32_t *matches_12, int32_t *n_matches);
 // stereo.cpp. tools/stereo_bench.py and the tests only: plba_stereo_associate's semantics, single-threaded, on the CPU
 int stereoCpu(const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
+// kf_match.cpp. tools/kfassoc_bench.py and the tests only: plba_kf_associate's semantics, single-threaded, on the CPU
+int kfAssocCpu(const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out);
 
 }  // namespace plslam

@@ -193,6 +193,9 @@ int MapHandler::setKeyframeStereo(int kf_idx, const StereoInput &in, const plba_
     f.ls_epl.assign(epl.begin(), epl.begin() + 2 * kl);
     f.has_features = true;
     f.has_endpoints = true;
+    f.has_pluker = prm.pluker != 0;
+    if (f.has_pluker) f.ls_NDc.assign(NDc.begin(), NDc.begin() + 6 * kl);
+    else f.ls_NDc.clear();
     if (pt_src) std::copy(psrc.begin(), psrc.begin() + kp, pt_src);
     if (ls_src) std::copy(lsrc.begin(), lsrc.begin() + kl, ls_src);
     if (stats) *stats = StereoStats{n_pt, n_ls, ms};

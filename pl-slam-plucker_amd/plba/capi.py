@@ -554,3 +554,112 @@ class StereoBatchView:
             r.update({k: self.o[k][b:b + kl].copy() for k in self.LS if pluker or k != "ls_NDc"})
             res.append(r)
         return res
+
+
+# ---- keyframe-to-keyframe association (plba_kfassoc_params / _batch / _out / plba_kf_associate)
+class PlbaKfassocParams(C.Structure):
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("fast_matching", C.c_int32), ("ws", C.c_int32), ("best_lr", C.c_int32), ("min_pt_matches", C.c_int32),
+                ("min_ls_matches", C.c_int32), ("line_query_in_grid_units", C.c_int32),
+                ("min_ratio_12_p", C.c_double), ("min_ratio_12_l", C.c_double), ("line_sim_th", C.c_double),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class PlbaKfassocBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("pt_off_p", _ip), ("pt_off_c", _ip), ("ls_off_p", _ip),
+                ("ls_off_c", _ip), ("DT", _dp), ("T_prev", _dp), ("T_curr", _dp), ("Tcw_prev", _dp), ("Tcw_curr", _dp),
+                ("pt_P_p", _dp), ("pdesc_p", _bp), ("ls_sP_p", _dp), ("ls_eP_p", _dp), ("ls_NDc_p", _dp),
+                ("ls_spl_p", _dp), ("ls_epl_p", _dp), ("ldesc_p", _bp), ("ls_lm_NDw", _dp), ("ls_new", _bp),
+                ("pt_pl_c", _dp), ("pt_P_c", _dp), ("pdesc_c", _bp), ("ls_spl_c", _dp), ("ls_epl_c", _dp),
+                ("ldesc_c", _bp)]
+
+
+class PlbaKfassocOut(C.Structure):
+    _fields_ = [("n_grid", _ip), ("n_matches", _ip), ("fallback", _ip), ("pt_m12", _ip), ("ls_m12", _ip),
+                ("pt_rec", _dp), ("ls_rec", _dp), ("ls_rejected", _bp)]
+
+
+def kfassoc_params(params=None) -> PlbaKfassocParams:
+    """PlbaKfassocParams from a dict: plba_kfassoc_default_params, then the dict's entries (width, height,
+    fx, fy, cx and cy have no default)."""
+    if isinstance(params, PlbaKfassocParams):
+        return params
+    from . import lib   # lib imports this module
+    p = PlbaKfassocParams()
+    lib.load().plba_kfassoc_default_params(C.byref(p))
+    for k, v in dict(params or {}).items():
+        if k not in dict(PlbaKfassocParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+class KfassocBatchView:
+    """Concatenates keyframe pairs into contiguous arrays, the PlbaKfassocBatch over them and the output
+    arrays of a call. A pair is a dict: DT [3][4], T_prev / T_curr / Tcw_prev / Tcw_curr [4][4]; of the previous
+    keyframe pt_P_p [n][3], pdesc_p, ls_sP_p, ls_eP_p [n][3], ls_NDc_p [n][6], ls_spl_p, ls_epl_p [n][2], ldesc_p,
+    ls_lm_NDw [n][6], ls_new [n] uint8; of the current one pt_pl_c [n][2], pt_P_c [n][3], pdesc_c, ls_spl_c,
+    ls_epl_c [n][2], ldesc_c. A missing feature key is an empty side."""
+
+    # key: (columns, dtype, the side's row-count key)
+    ROWS = (("pt_P_p", 3, "pt_p"), ("ls_sP_p", 3, "ls_p"), ("ls_eP_p", 3, "ls_p"), ("ls_NDc_p", 6, "ls_p"),
+            ("ls_spl_p", 2, "ls_p"), ("ls_epl_p", 2, "ls_p"), ("ls_lm_NDw", 6, "ls_p"), ("pt_pl_c", 2, "pt_c"),
+            ("pt_P_c", 3, "pt_c"), ("ls_spl_c", 2, "ls_c"), ("ls_epl_c", 2, "ls_c"))
+    DESC = (("pdesc_p", "pt_p"), ("ldesc_p", "ls_p"), ("pdesc_c", "pt_c"), ("ldesc_c", "ls_c"))
+    LEAD = {"pt_p": "pt_P_p", "ls_p": "ls_sP_p", "pt_c": "pt_pl_c", "ls_c": "ls_spl_c"}
+    POSES = (("DT", 12), ("T_prev", 16), ("T_curr", 16), ("Tcw_prev", 16), ("Tcw_curr", 16))
+
+    def __init__(self, pairs, desc_bytes=None):
+        pairs = list(pairs)
+        if desc_bytes is None:
+            desc_bytes = next((np.asarray(f[k]).shape[1] for f in pairs for k, _ in self.DESC
+                               if k in f and np.asarray(f[k]).ndim == 2 and np.asarray(f[k]).shape[1]), 32)
+        self.desc_bytes = db = int(desc_bytes)
+        self.n = n = len(pairs)
+        cnt = {s: [len(np.asarray(f.get(k, np.zeros((0, 1))))) for f in pairs] for s, k in self.LEAD.items()}
+        self.off = {}
+        for s, c in cnt.items():
+            self.off[s] = np.zeros(n + 1, np.int32)
+            self.off[s][1:] = np.cumsum(c, dtype=np.int64)
+        self.a = {}
+
+        def cat(key, per, dtype, side):
+            parts = [np.asarray(f.get(key, np.zeros((0, per))), dtype).reshape(-1, per) for f in pairs]
+            if [len(p) for p in parts] != cnt[side]:
+                raise ValueError(f"{key}: one row per feature")
+            return np.ascontiguousarray(np.concatenate(parts + [np.zeros((0, per), dtype)]))
+
+        for key, per, side in self.ROWS:
+            self.a[key] = cat(key, per, np.float64, side)
+        for key, side in self.DESC:
+            self.a[key] = cat(key, db, np.uint8, side)
+        self.a["ls_new"] = cat("ls_new", 1, np.uint8, "ls_p")
+        for key, per in self.POSES:
+            self.a[key] = np.ascontiguousarray(
+                np.concatenate([np.asarray(f[key], np.float64).reshape(1, per) for f in pairs] + [np.zeros((0, per))]))
+        kinds = {np.dtype(np.int32): _ip, np.dtype(np.float64): _dp, np.dtype(np.uint8): _bp}
+        self.struct = PlbaKfassocBatch(
+            n=n, desc_bytes=db, pt_off_p=_ptr(self.off["pt_p"], _ip), pt_off_c=_ptr(self.off["pt_c"], _ip),
+            ls_off_p=_ptr(self.off["ls_p"], _ip), ls_off_c=_ptr(self.off["ls_c"], _ip),
+            **{k: _ptr(v, kinds[v.dtype]) for k, v in self.a.items()})
+        npt, nls, P = max(int(self.off["pt_p"][-1]), 1), max(int(self.off["ls_p"][-1]), 1), max(2 * n, 1)
+        # every row is written: a fill that no result can equal shows one that was not
+        self.o = dict(n_grid=np.full(P, -7, np.int32), n_matches=np.full(P, -7, np.int32), fallback=np.full(P, -7, np.int32),
+                      pt_m12=np.full(npt, -7, np.int32), ls_m12=np.full(nls, -7, np.int32),
+                      pt_rec=np.full((npt, 9), np.nan), ls_rec=np.full((nls, 8), np.nan),
+                      ls_rejected=np.full(nls, 7, np.uint8))
+        self.out = PlbaKfassocOut(**{k: v.ctypes.data_as(kinds[v.dtype]) for k, v in self.o.items()})
+
+    def results(self) -> list:
+        """One dict per pair: n_grid, n_matches, fallback as (points, lines), and the previous rows' pt_m12,
+        pt_rec, ls_m12, ls_rec, ls_rejected, copied."""
+        res = []
+        for f in range(self.n):
+            a, b = self.off["pt_p"][f:f + 2]
+            c, d = self.off["ls_p"][f:f + 2]
+            r = {k: (int(self.o[k][2 * f]), int(self.o[k][2 * f + 1])) for k in ("n_grid", "n_matches", "fallback")}
+            r.update(pt_m12=self.o["pt_m12"][a:b].copy(), pt_rec=self.o["pt_rec"][a:b].copy(),
+                     ls_m12=self.o["ls_m12"][c:d].copy(), ls_rec=self.o["ls_rec"][c:d].copy(),
+                     ls_rejected=self.o["ls_rejected"][c:d].copy())
+            res.append(r)
+        return res

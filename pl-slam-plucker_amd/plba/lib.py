@@ -32,6 +32,7 @@ EXPORTED = [
     "plba_pgo_default_params", "plba_pgo_optimize",
     "plba_lcpose_default_params", "plba_lc_relative_pose",
     "plba_desc_match", "plba_grid_match", "plba_stereo_default_params", "plba_stereo_associate",
+    "plba_kfassoc_default_params", "plba_kf_associate",
     "plba_bow_set_vocab", "plba_bow_insert", "plba_bow_remove", "plba_bow_get",
 ]
 
@@ -102,6 +103,10 @@ def load(path: Optional[str] = None):
     L.plba_stereo_default_params.restype = None
     L.plba_stereo_associate.argtypes = [vp, C.POINTER(capi.PlbaStereoBatch), C.POINTER(capi.PlbaStereoParams),
                                         C.POINTER(capi.PlbaStereoOut)]
+    L.plba_kfassoc_default_params.argtypes = [C.POINTER(capi.PlbaKfassocParams)]
+    L.plba_kfassoc_default_params.restype = None
+    L.plba_kf_associate.argtypes = [vp, C.POINTER(capi.PlbaKfassocBatch), C.POINTER(capi.PlbaKfassocParams),
+                                    C.POINTER(capi.PlbaKfassocOut)]
     L.plba_bow_set_vocab.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaBowVocab)]
     L.plba_bow_insert.argtypes = [vp, C.c_int32, C.c_int32, bp, C.c_int32, dp, ip, C.c_int32, ip]
     L.plba_bow_remove.argtypes = [vp, C.c_int32, C.c_int32]
@@ -109,7 +114,7 @@ def load(path: Optional[str] = None):
     for name in EXPORTED:
         f = getattr(L, name)
         if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
-                        "plba_lcpose_default_params", "plba_stereo_default_params"):
+                        "plba_lcpose_default_params", "plba_stereo_default_params", "plba_kfassoc_default_params"):
             f.restype = C.c_int
     _lib = L
     return L
@@ -360,6 +365,19 @@ class Solver:
         self._check(self.L.plba_stereo_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
                     "plba_stereo_associate")
         return bv.results(bool(prm.pluker))
+
+    def kf_associate(self, pairs, params, desc_bytes=None) -> list:
+        """Keyframe-to-keyframe association (plba_kf_associate; MapHandler::matchKF2KFPoints / Lines,
+        src/mapHandler.cpp:237-590, up to the sequential part) of a batch of keyframe pairs
+        (capi.KfassocBatchView) in one call. params: a dict over plba_kfassoc_default_params with width,
+        height, fx, fy, cx, cy (or a capi.PlbaKfassocParams). One dict per pair, indexed by previous row:
+        n_grid, n_matches, fallback as (points, lines); pt_m12, pt_rec [.][9]; ls_m12, ls_rec [.][8],
+        ls_rejected. Needs no uploaded window and leaves one intact."""
+        bv = pairs if isinstance(pairs, capi.KfassocBatchView) else capi.KfassocBatchView(pairs, desc_bytes)
+        prm = capi.kfassoc_params(params)
+        self._check(self.L.plba_kf_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
+                    "plba_kf_associate")
+        return bv.results()
 
     def bow_set_vocab(self, slot: int, voc):
         """Uploads the vocabulary of a place-recognition slot (plba_bow_set_vocab; 0 points, 1 lines)

@@ -253,6 +253,20 @@ GRID_MATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaGridMatchBat
                             C.POINTER(C.c_int32))
 
 
+class PlslamKfMatchStats(C.Structure):
+    _fields_ = [("grid_matches", C.c_int32 * 2), ("fallback", C.c_int32 * 2), ("matches", C.c_int32 * 2),
+                ("created", C.c_int32 * 2), ("extended", C.c_int32 * 2), ("rejected", C.c_int32 * 2),
+                ("n_pairs", C.c_int32 * 2), ("pt_cap", C.c_int32), ("ls_cap", C.c_int32),
+                ("pt_pairs", C.POINTER(C.c_int32)), ("ls_pairs", C.POINTER(C.c_int32)), ("match_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: list(getattr(self, k)) for k in ("grid_matches", "fallback", "matches", "created", "extended", "rejected")}
+
+
+KFASSOC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaKfassocBatch), C.POINTER(capi.PlbaKfassocParams),
+                         C.POINTER(capi.PlbaKfassocOut))
+
+
 class PlslamMapMatchParams(C.Structure):
     _fields_ = [("fast_matching", C.c_int32), ("ws", C.c_int32), ("min_pt_matches", C.c_int32),
                 ("min_ls_matches", C.c_int32), ("best_lr", C.c_int32), ("has_points", C.c_int32),
@@ -321,7 +335,8 @@ HOST_EXPORTED = [
     "plslam_set_keyframe_features", "plslam_set_match_fn", "plslam_loop_closure_step_kf",
     "plslam_verify_loop_candidates", "plslam_desc_match_cpu",
     "plslam_line_cells", "plslam_grid_match_cpu",
-    "plslam_set_keyframe_stereo", "plslam_set_stereo_fn", "plslam_stereo_cpu",
+    "plslam_set_keyframe_stereo", "plslam_set_stereo_fn", "plslam_stereo_cpu", "plslam_kf_assoc_cpu",
+    "plslam_match_kf_to_kf", "plslam_look_for_common_matches", "plslam_set_keyframe_line_pluker", "plslam_set_kfassoc_fn",
     "plslam_set_keyframe_line_endpoints", "plslam_set_camera", "plslam_set_grid_match_fn",
     "plslam_mapmatch_default_params", "plslam_match_map_to_kf", "plslam_local_mapping_step_kf",
     "plslam_set_bow_fn", "plslam_bow_cpu", "plslam_set_vocabulary", "plslam_remove_keyframe", "plslam_insert_kf_bow",
@@ -501,6 +516,15 @@ def load_host(path: Optional[str] = None):
     L.plslam_set_stereo_fn.argtypes = [vp, STEREO_FN, vp]
     L.plslam_stereo_cpu.argtypes = [vp, C.POINTER(capi.PlbaStereoBatch), C.POINTER(capi.PlbaStereoParams),
                                     C.POINTER(capi.PlbaStereoOut)]
+    L.plslam_match_kf_to_kf.argtypes = [vp, C.c_int32, C.c_int32, dp, C.POINTER(capi.PlbaKfassocParams),
+                                        C.POINTER(PlslamKfMatchStats)]
+    L.plslam_look_for_common_matches.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(capi.PlbaKfassocParams),
+                                                 C.POINTER(PlslamMapMatchParams), C.POINTER(PlslamKfMatchStats),
+                                                 C.POINTER(PlslamMapMatchStats)]
+    L.plslam_set_keyframe_line_pluker.argtypes = [vp, C.c_int32, dp]
+    L.plslam_set_kfassoc_fn.argtypes = [vp, KFASSOC_FN, vp]
+    L.plslam_kf_assoc_cpu.argtypes = [vp, C.POINTER(capi.PlbaKfassocBatch), C.POINTER(capi.PlbaKfassocParams),
+                                      C.POINTER(capi.PlbaKfassocOut)]
     L.plslam_set_keyframe_line_endpoints.argtypes = [vp, C.c_int32, dp, dp]
     L.plslam_set_camera.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32]
     L.plslam_set_grid_match_fn.argtypes = [vp, GRID_MATCH_FN, vp]
@@ -560,6 +584,16 @@ def grid_match_cpu(problems, cols: int = 64, rows: int = 48, best_lr: bool = Tru
     if rc != 0:
         raise PlbaError(f"plslam_grid_match_cpu failed: {rc}")
     return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+
+
+def kf_assoc_cpu(pairs, params, desc_bytes=None) -> list:
+    """plslam_kf_assoc_cpu on the pairs of Solver.kf_associate (tests and tools/kfassoc_bench.py)."""
+    bv = pairs if isinstance(pairs, capi.KfassocBatchView) else capi.KfassocBatchView(pairs, desc_bytes)
+    prm = capi.kfassoc_params(params)
+    rc = load_host().plslam_kf_assoc_cpu(None, C.byref(bv.struct), C.byref(prm), C.byref(bv.out))
+    if rc != 0:
+        raise PlbaError(f"plslam_kf_assoc_cpu failed: {rc}")
+    return bv.results()
 
 
 def stereo_cpu(frames, params, desc_bytes=None) -> list:
@@ -1056,6 +1090,71 @@ class HostMap:
                                                       lsrc.ctypes.data_as(ip), C.byref(st)), "set_keyframe_stereo")
         self._kf_feat[kf_idx] = (st.n_pt, st.n_ls)
         return dict(n_pt=st.n_pt, n_ls=st.n_ls, pt_src=psrc[:st.n_pt].copy(), ls_src=lsrc[:st.n_ls].copy(), ms=st.ms)
+
+    def set_keyframe_line_pluker(self, kf_idx: int, NDc):
+        """The Plücker lines NDc [n_ls][6] (camera frame) of keyframe ``kf_idx``'s line features."""
+        a = np.ascontiguousarray(np.asarray(NDc, np.float64).reshape(-1, 6))
+        if len(a) != self._kf_feat.get(kf_idx, (0, 0))[1]:
+            raise ValueError("one row per line feature")
+        self._check(self.L.plslam_set_keyframe_line_pluker(self.h, kf_idx, a.ctypes.data_as(C.POINTER(C.c_double))),
+                    "set_keyframe_line_pluker")
+
+    def set_kfassoc_fn(self, fn):
+        """fn(batch, params, out) -> int; "cpu" for plslam_kf_assoc_cpu; None for the MI355X backend
+        (plba_kf_associate)."""
+        if fn is None:
+            self._kcb = None
+            self._check(self.L.plslam_set_kfassoc_fn(self.h, C.cast(None, KFASSOC_FN), None), "set_kfassoc_fn")
+            return
+        if fn == "cpu":
+            self._kcb = C.cast(self.L.plslam_kf_assoc_cpu, KFASSOC_FN)
+        else:
+            def tramp(user, bp_, pp, op):
+                try:
+                    return int(fn(bp_.contents, pp.contents, op.contents))
+                except Exception:  # never unwind through C
+                    import traceback
+                    traceback.print_exc()
+                    return -1
+            self._kcb = KFASSOC_FN(tramp)
+        self._check(self.L.plslam_set_kfassoc_fn(self.h, self._kcb, None), "set_kfassoc_fn")
+
+    def _kfmatch_stats(self, kf_prev_idx: int):
+        n = self._kf_feat.get(kf_prev_idx, (0, 0))
+        pp, lp = np.full((n[0] + 1, 2), -1, np.int32), np.full((n[1] + 1, 2), -1, np.int32)
+        ip = C.POINTER(C.c_int32)
+        return PlslamKfMatchStats(pt_cap=n[0], ls_cap=n[1], pt_pairs=pp.ctypes.data_as(ip), ls_pairs=lp.ctypes.data_as(ip)), pp, lp
+
+    @staticmethod
+    def _kfmatch_dict(st, pp, lp):
+        d = st.as_dict()
+        d["pt_pairs"], d["ls_pairs"] = pp[:st.n_pairs[0]].tolist(), lp[:st.n_pairs[1]].tolist()
+        return d
+
+    def match_kf_to_kf(self, kf_prev_idx: int, kf_curr_idx: int, DT=None, params=None) -> dict:
+        """matchKF2KFPoints + matchKF2KFLines between two keyframes with features: new landmarks are created,
+        existing ones extended, rejected lines reset. ``DT`` (4, 4), None for expmap(logmap(inverse(T_curr) *
+        T_prev)); ``params``: a dict over plba_kfassoc_default_params (or a capi.PlbaKfassocParams); without
+        width / height the camera of set_camera is used. Returns the statistics with the accepted pairs."""
+        st, pp, lp = self._kfmatch_stats(kf_prev_idx)
+        T = None if DT is None else np.ascontiguousarray(np.asarray(DT, np.float64).reshape(16))
+        prm = capi.kfassoc_params(params)
+        self._check(self.L.plslam_match_kf_to_kf(
+            self.h, kf_prev_idx, kf_curr_idx, T.ctypes.data_as(C.POINTER(C.c_double)) if T is not None else None,
+            C.byref(prm), C.byref(st)), "match_kf_to_kf")
+        return self._kfmatch_dict(st, pp, lp)
+
+    def look_for_common_matches(self, kf_prev_idx: int, kf_curr_idx: int, kf_params=None,
+                                map_params: Optional[PlslamMapMatchParams] = None) -> dict:
+        """match_kf_to_kf (DT None), then match_map_to_kf of the current keyframe: lookForCommonMatches without
+        the pose refinement. Returns dict(kf=..., map=...) of both statistics."""
+        st, pp, lp = self._kfmatch_stats(kf_prev_idx)
+        ms = PlslamMapMatchStats()
+        prm = capi.kfassoc_params(kf_params)
+        self._check(self.L.plslam_look_for_common_matches(
+            self.h, kf_prev_idx, kf_curr_idx, C.byref(prm), C.byref(map_params) if map_params is not None else None,
+            C.byref(st), C.byref(ms)), "look_for_common_matches")
+        return dict(kf=self._kfmatch_dict(st, pp, lp), map=ms.as_dict())
 
     def set_camera(self, fx: float, fy: float, cx: float, cy: float, width: int, height: int):
         self._check(self.L.plslam_set_camera(self.h, fx, fy, cx, cy, width, height), "set_camera")
