@@ -272,7 +272,8 @@ typedef struct plba_pgo_graph {
 } plba_pgo_graph;
 
 typedef struct plba_pgo_params {
-    double  user_lambda_init; /* setUserLambdaInit: 1e-10 (:5085); <= 0: τ·max|H_ii|, τ = 1e-5   */
+    double  user_lambda_init; /* setUserLambdaInit: 1e-10 (:5085); <= 0: τ·max|H_ii|, τ = 1e-5
+                                 always (g2o's default; plba_opts::tau is the window solver's)   */
     int32_t max_iters;        /* optimize(SlamConfig::maxItersPGO()) — 100 (src/slamConfig.cpp:79) */
     int32_t initial_guess;    /* 1: computeInitialGuess() (the reference calls it)              */
     int32_t max_trials;       /* OptimizationAlgorithmLevenberg maxTrialsAfterFailure: 10        */

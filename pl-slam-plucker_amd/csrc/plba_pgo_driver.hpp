@@ -332,6 +332,10 @@ int pgo_fetch(CtxBase *ctx, const PgoDev &P) {
     return PLBA_OK;
 }
 
+// g2o's default τ: the reference makes a fresh OptimizationAlgorithmLevenberg for every pose graph,
+// so plba_opts::tau (the window solver's) does not reach it
+constexpr double kPgoTau = 1e-5;
+
 // computeActiveErrors() after the initial guess, then OptimizationAlgorithmLevenberg::solve per
 // iteration: three read-backs per trial decide the next launch
 int pgo_levenberg(CtxBase *ctx, const PgoProblem &pb, PgoDev &P, Dev &dd, plba_pgo_result *res) {
@@ -365,8 +369,8 @@ int pgo_levenberg(CtxBase *ctx, const PgoProblem &pb, PgoDev &P, Dev &dd, plba_p
         if (int rc = pgo_fetch(ctx, P)) return rc;
         currentChi = hout[0];
         const double chiStart = currentChi;
-        if (it == 0) {  // computeLambdaInit
-            lambda = prm.user_lambda_init > 0.0 ? prm.user_lambda_init : ctx->opts.tau * hout[2];
+        if (it == 0) {  // computeLambdaInit: the pose graph's own OptimizationAlgorithmLevenberg, τ = 1e-5
+            lambda = prm.user_lambda_init > 0.0 ? prm.user_lambda_init : kPgoTau * hout[2];
             ni = 2.0;
         }
         const double lambdaStart = lambda;
