@@ -413,6 +413,33 @@ typedef struct plba_match_batch {       /* B descriptor-set pairs, concatenated 
  * nothing and returns PLBA_OK. */
 int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
 
+/* ---- Median descriptor of a batch of descriptor lists: the descriptor half of
+ *   void MapPoint::updateAverageDescDir() / MapLine::updateAverageDescDir()  (src/mapFeatures.cpp:52-86, :140-174)
+ * which loopClosureFuseLandmarks (src/mapHandler.cpp:5636, :5784) runs after every observation it
+ * appends. For a list of n descriptors, row i of the symmetric n x n Hamming table (zero diagonal)
+ * has a k-th smallest value, k = min(int(1 + 0.5 (n - 1)), n - 1); medoid[.] is the first i whose
+ * value is strictly smaller than that of every earlier row (the start value 99999 is above any
+ * distance), as a position within the list. Integer work: the result is exact. The k-th smallest
+ * value is found by counting, not by sorting.
+ * Defined where the reference is not: an empty list gives -1; a list of one gives 0 (the reference
+ * reads one past the row's end, k is clamped here as the host mirror clamps it).
+ * One kernel launch per call: a wave per list of at most 64 descriptors, a workgroup of four waves
+ * per longer list. The largest list is 1024 descriptors: a list sits in the workgroup's LDS whole
+ * (1024 x 64 bytes = 64 KiB). A longer one is refused, never truncated. */
+typedef struct plba_medoid_batch {      /* B descriptor lists, concatenated */
+    int32_t n;                          /* lists                                              */
+    int32_t desc_bytes;                 /* bytes per descriptor: a multiple of 4 in [4, 64]   */
+    const int32_t *list_ptr;            /* [n+1] row ranges into desc                         */
+    const uint8_t *desc;                /* [list_ptr[n]][desc_bytes]                          */
+} plba_medoid_batch;
+#define PLBA_MEDOID_MAX_N 1024
+/* Runs on the context's stream; needs no uploaded window and leaves one intact; shares
+ * plba_desc_match's device block and pinned host image. medoid: [n]. PLBA_E_INVALID for a NULL
+ * batch or array (desc may be NULL when list_ptr[n] == 0), n < 0, decreasing or negative offsets, a
+ * bad desc_bytes or a list of more than PLBA_MEDOID_MAX_N descriptors; n == 0 does nothing and
+ * returns PLBA_OK. */
+int plba_desc_medoid(plba_ctx *ctx, const plba_medoid_batch *b, int32_t *medoid);
+
 /* ---- Grid-guided descriptor matching, what the local-mapping associations try first:
  *   int StVO::matchGrid(points1, desc1, grid, desc2, w, matches_12)               (src2/matching.cpp:111-177)
  *   int StVO::matchGrid(lines1, desc1, grid, desc2, directions2, w, matches_12)   (:179-258)

@@ -158,8 +158,9 @@ int plslam_get_line(plslam_map *m, int32_t idx, double NDw[6], int32_t *inlier, 
  * ::loopClosureOptimizationCovGraphG2O (:5301-5531, ess = 0): the g2o VertexSE3 / EdgeSE3 graph of
  * the loop's KFs solved by plba_pgo_optimize (or the hook), then T_kf_w / x_kf_w of those KFs,
  * their landmarks (point3D, med_obs_dir, dir_list; line3D, med_obs_dir, dir_list) and every
- * later KF corrected, lc_idx_list[.][2] = 0, lc_state = LC_IDLE. loopClosureFuseLandmarks()
- * (:5533, descriptor matching) is the caller's. lc_idxs / lc_idx_list: [n][3] int, lc_pose_list:
+ * later KF corrected, lc_idx_list[.][2] = 0, lc_state = LC_IDLE. This entry point leaves out
+ * loopClosureFuseLandmarks() (:5294, :5526); plslam_loop_closure_optimization_fuse below runs it
+ * too. lc_idxs / lc_idx_list: [n][3] int, lc_pose_list:
  * [n][6] ([t; ω], include/mapHandler.h:186-187). The lists are filled by plslam_loop_closure_step
  * below (the relative pose of each accepted loop comes from plba_lc_relative_pose);
  * plslam_set_loop_closure sets them directly, for a caller that keeps its own verification. */
@@ -176,6 +177,56 @@ typedef struct plslam_pgo_stats {
     double  chi2_initial, chi2_final, solve_ms;
 } plslam_pgo_stats;
 int plslam_loop_closure_optimization(plslam_map *m, int32_t ess, plslam_pgo_stats *stats);
+/* ---- MapHandler::loopClosureFuseLandmarks() (src/mapHandler.cpp:5533-5808): for every loop whose
+ * lc_idx_list flag is 1, the rows (lm_idx0, lm_ldx0, lm_idx1, lm_ldx1) of lc_pt_idxs and then of
+ * lc_ls_idxs (plslam_get_lc_feature_idxs), in order. Per row one of four cases: the observation of the
+ * previous keyframe's feature added to landmark lm_idx1 (case 0, :5552), that of the current
+ * keyframe's feature added to lm_idx0 (case 1, :5567), a new landmark from both features (case 2, :5585),
+ * or lm_idx1's lists appended to lm_idx0 and lm_idx1 erased (case 3, :5612), with the reference's
+ * full_graph increments (case 0 names kf_curr_idx although the observation comes from kf_prev_idx,
+ * :5562; case 1 the other way round, :5579), the erase from map_points_kf_idx / map_lines_kf_idx of
+ * the erased landmark's first observer, the feature idx rewrites and the new index
+ * max_pt_idx / max_ls_idx (the size of the map, as in plslam_match_kf_to_kf). The changed landmarks are
+ * registered with the incremental window. The reference recomputes med_desc (and a point's
+ * med_obs_dir) after every appended observation; only the last recomputation of a landmark can be
+ * observed, so they are computed once per changed landmark when the rows are done: one
+ * plba_desc_medoid batch on the map's context (or the hook below), and the mean direction on the host.
+ * The keyframes need plslam_set_keyframe_features, for lines plslam_set_keyframe_line_endpoints too.
+ * Defined where the reference is not (pl-slam-plucker_amd/host/fuse_landmarks.cpp lists every case):
+ * a row with lm_idx0 == lm_idx1 != -1 is left untouched and counted; a feature index past a
+ * keyframe's arrays (for a new line also lm_ldx1 past the previous keyframe's lines, which :5747
+ * reads), a landmark index outside the map or an observer outside full_graph returns PLBA_E_INVALID
+ * with the map unchanged; a feature cannot be NULL here, a landmark can (erased by an earlier row, or
+ * culled): the row is skipped and counted; sigma_list is fused with the other lists. Lines: the
+ * reference uses the endpoint constructor and observation in a Plücker build too, which leave NDw,
+ * orthNDw and NDw_obs_list unset. Here the observation list of a line (NDw_obs_list, parallel to
+ * kf_obs_list) takes pts = (spl, epl), the image endpoints, with sigma2 = 1; a new line stores
+ * line3D = (sP, eP) in the world, med_obs_dir, and NDw = (sP x eP, eP - sP); le is not stored. */
+typedef struct plslam_fuse_stats {
+    int32_t loops, loops_skipped;           /* loops with flag 1 / with another flag                   */
+    int32_t rows[2][4];                     /* [points, lines][case]: rows that passed their guard     */
+    int32_t null_skipped[2][4];             /* rows whose landmark was NULL                            */
+    int32_t same_landmark[2];               /* rows with lm_idx0 == lm_idx1 != -1                      */
+    int32_t erased[2];                      /* landmarks deleted by case 3                             */
+    int32_t medoid_lists, pad;              /* lists of the medoid batch                               */
+    double  medoid_ms, total_ms;
+} plslam_fuse_stats;
+int plslam_fuse_landmarks(plslam_map *m, plslam_fuse_stats *stats);
+/* Medoid hook, in the style of plslam_set_match_fn: NULL = plba_desc_medoid. */
+typedef int (*plslam_medoid_fn)(void *user, const plba_medoid_batch *b, int32_t *medoid);
+int plslam_set_medoid_fn(plslam_map *m, plslam_medoid_fn fn, void *user);
+/* tools/fuse_bench.py and the tests only, not a product path: a single-threaded restatement of
+ * plba_desc_medoid's semantics on the CPU (the table and a sort of every row, as the reference), with
+ * the signature of the medoid hook. */
+int plslam_desc_medoid_cpu(void *user, const plba_medoid_batch *b, int32_t *medoid);
+/* plslam_loop_closure_optimization with the fuse: the pose graph and the map correction, then
+ * plslam_fuse_landmarks, then the flags cleared and lc_state = LC_IDLE. The reference clears the
+ * flags (:5290-5292, :5522-5523) before it calls loopClosureFuseLandmarks (:5294, :5526), whose
+ * test for flag 1 then fails for every loop: as written it fuses nothing. Here the fuse runs while the
+ * flags still name the loops that were just optimised. If the fuse is refused, the error is returned
+ * with the map corrected, not fused, the flags set and lc_state unchanged. */
+int plslam_loop_closure_optimization_fuse(plslam_map *m, int32_t ess, plslam_pgo_stats *pgo_stats,
+                                          plslam_fuse_stats *fuse_stats);
 /* ---- MapHandler::loopClosure() (src/mapHandler.cpp:4053-4116) after lookForLoopCandidates (which
  * plslam_loop_closure_kf below runs first; these entry points take its candidate from the caller):
  * the descriptor matching of isLoopClosure (:4327-4380, through
@@ -467,6 +518,9 @@ int plslam_get_lc_state(plslam_map *m, int32_t *state);
 /* lc_pose_list [n][6]; the kept index rows of loop `loop` (kind 1 points, 2 lines), [n][4] */
 int plslam_get_lc_pose_list(plslam_map *m, double *out, int32_t cap, int32_t *n);
 int plslam_get_lc_feature_idxs(plslam_map *m, int32_t kind, int32_t loop, int32_t *out, int32_t cap, int32_t *n);
+/* Sets the index rows of loop `loop` (kind 1 points, 2 lines), rows [n][4], for a caller that keeps its
+ * own verification, in the style of plslam_set_loop_closure; both lists grow to hold the loop. */
+int plslam_set_lc_feature_idxs(plslam_map *m, int32_t kind, int32_t loop, const int32_t *rows, int32_t n);
 
 /* MapLine::line3D / med_obs_dir (include/mapFeatures.h:93-94; never set in Plücker mode) */
 int plslam_set_line_geometry(plslam_map *m, int32_t idx, const double line3D[6], const double med_obs_dir[3]);

@@ -2484,6 +2484,16 @@ int plba_kf_associate(plba_ctx *ctx, const plba_kfassoc_batch *b, const plba_kfa
     return ctx ? kf_associate(ctx, b, p, out) : PLBA_E_INVALID;
 }
 
+// median descriptor (csrc/plba_assoc.hip, csrc/plba_medoid.hpp)
+int plba_desc_medoid(plba_ctx *ctx, const plba_medoid_batch *b, int32_t *medoid) {
+    if (!ctx) return PLBA_E_INVALID;
+    if (!b) {
+        ctx->set_error("median descriptor: NULL batch");
+        return PLBA_E_INVALID;
+    }
+    return desc_medoid(ctx, b->n, b->list_ptr, b->desc, b->desc_bytes, medoid);
+}
+
 // place recognition (csrc/plba_assoc.hip, csrc/plba_bow.hpp)
 int plba_bow_set_vocab(plba_ctx *ctx, int32_t slot, const plba_bow_vocab *v) {
     return ctx ? bow_set_vocab(ctx, slot, v) : PLBA_E_INVALID;

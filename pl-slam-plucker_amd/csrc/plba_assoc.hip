@@ -1,5 +1,5 @@
 // plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose,
-// the two descriptor matchers, the stereo and the keyframe association and place recognition. They share nothing
+// the two descriptor matchers, the stereo and the keyframe association, the median descriptor and place recognition. They share nothing
 // with the solver (no Dev, no step graph, no window arena), so they are a translation unit of their
 // own: an edit to a matcher does not rebuild the factorisation kernels. Each call is one upload, its
 // kernels and one read-back through a ScratchBlock. A Staged (csrc/plba_layout.hpp) lays the block
@@ -19,6 +19,7 @@
 #include "plba_stereo.hpp"
 #include "plba_kfassoc.hpp"
 #include "plba_bow.hpp"
+#include "plba_medoid.hpp"
 #include "plba_scratch.hpp"
 
 namespace plba {
@@ -756,6 +757,65 @@ int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_p
             if (out->ls_rejected) memcpy(out->ls_rejected + a1, rej + kbase1[p], r1);
         }
     }
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- median descriptor
+// The descriptor half of updateAverageDescDir (src/mapFeatures.cpp:57-86) for a batch of descriptor
+// lists: one upload, one launch of k_desc_medoid (csrc/plba_medoid.hpp), one read-back. The lists
+// of at most kMedShort rows are packed four to a workgroup, every longer one has its own.
+int desc_medoid(CtxBase *ctx, int n, const int32_t *list_ptr, const uint8_t *desc, int desc_bytes, int32_t *medoid) {
+    const char *const op = "median descriptor";
+    if (n < 0) {
+        ctx->set_error("median descriptor: n < 0");
+        return PLBA_E_INVALID;
+    }
+    if (n == 0) return PLBA_OK;
+    if (const int rc = check_desc_bytes(ctx, op, desc_bytes)) return rc;
+    if (!list_ptr || !medoid) {
+        ctx->set_error("median descriptor: NULL list_ptr / medoid");
+        return PLBA_E_INVALID;
+    }
+    int max_n = 0;
+    if (const int rc = check_offsets(ctx, op, "row", "list", list_ptr, n, &max_n)) return rc;
+    if (max_n > kMedMaxN) {  // the list sits in LDS whole
+        ctx->set_error("median descriptor: a list of %d descriptors is more than %d", max_n, kMedMaxN);
+        return PLBA_E_INVALID;
+    }
+    const size_t total = (size_t)list_ptr[n], dw = (size_t)desc_bytes / 4;
+    if (total && !desc) {
+        ctx->set_error("median descriptor: NULL desc");
+        return PLBA_E_INVALID;
+    }
+    (void)hipSetDevice(ctx->opts.device);
+    MedDev D{};
+    Staged B;
+    B.in(D.list_ptr, (size_t)n + 1, list_ptr);
+    B.in(D.order, n);  // filled below
+    B.in(D.desc, dw * total, desc);
+    B.out(D.medoid, n, medoid);
+    if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
+    B.stage(ctx->match.host, ctx->match.dev);
+    int32_t *order = B.host(D.order);
+    int n_short = 0;
+    for (int k = 0; k < n; ++k)
+        if (list_ptr[k + 1] - list_ptr[k] <= kMedShort) order[n_short++] = k;
+    int n_long = 0;
+    for (int k = 0; k < n; ++k)
+        if (list_ptr[k + 1] - list_ptr[k] > kMedShort) order[n_short + n_long++] = k;
+    if (const int rc = upload(ctx, ctx->match, B)) return rc;
+    D.n = n;
+    D.dwords = desc_bytes / 4;
+    D.n_short = n_short;
+    D.n_short_wg = (n_short + kMedWaves - 1) / kMedWaves;
+    const dim3 grid(D.n_short_wg + n_long);
+    const int W = D.dwords <= 8 ? 8 : 16;
+    const size_t lds = sizeof(uint32_t) * W * (size_t)std::max(kMedWaves * kMedShort, max_n);  // at most 64 KiB
+    if (W == 8) hipLaunchKernelGGL(k_desc_medoid<8>, grid, dim3(kMedNT), lds, ctx->stream, D);
+    else hipLaunchKernelGGL(k_desc_medoid<16>, grid, dim3(kMedNT), lds, ctx->stream, D);
+    PLBA_LAUNCHED(ctx, "k_desc_medoid");
+    if (const int rc = read_back(ctx, ctx->match, B)) return rc;
+    B.fetch();
     return PLBA_OK;
 }
 

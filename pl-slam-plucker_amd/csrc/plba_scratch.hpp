@@ -134,6 +134,7 @@ int grid_match(CtxBase *ctx, const plba_gridmatch_batch *b, int32_t *matches_12,
 int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp,
                      const plba_stereo_out *out);
 int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *pp, const plba_kfassoc_out *out);
+int desc_medoid(CtxBase *ctx, int n, const int32_t *list_ptr, const uint8_t *desc, int desc_bytes, int32_t *medoid);
 // and of plba_bow_set_vocab / _insert / _remove / _get
 int bow_set_vocab(CtxBase *ctx, int slot, const plba_bow_vocab *v);
 int bow_insert(CtxBase *ctx, int slot, int kf_id, const uint8_t *desc, int n_desc, double *scores, int32_t *ids, int cap,

@@ -298,18 +298,67 @@ int plslam_set_pgo_solver(plslam_map *m, plslam_pgo_solve_fn fn, void *user) {
     return PLBA_OK;
 }
 
+namespace {
+void export_pgo_stats(const PgoStats &st, plslam_pgo_stats *stats) {
+    stats->kf_prev_idx = st.kf_prev_idx; stats->kf_curr_idx = st.kf_curr_idx;
+    stats->n_vertices = st.n_vertices; stats->n_fixed = st.n_fixed; stats->n_edges = st.n_edges;
+    stats->n_loop_edges = st.n_loop_edges; stats->iterations = st.iterations; stats->trials = st.trials;
+    stats->chi2_initial = st.chi2_initial; stats->chi2_final = st.chi2_final; stats->solve_ms = st.solve_ms;
+}
+void export_fuse_stats(const FuseStats &st, plslam_fuse_stats *stats) {
+    stats->loops = st.loops; stats->loops_skipped = st.loops_skipped;
+    for (int k = 0; k < 2; ++k) {
+        for (int c = 0; c < 4; ++c) {
+            stats->rows[k][c] = st.rows[k][c];
+            stats->null_skipped[k][c] = st.null_skipped[k][c];
+        }
+        stats->same_landmark[k] = st.same_landmark[k];
+        stats->erased[k] = st.erased[k];
+    }
+    stats->medoid_lists = st.medoid_lists; stats->pad = 0;
+    stats->medoid_ms = st.medoid_ms; stats->total_ms = st.total_ms;
+}
+}  // namespace
+
 int plslam_loop_closure_optimization(plslam_map *m, int32_t ess, plslam_pgo_stats *stats) {
     if (!m) return PLBA_E_INVALID;
     PgoStats st;
     const int rc = ess ? m->mh.loopClosureOptimizationEssGraphG2O(&st) : m->mh.loopClosureOptimizationCovGraphG2O(&st);
     if (rc) return rc;
-    if (stats) {
-        stats->kf_prev_idx = st.kf_prev_idx; stats->kf_curr_idx = st.kf_curr_idx;
-        stats->n_vertices = st.n_vertices; stats->n_fixed = st.n_fixed; stats->n_edges = st.n_edges;
-        stats->n_loop_edges = st.n_loop_edges; stats->iterations = st.iterations; stats->trials = st.trials;
-        stats->chi2_initial = st.chi2_initial; stats->chi2_final = st.chi2_final; stats->solve_ms = st.solve_ms;
-    }
+    if (stats) export_pgo_stats(st, stats);
     return PLBA_OK;
+}
+
+int plslam_loop_closure_optimization_fuse(plslam_map *m, int32_t ess, plslam_pgo_stats *pgo_stats,
+                                          plslam_fuse_stats *fuse_stats) {
+    if (!m) return PLBA_E_INVALID;
+    PgoStats st;
+    FuseStats fs;
+    const int rc = m->mh.loopClosureOptimizationFuse(ess != 0, &st, &fs);
+    if (rc) return rc;
+    if (pgo_stats) export_pgo_stats(st, pgo_stats);
+    if (fuse_stats) export_fuse_stats(fs, fuse_stats);
+    return PLBA_OK;
+}
+
+int plslam_fuse_landmarks(plslam_map *m, plslam_fuse_stats *stats) {
+    if (!m) return PLBA_E_INVALID;
+    FuseStats fs;
+    const int rc = m->mh.fuseLandmarks(&fs);
+    if (rc) return rc;
+    if (stats) export_fuse_stats(fs, stats);
+    return PLBA_OK;
+}
+
+int plslam_set_medoid_fn(plslam_map *m, plslam_medoid_fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    m->mh.setMedoidFn(fn, user);
+    return PLBA_OK;
+}
+
+int plslam_desc_medoid_cpu(void *user, const plba_medoid_batch *b, int32_t *medoid) {
+    (void)user;
+    return descMedoidCpu(b, medoid);
 }
 
 int plslam_set_lcpose_solver(plslam_map *m, plslam_lcpose_solve_fn fn, void *user) {
@@ -720,6 +769,17 @@ int plslam_get_lc_feature_idxs(plslam_map *m, int32_t kind, int32_t loop, int32_
     if (n) *n = (int32_t)l.size();
     for (int i = 0; i < (int)l.size() && i < cap && out; ++i)
         for (int k = 0; k < 4; ++k) out[4 * i + k] = l[i][k];
+    return PLBA_OK;
+}
+
+int plslam_set_lc_feature_idxs(plslam_map *m, int32_t kind, int32_t loop, const int32_t *rows, int32_t n) {
+    if (!m || (kind != 1 && kind != 2) || loop < 0 || n < 0 || (n && !rows)) return PLBA_E_INVALID;
+    if ((int)m->mh.lc_pt_idxs.size() <= loop) m->mh.lc_pt_idxs.resize((size_t)loop + 1);
+    if ((int)m->mh.lc_ls_idxs.size() <= loop) m->mh.lc_ls_idxs.resize((size_t)loop + 1);
+    auto &l = (kind == 1 ? m->mh.lc_pt_idxs : m->mh.lc_ls_idxs)[loop];
+    l.resize((size_t)n);
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < 4; ++k) l[i][k] = rows[4 * i + k];
     return PLBA_OK;
 }
 

@@ -173,7 +173,11 @@ Vec3 xform(const Mat4 &T, const Vec3 &p) {  // T.block(0,0,3,3)·p + T.block(0,3
 int MapHandler::loopClosureOptimizationEssGraphG2O(PgoStats *stats) { return loopClosurePGO(true, stats); }
 int MapHandler::loopClosureOptimizationCovGraphG2O(PgoStats *stats) { return loopClosurePGO(false, stats); }
 
-int MapHandler::loopClosurePGO(bool ess, PgoStats *stats) {
+int MapHandler::loopClosureOptimizationFuse(bool ess, PgoStats *stats, FuseStats *fs) {
+    return loopClosurePGO(ess, stats, true, fs);
+}
+
+int MapHandler::loopClosurePGO(bool ess, PgoStats *stats, bool fuse, FuseStats *fs) {
     using clk = std::chrono::steady_clock;
     PgoStats st;
     // ---- the KF range (:5087-5097 / :5319-5330; the CovGraph variant then starts at KF 0)
@@ -334,8 +338,16 @@ int MapHandler::loopClosurePGO(bool ess, PgoStats *stats) {
         map_keyframes[i]->x_kf_w = logmap_se3(map_keyframes[i]->T_kf_w);
         correct_landmarks(i);
     }
+    // loopClosureFuseLandmarks() (:5294 / :5526), for loopClosureOptimizationFuse. The reference calls it
+    // after it has cleared the flags, so its own call finds no loop with flag 1; here it runs while the
+    // flags still name the loops of this optimisation (fuse_landmarks.cpp). A refused fuse leaves the
+    // flags and lc_state as they are: the map is corrected and not fused.
+    if (fuse) {
+        if (stats) *stats = st;
+        if (const int frc = fuseLandmarks(fs)) return frc;
+    }
     for (Vec3i &l : lc_idx_list) l[2] = 0;  // mark as optimised (:5290-5292)
-    lc_state = 0;                            // LC_IDLE (:5296), after loopClosureFuseLandmarks()
+    lc_state = 0;                            // LC_IDLE (:5296)
     if (stats) *stats = st;
     return PLBA_OK;
 }

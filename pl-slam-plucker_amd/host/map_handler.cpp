@@ -176,9 +176,14 @@ static int median_descriptor(const std::vector<Desc> &desc_list) {
 }
 
 void MapPoint::updateAverageDescDir() {
+    if (desc_list.empty()) return;
+    med_desc = desc_list[median_descriptor(desc_list)];
+    updateAverageDir();
+}
+
+void MapPoint::updateAverageDir() {
     const int n = (int)desc_list.size();
     if (n == 0) return;
-    med_desc = desc_list[median_descriptor(desc_list)];
     // direction: mean of the observation directions (the reference sums into an
     // uninitialised Vector3d, src/mapFeatures.cpp:89-92; zero-initialised here)
     Vec3 s{0.0, 0.0, 0.0};

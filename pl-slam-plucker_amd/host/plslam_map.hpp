@@ -103,6 +103,7 @@ struct MapPoint {
     MapPoint(int idx_, const Vec3 &p, const Desc &desc, int kf_obs, const Vec2 &obs, const Vec3 &dir, double sigma2);
     void addMapPointObservation(const Desc &desc, int kf_obs, const Vec2 &obs, const Vec3 &dir, double sigma2);
     void updateAverageDescDir();
+    void updateAverageDir();  // the direction half of updateAverageDescDir (src/mapFeatures.cpp:88-92)
 };
 
 // include/mapFeatures.h:68-107 (Plücker constructor, src/mapFeatures.cpp:114-138, 140-184
@@ -293,6 +294,20 @@ struct KfMatchStats {
 };
 using KfAssocFn = int (*)(void *user, const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out);
 
+// One loopClosureFuseLandmarks call (fuse_landmarks.cpp), per kind [points, lines]. The four cases in the
+// reference's order: observation added to the later landmark (:5552), to the earlier one (:5567), a new
+// landmark from both features (:5585), two landmarks fused and the second erased (:5612).
+struct FuseStats {
+    int loops = 0, loops_skipped = 0;            // loops with flag 1 / with another flag
+    int rows[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // rows that passed their guard, per case
+    int null_skipped[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};  // rows whose NULL guard failed, per case
+    int same_landmark[2] = {0, 0};               // rows with lm_idx0 == lm_idx1 != -1, left untouched
+    int erased[2] = {0, 0};                      // landmarks deleted by the fourth case
+    int medoid_lists = 0;                        // lists of the one medoid batch
+    double medoid_ms = 0, total_ms = 0;
+};
+using MedoidFn = int (*)(void *user, const plba_medoid_batch *b, int32_t *medoid);
+
 struct CullStats {
     int points_removed = 0, lines_removed = 0;
 };
@@ -346,9 +361,18 @@ class MapHandler {
     // the loop's first to its last KF, EdgeSE3 for covisible / consecutive pairs and for each
     // loop), optimised on the GPU (plba_pgo_optimize), then the KF poses, their landmarks and
     // every later KF corrected, lc_idx_list marked optimised, lc_state = LC_IDLE.
-    // loopClosureFuseLandmarks() (:5533, descriptor-matching landmark fusion) is the caller's.
+    // These two leave out loopClosureFuseLandmarks() (:5294, :5526); loopClosureOptimizationFuse runs
+    // the same body with the fuse below before the flags are cleared.
     int loopClosureOptimizationEssGraphG2O(PgoStats *stats = nullptr);
     int loopClosureOptimizationCovGraphG2O(PgoStats *stats = nullptr);
+    int loopClosureOptimizationFuse(bool ess, PgoStats *stats = nullptr, FuseStats *fs = nullptr);
+    // fuse_landmarks.cpp. loopClosureFuseLandmarks() (src/mapHandler.cpp:5533-5808) over lc_pt_idxs /
+    // lc_ls_idxs of the loops whose lc_idx_list flag is 1, points then lines, row by row; the median
+    // descriptors of the landmarks whose lists changed come from one medoid batch at the end
+    // (plba_desc_medoid, or the hook). What the reference leaves undefined is listed in the file's header.
+    // Anything invalid returns PLBA_E_INVALID before the map is touched.
+    int fuseLandmarks(FuseStats *stats = nullptr);
+    void setMedoidFn(MedoidFn fn, void *user) { medoid_fn_ = fn; medoid_user_ = user; }
     // include/mapHandler.h:186-200
     std::vector<Vec3i> lc_idxs, lc_idx_list;
     std::vector<Vec6> lc_poses, lc_pose_list;
@@ -498,7 +522,9 @@ class MapHandler {
     static bool inlierRatioGate(const LcCandidate &c, double lc_inlier_ratio, int &common_pt, int &common_ls,
                                 double &ratio_pt, double &ratio_ls);
     int lcRelativePose(const plba_lcpose_batch &b, plba_lcpose_out *out, uint8_t *pin, uint8_t *lin);
-    int loopClosurePGO(bool ess, PgoStats *stats);
+    int loopClosurePGO(bool ess, PgoStats *stats, bool fuse = false, FuseStats *fs = nullptr);
+    MedoidFn medoid_fn_ = nullptr;
+    void *medoid_user_ = nullptr;
     std::string err_;
     // per-call scratch reused across LBA calls (capacity kept; see Window::clear)
     Window win_;
@@ -525,6 +551,8 @@ long lineCells(double x1, double y1, double x2, double y2, std::vector<std::arra
 int gridMatchCpu(const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
 // the same with a window of four half-widths per problem (win [n][4]: left, right, up, down; b->ws is not read)
 int gridMatchCpuWin(const plba_gridmatch_batch *b, const int32_t *win, int32_t *matches_12, int32_t *n_matches);
+// fuse_landmarks.cpp. tools/fuse_bench.py and the tests only: plba_desc_medoid's semantics, single-threaded, on the CPU
+int descMedoidCpu(const plba_medoid_batch *b, int32_t *medoid);
 // stereo.cpp. tools/stereo_bench.py and the tests only: plba_stereo_associate's semantics, single-threaded, on the CPU
 int stereoCpu(const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
 // kf_match.cpp. tools/kfassoc_bench.py and the tests only: plba_kf_associate's semantics, single-threaded, on the CPU

@@ -366,6 +366,34 @@ class MatchBatchView:
             best_lr=int(bool(best_lr)), pad=0)
 
 
+# ---- median descriptor (plba_medoid_batch / plba_desc_medoid)
+class PlbaMedoidBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("list_ptr", _ip), ("desc", _bp)]
+
+
+MEDOID_MAX_N = 1024  # PLBA_MEDOID_MAX_N
+
+
+class MedoidBatchView:
+    """Contiguous copies of the CSR offsets list_ptr [B+1] and the descriptors desc [total][desc_bytes]
+    uint8 of a batch of descriptor lists, and the PlbaMedoidBatch over them."""
+
+    def __init__(self, list_ptr, desc, desc_bytes=None):
+        self.list_ptr = np.ascontiguousarray(list_ptr, dtype=np.int32).reshape(-1)
+        desc = np.asarray(desc, np.uint8)
+        if desc_bytes is None:
+            desc_bytes = desc.shape[1] if desc.ndim == 2 and desc.shape[1] else 32
+        self.desc_bytes = int(desc_bytes)
+        self.desc = np.ascontiguousarray(desc).reshape(-1)
+        n = len(self.list_ptr) - 1
+        if n < 0 or (n > 0 and int(self.list_ptr[-1]) * self.desc_bytes > self.desc.size):
+            raise ValueError("list_ptr is empty or reaches past the descriptors")
+        if self.desc.size == 0:
+            self.desc = np.zeros(1, np.uint8)
+        self.struct = PlbaMedoidBatch(n=n, desc_bytes=self.desc_bytes, list_ptr=_ptr(self.list_ptr, _ip),
+                                      desc=_ptr(self.desc, _bp))
+
+
 # ---- place recognition (plba_bow_vocab / plba_bow_*)
 class PlbaBowVocab(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("n_words", C.c_int32), ("desc_bytes", C.c_int32), ("pad", C.c_int32),

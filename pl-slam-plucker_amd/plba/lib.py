@@ -32,7 +32,7 @@ EXPORTED = [
     "plba_pgo_default_params", "plba_pgo_optimize",
     "plba_lcpose_default_params", "plba_lc_relative_pose",
     "plba_desc_match", "plba_grid_match", "plba_stereo_default_params", "plba_stereo_associate",
-    "plba_kfassoc_default_params", "plba_kf_associate",
+    "plba_kfassoc_default_params", "plba_kf_associate", "plba_desc_medoid",
     "plba_bow_set_vocab", "plba_bow_insert", "plba_bow_remove", "plba_bow_get",
 ]
 
@@ -107,6 +107,7 @@ def load(path: Optional[str] = None):
     L.plba_kfassoc_default_params.restype = None
     L.plba_kf_associate.argtypes = [vp, C.POINTER(capi.PlbaKfassocBatch), C.POINTER(capi.PlbaKfassocParams),
                                     C.POINTER(capi.PlbaKfassocOut)]
+    L.plba_desc_medoid.argtypes = [vp, C.POINTER(capi.PlbaMedoidBatch), ip]
     L.plba_bow_set_vocab.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaBowVocab)]
     L.plba_bow_insert.argtypes = [vp, C.c_int32, C.c_int32, bp, C.c_int32, dp, ip, C.c_int32, ip]
     L.plba_bow_remove.argtypes = [vp, C.c_int32, C.c_int32]
@@ -378,6 +379,18 @@ class Solver:
         self._check(self.L.plba_kf_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
                     "plba_kf_associate")
         return bv.results()
+
+    def desc_medoid(self, list_ptr, desc, desc_bytes=None) -> np.ndarray:
+        """Median descriptor (plba_desc_medoid; the descriptor half of updateAverageDescDir,
+        src/mapFeatures.cpp:57-86) of a batch of descriptor lists in one launch: CSR offsets list_ptr
+        [B+1] into desc [total][desc_bytes] uint8. Returns int32 [B]: the position within each list of
+        the first descriptor with the smallest median Hamming distance to the list, -1 for an empty
+        list. A list of more than capi.MEDOID_MAX_N descriptors is refused. Needs no uploaded window and
+        leaves one intact."""
+        bv = capi.MedoidBatchView(list_ptr, desc, desc_bytes)
+        out = np.full(max(bv.struct.n, 1), -1, np.int32)
+        self._check(self.L.plba_desc_medoid(self.ctx, C.byref(bv.struct), _p(out, C.c_int32)), "plba_desc_medoid")
+        return out[:bv.struct.n].copy()
 
     def bow_set_vocab(self, slot: int, voc):
         """Uploads the vocabulary of a place-recognition slot (plba_bow_set_vocab; 0 points, 1 lines)

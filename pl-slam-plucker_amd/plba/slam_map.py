@@ -205,6 +205,23 @@ class PlslamPgoStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class PlslamFuseStats(C.Structure):
+    _fields_ = [("loops", C.c_int32), ("loops_skipped", C.c_int32), ("rows", (C.c_int32 * 4) * 2),
+                ("null_skipped", (C.c_int32 * 4) * 2), ("same_landmark", C.c_int32 * 2), ("erased", C.c_int32 * 2),
+                ("medoid_lists", C.c_int32), ("pad", C.c_int32), ("medoid_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f in ("loops", "loops_skipped", "medoid_lists", "medoid_ms", "total_ms")}
+        d["rows"] = [list(r) for r in self.rows]
+        d["null_skipped"] = [list(r) for r in self.null_skipped]
+        d["same_landmark"] = list(self.same_landmark)
+        d["erased"] = list(self.erased)
+        return d
+
+
+MEDOID_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaMedoidBatch), C.POINTER(C.c_int32))
+
+
 class PlslamHlmStats(C.Structure):
     _fields_ = [("ret", C.c_int32), ("n_kf_list", C.c_int32), ("n_fixed_kf", C.c_int32), ("n_pt", C.c_int32),
                 ("n_ln", C.c_int32), ("n_pt_obs", C.c_int32), ("n_ls_obs", C.c_int32),
@@ -342,6 +359,8 @@ HOST_EXPORTED = [
     "plslam_set_bow_fn", "plslam_bow_cpu", "plslam_set_vocabulary", "plslam_remove_keyframe", "plslam_insert_kf_bow",
     "plslam_get_conf_matrix_row", "plslam_set_conf_matrix", "plslam_look_for_loop_candidates", "plslam_loop_closure_kf",
     "plslam_bow_cpu_new", "plslam_bow_cpu_free", "plslam_lc_search_default_params",
+    "plslam_fuse_landmarks", "plslam_set_medoid_fn", "plslam_desc_medoid_cpu", "plslam_loop_closure_optimization_fuse",
+    "plslam_set_lc_feature_idxs",
 ]
 
 
@@ -551,6 +570,11 @@ def load_host(path: Optional[str] = None):
                                          C.c_double, C.POINTER(PlslamLcStats)]
     L.plslam_lc_search_default_params.argtypes = [C.POINTER(PlslamLcSearchParams)]
     L.plslam_lc_search_default_params.restype = None
+    L.plslam_fuse_landmarks.argtypes = [vp, C.POINTER(PlslamFuseStats)]
+    L.plslam_set_medoid_fn.argtypes = [vp, MEDOID_FN, vp]
+    L.plslam_desc_medoid_cpu.argtypes = [vp, C.POINTER(capi.PlbaMedoidBatch), ip]
+    L.plslam_loop_closure_optimization_fuse.argtypes = [vp, C.c_int32, C.POINTER(PlslamPgoStats), C.POINTER(PlslamFuseStats)]
+    L.plslam_set_lc_feature_idxs.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32]
     for n in HOST_EXPORTED:
         if n not in ("plslam_map_last_error", "plslam_pluker_to_orth", "plslam_orth_to_pluker",
                      "plslam_mapmatch_default_params", "plslam_bow_cpu_new", "plslam_bow_cpu_free",
@@ -584,6 +608,16 @@ def grid_match_cpu(problems, cols: int = 64, rows: int = 48, best_lr: bool = Tru
     if rc != 0:
         raise PlbaError(f"plslam_grid_match_cpu failed: {rc}")
     return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+
+
+def desc_medoid_cpu(list_ptr, desc, desc_bytes=None) -> np.ndarray:
+    """plslam_desc_medoid_cpu on the lists of Solver.desc_medoid (tests and tools/fuse_bench.py)."""
+    bv = capi.MedoidBatchView(list_ptr, desc, desc_bytes)
+    out = np.full(max(bv.struct.n, 1), -1, np.int32)
+    rc = load_host().plslam_desc_medoid_cpu(None, C.byref(bv.struct), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise PlbaError(f"plslam_desc_medoid_cpu failed: {rc}")
+    return out[:bv.struct.n].copy()
 
 
 def kf_assoc_cpu(pairs, params, desc_bytes=None) -> list:
@@ -856,6 +890,45 @@ class HostMap:
         st = PlslamPgoStats()
         self._check(self.L.plslam_loop_closure_optimization(self.h, int(ess), C.byref(st)), "loop_closure")
         return st.as_dict()
+
+    # ---- loopClosureFuseLandmarks (src/mapHandler.cpp:5533-5808)
+    def set_lc_feature_idxs(self, kind: int, loop: int, rows):
+        """The rows (lm_idx0, lm_ldx0, lm_idx1, lm_ldx1) of loop ``loop`` (kind 1 points, 2 lines)."""
+        a = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1, 4))
+        self._check(self.L.plslam_set_lc_feature_idxs(self.h, kind, loop, a.ctypes.data_as(C.POINTER(C.c_int32)), len(a)),
+                    "set_lc_feature_idxs")
+
+    def set_medoid_fn(self, fn):
+        """fn(batch, medoid) -> int; "cpu" for plslam_desc_medoid_cpu (no trampoline: the C function
+        itself); None for the MI355X backend (plba_desc_medoid)."""
+        if fn is None:
+            self._medcb = None
+            self._check(self.L.plslam_set_medoid_fn(self.h, C.cast(None, MEDOID_FN), None), "set_medoid_fn")
+            return
+        if isinstance(fn, str) and fn == "cpu":
+            self._medcb = C.cast(self.L.plslam_desc_medoid_cpu, MEDOID_FN)
+        else:
+            def tramp(user, bp_, med):
+                try:
+                    return int(fn(bp_.contents, med))
+                except Exception:  # never unwind through C
+                    import traceback
+                    traceback.print_exc()
+                    return -1
+            self._medcb = MEDOID_FN(tramp)
+        self._check(self.L.plslam_set_medoid_fn(self.h, self._medcb, None), "set_medoid_fn")
+
+    def fuse_landmarks(self) -> dict:
+        st = PlslamFuseStats()
+        self._check(self.L.plslam_fuse_landmarks(self.h, C.byref(st)), "fuse_landmarks")
+        return st.as_dict()
+
+    def loop_closure_fuse(self, ess: bool = True):
+        """plslam_loop_closure_optimization_fuse: (pose-graph stats, fuse stats)."""
+        st, fs = PlslamPgoStats(), PlslamFuseStats()
+        self._check(self.L.plslam_loop_closure_optimization_fuse(self.h, int(ess), C.byref(st), C.byref(fs)),
+                    "loop_closure_fuse")
+        return st.as_dict(), fs.as_dict()
 
     # ---- loopClosure() from the candidate on (src/mapHandler.cpp:4053-4116)
     def set_lcpose_solver(self, fn: Optional[Callable]):
