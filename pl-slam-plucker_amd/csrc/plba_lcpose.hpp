@@ -15,7 +15,9 @@
 // Kept from the reference: fx in both Jacobian rows, the left-perturbation step applied on the
 // right, err_prev carried from the first loop into the refinement, lc_inl forced true in RobustGN.
 // Defined where the reference is not: a candidate with no active feature (empty, or emptied by the
-// outlier pass) is rejected with T_inc left as it was; a singular H is rejected (unc = +inf).
+// outlier pass) is rejected with T_inc left as it was; a singular H is rejected (unc = +inf); a
+// non-finite H or g (a match with z = 0) gives a NaN step, every later comparison is false and
+// the candidate is rejected at the caps.
 // No FMA contraction, like the checker (tests/ref_lcpose.py) and the se(3) maps of plba_math.hpp.
 #pragma once
 
@@ -125,15 +127,25 @@ __device__ void qr_solve(const double *H, const double *g, double *x, Work &w) {
     double *A = w.A, *c = w.c, *y = w.y;
     int *perm = w.perm;
     double maxn2 = 0.0;
+    bool finite = true;
     for (int j = 0; j < 6; ++j) {
         double s = 0.0;
         for (int i = 0; i < 6; ++i) {
             A[6 * i + j] = H[6 * i + j];
             s += H[6 * i + j] * H[6 * i + j];
+            finite = finite && isfinite(H[6 * i + j]);
         }
+        finite = finite && isfinite(g[j]);
         maxn2 = fmax(maxn2, s);
         perm[j] = j;
         c[j] = g[j];
+    }
+    // A non-finite system (a match with z = 0) has no pivot to compare: Eigen drops no rank on a NaN
+    // norm and its reflections spread the NaN, so x is NaN. (fmax and the pivot search below would
+    // skip the NaN, find rank 0 and return x = 0, a step that looks converged.)
+    if (!finite) {
+        for (int i = 0; i < 6; ++i) x[i] = NAN;
+        return;
     }
     const double th = sqrt(maxn2) * DBL_EPSILON / 6.0, thr = th * th;
     int nz = 6;

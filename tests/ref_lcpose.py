@@ -20,7 +20,8 @@ What the functions do, as restated here:
     forced true), t < lc_trs, r < lc_rot;
   * pose_inc = logmap(inverse(expmap(x_inc))) (variant 0) / logmap(inverse(T_inc)) (variant 1).
 Defined where the reference is not, as the device does: no active match -> accepted = 0 and T_inc
-stays; a singular H (inv fails or is not finite) -> unc = +inf.
+stays; a singular H (inv fails or is not finite) -> unc = +inf; a non-finite H or g (a match with
+z = 0) -> x = NaN and no exception, after which every comparison is false.
 The se(3) maps are the reference-ordered restatements of oracle/refhlm.cpp.
 """
 from __future__ import annotations
@@ -109,7 +110,11 @@ def line_rows(T, sP, eP, le, cam, hth):
 
 
 def qr_solve(H, g):
-    """x = ColPivHouseholderQR(H).solve(g): rank by Eigen's pivot threshold, the rest of x zero."""
+    """x = ColPivHouseholderQR(H).solve(g): rank by Eigen's pivot threshold, the rest of x zero.
+    A non-finite H or g (a match with z = 0) gives a NaN x: no comparison with a NaN norm holds, so
+    no rank is dropped, and the reflections spread the NaN over every entry."""
+    if not (np.isfinite(H).all() and np.isfinite(g).all()):
+        return np.full(6, np.nan)
     Q, R, P = scipy.linalg.qr(H, pivoting=True)
     thr = (np.sqrt((H * H).sum(axis=0).max()) * EPS / 6.0) ** 2
     nz = 6
@@ -139,6 +144,11 @@ def uncertainty(H):
 def relative_pose(prob, params) -> dict:
     """The fields of Solver.lc_relative_pose for one candidate, plus the residuals of the outlier pass
     (`out_res_pt`, `out_res_ln`: ‖e‖ of the matches it tested, NaN for the others)."""
+    with np.errstate(all="ignore"):   # a match with z = 0 divides by it, as the function does
+        return _relative_pose(prob, params)
+
+
+def _relative_pose(prob, params) -> dict:
     p = params
     cam = tuple(float(v) for v in prob.cam)
     hth = float(p.homog_th)

@@ -164,6 +164,166 @@ def test_generator_margins_of_the_gpu_fixtures(n_pt, n_ln, frac, variant):
             assert m[k] > 1e-6, (k, m)
 
 
+def _ids(cs):
+    return [c.name for c in cs]
+
+
+def _margins_ok(pr, p):
+    m = R.margins(pr, p)
+    return all(m[k] > 1e-6 for k in ("outlier", "e", "unc", "t", "r_deg")), m
+
+
+@pytest.mark.parametrize("variant", cases.VARIANTS)
+@pytest.mark.parametrize("case", cases.MARGIN_CASES, ids=_ids(cases.MARGIN_CASES))
+def test_generator_margins_of_the_candidates_away_from_the_defaults(case, variant):
+    ok, m = _margins_ok(case.problem(), case.params(variant))
+    assert ok, m
+    ref = case.reference(variant)
+    if case.prm and dict(case.prm).get("lc_inl"):   # the inlier share is a decision of GN too
+        share = (ref["n_inl_pt"] + ref["n_inl_ln"]) / (case.n_pt + case.n_ln)
+        assert abs(share - dict(case.prm)["lc_inl"]) > 1e-6
+    # the full runs of the clamp cases are compared only because they are well conditioned
+    assert np.linalg.cond(ref["H"]) <= 1e6
+
+
+@pytest.mark.parametrize("case", cases.ONE_PASS_CASES, ids=_ids(cases.ONE_PASS_CASES))
+def test_generator_margins_of_one_pass_from_the_identity(case):
+    ok, m = _margins_ok(case.problem(), case.params(capi.LCPOSE_GN, **cases.ONE_PASS))
+    assert ok, m
+
+
+@pytest.mark.parametrize("case,robust,gn", cases.REJECTED, ids=_ids([c for c, _, _ in cases.REJECTED]))
+def test_each_accept_condition_fails_alone(case, robust, gn):
+    """conditions: 1 e < lc_res | 2 unc < lc_unc | 4 inlier share > lc_inl (GN; forced in RobustGN) |
+    8 t < lc_trs | 16 r_deg < lc_rot."""
+    a, b = case.reference(capi.LCPOSE_ROBUST_GN), case.reference(capi.LCPOSE_GN)
+    assert (a["conditions"], b["conditions"]) == (robust, gn)
+    assert a["accepted"] == int(robust == 31) and b["accepted"] == int(gn == 31)
+    for ref in (a, b):   # a pose was reached: the rejection is the threshold's, not a failed run's
+        assert ref["n_inl_pt"] + ref["n_inl_ln"] >= 39 and np.isfinite(ref["unc"])
+
+
+def _unpermuted(o, ip, il):
+    o = dict(o)
+    for k, idx in (("pt_inlier", ip), ("ln_inlier", il)):
+        a = np.zeros_like(o[k])
+        a[idx] = o[k]
+        o[k] = a
+    return o
+
+
+def test_one_pass_bar_is_a_hundred_times_the_checkers_own_reordering_noise():
+    """The largest relative difference of H and e between the checker's one pass and its pass over the
+    same features in three other orders, over every one-pass candidate: 1.218e-15 measured (plain
+    elementwise arithmetic, the same on every machine); the device's tree over 256 partial sums matches no serial order, hence the factor 100."""
+    worst = 0.0
+    for case in cases.ONE_PASS_CASES:
+        ref = case.reference(capi.LCPOSE_GN, **cases.ONE_PASS)
+        for seed in (1, 2, 3):
+            q, ip, il = cases.permuted(case.problem(), seed)
+            o = _unpermuted(R.relative_pose(q, case.params(capi.LCPOSE_GN, **cases.ONE_PASS)), ip, il)
+            assert np.array_equal(o["pt_inlier"], ref["pt_inlier"]) and np.array_equal(o["ln_inlier"], ref["ln_inlier"])
+            fig = cases.one_pass_figures(o, ref)
+            worst = max(worst, fig["H"], fig["e"])
+            assert fig["T_inc"] <= cases.ONE_PASS_BAR, (case.name, fig)   # the bar times cond₂(H) holds for the step
+    print("one pass, reordering noise", worst)
+    assert 100.0 * worst <= cases.ONE_PASS_BAR <= 101.0 * worst, worst
+
+
+@pytest.mark.parametrize("variant", cases.VARIANTS)
+def test_noise_free_run_stagnates_at_the_same_pass_in_any_feature_order(variant):
+    """|e − err_prev| < ε ends both loops below their caps, and the count does not depend on the
+    summation order."""
+    case = cases.STAGNATION
+    ref = case.reference(variant)
+    n_ref = 1 if variant == capi.LCPOSE_ROBUST_GN else 0
+    assert 5 < ref["iters_first"] < 30 and ref["iters_ref"] == n_ref and ref["e"] > 100 * R.EPS
+    for seed in range(1, 6):
+        q, _, _ = cases.permuted(case.problem(), seed)
+        o = R.relative_pose(q, case.params(variant))
+        assert (o["iters_first"], o["iters_ref"]) == (ref["iters_first"], ref["iters_ref"]), seed
+    # the deciding differences are far from ε on the scale of e's own rounding (e ~ 8e-8, so ~1e-22):
+    # |e14 − e13| = 7.3e-17 = ε/3 stops the loop, |e13 − e12| = 5.7e-15 = 26 ε did not
+    n = ref["iters_first"]
+    e = [R.relative_pose(case.problem(), case.params(capi.LCPOSE_GN, max_iters_first=k))["e"] for k in (n - 2, n - 1, n)]
+    assert abs(e[2] - e[1]) < 0.5 * R.EPS and abs(e[1] - e[0]) > 10.0 * R.EPS, e
+
+
+def test_exact_observations_at_the_identity_stop_on_the_first_pass():
+    for variant in cases.VARIANTS:
+        ref = cases.AT_IDENTITY.reference(variant)
+        assert ref["iters_first"] == 1 and ref["e"] < R.EPS
+        assert np.array_equal(ref["T_inc"], np.eye(4)[:3])
+        assert not ref["x_inc"].any() and not ref["pose_inc"].any()   # logmap_se3's arm for θ <= 1e-6
+
+
+def test_both_sides_of_both_clamps_occur():
+    def first_pass(case):
+        pr = case.problem()
+        r_pt, _, _, G = R.point_res(np.eye(4), pr.pt_P, pr.pt_obs, pr.cam)
+        r_ln, _, _, Gs, Ge = R.line_res(np.eye(4), pr.ln_sP, pr.ln_eP, pr.ln_le, pr.cam)
+        return np.r_[r_pt, r_ln], np.r_[G[:, 2], Gs[:, 2], Ge[:, 2]] ** 2, dict(case.prm)["homog_th"]
+    # fmax(homog_th, r) on the first pass of the small motion: (below, above)
+    r, z2, hth = first_pass(cases.CLAMP_R_SMALL)
+    assert ((r < hth).sum(), (r > hth).sum()) == (12, 40) and (z2 > hth).all()
+    # ... and on the last pass of the ordinary scene, whose first pass is all above
+    r, z2, hth = first_pass(cases.CLAMP_R)
+    assert (r > hth).all() and (z2 > hth).all()
+    for v in cases.VARIANTS:
+        ref = cases.CLAMP_R.reference(v)
+        res = np.r_[ref["out_res_pt"], ref["out_res_ln"]]
+        assert (res < hth).sum() >= 5 and (res > hth).sum() >= 5
+    # fmax(homog_th, gz²) on the first pass of the scene at a tenth of its size
+    r, z2, hth = first_pass(cases.CLAMP_Z)
+    assert ((z2 < hth).sum(), (z2 > hth).sum()) == (24, 40)
+
+
+@pytest.mark.parametrize("case", cases.FEW, ids=_ids(cases.FEW))
+def test_few_feature_candidates_agree_with_their_reordered_runs_within_a_tenth_of_each_bar(case):
+    for variant in cases.VARIANTS:
+        ref = case.reference(variant)
+        assert 1e3 <= np.linalg.cond(ref["H"]) <= 1e6
+        for seed in (0, 1, 2):
+            q, ip, il = cases.permuted(case.problem(), seed)
+            o = _unpermuted(R.relative_pose(q, case.params(variant)), ip, il)
+            assert np.array_equal(o["pt_inlier"], ref["pt_inlier"]) and np.array_equal(o["ln_inlier"], ref["ln_inlier"])
+            fig = cases.parity_figures(o, ref)
+            assert max(fig.values()) <= 0.1, (variant, seed, fig)
+
+
+@pytest.mark.parametrize("case", cases.RANK_DEFICIENT, ids=_ids(cases.RANK_DEFICIENT))
+def test_rank_deficient_candidates_are_rejected_on_the_uncertainty(case):
+    for variant in cases.VARIANTS:
+        ref = case.reference(variant)
+        assert ref["accepted"] == 0 and not (ref["conditions"] & 2)
+        assert np.linalg.cond(ref["H"]) > 1e15
+
+
+def test_a_point_behind_the_camera_is_an_ordinary_outlier():
+    pr, k = cases.BEHIND.problem(), cases.BEHIND.mirror
+    assert (pr.T_true[:3, :3] @ pr.pt_P[k] + pr.T_true[:3, 3])[2] < -1.0
+    for variant in cases.VARIANTS:
+        ref = cases.BEHIND.reference(variant)
+        assert ref["accepted"] == 1 and np.isfinite(ref["out_res_pt"]).all()
+        assert not ref["pt_inlier"][k] and ref["n_inl_pt"] == 39 and ref["n_inl_ln"] == 12
+
+
+def test_a_point_with_zero_depth_gives_a_nan_step_and_a_rejection():
+    """Defined here, where the reference is not: a non-finite H or g gives a NaN x and no exception.
+    Every comparison with NaN is then false: no stop test holds, both loops run to their caps, no match
+    is an outlier (‖e‖ > sqrt(7.815) is false), e and t fail their tests and r_deg = 0 passes."""
+    pr = cases.ZERO_DEPTH.problem()
+    assert pr.pt_P[cases.ZERO_DEPTH.zero_z, 2] == 0.0
+    assert np.isnan(R.qr_solve(np.full((6, 6), np.nan), np.ones(6))).all()
+    assert np.isnan(R.qr_solve(np.eye(6), np.r_[np.inf, np.zeros(5)])).all()
+    for variant in cases.VARIANTS:
+        ref = cases.ZERO_DEPTH.reference(variant)
+        assert ref["accepted"] == 0 and ref["conditions"] == 4 | 16
+        assert (ref["iters_first"], ref["iters_ref"]) == (5, 10 if variant == capi.LCPOSE_ROBUST_GN else 0)
+        assert ref["pt_inlier"].all() and ref["ln_inlier"].all() and np.isnan(ref["T_inc"]).all()
+        assert ref["unc"] == np.inf and np.isnan(ref["e"])
+
+
 def test_generator_outliers_are_gross_and_noise_is_bounded():
     pr = cases.problem(300, 100, 0.25)
     T = pr.T_true
