@@ -1096,7 +1096,6 @@ void stage_system_arrays(plba_ctx *ctx, const plba_graph *g, const WindowStructu
         d.bcr_sl[2] = N * (int64_t)bcr_X_doubles(bw);
         d.bcr_sl[3] = 2 * N;
         d.bcr_sl[4] = kBcrCtl;
-        d.bcr_sl[5] = N * (int64_t)kBcrStamps;
         ALLOC(d.bcr_pub, (size_t)W * d.bcr_sl[0]);
         ALLOC(d.bcr_x, (size_t)W * d.bcr_sl[1]);
         ALLOC(d.bcr_X, (size_t)W * d.bcr_sl[2]);
@@ -1106,7 +1105,6 @@ void stage_system_arrays(plba_ctx *ctx, const plba_graph *g, const WindowStructu
         UPLOAD(d.h_kf, h.h_kf);
         ZALLOC(d.bcr_flag, (size_t)W * d.bcr_sl[3]);
         ZALLOC(d.bcr_ctl, (size_t)W * kBcrCtl);
-        ZALLOC(d.bcr_stamps, (size_t)W * d.bcr_sl[5]);
         // the schedule's starting state, restored if a hand-off wait times out (run_schedule)
         ALLOC(ctx->bk_T, (size_t)n_kf * 12);
         ALLOC(ctx->bk_X, (size_t)std::max(n_lm, 1) * 4);
@@ -1117,7 +1115,6 @@ void stage_system_arrays(plba_ctx *ctx, const plba_graph *g, const WindowStructu
         ALLOC(ctx->bk_level, (size_t)std::max(E, 1));
         ALLOC(ctx->bk_xl, (size_t)std::max(n_lm, 1) * 4);
     }
-    if (!d.band_mode) ZALLOC(d.bcr_stamps, kBcrStamps);  // dense-path phase stamps (PLBA_DIAG bit 8)
     ALLOC(d.bs, (size_t)W * n);
     // k_lm_solve reads x_p[6·max(h, 0) ..] for fixed-pose slots too
     for (int b = 0; b < nbx; ++b) ZALLOC(d.xpb[b], std::max(n, 6));
@@ -1166,9 +1163,6 @@ void stage_system_arrays(plba_ctx *ctx, const plba_graph *g, const WindowStructu
         // one staging block: Tcw | pt_xyz | ln_orth | χ² (doubles), then the byte outputs
         ALLOC(ctx->d_outd, out_doubles(n_kf, n_pt, n_ln, E) + ((size_t)Ep + E + 7) / 8);
     }
-#if defined(PLBA_STAMPS) || defined(PLBA_PHASE_STAMPS) || defined(PLBA_LMS_STAMPS)
-    ZALLOC(d.stamps, 17 * 8);
-#endif
 }
 #undef ALLOC
 #undef ZALLOC
@@ -2253,30 +2247,6 @@ int plba_kernel_times(plba_ctx *ctx, const char **names, double *ms, int32_t *la
         if (ms) ms[k] = ctx->k_ms[k];
         if (launches) launches[k] = ctx->k_n[k];
     }
-    return PLBA_OK;
-}
-
-// Diagnostic build only: per-wave, per-phase cycle sums of the banded factorisation.
-int plba_debug_stamps(plba_ctx *ctx, unsigned long long *out /* [17][8] */) {
-#if defined(PLBA_STAMPS) || defined(PLBA_PHASE_STAMPS) || defined(PLBA_LMS_STAMPS)
-    if (!ctx || !ctx->d.stamps) return PLBA_E_STATE;
-    PLBA_CHECK(d2h(ctx, out, ctx->d.stamps, 17 * 8 * sizeof(unsigned long long)));
-    return PLBA_OK;
-#else
-    (void)ctx; (void)out;
-    return PLBA_E_STATE;
-#endif
-}
-
-// Diagnostics only (PLBA_DIAG bit 8): per-workgroup phase timestamps of the last block-cyclic-
-// reduction launch, [bcr_rows][32] s_memrealtime ticks (100 MHz).
-int plba_debug_bcr_stamps(plba_ctx *ctx, unsigned long long *out, int32_t cap, int32_t *rows) {
-    if (!ctx || !out || !rows) return PLBA_E_INVALID;
-    if (!ctx->uploaded || !ctx->d.bcr_stamps) return PLBA_E_STATE;  // BCR rows, or 1 row (dense path)
-    const int rows_ = std::max(ctx->d.bcr_N, 1);
-    const int n = std::min(cap / kBcrStamps, rows_);
-    *rows = rows_;
-    PLBA_CHECK(d2h(ctx, out, ctx->d.bcr_stamps, sizeof(unsigned long long) * (size_t)n * kBcrStamps));
     return PLBA_OK;
 }
 

@@ -188,7 +188,7 @@ __host__ __device__ constexpr size_t twisted_merge_doubles(int bw) {
 }
 
 template <int BW>
-__device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int ring, unsigned long long *stamps) {
+__device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int ring) {
     constexpr int NT = band_nt(BW), W = BW + 1, NW = NT - 64;
     constexpr int UR = band_ur(BW), UPB = 6 / UR, UE = UR * 6;  // rows per owner, owners per block, entries
     static_assert(UPB * bd_blocks(W) <= NW, "one owned (part) block per worker thread");
@@ -281,11 +281,6 @@ __device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int 
         if (fail && lane == 0) s_fail = 1;
     }
     lds_barrier();
-#ifdef PLBA_STAMPS
-    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long st_last;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-#endif
     int sk = 0, kR = 0, kRK = 1;                  // k % W (rhs row slots), k % R, (k+1) % RK
     int sB = BW % kBandStage, sW = W % kBandStage; // staging slots of rows k+BW, k+W
     int fr0 = 0;                                  // (first step of the current flush batch) % RK
@@ -326,7 +321,6 @@ __device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int 
             }
             if (wtl < 6) bwin[slot(BW) * 6 + wtl] = k + BW < nrows ? sr[W * 36 + wtl] : 0.0;
         }
-        STAMP(0);
         // ---- phase 1: L_{k+w,k} = A_{k+w,k} S_k^{-1}   (w = 1 on wave 0, w >= 2 on the workers)
         if (crit) {
             if (lnl < 36 && wmax >= 1) {
@@ -354,9 +348,7 @@ __device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int 
                 }
             }
         }
-        STAMP(1);
         lds_barrier();
-        STAMP(2);
         // ---- phase 2 (the worker waves first put row k+W+1 in flight)
         if (!crit) stage_row(k + W + 1, sB, wv_s - 1, lnl);  // (row k+BW's buffer: consumed at the top)
         if (crit) {
@@ -424,7 +416,6 @@ __device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int 
                 const double *cs = stg(sW) + BW * 36;  // row k+W
                 ((double2 *)(col + ((size_t)(kb ^ 1) * W + BW) * 36))[wtl] = ((const double2 *)cs)[wtl];
             }
-            STAMP(5);
             // b_i -= L_ik y_k for w >= 2 (last worker wave)
             {
                 const int t2 = NW - 1 - wtl;  // 0.. on the last wave
@@ -436,7 +427,6 @@ __device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int 
                     bwin[slot(wr) * 6 + r] -= sacc;
                 }
             }
-            STAMP(6);
             if (kR == R - 1 || k == nsteps - 1) {  // flush the staged steps k0..k to global
                 const int k0 = k - kR;
                 const int cnt = kR + 1;
@@ -457,14 +447,11 @@ __device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int 
                     g.zb[(size_t)k0 * 6 + t2] = ringZ[(sl >= RK ? sl - RK : sl) * 6 + t2 % 6];
                 }
             }
-            STAMP(7);
             // the staged row lands before the barrier (issued at the start of this phase; read at
             // the top of step k+2)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        STAMP(3);
         lds_barrier();
-        STAMP(4);
         sk = (sk + 1 == W) ? 0 : sk + 1;
         sB = (sB + 1 == kBandStage) ? 0 : sB + 1;
         sW = (sW + 1 == kBandStage) ? 0 : sW + 1;
@@ -472,10 +459,6 @@ __device__ __forceinline__ bool band_forward(const BandSeg &g, double *lds, int 
         kRK = (kRK + 1 == RK) ? 0 : kRK + 1;
         oo = (oo == 0) ? oCl - 1 : oo - 1;
     }
-#ifdef PLBA_STAMPS
-    if (stamps && (tid & 63) == 0)
-        for (int q = 0; q < 8; ++q) atomicAdd(&stamps[(tid >> 6) * 8 + q], st_acc[q]);
-#endif
     __syncthreads();  // drains every wave's flush stores: the backward pass reads them
     const bool failed = s_fail != 0;
     if (g.sep && !failed) {  // rows nsteps..nsteps+BW-1, blocks w <= row (later columns) and their right-hand sides
@@ -770,7 +753,7 @@ __global__ __launch_bounds__(band_nt(BW)) void k_rcs_factor_band(Dev d0) {
     TRIAL_SLOT(blockIdx.y)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const BandSeg g{d.Bd, d.bs, d.Lband, d.Kinv, d.zb, d.nf, d.nf, nullptr};
-    const bool fail = band_forward<BW>(g, lds, d.ring, d.stamps) || diag_fail(d);
+    const bool fail = band_forward<BW>(g, lds, d.ring) || diag_fail(d);
     if (threadIdx.x == 0) *d.solve_okp = fail ? 0 : 1;
     if (!fail && threadIdx.x < 64) {
         double *col, *piv, *bwin, *Lcol, *Kv, *xr, *part, *ys, *ringL, *ringK, *ringZ;
@@ -799,20 +782,7 @@ __device__ __forceinline__ void k_rcs_factor_twisted_body(const Dev &d) {
     const int m = d.tw_m, n1 = d.nf - BW - d.tw_m;
     const BandSeg g = seg == 0 ? BandSeg{d.Bd, d.bs, d.Lband, d.Kinv, d.zb, d.nf, m, d.tw_sep}
                                : BandSeg{d.Bd2, d.bs2, d.Lband2, d.Kinv2, d.zb2, d.nf, n1, d.tw_sep + sep_stride};
-#ifdef PLBA_STAMPS
-    unsigned long long tw_t0 = __builtin_readcyclecounter();
-#endif
-    const bool fail = band_forward<BW>(g, lds, d.ring, seg == 0 ? d.stamps : nullptr) || diag_fail(d);
-#ifdef PLBA_STAMPS
-    unsigned long long tw_t1 = __builtin_readcyclecounter();
-#define TW_MARK(q, t)                                                     \
-    do {                                                                  \
-        if (tid == 0) atomicAdd(&d.stamps[16 * 8 + (q)], (t));            \
-    } while (0)
-    if (seg == 0) TW_MARK(0, tw_t1 - tw_t0); else TW_MARK(1, tw_t1 - tw_t0);
-#else
-#define TW_MARK(q, t) do {} while (0)
-#endif
+    const bool fail = band_forward<BW>(g, lds, d.ring) || diag_fail(d);
     // hand-off (MI355X_MICROARCH.md §Workgroup dispatch…, counter form): every wave drains its
     // L / z / separator stores, one agent release by lane 0, then the arrival counter; the
     // workgroup whose add returns 1 is last and acquires once before reading the other's data
@@ -892,9 +862,6 @@ __device__ __forceinline__ void k_rcs_factor_twisted_body(const Dev &d) {
     }
     if (tid == 0) s_sfail = 0;
     __syncthreads();
-#ifdef PLBA_STAMPS
-    TW_MARK(5, __builtin_readcyclecounter() - tw_t1);  // hand-off + separator assembly
-#endif
     for (int P = 0; P < BW; ++P) {
         const double *colP = colA + (size_t)(P & 1) * BW * 36;
         if (own && oJ == P && oI > P) {  // rows oh..oh+UR-1 of L_IP = A_IP S_PP⁻¹ (S symmetric: S⁻¹ a_r)
@@ -962,10 +929,6 @@ __device__ __forceinline__ void k_rcs_factor_twisted_body(const Dev &d) {
         if (f && (tid & 63) == 0) s_sfail = 1;
     }
     __syncthreads();
-#ifdef PLBA_STAMPS
-    unsigned long long tw_t2 = __builtin_readcyclecounter();
-    TW_MARK(2, tw_t2 - tw_t1);
-#endif
     if (!s_sfail) {
     // back substitution x_P = S_PP⁻¹ y_P − Σ_{I>P} L_IPᵀ x_I, right-looking: x_I is final once the
     // blocks below it are done, and its contribution is removed from every P < I in one pass.
@@ -1004,13 +967,8 @@ __device__ __forceinline__ void k_rcs_factor_twisted_body(const Dev &d) {
     }
     __syncthreads();
     for (int t = tid; t < d.nf * 6; t += NT) d.xp[t] = xl[t];
-#ifdef PLBA_STAMPS
-    if (tid == 0) TW_MARK(3, __builtin_readcyclecounter() - tw_t2);
-    if (tid == 0) TW_MARK(4, 1);
-#endif
     }  // separator solved
     }  // both segments eliminated
-#undef TW_MARK
     __syncthreads();
     if (tid == 0) *d.solve_okp = s_sfail ? 0 : 1;
     pose_update_wg<NT>(d, s_sfail != 0);  // applied even after a failed solve, with the previous x_p (A13)

@@ -54,8 +54,7 @@ __host__ __device__ constexpr size_t cl_lds_doubles(int bw) {
 // `fail` is uniform on wave 0 (a zero pivot was met). The critical wave issues no global
 // memory operation (no vmcnt waits on the chain); workers stream rows bw+2 steps ahead.
 template <int BW>
-__device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, bool load_window, double *lds, bool &fail,
-                                           unsigned long long *stamps = nullptr) {
+__device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, bool load_window, double *lds, bool &fail) {
     constexpr int W = BW + 1, W1 = BW + 2, NT = kClNT, NW = NT - 64, PD = kClPD;
     constexpr int XS = W * 36 + 6;                  // X buffer: W blocks + z
     constexpr int NPT6 = (BW - 1) * BW / 2 * 6;     // trailing (block pair, row) tasks
@@ -123,11 +122,6 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
 #pragma unroll
     for (int u = 0; u < PD; ++u) prefetch(k0 + u, wpf[u]);
     if (__builtin_amdgcn_readfirstlane(tid) < 64) __builtin_amdgcn_s_setprio(3);
-#ifdef PLBA_STAMPS
-    unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long st_last;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last)::"memory");
-#endif
     for (int kb = k0; kb < k1; kb += PD) {
 #pragma unroll
         for (int u = 0; u < PD; ++u) {
@@ -144,7 +138,6 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
                     for (int r = 0; r < 6; ++r) pA[cs * 36 + cc * 6 + r] = v[r];
                 }
                 double a1[36];
-                STAMP(0);
                 // B: every lane factors S_k = A_{k,k} (the pivot group's just-published columns) in
                 // its own registers and applies S_k⁻¹ to its own column (X_i = L_{i,k}ᵀ, z_k on the
                 // rhs lane). Replaces a Gauss–Jordan across the lanes whose 72 v_readlane a step were
@@ -168,7 +161,6 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
 #pragma unroll
                 for (int q = 0; q < 36; ++q) a1[q] = pA[s1 * 36 + q];
                 __builtin_amdgcn_sched_barrier(0);
-                STAMP(1);
                 // C: publish X_i = L_{i,k}ᵀ (lane 6s+c holds row c of L_{i,k}) and z_k
                 if (clane && cs != sk) {
 #pragma unroll
@@ -182,9 +174,7 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
 #pragma unroll
                     for (int r = 0; r < 6; ++r) X[W * 36 + r] = v[r];
                 }
-                STAMP(2);
                 lds_barrier();
-                STAMP(3);
                 // E/F: column k+1 through step k. Lane group s now stands for row
                 // i = k+1 + ((s - s1) mod W); the pivot's group takes the new bottom block
                 // (k+1+bw, k+1), resident since the workers' previous step.
@@ -208,10 +198,8 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
 #pragma unroll
                     for (int r = 0; r < 6; ++r) v[r] = o[r] - acc[r];
                 }
-                STAMP(4);
             } else {
                 lds_barrier();
-                STAMP(3);
                 // block row k+2+bw enters slot lk (row k is consumed)
                 if (wt < NROW) {
                     const double val = k + 2 + BW < nrows ? wpf[u] : 0.0;
@@ -219,7 +207,6 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
                     else bwin[lk * 6 + (wt - W * 36)] = val;
                 }
                 prefetch(k + PD, wpf[u]);
-                STAMP(4);
                 // trailing update A_ij -= L_ik A_jkᵀ, k+2 <= j <= i <= k+bw (row p_a of the block)
                 if (k + p_wi < nrows) {
                     int si = sk + p_wi, sj = sk + p_wj, li = lk + p_wi;
@@ -239,7 +226,6 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
                         dst[b] -= acc;
                     }
                 }
-                STAMP(5);
                 // b_i -= A_ik z_k, k+2 <= i <= k+bw
                 if (k + r_wi < nrows) {
                     int si = sk + r_wi, li = lk + r_wi;
@@ -250,7 +236,6 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
                     for (int m = 0; m < 6; ++m) acc = fma(pA[si * 36 + r_a * 6 + m], X[W * 36 + m], acc);
                     bwin[li * 6 + r_a] -= acc;
                 }
-                STAMP(6);
                 // flush L_{k+w,k} (w = 1..bw) and z_k to HBM
                 if (fl < BW * 36) {
                     const int w = 1 + fl / 36, e = fl % 36, i = k + w;
@@ -262,16 +247,11 @@ __device__ __forceinline__ void cl_forward(const BandSeg &g, int k0, int k1, boo
                 } else if (fl < NFL) {
                     g.zb[(size_t)k * 6 + (fl - BW * 36)] = X[W * 36 + (fl - BW * 36)];
                 }
-                STAMP(7);
             }
             sk = s1;
             lk = l1;
         }
     }
-#ifdef PLBA_STAMPS
-    if (stamps && (tid & 63) == 0)
-        for (int q = 0; q < 8; ++q) atomicAdd(&stamps[(tid >> 6) * 8 + q], st_acc[q]);
-#endif
     __syncthreads();
     // column k1 (through step k1-1) lives in the critical wave's registers: write it back
     if (k1 < nrows) {
@@ -346,22 +326,10 @@ __global__ __launch_bounds__(kClNT) void k_rcs_factor_twisted_cl(Dev d0) {
         const size_t sep_stride = (size_t)BW * W * 36 + (size_t)BW * 6;
         double *sep0 = d.tw_sep, *sep1 = d.tw_sep + sep_stride;
         bool fail = false;
-#if defined(PLBA_STAMPS) || defined(PLBA_PHASE_STAMPS)  // (phase marks alone: no per-step stamps)
-        unsigned long long t0 = __builtin_readcyclecounter();
-#define CL_MARK(q)                                                                       \
-    do {                                                                                 \
-        const unsigned long long t1 = __builtin_readcyclecounter();                      \
-        if (tid == 0) atomicAdd(&d.stamps[16 * 8 + (q)], t1 - t0);                        \
-        t0 = t1;                                                                         \
-    } while (0)
-#else
-#define CL_MARK(q) do {} while (0)
-#endif
         const BandSeg g = seg == 0 ? BandSeg{d.Bd, d.bs, d.Lband, nullptr, d.zb, m + BW, m, nullptr}
                                    : BandSeg{d.Bd2, d.bs2, d.Lband2, nullptr, d.zb2, n1 + BW, n1, nullptr};
         const int mine = seg == 0 ? m : n1;
-        cl_forward<BW>(g, 0, mine, true, lds, fail, seg == 0 ? d.stamps : nullptr);
-        CL_MARK(seg);
+        cl_forward<BW>(g, 0, mine, true, lds, fail);
         cl_store_sep<BW>(lds, mine, seg == 0 ? sep0 : sep1);
         // the separator rows' original band A_sep (the merge subtracts it), loaded while the stores
         // drain, so the last arriver's merge takes one global round trip instead of two or three
@@ -435,10 +403,8 @@ __global__ __launch_bounds__(kClNT) void k_rcs_factor_twisted_cl(Dev d0) {
             }
         }
         __syncthreads();
-        CL_MARK(2);
         bool fail2 = false;
         cl_forward<BW>(g0, m, m + BW, false, lds, fail2);
-        CL_MARK(3);
         if (tid == 0) {
             if (fail2 || diag_fail(d)) s_fail = 1;
             *d.solve_okp = s_fail ? 0 : 1;
@@ -457,8 +423,6 @@ __global__ __launch_bounds__(kClNT) void k_rcs_factor_twisted_cl(Dev d0) {
             else if (tid < 128) band_backward_rl<BW, true>(d.Lband2, d.zb2, n1, n1 + BW, xsr, xl, true, d.nf, tid - 64);
             __syncthreads();
             for (int t = tid; t < d.nf * 6; t += kClNT) d.xp[t] = xl[t];
-            CL_MARK(4);
-            CL_MARK(5);  // (count: one unit of t1 - t0 ~ 0 is not a count; see stamp_diag.py)
         }
         __syncthreads();
         pose_update_wg<kClNT>(d, s_fail != 0);  // applied even after a failed solve, with the previous x_p (A13)

@@ -217,15 +217,6 @@ __device__ __forceinline__ void ldl6_solve(const double (&l)[36], const double (
         for (int q = i + 1; q < 6; ++q) v[i] = fma(-l[q * 6 + i], v[q], v[i]);
 }
 
-// PLBA_DIAG bit 8 (diagnostics only): per-workgroup phase timestamps (s_memrealtime, 100 MHz)
-// into bcr_stamps[m][kBcrStamps]; read with plba_debug_bcr_stamps / tools/bcr_stamps.py
-constexpr int kBcrStamps = 32;
-#define BCR_STAMP(slot)                                                                          \
-    do {                                                                                         \
-        if ((d.diag & 8) && threadIdx.x == 0)                                                    \
-            d.bcr_stamps[(size_t)m * kBcrStamps + (slot)] = __builtin_amdgcn_s_memrealtime();         \
-    } while (0)
-
 // tile index of Gram block (u, v), u >= v
 __device__ __forceinline__ int gtile(int u, int v) { return u * (u + 1) / 2 + v; }
 
@@ -258,7 +249,6 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
         const bool root = m == 0;
         const int lm = root ? L : __builtin_ctz(m);
         const bool hasU = !root, hasC = !root && m + (1 << lm) < N;
-        BCR_STAMP(0);
         // ---- D_m (lower blocks; diagonal blocks full), b_m and, for odd m, the band couplings
         //      U = A(m, m-1), V = A(m, m+1); rows past nf are identity / zero. Every global load of
         //      a thread is issued before its LDS stores.
@@ -303,7 +293,6 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
         }
         for (int t = tid; t < S * WS; t += NT) Wm[t] = 0.0;
         __syncthreads();
-        BCR_STAMP(1);
         // ---- survivor phases: contributions of the neighbours eliminated at levels < lm. Every
         //      sc1 load of a phase is issued before the first use (no per-element round trip).
         double fail_in = 0.0;  // failure words flowing in (forward)
@@ -367,7 +356,6 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
             if (tid < S) Rm[tid * RS + 2 * S] -= gba + gbb;
             if (tid == 0) fail_in += fa + fb;
             __syncthreads();
-            BCR_STAMP(2 + lp);
         }
         // ---- elimination of super-row m: block LDLᵀ of D_m with 6x6 pivots, [U | V | b] carried
         //      as right-hand sides. Step k: W(k, ·) = P_k⁻¹ M(k, ·) (one thread per column), then
@@ -400,7 +388,7 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
             // A2: W(k, col) = P_k⁻¹ M(k, col) for the D columns of later blocks and the active R
             // columns (P_k factors broadcast from LDS)
             const int nWd = S - 6 * (k + 1);
-            if (tid < nWd + nU + nV + 1 && !(d.diag & 32)) {  // (diag 32/16: timing experiments only)
+            if (tid < nWd + nU + nV + 1) {
                 double v[6];
                 int col;
                 if (tid < nWd) {
@@ -425,7 +413,7 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
                 for (int q = 0; q < 6; ++q) Wm[(6 * k + q) * WS + col] = v[q];
             }
             __syncthreads();
-            if (k + 1 < BW && !(d.diag & 16)) {
+            if (k + 1 < BW) {
                 const double *Wk = Wm + (size_t)(6 * k) * WS;
                 if (tid >= NTW) {
                     // lookahead: the next pivot block P_{k+1} = D(k+1,k+1) - D(k+1,k) W(k,k+1), one
@@ -517,10 +505,8 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
                 }
             }
             __syncthreads();
-            BCR_STAMP(20 + k);
         }
         if (fail) s_fail = 1;  // (benign race: every writer stores 1)
-        BCR_STAMP(12);
         const uint32_t epoch = s_epoch;
         __syncthreads();
         const double fail_fwd = fail_in + (s_fail ? 1.0 : 0.0);  // meaningful on tid 0
@@ -551,7 +537,6 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
             if (tid == 0) st_sc1(pub + (size_t)BCR_T16(BW) * BCR_T16(BW) * 256, fail_fwd);
             bcr_publish(&d.bcr_flag[2 * m], epoch);
         }
-        BCR_STAMP(13);
         // ---- X = D_m⁻¹ RHS (block back substitution, right-looking, into Rm) for the active
         //      columns; x_m = X_b - X_U x_a - X_V x_c once the neighbours are solved
         const int ncol = nU + nV + 1;
@@ -572,7 +557,6 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
             }
             __syncthreads();
         }
-        BCR_STAMP(14);
         // ---- X = D_m⁻¹ [U | V | b] for the backward kernel (split mode); the root holds the solution
         //      x_0 itself. Fused mode (default): X stays in Rm and this workgroup back-substitutes its
         //      own super-row below, so X never goes through memory and the second launch is gone.
@@ -595,7 +579,6 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
             }
             bcr_publish(&d.bcr_flag[1], epoch);
         }
-        BCR_STAMP(16);
         if (fused) {
             // ---- back substitution of this super-row: x_m = X_b - X_U x_a - X_V x_c once the
             //      neighbours (higher levels: later tickets, co-resident by the selection rule — a
@@ -697,7 +680,6 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
             const double ssum = block_sum<NT>(sc, s_sum);
             if (tid == 0) d.part_ps[m] = ssum;
         }
-        BCR_STAMP(18);
         // ---- arrival: the last workgroup resets the ticket counter for the next launch (fused: and
         //      advances the epoch, as the backward launch's last workgroup does in split mode)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -710,7 +692,6 @@ __global__ __launch_bounds__(kBcrNT) void k_rcs_factor_bcr(Dev d0) {
                 if (fused) __hip_atomic_store(&d.bcr_ctl[0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        BCR_STAMP(17);
     }
 }
 

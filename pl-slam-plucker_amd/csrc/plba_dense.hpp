@@ -30,12 +30,6 @@ namespace plba {
 constexpr int kFacThreads = 1024;
 constexpr int kSolveLdsN = 6144;  // y held in (dynamic) LDS up to this n (48 KiB), in Wbuf beyond
 constexpr int kSolveTilesLds = 256;  // tile_first staged in LDS for the first 256 tiles
-// PLBA_DIAG bit 8 (diagnostics only): phase timestamps of the dense solve (slots 12-15)
-#define SOLVE_STAMP(slot)                                                                         \
-    do {                                                                                         \
-        if ((d.diag & 8) && d.bcr_stamps && blockIdx.x == 0 && threadIdx.x == 0)                 \
-            d.bcr_stamps[slot] = __builtin_amdgcn_s_memrealtime();                              \
-    } while (0)
 // ---- solve L D Lᵀ x = b_s through the envelope-aware dense factor in Ad (unit L below the
 // diagonal, D on it), tile by tile; one workgroup of kFacThreads. x -> xp.
 // Forward: wave 0 solves the diagonal tile (its row of L in registers, y_j broadcast by
@@ -67,7 +61,6 @@ __device__ __forceinline__ void dense_solve_wg(const Dev &d) {
         const int fend = min(n, (d.tile_last[K] + 1) * kTile);
         const int i1 = k0 + kb + tid - 64;  // this thread's first row of the update
         double cf[kTile];
-        if (K == 5) SOLVE_STAMP(16);
         if (tid < 64) {
             double yi = (tid < kb) ? y[k0 + tid] : 0.0;
             // loads at clamped (always valid) addresses, selected after: no per-element branches
@@ -81,14 +74,12 @@ __device__ __forceinline__ void dense_solve_wg(const Dev &d) {
                 if (tid > j && tid < kb) yi -= l[j] * yj;
             }
             if (tid < kb) y[k0 + tid] = yi;
-            if (K == 5) SOLVE_STAMP(17);
         } else {
             const double *row = Ad + (size_t)min(i1, n - 1) + (size_t)k0 * n;
 #pragma unroll
             for (int p = 0; p < kTile; ++p) cf[p] = row[(size_t)min(p, kb - 1) * n];
         }
         __syncthreads();
-        if (K == 5) SOLVE_STAMP(18);
         if (tid >= 64) {
             if (i1 < fend && tile_first(i1 / kTile) <= K) {
                 double s = 0.0;
@@ -105,11 +96,9 @@ __device__ __forceinline__ void dense_solve_wg(const Dev &d) {
             }
         }
         __syncthreads();
-        if (K == 5) SOLVE_STAMP(19);
     }
     for (int i = tid; i < n; i += kFacThreads) y[i] = y[i] / Ad[(size_t)i + (size_t)i * n];
     __syncthreads();
-    SOLVE_STAMP(13);
     // backward: Lᵀ x = y, tile by tile from the bottom
     for (int K = nt - 1; K >= 0; --K) {
         const int k0 = K * kTile, kb = min(kTile, n - k0);
@@ -267,7 +256,9 @@ __global__ __launch_bounds__(kFacThreads) void k_rcs_factor(Dev d0) {
 
 constexpr int kDT = 32;            // tile
 constexpr int kDensePanelNT = 64;  // one wave: two row tiles per workgroup
-// PLBA_DIAG bit 8 (diagnostics only): phase timestamps of panel / update K = 5, workgroup 0
+// Retired phase mark of k_dense_panel (PLBA_DIAG bit 8, which read_tuning masks off: never taken).
+// Kept in that kernel alone because its instruction schedule depends on it: without the marks the
+// panel launch measured 31.6 -> 32.3 us at C3 (forced dense).
 #define DENSE_STAMP(slot)                                                                                   \
     do {                                                                                                   \
         if ((d.diag & 8) && K == 5 && blockIdx.x == ((slot) < 8 ? 1u : 0u) && threadIdx.x == 0)           \
@@ -356,7 +347,7 @@ __global__ __launch_bounds__(kDensePanelNT) void k_dense_panel(Dev d, int K) {
     for (int c = 1; c < kDT; ++c)
 #pragma unroll
         for (int p = 0; p < c; ++p) a[c] -= a[p] * readlane_f64(t[p], c);  // L[c][p]
-    DENSE_STAMP(5);  // (the compiler sinks part of the solve past this stamp)
+    DENSE_STAMP(5);  // (the compiler sinks part of the solve past this mark)
     if (!live) return;
     // W_IK = L_IK·D_K into Wbuf column-major ([kTile][n]: a lane per row, coalesced) and L_IK
 #pragma unroll
@@ -367,6 +358,7 @@ __global__ __launch_bounds__(kDensePanelNT) void k_dense_panel(Dev d, int K) {
         }
     DENSE_STAMP(6);
 }
+#undef DENSE_STAMP
 
 // trailing tile index t -> (I, J) with K < J <= I < nt, row-major over the lower triangle
 __device__ __forceinline__ void dense_tile_of(int t, int K, int &I, int &J) {
@@ -380,7 +372,6 @@ __device__ __forceinline__ void dense_tile_of(int t, int K, int &I, int &J) {
 
 __global__ __launch_bounds__(64) void k_dense_update(Dev d, int K) {
     TRIAL_GUARD
-    DENSE_STAMP(8);
     if (d.ctrl->solve_ok[0] == 0) return;
     __shared__ double Ws[kDT][kDT + 1];  // W_IK rows
     __shared__ double Ls[kDT][kDT + 1];  // L_JK rows
@@ -410,7 +401,6 @@ __global__ __launch_bounds__(64) void k_dense_update(Dev d, int K) {
         Ls[p][rr] = (j0 + p < n && rr < kb) ? lv[u] : 0.0;
     }
     __syncthreads();
-    DENSE_STAMP(9);
     dbl4 acc[2][2];
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi)
@@ -427,7 +417,6 @@ __global__ __launch_bounds__(64) void k_dense_update(Dev d, int K) {
         acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
         acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
     }
-    DENSE_STAMP(10);
     if (I == J && lane < kDT && i0 + lane < n) {
         // forward substitution of rows I against tile K: y_I -= L_IK·y_K (Ls holds L_IK here),
         // summed in column order like the single-workgroup solve
@@ -463,6 +452,14 @@ __global__ __launch_bounds__(64) void k_dense_update(Dev d, int K) {
             }
 }
 
+// Retired phase mark (PLBA_DIAG bit 8, which read_tuning masks off: never taken, bcr_stamps is
+// null). Kept in k_dense_solve alone because the register allocation depends on it: without the
+// three marks the kernel spills six more VGPRs (scratch 196 -> 204 bytes a lane).
+#define SOLVE_STAMP(slot)                                                                         \
+    do {                                                                                         \
+        if ((d.diag & 8) && d.bcr_stamps && blockIdx.x == 0 && threadIdx.x == 0)                 \
+            d.bcr_stamps[slot] = __builtin_amdgcn_s_memrealtime();                              \
+    } while (0)
 // forward / backward substitution through the dense factor + pose update (one workgroup)
 __global__ __launch_bounds__(kFacThreads) void k_dense_solve(Dev d0) {
     TRIAL_SLOT(0)
@@ -477,5 +474,6 @@ __global__ __launch_bounds__(kFacThreads) void k_dense_solve(Dev d0) {
     pose_update_wg<kFacThreads>(d, !ok);  // applied even after a failed solve, with the previous x_p (A13)
     SOLVE_STAMP(15);
 }
+#undef SOLVE_STAMP
 
 }  // namespace plba

@@ -144,7 +144,6 @@ struct Dev {
     int32_t bw, band_mode;              // bandwidth in pose blocks; 1 = banded factorisation
     int32_t dense_mfma;                 // dense RCS on many workgroups + MFMA (plba_dense.hpp)
     int32_t ring;                       // steps of L / S^-1 / z staged in LDS between global flushes
-    unsigned long long *stamps;         // diagnostic build only (PLBA_STAMPS): per-phase cycle sums
     int32_t *first_blk;                 // [nf] first block column of each block row (lower)
     double *Bd;                         // [nf][bw+1][36]  block (i, i-w), row-major 6x6
     double *Lband;                      // [nf][bw+1][36]  L_{i,i-w} (w >= 1)
@@ -192,7 +191,8 @@ struct Dev {
     double *gat;                        // [n_lm_g*4 + 3*E_g] final gather buffer
     // two-sided banded factorisation (k_rcs_factor_twisted)
     int32_t cl;                         // column-lane factorisation (plba_band_cl.hpp)
-    int32_t diag;                       // PLBA_DIAG timing-experiment bits (0 in every real run)
+    int32_t diag;                       // PLBA_DIAG test bits (0 in every real run): 64 times out every
+                                        // BCR hand-off (bcr_poll), 128 fails factorisations by λ (diag_fail)
     int32_t twisted, tw_m;              // enabled; rows 0..tw_m-1 top-down, separator tw_m..tw_m+bw-1
     double *Bd2, *bs2;                  // block-reversed band / rhs (row r' = nf-1-i)
     double *Lband2, *Kinv2, *zb2;       // factors of the bottom segment (reversed numbering)
@@ -207,8 +207,8 @@ struct Dev {
     double *bcr_X;                      // [N][6 bw][12 bw + 1] X = D_m⁻¹[U | V | b] (forward -> backward)
     uint32_t *bcr_flag;                 // [N][2] forward / backward hand-off flags (epoch)
     uint32_t *bcr_ctl;                  // [kBcrCtl] epoch, forward arrivals / tickets, backward arrivals / tickets
-    unsigned long long *bcr_stamps;     // [N][32] phase timestamps (PLBA_DIAG bit 8 only)
-    int64_t bcr_sl[6];                  // per trial slot strides of bcr_pub, _x, _X, _flag, _ctl, _stamps
+    unsigned long long *bcr_stamps;     // never allocated: target of the retired phase marks kept in plba_dense.hpp
+    int64_t bcr_sl[5];                  // per trial slot strides of bcr_pub, _x, _X, _flag, _ctl
 };
 
 
@@ -281,7 +281,6 @@ __device__ __forceinline__ Dev slot_view(const Dev &d0, int s) {
             d.bcr_X += ss * d0.bcr_sl[2];
             d.bcr_flag += ss * d0.bcr_sl[3];
             d.bcr_ctl += ss * d0.bcr_sl[4];
-            d.bcr_stamps += ss * d0.bcr_sl[5];
         }
         d.part_lm += ss * sl_lms(d0);
         d.part_lms += ss * sl_lms(d0);
@@ -352,20 +351,6 @@ __device__ __forceinline__ bool arrive_last(int32_t *counter, int32_t total) {
     __syncthreads();
     return s_last_arrival != 0;
 }
-
-#ifdef PLBA_STAMPS
-#define STAMP(slot)                                                                         \
-    do {                                                                                    \
-        __builtin_amdgcn_sched_barrier(0);                                                  \
-        unsigned long long _t;                                                              \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");          \
-        __builtin_amdgcn_sched_barrier(0);                                                  \
-        if ((threadIdx.x & 63) == 0) { st_acc[slot] += _t - st_last; }                      \
-        st_last = _t;                                                                       \
-    } while (0)
-#else
-#define STAMP(slot) do {} while (0)
-#endif
 
 // Wave-level LDS ordering: this wave's LDS writes are complete and visible to its other lanes.
 // Unlike a wavefront fence it does not wait for global loads/stores (vmcnt), so prefetches and

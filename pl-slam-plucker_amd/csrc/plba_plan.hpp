@@ -44,7 +44,8 @@ struct Tuning {
     bool host_build = false;    // PLBA_HOST_BUILD: window structure built on the host. bitwise
     bool timing = false;        // PLBA_TIMING: upload / schedule phase log on stderr. bitwise
     bool timing_any = false;    //   (set at all: the device build's stage log too)
-    int diag = 0;               // PLBA_DIAG=<mask> (set at all): timing experiments, WRONG results
+    int diag = 0;               // PLBA_DIAG=<mask> (set at all), tests only: 64 times out every BCR hand-off,
+                                //   128 fails factorisations as a function of λ; other bits are ignored
 };
 
 inline Tuning read_tuning() {
@@ -75,7 +76,7 @@ inline Tuning read_tuning() {
     t.host_build = flag("PLBA_HOST_BUILD");
     t.timing = flag("PLBA_TIMING");
     t.timing_any = getenv("PLBA_TIMING") != nullptr;
-    if (const char *e = getenv("PLBA_DIAG")) t.diag = atoi(e);
+    if (const char *e = getenv("PLBA_DIAG")) t.diag = atoi(e) & (64 | 128);
     return t;
 }
 

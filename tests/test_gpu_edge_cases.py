@@ -180,6 +180,7 @@ ENV_SWITCHES = [
     ({"PLBA_FACTOR": "band"}, False),           # 16-wave band kernel
     ({"PLBA_NO_TWIST": "1"}, False),
     ({"PLBA_SPEC": "1"}, True),                # one trial slot
+    ({"PLBA_DIAG": "63"}, True),               # retired timing bits: ignored
 ]
 
 
