@@ -124,9 +124,11 @@ def test_hlm_rerun_is_bitwise_deterministic(solver):
 GBA_CASES = [("C1L", {}), ("C2", {}), ("C2", {"lambda0": 1e-7, "err_per_obs": 1}),
              # λ0 = 1e-24: a non-positive landmark pivot fails the solve (X unchanged), as the
              # oracle's unpivoted LDLᵀ fails on its exactly zero one. With the
-             # reference's infinite error only: with a finite one the second linearisation's
-             # error change (unchanged X, poses re-derived from x) is 1-2 ulp against GBA's
-             # DBL_EPSILON stop test, so whether a second (failing) solve runs is rounding
+             # reference's infinite error only. With a finite one, on C1 (no lines) the second
+             # linearisation's error change (unchanged X, poses re-derived from x) is 1-2 ulp
+             # against GBA's DBL_EPSILON stop test, so whether a second (failing) solve runs is
+             # rounding; on C1L and C2 the aliased endpoint reads raise err by ~0.01, the second
+             # solve fails too and is a rejection: test_gpu_hlm_cases.py, "reject with failed solves"
              ("C1", {"lambda0": 1e-24}), ("C1L", {"lambda0": 1e-24}), ("C2", {"lambda0": 1e-24}),
              ("C3", {"max_iters": 6}),
              ("C3", {}), ("C4", {}), ("C4", {"lambda0": 1e-7, "err_per_obs": 1, "max_iters": 8})]
