@@ -1,10 +1,12 @@
 // plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose,
-// the two descriptor matchers, the stereo and the keyframe association, the median descriptor and place recognition. They share nothing
-// with the solver (no Dev, no step graph, no window arena), so they are a translation unit of their
-// own: an edit to a matcher does not rebuild the factorisation kernels. Each call is one upload, its
-// kernels and one read-back through a ScratchBlock. A Staged (csrc/plba_layout.hpp) lays the block
-// out: the call declares each array once, by its kernel-struct field, role, count and host source or
-// destination; stage() then fills the pinned image and the fields, fetch() delivers the outputs.
+// the two descriptor matchers, the stereo and the keyframe association, the median descriptor and
+// place recognition. They share nothing with the solver (no Dev, no step graph, no window arena), so
+// they are a translation unit of their own: an edit to a matcher does not rebuild the factorisation
+// kernels. Each call is one upload, its kernels and one read-back through a ScratchBlock. A Staged
+// (csrc/plba_layout.hpp) lays the block out: the call declares each array once, by its kernel-struct
+// field, role, count and host source or destination; stage() then fills the pinned image and the
+// fields, fetch() delivers the outputs. The two association calls run in phases (validate, plan,
+// fill, launch, scatter) over a plan of csrc/plba_assoc_plan.hpp, which needs no device.
 // The extern "C" symbols are forwarders in plba.hip.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +22,7 @@
 #include "plba_kfassoc.hpp"
 #include "plba_bow.hpp"
 #include "plba_medoid.hpp"
+#include "plba_assoc_plan.hpp"
 #include "plba_scratch.hpp"
 
 namespace plba {
@@ -49,6 +52,23 @@ int check_offsets(CtxBase *ctx, const char *op, const char *kind, const char *un
             return PLBA_E_INVALID;
         }
         if (max_span) *max_span = std::max(*max_span, off[k + 1] - off[k]);
+    }
+    return PLBA_OK;
+}
+
+// Every coordinate of `rows` rows of PER values (x, y[, x, y]) lies at most one image size outside the
+// image, which bounds the walk of a rasterised line.
+// "<op>: coordinate V of <side> <kind> row K is not finite or outside [A, B]"
+template <typename T, int PER>
+int check_coords(CtxBase *ctx, const char *op, const char *side, const char *kind, const T *c, size_t rows, double width,
+                 double height) {
+    for (size_t e = 0; e < rows * PER; ++e) {
+        const double v = c[e], size = (e & 1) ? height : width;
+        if (!(v >= -size && v <= 2.0 * size)) {  // false for NaN
+            ctx->set_error("%s: coordinate %g of %s %s row %zu is not finite or outside [%g, %g]", op, v, side, kind, e / PER,
+                           -size, 2.0 * size);
+            return PLBA_E_INVALID;
+        }
     }
     return PLBA_OK;
 }
@@ -96,6 +116,27 @@ int grid_launch(CtxBase *ctx, const GmDev &D, int max_train) {
         PLBA_LAUNCHED(ctx, "k_grid_cols");
     }
     hipLaunchKernelGGL(k_grid_rows, dim3(n), dim3(kGmRowsNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_grid_rows");
+    return PLBA_OK;
+}
+
+// the arrays of a GmDev that the struct O owns (an StDev or a KfDev, whose kernels make the cells)
+template <typename Owner>
+void grid_bind(GmDev &D, const Owner &O) {
+    D.off1 = O.off1; D.off2 = O.off2; D.kind = O.kind;
+    D.cell1 = O.cell1; D.cell1e = O.cell1e; D.cell_off2 = O.cell_off2; D.cells2 = O.cells2; D.dir2 = O.dir2;
+}
+
+// The brute-force matcher's device side on a DmDev that is bound and has its scalars: k_desc_nn over
+// both directions of every pair, then k_desc_cross
+int desc_launch(CtxBase *ctx, const DmDev &M, int max_rows) {
+    hipStream_t s = ctx->stream;
+    if (max_rows > 0) {  // a workgroup past its pair's rows in its direction, or of a pair that its gate switches off, returns at once
+        const dim3 grid(M.n, (max_rows + kDmNT - 1) / kDmNT, 2);
+        if (M.dwords <= 8) hipLaunchKernelGGL(k_desc_nn<8>, grid, dim3(kDmNT), 0, s, M);
+        else hipLaunchKernelGGL(k_desc_nn<16>, grid, dim3(kDmNT), 0, s, M);
+        PLBA_LAUNCHED(ctx, "k_desc_nn");
+    }
+    hipLaunchKernelGGL(k_desc_cross, dim3(M.n), dim3(kDmNT), 0, s, M); PLBA_LAUNCHED(ctx, "k_desc_cross");
     return PLBA_OK;
 }
 
@@ -201,17 +242,10 @@ int desc_match(CtxBase *ctx, const plba_match_batch *b, int32_t *matches_12, int
     if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
     B.stage(ctx->match.host, ctx->match.dev);
     if (const int rc = upload(ctx, ctx->match, B)) return rc;
-    hipStream_t s = ctx->stream;
     D.n = n;
     D.dwords = b->desc_bytes / 4;
     D.best_lr = b->best_lr != 0;
-    if (max_rows > 0) {  // a workgroup past its pair's rows in its direction returns at once
-        const dim3 grid(n, (max_rows + kDmNT - 1) / kDmNT, 2);
-        if (D.dwords <= 8) hipLaunchKernelGGL(k_desc_nn<8>, grid, dim3(kDmNT), 0, s, D);
-        else hipLaunchKernelGGL(k_desc_nn<16>, grid, dim3(kDmNT), 0, s, D);
-        PLBA_LAUNCHED(ctx, "k_desc_nn");
-    }
-    hipLaunchKernelGGL(k_desc_cross, dim3(n), dim3(kDmNT), 0, s, D); PLBA_LAUNCHED(ctx, "k_desc_cross");
+    if (const int rc = desc_launch(ctx, D, max_rows)) return rc;
     if (const int rc = read_back(ctx, ctx->match, B)) return rc;
     B.fetch();
     return PLBA_OK;
@@ -315,14 +349,13 @@ int grid_match(CtxBase *ctx, const plba_gridmatch_batch *b, int32_t *matches_12,
 // of frames: one upload, k_stereo_cells, the matcher's three launches with the window
 // (matching_s_ws, 0, 0, 0), k_stereo_gate (csrc/plba_stereo.hpp), one read-back. Frame f is the
 // matcher's problems 2 f (points) and 2 f + 1 (lines).
-int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp, const plba_stereo_out *out) {
+namespace {
+
+// everything that refuses the call, and the table; no device call
+int stereo_validate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp, const plba_stereo_out *out,
+                    ProblemTable &T) {
     const char *const op = "stereo association";
-    if (!b || b->n < 0) {
-        ctx->set_error("stereo association: NULL batch or n < 0");
-        return PLBA_E_INVALID;
-    }
     const int n = b->n;
-    if (n == 0) return PLBA_OK;
     if (n > (INT32_MAX - 1) / 2) {
         ctx->set_error("stereo association: %d frames", n);
         return PLBA_E_INVALID;
@@ -340,143 +373,98 @@ int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo
     }
     for (const int32_t *off : {b->pt_off_l, b->pt_off_r, b->ls_off_l, b->ls_off_r})
         if (const int rc = check_offsets(ctx, op, "row", "frame", off, n)) return rc;
-    // the rows of each side, counted from the first frame's offset
-    const int32_t *const offs[2][2] = {{b->pt_off_l, b->pt_off_r}, {b->ls_off_l, b->ls_off_r}};
-    size_t cnt[2][2];
-    for (int kd = 0; kd < 2; ++kd)
-        for (int sd = 0; sd < 2; ++sd) cnt[kd][sd] = (size_t)(offs[kd][sd][n] - offs[kd][sd][0]);
-    const size_t N1 = cnt[0][0] + cnt[1][0], N2 = cnt[0][1] + cnt[1][1], db = (size_t)b->desc_bytes, dw = db / 4;
-    const int stride = std::max(prm.cols, prm.rows);
-    const size_t nc = cnt[0][1] + cnt[1][1] * (size_t)stride;
-    if (N1 > (size_t)INT32_MAX || N2 > (size_t)INT32_MAX || nc > (size_t)INT32_MAX) {
-        ctx->set_error("stereo association: %zu left rows, %zu right rows or %zu cells are more than %d", N1, N2, nc, INT32_MAX);
+    const int bad = T.init(b->pt_off_l, b->pt_off_r, b->ls_off_l, b->ls_off_r, n, prm.cols, prm.rows);
+    if (bad == T.kTooMany) {
+        ctx->set_error("stereo association: %zu left rows, %zu right rows or %zu cells are more than %d", T.N1, T.N2, T.nc, INT32_MAX);
         return PLBA_E_INVALID;
     }
-    if ((cnt[0][0] && (!b->pt_l || !b->pdesc_l)) || (cnt[0][1] && (!b->pt_r || !b->pdesc_r)) ||
-        (cnt[1][0] && (!b->ls_l || !b->ldesc_l)) || (cnt[1][1] && (!b->ls_r || !b->ldesc_r))) {
+    if ((T.cnt[0][0] && (!b->pt_l || !b->pdesc_l)) || (T.cnt[0][1] && (!b->pt_r || !b->pdesc_r)) ||
+        (T.cnt[1][0] && (!b->ls_l || !b->ldesc_l)) || (T.cnt[1][1] && (!b->ls_r || !b->ldesc_r))) {
         ctx->set_error("stereo association: NULL coordinate or descriptor array");
         return PLBA_E_INVALID;
     }
-    int max_rows = 0, max_train = 0;
-    for (int f = 0; f < n; ++f)
-        for (int kd = 0; kd < 2; ++kd) {
-            const int r1 = offs[kd][0][f + 1] - offs[kd][0][f], r2 = offs[kd][1][f + 1] - offs[kd][1][f];
-            max_rows = std::max(max_rows, std::max(r1, r2));
-            max_train = std::max(max_train, r2);
-        }
-    if (max_train > kGmMaxTrain) {  // the low 16 bits of a key
-        ctx->set_error("stereo association: %d right rows in a problem are more than %d", max_train, kGmMaxTrain);
+    if (bad == T.kTooWide) {
+        ctx->set_error("stereo association: %d right rows in a problem are more than %d", T.max_train, kGmMaxTrain);
         return PLBA_E_INVALID;
     }
-    // a coordinate at most one image size outside the image: the bound of a right line's walk
+    // the bound of a right line's walk
     const float *const coords[2][2] = {{b->pt_l, b->pt_r}, {b->ls_l, b->ls_r}};
     for (int kd = 0; kd < 2; ++kd)
         for (int sd = 0; sd < 2; ++sd) {
-            if (!cnt[kd][sd]) continue;
-            const int per = kd ? 4 : 2;
-            const float *c = coords[kd][sd] + (size_t)per * offs[kd][sd][0];
-            for (size_t e = 0; e < cnt[kd][sd] * per; ++e) {
-                const double v = c[e], size = (e & 1) ? prm.height : prm.width;
-                if (!(v >= -size && v <= 2.0 * size)) {  // false for NaN
-                    ctx->set_error("stereo association: coordinate %g of %s %s row %zu is not finite or outside [%g, %g]", v,
-                                   sd ? "right" : "left", kd ? "line" : "point", e / per, -size, 2.0 * size);
-                    return PLBA_E_INVALID;
-                }
-            }
+            const size_t rows = T.cnt[kd][sd];
+            if (!rows) continue;
+            const float *c = coords[kd][sd] + (size_t)(kd ? 4 : 2) * T.offs[kd][sd][0];
+            const char *const side = sd ? "right" : "left";
+            if (const int rc = kd ? check_coords<float, 4>(ctx, op, side, "line", c, rows, prm.width, prm.height)
+                                  : check_coords<float, 2>(ctx, op, side, "point", c, rows, prm.width, prm.height))
+                return rc;
         }
-    (void)hipSetDevice(ctx->opts.device);
-    const int np = 2 * n;
-    const size_t P = (size_t)np;
-    // the matcher's arrays are bound in S where the stereo kernels use them too, and handed to D below;
-    // the inputs are all filled here, problem by problem
-    StDev S{};
-    GmDev D{};
-    Staged B;
-    B.in(S.off1, P + 1);
-    B.in(S.off2, P + 1);
-    B.in(S.kind, P);
-    B.in(S.kbase, P);
-    B.in(S.cbase, P + 1);
-    B.in(D.ws, 4 * P);
-    B.in(D.nnr, P);
-    B.in(D.sim_th, P);
-    B.in(S.desc1, dw * N1);
-    B.in(D.desc2, dw * N2);
-    B.in(S.co1, 4 * N1);
-    B.in(S.co2, 4 * N2);
-    B.out(S.count, P);  // the outputs are scattered to the caller's arrays below
-    B.out(S.src, N1);
-    B.out(S.odesc, dw * N1);
-    B.out(S.ptd, kStPtDoubles * cnt[0][0]);
-    B.out(S.lsd, kStLsDoubles * cnt[1][0]);
-    const size_t o_best = B.dev(D.best, N1);
-    B.dev(D.second, N1);
-    const size_t key_bytes = B.mark() - o_best;  // the two key arrays start as kGmNone
-    B.dev(D.m12, N1);
-    B.dev(D.m21, N2);
-    B.dev(D.count, P);
-    B.dev(S.cell1, 2 * N1);
-    B.dev(S.cell1e, 2 * N1);
-    B.dev(S.cell_off2, N2 + 1);
-    B.dev(S.cells2, 2 * nc);
-    B.dev(S.dir2, 2 * N2);
-    if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
-    B.stage(ctx->match.host, ctx->match.dev);
-    int32_t *off1 = B.host(S.off1), *off2 = B.host(S.off2), *kind = B.host(S.kind), *kbase = B.host(S.kbase),
-            *cbase = B.host(S.cbase), *ws = B.host(D.ws);
-    double *nnr = B.host(D.nnr), *sim_th = B.host(D.sim_th);
-    uint8_t *const desc_h[2] = {(uint8_t *)B.host(S.desc1), (uint8_t *)B.host(D.desc2)};
-    float *const co_h[2] = {B.host(S.co1), B.host(S.co2)};
+    return PLBA_OK;
+}
+
+// the inputs into the staged image, problem by problem
+void stereo_fill(const StereoPlan &P, const plba_stereo_batch *b, const plba_stereo_params &prm) {
+    const ProblemTable &T = P.T;
+    const Staged &B = P.B;
     const uint8_t *const descs[2][2] = {{b->pdesc_l, b->pdesc_r}, {b->ldesc_l, b->ldesc_r}};
-    off1[0] = off2[0] = cbase[0] = 0;
-    for (int p = 0; p < np; ++p) {
-        const int f = p / 2, kd = p % 2, per = kd ? 4 : 2;
-        const int a1 = offs[kd][0][f], r1 = offs[kd][0][f + 1] - a1, a2 = offs[kd][1][f], r2 = offs[kd][1][f + 1] - a2;
-        kind[p] = kd;
-        kbase[p] = a1 - offs[kd][0][0];
-        off1[p + 1] = off1[p] + r1;
-        off2[p + 1] = off2[p] + r2;
-        cbase[p + 1] = cbase[p] + r2 * (kd ? stride : 1);
+    const float *const coords[2][2] = {{b->pt_l, b->pt_r}, {b->ls_l, b->ls_r}};
+    int32_t *off1 = B.host(P.S.off1), *off2 = B.host(P.S.off2), *ws = B.host(P.D.ws);
+    T.fill(off1, off2, B.host(P.S.kind), B.host(P.S.kbase), nullptr, B.host(P.S.cbase), descs, (size_t)b->desc_bytes,
+           (uint8_t *)B.host(P.S.desc1), (uint8_t *)B.host(P.D.desc2));
+    double *nnr = B.host(P.D.nnr), *sim_th = B.host(P.D.sim_th);
+    float *const co_h[2] = {B.host(P.S.co1), B.host(P.S.co2)};
+    for (int p = 0; p < 2 * T.n; ++p) {
+        const ProblemTable::Problem q = T.at(p);
+        const int per = q.kind ? 4 : 2;
         ws[4 * p] = prm.matching_s_ws;  // w.width = (matchingSWs, 0), w.height = (0, 0) (:142-144)
         ws[4 * p + 1] = ws[4 * p + 2] = ws[4 * p + 3] = 0;
         nnr[p] = prm.min_ratio_12_p;  // matching.cpp:160, :241: for lines too
         sim_th[p] = prm.line_sim_th;
-        if (r1) memcpy(desc_h[0] + db * off1[p], descs[kd][0] + db * a1, db * r1);
-        if (r2) memcpy(desc_h[1] + db * off2[p], descs[kd][1] + db * a2, db * r2);
         for (int sd = 0; sd < 2; ++sd) {
-            const int a = sd ? a2 : a1, r = sd ? r2 : r1;
+            const int a = sd ? q.a2 : q.a1, r = sd ? q.r2 : q.r1;
             float *dst = co_h[sd] + 4 * (size_t)(sd ? off2[p] : off1[p]);
-            const float *src = coords[kd][sd];
+            const float *src = coords[q.kind][sd];
             for (int i = 0; i < r; ++i)
                 for (int e = 0; e < 4; ++e) dst[4 * i + e] = e < per ? src[(size_t)per * (a + i) + e] : 0.0f;
         }
     }
-    if (const int rc = upload(ctx, ctx->match, B)) return rc;
+}
+
+// the scalars of both structs, the matcher's arrays handed over from S, and the five launches
+int stereo_launch(CtxBase *ctx, StereoPlan &P, int desc_bytes, const plba_stereo_params &prm) {
+    StDev &S = P.S;
+    GmDev &D = P.D;
+    const int np = 2 * P.T.n, max_rows = P.T.max_rows;
     hipStream_t s = ctx->stream;
     S.m12 = D.m12;
     S.inv_w = prm.cols / (double)prm.width;   // :47-48
     S.inv_h = prm.rows / (double)prm.height;
-    S.dwords = b->desc_bytes / 4;
-    S.stride = stride;
+    S.dwords = desc_bytes / 4;
+    S.stride = P.T.stride;
     S.prm = prm;
-    D.off1 = S.off1; D.off2 = S.off2; D.kind = S.kind; D.desc1 = S.desc1;
-    D.cell1 = S.cell1; D.cell1e = S.cell1e; D.cell_off2 = S.cell_off2; D.cells2 = S.cells2; D.dir2 = S.dir2;
-    if (const int rc = grid_prepare(ctx, D, np, b->desc_bytes, prm.cols, prm.rows, prm.best_lr, key_bytes)) return rc;
+    grid_bind(D, S);
+    D.desc1 = S.desc1;
+    if (const int rc = grid_prepare(ctx, D, np, desc_bytes, prm.cols, prm.rows, prm.best_lr, P.key_bytes)) return rc;
     if (max_rows > 0) {  // a thread past its problem's rows does nothing
         hipLaunchKernelGGL(k_stereo_cells, dim3(np, (max_rows + kStNT - 1) / kStNT), dim3(kStNT), 0, s, S);
         PLBA_LAUNCHED(ctx, "k_stereo_cells");
     }
-    if (const int rc = grid_launch(ctx, D, max_train)) return rc;
+    if (const int rc = grid_launch(ctx, D, P.T.max_train)) return rc;
     hipLaunchKernelGGL(k_stereo_gate, dim3(np), dim3(kStNT), 0, s, S); PLBA_LAUNCHED(ctx, "k_stereo_gate");
-    if (const int rc = read_back(ctx, ctx->match, B)) return rc;
-    // the first count[p] rows of each problem, to the frame's left offset in the caller's arrays
-    const int32_t *count = B.host(S.count), *src = B.host(S.src);
-    const double *ptd = B.host(S.ptd), *lsd = B.host(S.lsd);
-    const uint8_t *odesc_h = (const uint8_t *)B.host(S.odesc);
-    for (int p = 0; p < np; ++p) {
-        const int f = p / 2, kd = p % 2, k = count[p], a1 = offs[kd][0][f];
-        if (k < 0 || k > off1[p + 1] - off1[p]) {
-            ctx->set_error("stereo association: the device returned %d survivors for %d rows", k, off1[p + 1] - off1[p]);
+    return PLBA_OK;
+}
+
+// the first count[p] rows of each problem, to the frame's left offset in the caller's arrays
+int stereo_scatter(CtxBase *ctx, const StereoPlan &P, size_t db, int pluker, const plba_stereo_out *out) {
+    const Staged &B = P.B;
+    const int32_t *count = B.host(P.S.count), *src = B.host(P.S.src), *off1 = B.host(P.S.off1), *kbase = B.host(P.S.kbase);
+    const double *ptd = B.host(P.S.ptd), *lsd = B.host(P.S.lsd);
+    const uint8_t *odesc_h = (const uint8_t *)B.host(P.S.odesc);
+    for (int p = 0; p < 2 * P.T.n; ++p) {
+        const ProblemTable::Problem q = P.T.at(p);
+        const int f = q.f, kd = q.kind, k = count[p], a1 = q.a1;
+        if (k < 0 || k > q.r1) {
+            ctx->set_error("stereo association: the device returned %d survivors for %d rows", k, q.r1);
             return PLBA_E_DEVICE;
         }
         (kd ? out->n_ls : out->n_pt)[f] = k;
@@ -501,10 +489,31 @@ int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo
             cols_out(out->ls_sP, lsd, kStLsDoubles, 6, 3);
             cols_out(out->ls_eP, lsd, kStLsDoubles, 9, 3);
             cols_out(out->ls_le, lsd, kStLsDoubles, 12, 3);
-            if (prm.pluker) cols_out(out->ls_NDc, lsd, kStLsDoubles, 15, 6);
+            if (pluker) cols_out(out->ls_NDc, lsd, kStLsDoubles, 15, 6);
         }
     }
     return PLBA_OK;
+}
+
+}  // namespace
+
+int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp, const plba_stereo_out *out) {
+    if (!b || b->n < 0) {
+        ctx->set_error("stereo association: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    if (b->n == 0) return PLBA_OK;
+    StereoPlan P;
+    if (const int rc = stereo_validate(ctx, b, pp, out, P.T)) return rc;
+    (void)hipSetDevice(ctx->opts.device);
+    P.declare((size_t)b->desc_bytes / 4);
+    if (const int rc = ctx->match.reserve(*ctx, P.B.total(), P.B.outputs_end(), "stereo association")) return rc;
+    P.B.stage(ctx->match.host, ctx->match.dev);
+    stereo_fill(P, b, *pp);
+    if (const int rc = upload(ctx, ctx->match, P.B)) return rc;
+    if (const int rc = stereo_launch(ctx, P, b->desc_bytes, *pp)) return rc;
+    if (const int rc = read_back(ctx, ctx->match, P.B)) return rc;
+    return stereo_scatter(ctx, P, (size_t)b->desc_bytes, pp->pluker, out);
 }
 
 // ---------------------------------------------------------------- keyframe-to-keyframe association
@@ -513,14 +522,13 @@ int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo
 // launches with the window (ws, ws, ws, ws), the brute-force matcher's two, gated per problem on the
 // device by the grid count, k_kf_geom (csrc/plba_kfassoc.hpp), one read-back. Pair f is the matcher's
 // problems 2 f (points) and 2 f + 1 (lines).
-int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *pp, const plba_kfassoc_out *out) {
+namespace {
+
+// everything that refuses the call, and the table; no device call
+int kf_validate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *pp, const plba_kfassoc_out *out,
+                ProblemTable &T) {
     const char *const op = "keyframe association";
-    if (!b || b->n < 0) {
-        ctx->set_error("keyframe association: NULL batch or n < 0");
-        return PLBA_E_INVALID;
-    }
     const int n = b->n;
-    if (n == 0) return PLBA_OK;
     if (n > (INT32_MAX - 1) / 2) {
         ctx->set_error("keyframe association: %d pairs", n);
         return PLBA_E_INVALID;
@@ -539,36 +547,21 @@ int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_p
     }
     for (const int32_t *off : {b->pt_off_p, b->pt_off_c, b->ls_off_p, b->ls_off_c})
         if (const int rc = check_offsets(ctx, op, "row", "pair", off, n)) return rc;
-    // the rows of each side, counted from the first pair's offset
-    const int32_t *const offs[2][2] = {{b->pt_off_p, b->pt_off_c}, {b->ls_off_p, b->ls_off_c}};
-    size_t cnt[2][2];
-    for (int kd = 0; kd < 2; ++kd)
-        for (int sd = 0; sd < 2; ++sd) cnt[kd][sd] = (size_t)(offs[kd][sd][n] - offs[kd][sd][0]);
-    const size_t N1 = cnt[0][0] + cnt[1][0], N2 = cnt[0][1] + cnt[1][1], db = (size_t)b->desc_bytes, dw = db / 4;
-    const int stride = std::max(prm.cols, prm.rows);
-    const size_t nc = cnt[0][1] + cnt[1][1] * (size_t)stride;
-    if (N1 > (size_t)INT32_MAX || N2 > (size_t)INT32_MAX || nc > (size_t)INT32_MAX) {
-        ctx->set_error("keyframe association: %zu previous rows, %zu current rows or %zu cells are more than %d", N1, N2, nc,
-                       INT32_MAX);
+    const int bad = T.init(b->pt_off_p, b->pt_off_c, b->ls_off_p, b->ls_off_c, n, prm.cols, prm.rows);
+    if (bad == T.kTooMany) {
+        ctx->set_error("keyframe association: %zu previous rows, %zu current rows or %zu cells are more than %d", T.N1, T.N2,
+                       T.nc, INT32_MAX);
         return PLBA_E_INVALID;
     }
-    if ((cnt[0][0] && (!b->pt_P_p || !b->pdesc_p)) || (cnt[0][1] && (!b->pt_pl_c || !b->pt_P_c || !b->pdesc_c)) ||
-        (cnt[1][0] && (!b->ls_sP_p || !b->ls_eP_p || !b->ls_NDc_p || !b->ls_spl_p || !b->ls_epl_p || !b->ldesc_p ||
-                       !b->ls_lm_NDw || !b->ls_new)) ||
-        (cnt[1][1] && (!b->ls_spl_c || !b->ls_epl_c || !b->ldesc_c))) {
+    if ((T.cnt[0][0] && (!b->pt_P_p || !b->pdesc_p)) || (T.cnt[0][1] && (!b->pt_pl_c || !b->pt_P_c || !b->pdesc_c)) ||
+        (T.cnt[1][0] && (!b->ls_sP_p || !b->ls_eP_p || !b->ls_NDc_p || !b->ls_spl_p || !b->ls_epl_p || !b->ldesc_p ||
+                         !b->ls_lm_NDw || !b->ls_new)) ||
+        (T.cnt[1][1] && (!b->ls_spl_c || !b->ls_epl_c || !b->ldesc_c))) {
         ctx->set_error("keyframe association: NULL feature or descriptor array");
         return PLBA_E_INVALID;
     }
-    int max_rows = 0, max_prev = 0, max_train = 0;
-    for (int f = 0; f < n; ++f)
-        for (int kd = 0; kd < 2; ++kd) {
-            const int r1 = offs[kd][0][f + 1] - offs[kd][0][f], r2 = offs[kd][1][f + 1] - offs[kd][1][f];
-            max_rows = std::max(max_rows, std::max(r1, r2));
-            max_prev = std::max(max_prev, r1);
-            max_train = std::max(max_train, r2);
-        }
-    if (max_train > kGmMaxTrain) {  // the low 16 bits of a key
-        ctx->set_error("keyframe association: %d current rows in a problem are more than %d", max_train, kGmMaxTrain);
+    if (bad == T.kTooWide) {
+        ctx->set_error("keyframe association: %d current rows in a problem are more than %d", T.max_train, kGmMaxTrain);
         return PLBA_E_INVALID;
     }
     const double *const poses[5] = {b->DT, b->T_prev, b->T_curr, b->Tcw_prev, b->Tcw_curr};
@@ -580,166 +573,114 @@ int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_p
                                e / (k ? 16 : 12));
                 return PLBA_E_INVALID;
             }
-    // a current coordinate at most one image size outside the image: the bound of a line's walk
+    // the bound of a current line's walk
     const double *const ccoords[3] = {b->pt_pl_c, b->ls_spl_c, b->ls_epl_c};
     for (int k = 0; k < 3; ++k) {
         const int kd = k ? 1 : 0;
-        if (!cnt[kd][1]) continue;
-        const double *c = ccoords[k] + 2 * (size_t)offs[kd][1][0];
-        for (size_t e = 0; e < 2 * cnt[kd][1]; ++e) {
-            const double v = c[e], size = (e & 1) ? prm.height : prm.width;
-            if (!(v >= -size && v <= 2.0 * size)) {  // false for NaN
-                ctx->set_error("keyframe association: coordinate %g of current %s row %zu is not finite or outside [%g, %g]", v,
-                               kd ? "line" : "point", e / 2, -size, 2.0 * size);
-                return PLBA_E_INVALID;
-            }
-        }
+        if (!T.cnt[kd][1]) continue;
+        const double *c = ccoords[k] + 2 * (size_t)T.offs[kd][1][0];
+        if (const int rc = check_coords<double, 2>(ctx, op, "current", kd ? "line" : "point", c, T.cnt[kd][1], prm.width, prm.height))
+            return rc;
     }
-    (void)hipSetDevice(ctx->opts.device);
-    const int np = 2 * n;
-    const size_t P = (size_t)np;
-    // the arrays that several kernels use are bound in K and handed to the matchers' structs below; the
-    // inputs are all filled here, problem by problem
-    KfDev K{};
-    GmDev D{};
-    DmDev M{};
-    Staged B;
-    B.in(K.off1, P + 1);
-    B.in(K.off2, P + 1);
-    B.in(K.kind, P);
-    B.in(K.kbase1, P);
-    B.in(K.kbase2, P);
-    B.in(K.cbase, P + 1);
-    B.in(K.gate_min, P);
-    B.in(D.ws, 4 * P);
-    B.in(D.nnr, P);
-    B.in(D.sim_th, P);
-    B.in(M.nnr, P);
-    B.in(K.pose, (size_t)kKfPoseDoubles * n);
-    B.in(D.desc1, dw * N1);
-    B.in(D.desc2, dw * N2);
-    B.in(K.q_pt, 3 * cnt[0][0]);
-    B.in(K.q_ls, kKfQLsDoubles * cnt[1][0]);
-    B.in(K.ls_new, cnt[1][0]);
-    B.in(K.t_pt, kKfTPtDoubles * cnt[0][1]);
-    B.in(K.t_ls, kKfTLsDoubles * cnt[1][1]);
-    B.out(K.res, 3 * P);  // the outputs are scattered to the caller's arrays below
-    B.out(K.m12, N1);
-    B.out(K.ptd, kKfPtDoubles * cnt[0][0]);
-    B.out(K.lsd, kKfLsDoubles * cnt[1][0]);
-    B.out(K.rej, cnt[1][0]);
-    const size_t o_best = B.dev(D.best, N1);
-    B.dev(D.second, N1);
-    const size_t key_bytes = B.mark() - o_best;  // the two key arrays start as kGmNone
-    B.dev(D.m12, N1);
-    B.dev(D.m21, N2);
-    B.dev(D.count, P);
-    B.dev(K.cell1, 2 * N1);
-    B.dev(K.cell1e, 2 * N1);
-    B.dev(K.cell_off2, N2 + 1);
-    B.dev(K.cells2, 2 * nc);
-    B.dev(K.dir2, 2 * N2);
-    B.dev(M.nn12, N1);
-    B.dev(M.nn21, N2);
-    B.dev(M.m12, N1);
-    B.dev(M.count, P);
-    if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
-    B.stage(ctx->match.host, ctx->match.dev);
-    int32_t *off1 = B.host(K.off1), *off2 = B.host(K.off2), *kind = B.host(K.kind), *kbase1 = B.host(K.kbase1),
-            *kbase2 = B.host(K.kbase2), *cbase = B.host(K.cbase), *gate_min = B.host(K.gate_min), *ws = B.host(D.ws);
-    double *nnr = B.host(D.nnr), *sim_th = B.host(D.sim_th), *pose = B.host(K.pose);
-    float *fnnr = B.host(M.nnr);
-    uint8_t *const desc_h[2] = {(uint8_t *)B.host(D.desc1), (uint8_t *)B.host(D.desc2)};
+    return PLBA_OK;
+}
+
+// the inputs into the staged image: the poses pair by pair, the matchers' inputs problem by problem, the rows
+void kf_fill(const KfPlan &P, const plba_kfassoc_batch *b, const plba_kfassoc_params &prm) {
+    const ProblemTable &T = P.T;
+    const Staged &B = P.B;
+    const double *const poses[5] = {b->DT, b->T_prev, b->T_curr, b->Tcw_prev, b->Tcw_curr};
     const uint8_t *const descs[2][2] = {{b->pdesc_p, b->pdesc_c}, {b->ldesc_p, b->ldesc_c}};
-    for (int f = 0; f < n; ++f) {
+    double *pose = B.host(P.K.pose);
+    for (int f = 0; f < T.n; ++f) {
         double *q = pose + (size_t)kKfPoseDoubles * f;
         memcpy(q, b->DT + 12 * (size_t)f, 12 * sizeof(double));
         for (int k = 1; k < 5; ++k) memcpy(q + 12 + 16 * (k - 1), poses[k] + 16 * (size_t)f, 16 * sizeof(double));
     }
-    off1[0] = off2[0] = cbase[0] = 0;
-    for (int p = 0; p < np; ++p) {
-        const int f = p / 2, kd = p % 2;
-        const int a1 = offs[kd][0][f], r1 = offs[kd][0][f + 1] - a1, a2 = offs[kd][1][f], r2 = offs[kd][1][f + 1] - a2;
-        const int min_matches = kd ? prm.min_ls_matches : prm.min_pt_matches;
-        kind[p] = kd;
-        kbase1[p] = a1 - offs[kd][0][0];
-        kbase2[p] = a2 - offs[kd][1][0];
-        off1[p + 1] = off1[p] + r1;
-        off2[p + 1] = off2[p] + r2;
-        cbase[p + 1] = cbase[p] + r2 * (kd ? stride : 1);
-        gate_min[p] = (r2 > min_matches && r1 > min_matches) ? min_matches : INT32_MIN;  // :277-279, :424-426
+    T.fill(B.host(P.K.off1), B.host(P.K.off2), B.host(P.K.kind), B.host(P.K.kbase1), B.host(P.K.kbase2), B.host(P.K.cbase),
+           descs, (size_t)b->desc_bytes, (uint8_t *)B.host(P.D.desc1), (uint8_t *)B.host(P.D.desc2));
+    int32_t *gate_min = B.host(P.K.gate_min), *ws = B.host(P.D.ws);
+    double *nnr = B.host(P.D.nnr), *sim_th = B.host(P.D.sim_th);
+    float *fnnr = B.host(P.M.nnr);
+    for (int p = 0; p < 2 * T.n; ++p) {
+        const ProblemTable::Problem q = T.at(p);
+        const int min_matches = q.kind ? prm.min_ls_matches : prm.min_pt_matches;
+        gate_min[p] = (q.r2 > min_matches && q.r1 > min_matches) ? min_matches : INT32_MIN;  // :277-279, :424-426
         for (int e = 0; e < 4; ++e) ws[4 * p + e] = prm.ws;  // :269-272, :416-419
         nnr[p] = prm.min_ratio_12_p;  // matching.cpp:160, :241: for lines too
         sim_th[p] = prm.line_sim_th;
-        fnnr[p] = (float)(kd ? prm.min_ratio_12_l : prm.min_ratio_12_p);  // :280, :427
-        if (r1) memcpy(desc_h[0] + db * off1[p], descs[kd][0] + db * a1, db * r1);
-        if (r2) memcpy(desc_h[1] + db * off2[p], descs[kd][1] + db * a2, db * r2);
+        fnnr[p] = (float)(q.kind ? prm.min_ratio_12_l : prm.min_ratio_12_p);  // :280, :427
     }
-    {  // the rows of each kind keep the caller's order from the first pair's offset
-        const size_t ap = (size_t)offs[0][0][0], al = (size_t)offs[1][0][0], cp = (size_t)offs[0][1][0], cl = (size_t)offs[1][1][0];
-        if (cnt[0][0]) memcpy(B.host(K.q_pt), b->pt_P_p + 3 * ap, 3 * cnt[0][0] * sizeof(double));
-        double *q = B.host(K.q_ls);
-        for (size_t i = 0; i < cnt[1][0]; ++i, q += kKfQLsDoubles) {
-            const size_t r = al + i;
-            memcpy(q, b->ls_sP_p + 3 * r, 3 * sizeof(double));
-            memcpy(q + 3, b->ls_eP_p + 3 * r, 3 * sizeof(double));
-            memcpy(q + 6, b->ls_NDc_p + 6 * r, 6 * sizeof(double));
-            memcpy(q + 12, b->ls_spl_p + 2 * r, 2 * sizeof(double));
-            memcpy(q + 14, b->ls_epl_p + 2 * r, 2 * sizeof(double));
-            memcpy(q + 16, b->ls_lm_NDw + 6 * r, 6 * sizeof(double));
-        }
-        if (cnt[1][0]) memcpy(B.host(K.ls_new), b->ls_new + al, cnt[1][0]);
-        double *t = B.host(K.t_pt);
-        for (size_t i = 0; i < cnt[0][1]; ++i, t += kKfTPtDoubles) {
-            memcpy(t, b->pt_pl_c + 2 * (cp + i), 2 * sizeof(double));
-            memcpy(t + 2, b->pt_P_c + 3 * (cp + i), 3 * sizeof(double));
-        }
-        t = B.host(K.t_ls);
-        for (size_t i = 0; i < cnt[1][1]; ++i, t += kKfTLsDoubles) {
-            memcpy(t, b->ls_spl_c + 2 * (cl + i), 2 * sizeof(double));
-            memcpy(t + 2, b->ls_epl_c + 2 * (cl + i), 2 * sizeof(double));
-        }
+    // the rows of each kind keep the caller's order from the first pair's offset
+    const size_t ap = (size_t)T.offs[0][0][0], al = (size_t)T.offs[1][0][0], cp = (size_t)T.offs[0][1][0], cl = (size_t)T.offs[1][1][0];
+    if (T.cnt[0][0]) memcpy(B.host(P.K.q_pt), b->pt_P_p + 3 * ap, 3 * T.cnt[0][0] * sizeof(double));
+    double *q = B.host(P.K.q_ls);
+    for (size_t i = 0; i < T.cnt[1][0]; ++i, q += kKfQLsDoubles) {
+        const size_t r = al + i;
+        memcpy(q, b->ls_sP_p + 3 * r, 3 * sizeof(double));
+        memcpy(q + 3, b->ls_eP_p + 3 * r, 3 * sizeof(double));
+        memcpy(q + 6, b->ls_NDc_p + 6 * r, 6 * sizeof(double));
+        memcpy(q + 12, b->ls_spl_p + 2 * r, 2 * sizeof(double));
+        memcpy(q + 14, b->ls_epl_p + 2 * r, 2 * sizeof(double));
+        memcpy(q + 16, b->ls_lm_NDw + 6 * r, 6 * sizeof(double));
     }
-    if (const int rc = upload(ctx, ctx->match, B)) return rc;
+    if (T.cnt[1][0]) memcpy(B.host(P.K.ls_new), b->ls_new + al, T.cnt[1][0]);
+    double *t = B.host(P.K.t_pt);
+    for (size_t i = 0; i < T.cnt[0][1]; ++i, t += kKfTPtDoubles) {
+        memcpy(t, b->pt_pl_c + 2 * (cp + i), 2 * sizeof(double));
+        memcpy(t + 2, b->pt_P_c + 3 * (cp + i), 3 * sizeof(double));
+    }
+    t = B.host(P.K.t_ls);
+    for (size_t i = 0; i < T.cnt[1][1]; ++i, t += kKfTLsDoubles) {
+        memcpy(t, b->ls_spl_c + 2 * (cl + i), 2 * sizeof(double));
+        memcpy(t + 2, b->ls_epl_c + 2 * (cl + i), 2 * sizeof(double));
+    }
+}
+
+// the scalars of the three structs, the matchers' arrays handed over from K, and the launches
+int kf_launch(CtxBase *ctx, KfPlan &P, int desc_bytes, const plba_kfassoc_params &prm) {
+    KfDev &K = P.K;
+    GmDev &D = P.D;
+    DmDev &M = P.M;
+    const int np = 2 * P.T.n, max_rows = P.T.max_rows;
     hipStream_t s = ctx->stream;
     K.gm12 = D.m12; K.gcount = D.count; K.fm12 = M.m12; K.fcount = M.count;
     K.inv_w = prm.cols / (double)prm.width;
     K.inv_h = prm.rows / (double)prm.height;
-    K.stride = stride;
+    K.stride = P.T.stride;
     K.prm = prm;
-    D.off1 = K.off1; D.off2 = K.off2; D.kind = K.kind;
-    D.cell1 = K.cell1; D.cell1e = K.cell1e; D.cell_off2 = K.cell_off2; D.cells2 = K.cells2; D.dir2 = K.dir2;
+    grid_bind(D, K);
     M.off1 = K.off1; M.off2 = K.off2; M.desc1 = D.desc1; M.desc2 = D.desc2;
     M.n = np;
-    M.dwords = b->desc_bytes / 4;
+    M.dwords = desc_bytes / 4;
     M.best_lr = prm.best_lr != 0;
     M.gate_count = D.count;
     M.gate_min = K.gate_min;
     if (prm.fast_matching) {
-        if (const int rc = grid_prepare(ctx, D, np, b->desc_bytes, prm.cols, prm.rows, prm.best_lr, key_bytes)) return rc;
+        if (const int rc = grid_prepare(ctx, D, np, desc_bytes, prm.cols, prm.rows, prm.best_lr, P.key_bytes)) return rc;
         if (max_rows > 0) {  // a thread past its problem's rows does nothing
             hipLaunchKernelGGL(k_kf_cells, dim3(np, (max_rows + kKfNT - 1) / kKfNT), dim3(kKfNT), 0, s, K);
             PLBA_LAUNCHED(ctx, "k_kf_cells");
         }
-        if (const int rc = grid_launch(ctx, D, max_train)) return rc;
+        if (const int rc = grid_launch(ctx, D, P.T.max_train)) return rc;
     } else {  // the grid count is 0 (:249)
-        PLBA_CHECK(hipMemsetAsync(D.count, 0, sizeof(int32_t) * P, s));
+        PLBA_CHECK(hipMemsetAsync(D.count, 0, sizeof(int32_t) * np, s));
     }
-    if (max_rows > 0) {  // a workgroup past its problem's rows in its direction, or of a problem that keeps its grid matches, returns at once
-        const dim3 grid(np, (max_rows + kDmNT - 1) / kDmNT, 2);
-        if (M.dwords <= 8) hipLaunchKernelGGL(k_desc_nn<8>, grid, dim3(kDmNT), 0, s, M);
-        else hipLaunchKernelGGL(k_desc_nn<16>, grid, dim3(kDmNT), 0, s, M);
-        PLBA_LAUNCHED(ctx, "k_desc_nn");
-    }
-    hipLaunchKernelGGL(k_desc_cross, dim3(np), dim3(kDmNT), 0, s, M); PLBA_LAUNCHED(ctx, "k_desc_cross");
-    hipLaunchKernelGGL(k_kf_geom, dim3(np, std::max(1, (max_prev + kKfNT - 1) / kKfNT)), dim3(kKfNT), 0, s, K);
+    if (const int rc = desc_launch(ctx, M, max_rows)) return rc;  // a problem that keeps its grid matches is gated off
+    hipLaunchKernelGGL(k_kf_geom, dim3(np, std::max(1, (P.T.max_prev + kKfNT - 1) / kKfNT)), dim3(kKfNT), 0, s, K);
     PLBA_LAUNCHED(ctx, "k_kf_geom");
-    if (const int rc = read_back(ctx, ctx->match, B)) return rc;
-    const int32_t *res = B.host(K.res), *m12 = B.host(K.m12);
-    const double *ptd = B.host(K.ptd), *lsd = B.host(K.lsd);
-    const uint8_t *rej = B.host(K.rej);
-    for (int p = 0; p < np; ++p) {
-        const int f = p / 2, kd = p % 2, a1 = offs[kd][0][f], r1 = off1[p + 1] - off1[p];
+    return PLBA_OK;
+}
+
+// every previous row's match and record, to the pair's previous offset in the caller's arrays
+int kf_scatter(CtxBase *ctx, const KfPlan &P, const plba_kfassoc_out *out) {
+    const Staged &B = P.B;
+    const int32_t *res = B.host(P.K.res), *m12 = B.host(P.K.m12), *off1 = B.host(P.K.off1), *kbase1 = B.host(P.K.kbase1);
+    const double *ptd = B.host(P.K.ptd), *lsd = B.host(P.K.lsd);
+    const uint8_t *rej = B.host(P.K.rej);
+    for (int p = 0; p < 2 * P.T.n; ++p) {
+        const ProblemTable::Problem q = P.T.at(p);
+        const int kd = q.kind, a1 = q.a1, r1 = q.r1;
         if (res[3 * p + 1] < 0 || res[3 * p + 1] > r1) {
             ctx->set_error("keyframe association: the device returned %d matches for %d rows", res[3 * p + 1], r1);
             return PLBA_E_DEVICE;
@@ -758,6 +699,27 @@ int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_p
         }
     }
     return PLBA_OK;
+}
+
+}  // namespace
+
+int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *pp, const plba_kfassoc_out *out) {
+    if (!b || b->n < 0) {
+        ctx->set_error("keyframe association: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    if (b->n == 0) return PLBA_OK;
+    KfPlan P;
+    if (const int rc = kf_validate(ctx, b, pp, out, P.T)) return rc;
+    (void)hipSetDevice(ctx->opts.device);
+    P.declare((size_t)b->desc_bytes / 4);
+    if (const int rc = ctx->match.reserve(*ctx, P.B.total(), P.B.outputs_end(), "keyframe association")) return rc;
+    P.B.stage(ctx->match.host, ctx->match.dev);
+    kf_fill(P, b, *pp);
+    if (const int rc = upload(ctx, ctx->match, P.B)) return rc;
+    if (const int rc = kf_launch(ctx, P, b->desc_bytes, *pp)) return rc;
+    if (const int rc = read_back(ctx, ctx->match, P.B)) return rc;
+    return kf_scatter(ctx, P, out);
 }
 
 // ---------------------------------------------------------------- median descriptor
@@ -790,10 +752,7 @@ int desc_medoid(CtxBase *ctx, int n, const int32_t *list_ptr, const uint8_t *des
     (void)hipSetDevice(ctx->opts.device);
     MedDev D{};
     Staged B;
-    B.in(D.list_ptr, (size_t)n + 1, list_ptr);
-    B.in(D.order, n);  // filled below
-    B.in(D.desc, dw * total, desc);
-    B.out(D.medoid, n, medoid);
+    medoid_plan(B, D, (size_t)n, total, dw, list_ptr, desc, medoid);
     if (const int rc = ctx->match.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
     B.stage(ctx->match.host, ctx->match.dev);
     int32_t *order = B.host(D.order);

@@ -1,0 +1,119 @@
+// plba_assoc_args.hpp — the kernel-argument structs of the matchers, the two association calls and the
+// median descriptor, with the constants their host side sizes blocks and grids by. Standard C++ only:
+// no HIP type, no kernel, so the host-only plans (csrc/plba_assoc_plan.hpp) and the layout test
+// (tests/cpp/layout_check.cpp) read what the kernels read. Each kernel header includes this one and
+// documents its fields' use.
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/plba.h"
+
+namespace plba {
+
+// ---------------------------------------------------------------- csrc/plba_match.hpp
+constexpr int kDmNT = 256;    // threads of a workgroup = query rows of a tile
+
+struct DmDev {
+    const int32_t *off1, *off2;   // [n+1] row ranges of each pair
+    const uint32_t *desc1, *desc2;  // [.][desc_bytes / 4]
+    const float *nnr;             // [n]
+    int32_t *nn12, *nn21;         // [off1[n]], [off2[n]] nearest row after the ratio test, or -1
+    int32_t *m12;                 // [off1[n]] matches_12
+    int32_t *count;               // [n]
+    int32_t n, dwords, best_lr;
+    // plba_kf_associate's fallback: a pair runs only if gate_count[pair] < gate_min[pair]; NULL: every pair
+    const int32_t *gate_count, *gate_min;
+};
+
+// ---------------------------------------------------------------- csrc/plba_gridmatch.hpp
+constexpr int kGmNT = 64;       // threads of a workgroup = train rows of a block (one wave)
+constexpr int kGmMaxTrain = 65535;         // i2 takes the key's low 16 bits
+
+struct GmDev {
+    const int32_t *off1, *off2;      // [n+1] row ranges of each problem
+    const uint32_t *desc1, *desc2;   // [.][desc_bytes / 4]
+    const int32_t *cell1, *cell1e;   // [off1[n]][2] query cell; second cell of a line query
+    const int32_t *cell_off2;        // [off2[n]+1] CSR over the train rows
+    const int32_t *cells2;           // [.][2]
+    const double *dir2;              // [off2[n]][2]
+    const int32_t *kind;             // [n]
+    const int32_t *ws;               // [n][4] window half-widths: left, right (x), up, down (y)
+    const double *nnr, *sim_th;      // [n]
+    uint32_t *best, *second;         // [off1[n]] smallest and second-smallest seen key of a row
+    int32_t *m21;                    // [off2[n]] matches_21 (best_lr)
+    int32_t *m12;                    // [off1[n]] matches_12
+    int32_t *count;                  // [n]
+    int32_t n, dwords, cols, rows, best_lr;
+};
+
+// ---------------------------------------------------------------- csrc/plba_stereo.hpp
+constexpr int kStNT = 256;  // threads of both kernels
+constexpr int kStPtDoubles = 6;    // a point record: pl[2], disp, P[3]
+constexpr int kStLsDoubles = 21;   // a line record: spl[2], epl[2], sdisp, edisp, sP[3], eP[3], le[3], NDc[6]
+
+struct StDev {
+    const int32_t *off1, *off2;    // [2n+1] left / right row ranges of each problem
+    const int32_t *kind;           // [2n] 0 points, 1 lines
+    const int32_t *kbase;          // [2n] first output record of the problem within its kind
+    const int32_t *cbase;          // [2n+1] first cell of the problem's right rows
+    const float *co1, *co2;        // [.][4] (x, y, -, -) of a point, (sx, sy, ex, ey) of a line
+    const uint32_t *desc1;         // [off1[2n]][dwords]
+    int32_t *cell1, *cell1e;       // [off1[2n]][2]
+    int32_t *cell_off2;            // [off2[2n]+1]
+    int32_t *cells2;               // [cbase[2n]][2]
+    double *dir2;                  // [off2[2n]][2]
+    const int32_t *m12;            // [off1[2n]] the matcher's result
+    int32_t *count;                // [2n] survivors
+    int32_t *src;                  // [off1[2n]] left index of each survivor, from off1[p]
+    uint32_t *odesc;               // [off1[2n]][dwords]
+    double *ptd, *lsd;             // point records [.][kStPtDoubles], line records [.][kStLsDoubles]
+    double inv_w, inv_h;           // cols / (double)width, rows / (double)height
+    int32_t dwords, stride;        // stride: cells of a right line, max(cols, rows)
+    plba_stereo_params prm;
+};
+
+// ---------------------------------------------------------------- csrc/plba_kfassoc.hpp
+constexpr int kKfNT = 256;  // threads of both kernels
+constexpr int kKfPtDoubles = 9;   // a point record: P3d[3], dir_prev[3], dir_curr[3]
+constexpr int kKfLsDoubles = 8;   // a line record: new_pluker_lw[6], |err_prev|, |err_curr|
+constexpr int kKfPoseDoubles = 76;  // a pair's poses: DT[12], T_prev, T_curr, Tcw_prev, Tcw_curr [16] each
+constexpr int kKfQLsDoubles = 22;   // a previous line row: sP[3], eP[3], NDc[6], spl[2], epl[2], lm_NDw[6]
+constexpr int kKfTPtDoubles = 5;    // a current point row: pl[2], P[3]
+constexpr int kKfTLsDoubles = 4;    // a current line row: spl[2], epl[2]
+
+struct KfDev {
+    const int32_t *off1, *off2;    // [2n+1] previous / current row ranges of each problem
+    const int32_t *kind;           // [2n] 0 points, 1 lines
+    const int32_t *kbase1, *kbase2;  // [2n] first previous / current row of the problem within its kind
+    const int32_t *cbase;          // [2n+1] first cell of the problem's current rows
+    const int32_t *gate_min;       // [2n] the fallback's bound on the grid count, or INT_MIN
+    const double *pose;            // [n][kKfPoseDoubles]
+    const double *q_pt, *q_ls;     // previous rows: [.][3], [.][kKfQLsDoubles]
+    const uint8_t *ls_new;         // [.] per previous line row
+    const double *t_pt, *t_ls;     // current rows: [.][kKfTPtDoubles], [.][kKfTLsDoubles]
+    int32_t *cell1, *cell1e;       // [off1[2n]][2]
+    int32_t *cell_off2;            // [off2[2n]+1]
+    int32_t *cells2;               // [cbase[2n]][2]
+    double *dir2;                  // [off2[2n]][2]
+    const int32_t *gm12, *gcount;  // the grid matcher's result
+    const int32_t *fm12, *fcount;  // the brute-force matcher's, where it ran
+    int32_t *res;                  // [2n][3] grid count, match count, fallback
+    int32_t *m12;                  // [off1[2n]]
+    double *ptd, *lsd;             // point records [.][kKfPtDoubles], line records [.][kKfLsDoubles]
+    uint8_t *rej;                  // [.] per previous line row
+    double inv_w, inv_h;           // cols / (double)width, rows / (double)height
+    int32_t stride, pad;           // stride: cells of a current line, max(cols, rows)
+    plba_kfassoc_params prm;
+};
+
+// ---------------------------------------------------------------- csrc/plba_medoid.hpp
+struct MedDev {
+    const int32_t *list_ptr;   // [n+1]
+    const uint32_t *desc;      // [list_ptr[n]][dwords]
+    const int32_t *order;      // [n] the short lists, then the long ones
+    int32_t *medoid;           // [n]
+    int32_t n, dwords, n_short, n_short_wg;
+};
+
+}  // namespace plba

@@ -36,33 +36,14 @@
 
 #include <limits.h>
 
-#include "../../include/plba.h"
+#include "plba_assoc_args.hpp"  // GmDev, kGmNT, kGmMaxTrain
 
 namespace plba {
 
-constexpr int kGmNT = 64;       // threads of a workgroup = train rows of a block (one wave)
 constexpr int kGmTile = 256;    // query rows staged through LDS at a time
 constexpr int kGmCells = 4096;   // in-grid cells of a block's train rows kept in LDS (64 rasterised lines fit)
 constexpr int kGmRowsNT = 256;  // threads of k_grid_rows
 constexpr uint32_t kGmNone = 0xFFFFFFFFu;  // no key: above every (d << 16) | i2
-constexpr int kGmMaxTrain = 65535;         // i2 takes the key's low 16 bits
-
-struct GmDev {
-    const int32_t *off1, *off2;      // [n+1] row ranges of each problem
-    const uint32_t *desc1, *desc2;   // [.][desc_bytes / 4]
-    const int32_t *cell1, *cell1e;   // [off1[n]][2] query cell; second cell of a line query
-    const int32_t *cell_off2;        // [off2[n]+1] CSR over the train rows
-    const int32_t *cells2;           // [.][2]
-    const double *dir2;              // [off2[n]][2]
-    const int32_t *kind;             // [n]
-    const int32_t *ws;               // [n][4] window half-widths: left, right (x), up, down (y)
-    const double *nnr, *sim_th;      // [n]
-    uint32_t *best, *second;         // [off1[n]] smallest and second-smallest seen key of a row
-    int32_t *m21;                    // [off2[n]] matches_21 (best_lr)
-    int32_t *m12;                    // [off1[n]] matches_12
-    int32_t *count;                  // [n]
-    int32_t n, dwords, cols, rows, best_lr;
-};
 
 // GridStructure::get's bounds (src2/gridStructure.cpp:67-71) for one axis with the two half-widths of
 // a GridWindow pair (w.width or w.height: below, above), [lo, hi) kept inside [0, size] so that an

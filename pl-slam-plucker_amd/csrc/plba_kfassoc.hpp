@@ -23,36 +23,9 @@
 
 #include <limits.h>
 
-#include "plba_kfassoc_geom.hpp"
+#include "plba_kfassoc_geom.hpp"  // and with it plba_assoc_args.hpp: KfDev, kKfNT
 
 namespace plba {
-
-constexpr int kKfNT = 256;  // threads of both kernels
-
-struct KfDev {
-    const int32_t *off1, *off2;    // [2n+1] previous / current row ranges of each problem
-    const int32_t *kind;           // [2n] 0 points, 1 lines
-    const int32_t *kbase1, *kbase2;  // [2n] first previous / current row of the problem within its kind
-    const int32_t *cbase;          // [2n+1] first cell of the problem's current rows
-    const int32_t *gate_min;       // [2n] the fallback's bound on the grid count, or INT_MIN
-    const double *pose;            // [n][kKfPoseDoubles]
-    const double *q_pt, *q_ls;     // previous rows: [.][3], [.][kKfQLsDoubles]
-    const uint8_t *ls_new;         // [.] per previous line row
-    const double *t_pt, *t_ls;     // current rows: [.][kKfTPtDoubles], [.][kKfTLsDoubles]
-    int32_t *cell1, *cell1e;       // [off1[2n]][2]
-    int32_t *cell_off2;            // [off2[2n]+1]
-    int32_t *cells2;               // [cbase[2n]][2]
-    double *dir2;                  // [off2[2n]][2]
-    const int32_t *gm12, *gcount;  // the grid matcher's result
-    const int32_t *fm12, *fcount;  // the brute-force matcher's, where it ran
-    int32_t *res;                  // [2n][3] grid count, match count, fallback
-    int32_t *m12;                  // [off1[2n]]
-    double *ptd, *lsd;             // point records [.][kKfPtDoubles], line records [.][kKfLsDoubles]
-    uint8_t *rej;                  // [.] per previous line row
-    double inv_w, inv_h;           // cols / (double)width, rows / (double)height
-    int32_t stride, pad;           // stride: cells of a current line, max(cols, rows)
-    plba_kfassoc_params prm;
-};
 
 __global__ __launch_bounds__(kKfNT) void k_kf_cells(KfDev D) {
     const int p = blockIdx.x, i = blockIdx.y * kKfNT + threadIdx.x;

@@ -11,12 +11,7 @@
 
 namespace plba {
 
-constexpr int kKfPtDoubles = 9;   // a point record: P3d[3], dir_prev[3], dir_curr[3]
-constexpr int kKfLsDoubles = 8;   // a line record: new_pluker_lw[6], |err_prev|, |err_curr|
-constexpr int kKfPoseDoubles = 76;  // a pair's poses: DT[12], T_prev, T_curr, Tcw_prev, Tcw_curr [16] each
-constexpr int kKfQLsDoubles = 22;   // a previous line row: sP[3], eP[3], NDc[6], spl[2], epl[2], lm_NDw[6]
-constexpr int kKfTPtDoubles = 5;    // a current point row: pl[2], P[3]
-constexpr int kKfTLsDoubles = 4;    // a current line row: spl[2], epl[2]
+// kKf*Doubles, the widths of its rows and records, are in csrc/plba_assoc_args.hpp
 constexpr int kKfNoCell = -(1 << 30);  // both coordinates of a cell that has no int value
 
 // t0 + (t1 + t2)

@@ -27,24 +27,11 @@
 
 #include <limits.h>
 
-#include "../../include/plba.h"
+#include "plba_assoc_args.hpp"  // DmDev, kDmNT
 
 namespace plba {
 
-constexpr int kDmNT = 256;    // threads of a workgroup = query rows of a tile
 constexpr int kDmTile = 256;  // train rows staged through LDS at a time
-
-struct DmDev {
-    const int32_t *off1, *off2;   // [n+1] row ranges of each pair
-    const uint32_t *desc1, *desc2;  // [.][desc_bytes / 4]
-    const float *nnr;             // [n]
-    int32_t *nn12, *nn21;         // [off1[n]], [off2[n]] nearest row after the ratio test, or -1
-    int32_t *m12;                 // [off1[n]] matches_12
-    int32_t *count;               // [n]
-    int32_t n, dwords, best_lr;
-    // plba_kf_associate's fallback: a pair runs only if gate_count[pair] < gate_min[pair]; NULL: every pair
-    const int32_t *gate_count, *gate_min;
-};
 
 // uniform over the workgroup: the pair is switched off by its gate
 __device__ inline bool dm_gated_off(const DmDev &D, int pair) {

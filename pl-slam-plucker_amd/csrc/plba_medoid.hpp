@@ -29,7 +29,7 @@
 
 #include <limits.h>
 
-#include "../../include/plba.h"
+#include "plba_assoc_args.hpp"  // MedDev
 
 namespace plba {
 
@@ -37,14 +37,6 @@ constexpr int kMedNT = 256;       // threads of a workgroup
 constexpr int kMedWaves = kMedNT / 64;
 constexpr int kMedShort = 64;     // rows of a list that one wave takes, a lane per row
 constexpr int kMedMaxN = PLBA_MEDOID_MAX_N;  // rows of the longest list (1024)
-
-struct MedDev {
-    const int32_t *list_ptr;   // [n+1]
-    const uint32_t *desc;      // [list_ptr[n]][dwords]
-    const int32_t *order;      // [n] the short lists, then the long ones
-    int32_t *medoid;           // [n]
-    int32_t n, dwords, n_short, n_short_wg;
-};
 
 // The k-th smallest (0-based) of d(q, row j), j < n, rows of W dwords at `rows`: rank selection by
 // bisection on the value, each probe one counting pass.

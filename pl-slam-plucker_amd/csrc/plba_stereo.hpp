@@ -23,32 +23,9 @@
 //                   its descriptor row.
 #pragma once
 
-#include "plba_stereo_geom.hpp"
+#include "plba_stereo_geom.hpp"  // and with it plba_assoc_args.hpp: StDev, kStNT
 
 namespace plba {
-
-constexpr int kStNT = 256;  // threads of both kernels
-
-struct StDev {
-    const int32_t *off1, *off2;    // [2n+1] left / right row ranges of each problem
-    const int32_t *kind;           // [2n] 0 points, 1 lines
-    const int32_t *kbase;          // [2n] first output record of the problem within its kind
-    const int32_t *cbase;          // [2n+1] first cell of the problem's right rows
-    const float *co1, *co2;        // [.][4] (x, y, -, -) of a point, (sx, sy, ex, ey) of a line
-    const uint32_t *desc1;         // [off1[2n]][dwords]
-    int32_t *cell1, *cell1e;       // [off1[2n]][2]
-    int32_t *cell_off2;            // [off2[2n]+1]
-    int32_t *cells2;               // [cbase[2n]][2]
-    double *dir2;                  // [off2[2n]][2]
-    const int32_t *m12;            // [off1[2n]] the matcher's result
-    int32_t *count;                // [2n] survivors
-    int32_t *src;                  // [off1[2n]] left index of each survivor, from off1[p]
-    uint32_t *odesc;               // [off1[2n]][dwords]
-    double *ptd, *lsd;             // point records [.][kStPtDoubles], line records [.][kStLsDoubles]
-    double inv_w, inv_h;           // cols / (double)width, rows / (double)height
-    int32_t dwords, stride;        // stride: cells of a right line, max(cols, rows)
-    plba_stereo_params prm;
-};
 
 __global__ __launch_bounds__(kStNT) void k_stereo_cells(StDev D) {
     const int p = blockIdx.x, i = blockIdx.y * kStNT + threadIdx.x;

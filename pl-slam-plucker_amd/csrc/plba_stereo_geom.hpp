@@ -8,7 +8,7 @@
 
 #include <math.h>
 
-#include "../../include/plba.h"
+#include "plba_assoc_args.hpp"  // kStPtDoubles, kStLsDoubles
 
 #if defined(__HIPCC__)
 #define PLBA_ST_FN __host__ __device__ inline
@@ -23,8 +23,6 @@
 
 namespace plba {
 
-constexpr int kStPtDoubles = 6;    // a point record: pl[2], disp, P[3]
-constexpr int kStLsDoubles = 21;   // a line record: spl[2], epl[2], sdisp, edisp, sP[3], eP[3], le[3], NDc[6]
 // gate bits, 0 = the row survives. Points: epipolar, disparity. Lines: the five of :372-375 in order.
 enum { kStPtEpip = 1, kStPtDisp = 2 };
 enum { kStLsDispS = 1, kStLsDispE = 2, kStLsHorizL = 4, kStLsHorizR = 8, kStLsOverlap = 16 };

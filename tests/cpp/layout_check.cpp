@@ -1,13 +1,16 @@
-// TEST PROGRAM: the staged-block builder and the tile envelope (csrc/plba_layout.hpp) on the host
-// alone, on plain heap memory, built with the address and undefined-behaviour sanitizers. Prints
-// "layout_check ok" and exits 0, or names the first check that failed.
+// TEST PROGRAM: the staged-block builder and the tile envelope (csrc/plba_layout.hpp), and the problem
+// table and the plans of the association calls (csrc/plba_assoc_plan.hpp), on the host alone, on plain
+// heap memory, built with the address and undefined-behaviour sanitizers. Prints "layout_check ok" and
+// exits 0, or names the first check that failed.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "../../include/plba.h"
+#include "plba_assoc_plan.hpp"
 #include "plba_layout.hpp"
 
+using plba::ProblemTable;
 using plba::Staged;
 using plba::TileEnvelope;
 using plba::tile_envelope;
@@ -60,6 +63,12 @@ struct Ref {
     size_t add(size_t count) { return add(sizeof(T) * count); }
 };
 
+// the fields that a plan's stage() bound into `base` lie at the offsets ref, one by one
+template <size_t N>
+static void check_bound(const std::vector<char> &base, const void *const (&field)[N], const size_t (&ref)[N]) {
+    for (size_t i = 0; i < N; ++i) CHECK((size_t)((const char *)field[i] - base.data()) == ref[i]);
+}
+
 static void check_builder() {
     // an empty input, a 1-byte input, a 128-byte output, a 257-byte device-only array in a marked range
     struct {
@@ -107,8 +116,10 @@ static void check_builder() {
     C.fetch();  // nothing to deliver
 }
 
-// One shape of each entry point's case file (tests/*_cases.py), declared as the entry point declares
-// it, against the sequence of offsets the entry point computed before the builder.
+// One shape of each entry point's case file (tests/*_cases.py) against the sequence of offsets the
+// entry point computed before the builder. The stereo and the keyframe association and the median
+// descriptor run the entry point's own plan (csrc/plba_assoc_plan.hpp); the others, whose declarations
+// are in csrc/plba_assoc.hip, are declared here as the entry point declares them.
 static void check_entry_point_offsets() {
     {  // relative pose, lcpose_cases (300, 100): one candidate
         const size_t n = 1, np = 300, nl = 100;
@@ -200,32 +211,75 @@ static void check_entry_point_offsets() {
         const size_t keys_end = L.total;
         const size_t ref_dev[] = {L.add<int32_t>(N1), L.add<int32_t>(N2), L.add<int32_t>(P), L.add<int32_t>(2 * N1),
                                   L.add<int32_t>(2 * N1), L.add<int32_t>(N2 + 1), L.add<int32_t>(2 * nc), L.add<double>(2 * N2)};
-        struct {
-            const int32_t *off1, *off2, *kind, *kbase, *cbase, *ws;
-            const double *nnr, *sim_th;
-            const uint32_t *desc1, *desc2;
-            const float *co1, *co2;
-            int32_t *count, *src, *m12, *m21, *gcount, *cell1, *cell1e, *cell_off2, *cells2;
-            uint32_t *odesc, *best, *second;
-            double *ptd, *lsd, *dir2;
-        } S{};
+        const int32_t pt_l[] = {0, 50}, pt_r[] = {0, 45}, ls_l[] = {0, 20}, ls_r[] = {0, 22};
+        plba::StereoPlan Q;
+        CHECK(Q.T.init(pt_l, pt_r, ls_l, ls_r, 1, 64, 48) == ProblemTable::kOk);
+        CHECK(Q.T.N1 == N1 && Q.T.N2 == N2 && Q.T.nc == nc && Q.T.cnt[0][0] == npl && Q.T.cnt[1][0] == nll);
+        Q.declare(db / 4);
+        std::vector<char> dev(Q.B.total());
+        Q.B.stage(nullptr, dev.data());
+        const plba::StDev &S = Q.S;
+        const plba::GmDev &D = Q.D;
+        check_bound(dev, {S.off1, S.off2, S.kind, S.kbase, S.cbase, D.ws, D.nnr, D.sim_th, S.desc1, D.desc2, S.co1, S.co2}, ref);
+        check_bound(dev, {S.count, S.src, S.odesc, S.ptd, S.lsd}, ref_out);
+        check_bound(dev, {D.best, D.second}, ref_keys);
+        check_bound(dev, {D.m12, D.m21, D.count, S.cell1, S.cell1e, S.cell_off2, S.cells2, S.dir2}, ref_dev);
+        CHECK(Q.key_bytes == keys_end - ref_keys[0]);
+        CHECK(Q.B.inputs_end() == inputs_end && Q.B.outputs_end() == outputs_end && Q.B.total() == L.total);
+    }
+    // keyframe association, kfassoc_cases "empty_side" (30 x 0 points, 0 x 12 lines) and "mixed" (50 x 45 points,
+    // 20 x 22 lines): one pair, a 64 x 48 grid
+    for (const bool mixed : {false, true}) {
+        const int32_t pt_p[] = {0, mixed ? 50 : 30}, pt_c[] = {0, mixed ? 45 : 0}, ls_p[] = {0, mixed ? 20 : 0},
+                      ls_c[] = {0, mixed ? 22 : 12};
+        const size_t P = 2, db = 32, c00 = pt_p[1], c01 = pt_c[1], c10 = ls_p[1], c11 = ls_c[1], N1 = c00 + c10, N2 = c01 + c11,
+                     nc = c01 + c11 * 64;
+        Ref L;
+        const size_t ref[] = {L.add<int32_t>(P + 1), L.add<int32_t>(P + 1), L.add<int32_t>(P), L.add<int32_t>(P),
+                              L.add<int32_t>(P), L.add<int32_t>(P + 1), L.add<int32_t>(P), L.add<int32_t>(4 * P),
+                              L.add<double>(P), L.add<double>(P), L.add<float>(P), L.add<double>(76 * P / 2), L.add(db * N1),
+                              L.add(db * N2), L.add<double>(3 * c00), L.add<double>(22 * c10), L.add(c10), L.add<double>(5 * c01),
+                              L.add<double>(4 * c11)};
+        const size_t inputs_end = L.total;
+        const size_t ref_out[] = {L.add<int32_t>(3 * P), L.add<int32_t>(N1), L.add<double>(9 * c00), L.add<double>(8 * c10),
+                                  L.add(c10)};
+        const size_t outputs_end = L.total;
+        const size_t ref_keys[] = {L.add<uint32_t>(N1), L.add<uint32_t>(N1)};
+        const size_t keys_end = L.total;
+        const size_t ref_dev[] = {L.add<int32_t>(N1), L.add<int32_t>(N2), L.add<int32_t>(P), L.add<int32_t>(2 * N1),
+                                  L.add<int32_t>(2 * N1), L.add<int32_t>(N2 + 1), L.add<int32_t>(2 * nc), L.add<double>(2 * N2),
+                                  L.add<int32_t>(N1), L.add<int32_t>(N2), L.add<int32_t>(N1), L.add<int32_t>(P)};
+        plba::KfPlan Q;
+        CHECK(Q.T.init(pt_p, pt_c, ls_p, ls_c, 1, 64, 48) == ProblemTable::kOk);
+        Q.declare(db / 4);
+        std::vector<char> dev(Q.B.total());
+        Q.B.stage(nullptr, dev.data());
+        const plba::KfDev &K = Q.K;
+        const plba::GmDev &D = Q.D;
+        const plba::DmDev &M = Q.M;
+        check_bound(dev, {K.off1, K.off2, K.kind, K.kbase1, K.kbase2, K.cbase, K.gate_min, D.ws, D.nnr, D.sim_th, M.nnr, K.pose,
+                          D.desc1, D.desc2, K.q_pt, K.q_ls, K.ls_new, K.t_pt, K.t_ls}, ref);
+        check_bound(dev, {K.res, K.m12, K.ptd, K.lsd, K.rej}, ref_out);
+        check_bound(dev, {D.best, D.second}, ref_keys);
+        check_bound(dev, {D.m12, D.m21, D.count, K.cell1, K.cell1e, K.cell_off2, K.cells2, K.dir2, M.nn12, M.nn21, M.m12, M.count},
+                    ref_dev);
+        CHECK(Q.key_bytes == keys_end - ref_keys[0]);
+        CHECK(Q.B.inputs_end() == inputs_end && Q.B.outputs_end() == outputs_end && Q.B.total() == L.total);
+    }
+    {  // median descriptor, medoid_cases wave_lists: lists of 63, 64 and 65 descriptors of 32 bytes
+        const size_t n = 3, total = 192, db = 32;
+        Ref L;
+        const size_t ref[] = {L.add<int32_t>(n + 1), L.add<int32_t>(n), L.add(db * total)};
+        const size_t inputs_end = L.total;
+        const size_t ref_out[] = {L.add<int32_t>(n)};
+        plba::MedDev D{};
         Staged B;
-        const size_t got[] = {B.in(S.off1, P + 1), B.in(S.off2, P + 1), B.in(S.kind, P), B.in(S.kbase, P), B.in(S.cbase, P + 1),
-                              B.in(S.ws, 4 * P), B.in(S.nnr, P), B.in(S.sim_th, P), B.in(S.desc1, db / 4 * N1),
-                              B.in(S.desc2, db / 4 * N2), B.in(S.co1, 4 * N1), B.in(S.co2, 4 * N2)};
-        const size_t got_out[] = {B.out(S.count, P), B.out(S.src, N1), B.out(S.odesc, db / 4 * N1), B.out(S.ptd, 6 * npl),
-                                  B.out(S.lsd, 21 * nll)};
-        const size_t got_keys[] = {B.dev(S.best, N1), B.dev(S.second, N1)};
-        const size_t got_keys_end = B.mark();
-        const size_t got_dev[] = {B.dev(S.m12, N1), B.dev(S.m21, N2), B.dev(S.gcount, P), B.dev(S.cell1, 2 * N1),
-                                  B.dev(S.cell1e, 2 * N1), B.dev(S.cell_off2, N2 + 1), B.dev(S.cells2, 2 * nc),
-                                  B.dev(S.dir2, 2 * N2)};
-        for (int i = 0; i < 12; ++i) CHECK(got[i] == ref[i]);
-        for (int i = 0; i < 5; ++i) CHECK(got_out[i] == ref_out[i]);
-        for (int i = 0; i < 2; ++i) CHECK(got_keys[i] == ref_keys[i]);
-        for (int i = 0; i < 8; ++i) CHECK(got_dev[i] == ref_dev[i]);
-        CHECK(got_keys_end == keys_end);
-        CHECK(B.inputs_end() == inputs_end && B.outputs_end() == outputs_end && B.total() == L.total);
+        plba::medoid_plan(B, D, n, total, db / 4, nullptr, nullptr, nullptr);
+        std::vector<char> dev(B.total());
+        B.stage(nullptr, dev.data());
+        check_bound(dev, {D.list_ptr, D.order, D.desc}, ref);
+        check_bound(dev, {D.medoid}, ref_out);
+        CHECK(B.inputs_end() == inputs_end && B.outputs_end() == L.total && B.total() == L.total);
     }
     {  // place recognition, bow_cases: 257 descriptors of 32 bytes against 3 live rows; then 8193, sorted out of LDS
         for (const size_t n_desc : {(size_t)257, (size_t)8193}) {
@@ -254,9 +308,102 @@ static void check_entry_point_offsets() {
     }
 }
 
+// what ProblemTable::fill writes for a table, into arrays of exactly the sizes the plans declare (the
+// sanitizer sees a write past one), the descriptor rows of db bytes gathered from descs
+struct Filled {
+    std::vector<int32_t> off1, off2, kind, kbase1, kbase2, cbase;
+    std::vector<uint8_t> desc1, desc2;
+    Filled(const ProblemTable &T, const uint8_t *const descs[2][2], size_t db)
+        : off1(2 * T.n + 1, -7), off2(off1), kind(2 * T.n, -7), kbase1(kind), kbase2(kind), cbase(off1),
+          desc1(db * T.N1), desc2(db * T.N2) {
+        T.fill(off1.data(), off2.data(), kind.data(), kbase1.data(), kbase2.data(), cbase.data(), descs, db, desc1.data(),
+               desc2.data());
+    }
+};
+using I32 = std::vector<int32_t>;
+
+static void check_problem_table() {
+    const uint8_t *const none[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    ProblemTable T;
+    {  // one unit without a row
+        const int32_t z[] = {0, 0};
+        CHECK(T.init(z, z, z, z, 1, 64, 48) == ProblemTable::kOk);
+        CHECK(T.N1 == 0 && T.N2 == 0 && T.nc == 0 && T.max_rows == 0 && T.max_prev == 0 && T.max_train == 0);
+        const Filled F(T, none, 32);
+        CHECK(F.off1 == (I32{0, 0, 0}) && F.off2 == F.off1 && F.cbase == F.off1);
+        CHECK(F.kind == (I32{0, 1}) && F.kbase1 == (I32{0, 0}) && F.kbase2 == F.kbase1);
+    }
+    {  // points only, then lines only: 3 x 2 rows of one byte
+        const int32_t z[] = {0, 0}, a[] = {0, 3}, b[] = {0, 2};
+        const uint8_t d1[] = {9, 8, 7}, d2[] = {6, 5};
+        const uint8_t *const descs[2][2] = {{d1, d2}, {d1, d2}};
+        CHECK(T.init(a, b, z, z, 1, 64, 48) == ProblemTable::kOk);
+        CHECK(T.N1 == 3 && T.N2 == 2 && T.nc == 2 && T.cnt[0][0] == 3 && T.cnt[1][1] == 0 && T.max_rows == 3);
+        const Filled Fp(T, descs, 1);
+        CHECK(Fp.off1 == (I32{0, 3, 3}) && Fp.off2 == (I32{0, 2, 2}) && Fp.cbase == (I32{0, 2, 2}));
+        CHECK(Fp.desc1 == (std::vector<uint8_t>{9, 8, 7}) && Fp.desc2 == (std::vector<uint8_t>{6, 5}));
+        CHECK(T.init(z, z, a, b, 1, 64, 48) == ProblemTable::kOk);
+        CHECK(T.N1 == 3 && T.N2 == 2 && T.nc == 2 * 64 && T.cnt[0][0] == 0 && T.cnt[1][1] == 2 && T.max_train == 2);
+        const Filled Fl(T, descs, 1);
+        CHECK(Fl.off1 == (I32{0, 0, 3}) && Fl.off2 == (I32{0, 0, 2}) && Fl.cbase == (I32{0, 0, 128}));
+        CHECK(Fl.desc1 == Fp.desc1 && Fl.desc2 == Fp.desc2);
+    }
+    // Two units whose first offsets are not zero, with a problem without side-1 rows (the lines of unit 0) and one
+    // without side-2 rows (the points of unit 1) between others; descriptor rows of 4 bytes, row r of an array
+    // tagged (array, r), each array exactly as long as its last offset. cols < rows, then cols > rows.
+    for (const int cols : {3, 7}) {
+        const int rows = 5, stride = cols > rows ? cols : rows;
+        const int32_t pt1[] = {5, 7, 10}, pt2[] = {2, 3, 3}, ls1[] = {1, 1, 4}, ls2[] = {4, 6, 7};
+        CHECK(T.init(pt1, pt2, ls1, ls2, 2, cols, rows) == ProblemTable::kOk);
+        CHECK(T.stride == stride && T.cnt[0][0] == 5 && T.cnt[0][1] == 1 && T.cnt[1][0] == 3 && T.cnt[1][1] == 3);
+        CHECK(T.N1 == 8 && T.N2 == 4 && T.nc == 1 + 3 * (size_t)stride);
+        CHECK(T.max_prev == 3 && T.max_train == 2 && T.max_rows == 3);
+        const ProblemTable::Problem q = T.at(3);
+        CHECK(q.f == 1 && q.kind == 1 && q.a1 == 1 && q.r1 == 3 && q.a2 == 6 && q.r2 == 1);
+        std::vector<uint8_t> src[2][2];
+        const int last[2][2] = {{10, 3}, {4, 7}};
+        for (int kd = 0; kd < 2; ++kd)
+            for (int sd = 0; sd < 2; ++sd)
+                for (int r = 0; r < last[kd][sd]; ++r)
+                    for (int e = 0; e < 4; ++e) src[kd][sd].push_back((uint8_t)(64 * (2 * kd + sd) + 4 * r + e));
+        const uint8_t *const descs[2][2] = {{src[0][0].data(), src[0][1].data()}, {src[1][0].data(), src[1][1].data()}};
+        const Filled F(T, descs, 4);
+        CHECK(F.off1 == (I32{0, 2, 2, 5, 8}) && F.off2 == (I32{0, 1, 3, 3, 4}));
+        CHECK(F.cbase == (I32{0, 1, 1 + 2 * stride, 1 + 2 * stride, 1 + 3 * stride}));
+        CHECK(F.kind == (I32{0, 1, 0, 1}) && F.kbase1 == (I32{0, 0, 2, 0}) && F.kbase2 == (I32{0, 0, 1, 2}));
+        // side 1: point rows 5, 6 | - | point rows 7, 8, 9 | line rows 1, 2, 3; side 2: point row 2 | line rows 4, 5 | - | line row 6
+        const int want1[8][2] = {{0, 5}, {0, 6}, {0, 7}, {0, 8}, {0, 9}, {1, 1}, {1, 2}, {1, 3}};
+        const int want2[4][2] = {{0, 2}, {1, 4}, {1, 5}, {1, 6}};
+        for (int i = 0; i < 8; ++i)
+            for (int e = 0; e < 4; ++e) CHECK(F.desc1[4 * i + e] == src[want1[i][0]][0][4 * want1[i][1] + e]);
+        for (int i = 0; i < 4; ++i)
+            for (int e = 0; e < 4; ++e) CHECK(F.desc2[4 * i + e] == src[want2[i][0]][1][4 * want2[i][1] + e]);
+    }
+    {  // a side-2 span of kGmMaxTrain is accepted, one more is refused: offsets only
+        const int32_t z[] = {0, 0, 0}, at[] = {3, 3, 3 + plba::kGmMaxTrain}, over[] = {3, 3, 4 + plba::kGmMaxTrain};
+        CHECK(T.init(z, at, z, z, 2, 64, 48) == ProblemTable::kOk && T.max_train == plba::kGmMaxTrain);
+        CHECK(T.init(z, z, z, over, 2, 64, 48) == ProblemTable::kTooWide && T.max_train == plba::kGmMaxTrain + 1);
+        CHECK(T.init(over, z, over, z, 2, 64, 48) == ProblemTable::kOk && T.max_prev == plba::kGmMaxTrain + 1);  // side 1 may
+    }
+    {  // lines whose cells pass INT32_MAX are refused, every problem within kGmMaxTrain; the sum is a size_t
+        const int n = 513;  // 513 * 65535 * 64 = 2151645120
+        I32 z(n + 1, 0), ls2(n + 1);
+        for (int f = 0; f <= n; ++f) ls2[f] = f * plba::kGmMaxTrain;
+        CHECK(T.init(z.data(), z.data(), z.data(), ls2.data(), n, 64, 48) == ProblemTable::kTooMany);
+        CHECK(T.nc == (size_t)513 * 65535 * 64 && T.N2 == (size_t)513 * 65535 && T.max_train == plba::kGmMaxTrain);
+        CHECK(T.init(z.data(), z.data(), z.data(), ls2.data(), n - 1, 64, 48) == ProblemTable::kOk);  // 2147450880
+        // the widest grid: one line owns INT32_MAX cells, two lines are too many
+        const int32_t one[] = {0, 1}, two[] = {0, 2};
+        CHECK(T.init(one, one, one, one, 1, INT32_MAX, 1) == ProblemTable::kTooMany && T.nc == (size_t)INT32_MAX + 1);
+        CHECK(T.init(z.data(), z.data(), one, one, 1, 1, INT32_MAX) == ProblemTable::kOk && T.nc == (size_t)INT32_MAX);
+        CHECK(T.init(z.data(), z.data(), two, two, 1, 1, INT32_MAX) == ProblemTable::kTooMany);
+    }
+}
+
 int main() {
     check_builder();
     check_entry_point_offsets();
+    check_problem_table();
     const int tile = 16;
     {  // no free pose: one zeroed tile
         const TileEnvelope te = tile_envelope({}, 0, tile);

@@ -1,6 +1,7 @@
-"""The block layout builder and the tile envelope (csrc/plba_layout.hpp) on the host: a stand-alone
-program (tests/cpp/layout_check.cpp) built with the address and undefined-behaviour sanitizers, run
-as a child process."""
+"""The block layout builder and the tile envelope (csrc/plba_layout.hpp) and the problem table and plans
+of the association calls (csrc/plba_assoc_plan.hpp) on the host: a stand-alone program
+(tests/cpp/layout_check.cpp) built with the address and undefined-behaviour sanitizers, run as a child
+process."""
 import os
 import subprocess
 
