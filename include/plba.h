@@ -374,6 +374,119 @@ void plba_lcpose_default_params(plba_lcpose_params *p);
 int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *p,
                           plba_lcpose_out *out, uint8_t *pt_inlier, uint8_t *ln_inlier);
 
+/* ---- Frame-to-frame pose, the numerical routine of the per-frame loop:
+ *   void StereoFrameHandler::optimizePose()                 (src2/stereoFrameHandler.cpp:307-405)
+ * with gaussNewtonOptimizationRobust / optimizeFunctionsRobust (:446-494, :1010-1277; the endpoint
+ * line model), gaussNewtonOptimizationforPluker / optimizeFunctionsUsingPluker (:803-853, :564-801;
+ * a USE_LINE_PLUKER build), removeOutliers (:1303-1396), isGoodSolution (:292-305), the MAD scales
+ * of src2/auxiliar.cpp:387-460 and StereoFrame::lineSegmentOverlap (src2/stereoFrame.cpp:547-653).
+ * The matches of the previous frame's features with the current frame (what matchF2FPoints / Lines
+ * leave, :131-180) go in; DT, DT_cov, err_norm and the eigenvalues of DT_cov come out.
+ *   DT = the previous frame's DT if use_motion_model and isGoodSolution(prev) else I (:317-326);
+ *   fewer than min_features matches: DT = I (:377-381);
+ *   else a first loop of at most max_iters passes on a copy DT_; if isGoodSolution(DT_, cov, err):
+ *   removeOutliers(DT_) over ALL matches with r·sqrt(sigma2), mean and 1.4826·MAD by
+ *   vector_mean_stdv_mad, |r − mean| > inlier_k·stdv is an outlier (points only with has_points,
+ *   lines only with has_lines); then, with at least min_features inliers, a second loop of at most
+ *   max_iters_ref passes that starts again from the INITIAL DT (:352/:356), else DT = I. If the first
+ *   solution is not good, the endpoint model runs one loop of max_iters_ref passes on all matches
+ *   from the initial DT (:371) and the Plücker model does nothing (:369).
+ *   The end (:385-404): isGoodSolution(DT, cov, err) and DT != I (exactly) gives
+ *   DT = expmap(logmap(inverse(DT))), DT_cov, err_norm and the eigenvalues; anything else gives
+ *   DT = I, DT_cov = 0, err_norm = -1, eigenvalues 0.
+ * A pass: the residual lists of the active matches; s_p, s_l = vector_stdv_mad of each (element n/2
+ * of the sorted list, the deviations rounded through float by fabsf, an empty list gives 0), clamped
+ * to [1e-4, sqrt(7.815)]; w = 1/(1 + (r/s)²), for a line times lineSegmentOverlap of the previous
+ * frame's segment and the projected endpoints; H += w·JJᵀ, g += w·J·r, e += w·r², e /= N_l + N_p.
+ * Stop if |e − e_prev| < min_error_change or e < min_error; x = H⁻¹g by ColPivHouseholderQR; if its
+ * logAbsDeterminant() < 0 the loop's DT is restored, err = −1 and cov = I; DT ← inverse(expmap(x))·DT
+ * (on the left); stop if ‖x‖ < min_error_change. After the loop cov = H⁻¹, err = e.
+ * Line residuals. PLBA_TRACK_ENDPOINTS: (l·π(sP'), l·π(eP')) with the current frame's line l = le.
+ * PLBA_TRACK_PLUCKER: the line n' = R·N + t×(R·D) (TransformForPluker, include2/stereoFrameHandler.h
+ * :114-122) in pixels, l = K_pl·n' with K_pl = [fy 0 0; 0 fx 0; −fy·cx −fx·cy fx·fy]
+ * (src2/pinholeStereoCamera.cpp:123-125), and the distances of the current frame's two endpoints to
+ * it; g (only) is built with r = ‖e‖·sqrt(sigma2), e and the weight with ‖e‖ (:757-781).
+ * isGoodSolution here is: smallest eigenvalue >= 0, largest <= 1, 0 <= err <= 1, DT finite, each
+ * comparison as written, so that a NaN anywhere is "not good" (the reference's negated comparisons
+ * let a NaN covariance or error pass).
+ * Defined where the reference is not: a pass with no active match divides 0 by 0: err is NaN, the
+ * solution is not good and the identity is returned; a non-finite H or g (a match with z = 0) gives
+ * a NaN step and takes the same route, after its iteration caps; a singular last H (H.inverse() is
+ * inf / NaN in the reference) gives a NaN covariance, which is not good. None of them disturbs the
+ * rest of the batch. Modes 0 and 2 of the endpoint build (gaussNewtonOptimization,
+ * levenbergMarquardtOptimization) are dead in the reference (mode = 1) and are not here. */
+#define PLBA_TRACK_MAX_N 2048           /* matches of one kind in one problem: the residual list of a
+                                           kind sits in a workgroup's LDS whole for the rank selection */
+#define PLBA_TRACK_PLUCKER   0          /* plba_track_params.line_model */
+#define PLBA_TRACK_ENDPOINTS 1
+/* plba_track_out.branch: the path optimizePose took */
+#define PLBA_TRACK_OK              0    /* refined, final test passed: DT is the estimate            */
+#define PLBA_TRACK_FEW_BEFORE      1    /* fewer than min_features matches (:377-381)                */
+#define PLBA_TRACK_FIRST_NOT_GOOD  2    /* the first solution failed isGoodSolution (:366-375); in the
+                                           endpoint model err_norm >= 0 tells that the loop on all
+                                           matches still passed the final test                       */
+#define PLBA_TRACK_FEW_AFTER       3    /* fewer than min_features inliers after removal (:360-364)  */
+#define PLBA_TRACK_FINAL_NOT_GOOD  4    /* refined, but the final test failed (:395-404)             */
+
+typedef struct plba_track_batch {       /* K frame pairs, concatenated */
+    int32_t n;                          /* problems                                                  */
+    const int32_t *pt_off, *ln_off;     /* [n+1] match ranges                                        */
+    const double *pt_P;                 /* [.][3] stereo_pt[i1]->P of the previous frame             */
+    const double *pt_obs;               /* [.][2] pl_obs: the current frame's pixel (:148)           */
+    const double *pt_sigma2;            /* [.]                                                       */
+    const double *ln_sP, *ln_eP;        /* [.][3] endpoints in the previous frame's camera           */
+    const double *ln_NDc;               /* [.][6] Plücker line (N, D) there; PLBA_TRACK_PLUCKER only */
+    const double *ln_le;                /* [.][3] le_obs (:175); PLBA_TRACK_ENDPOINTS only           */
+    const double *ln_obs;               /* [.][4] spl_obs, epl_obs (:173-174); PLBA_TRACK_PLUCKER only */
+    const double *ln_seg;               /* [.][4] spl, epl: the previous frame's own segment         */
+    const double *ln_sigma2;            /* [.]                                                       */
+    const double *prev;                 /* [n][53] the previous frame's DT (row-major 4x4), DT_cov
+                                           (6x6) and err_norm; read only with use_motion_model       */
+    double fx, fy, cx, cy;
+} plba_track_batch;
+
+typedef struct plba_track_params {
+    double  homog_th;          /* Config::homogTh()        1e-7 (src2/config.cpp:80)                 */
+    double  min_error;         /* Config::minError()       1e-7 (:84)                                */
+    double  min_error_change;  /* Config::minErrorChange() 1e-7 (:85)                                */
+    double  inlier_k;          /* Config::inlierK()        4.0  (:86)                                */
+    int32_t min_features;      /* Config::minFeatures()    10   (:81)                                */
+    int32_t max_iters;         /* Config::maxIters()       5    (:82)                                */
+    int32_t max_iters_ref;     /* Config::maxItersRef()    10   (:83)                                */
+    int32_t has_points;        /* Config::hasPoints()      1    (:46)                                */
+    int32_t has_lines;         /* Config::hasLines()       1    (:47)                                */
+    int32_t use_motion_model;  /* Config::useMotionModel() 0    (:53)                                */
+    int32_t line_model;        /* PLBA_TRACK_PLUCKER (the default) or PLBA_TRACK_ENDPOINTS           */
+    int32_t pad;
+} plba_track_params;
+
+typedef struct plba_track_out {
+    int32_t branch;            /* PLBA_TRACK_OK ...                                                  */
+    int32_t iters_first;       /* passes (H / g builds) of the first loop                            */
+    int32_t iters_ref;         /* passes of the second loop                                          */
+    int32_t n_inl_pt, n_inl_ln;/* matches still active at the end                                    */
+    int32_t pad;
+    double  err_norm;          /* curr_frame->err_norm                                               */
+    double  s_p, s_l;          /* the scales of the last pass (0 if there was none)                  */
+    double  DT[16];            /* curr_frame->DT, row-major 4x4                                      */
+    double  DT_cov[36];        /* curr_frame->DT_cov                                                 */
+    double  DT_cov_eig[6];     /* ascending                                                          */
+    double  DT_solver[16];     /* the solver's own DT, before the inversion                          */
+    double  H[36];             /* last pass, row-major (0 if there was none)                         */
+} plba_track_out;
+
+void plba_track_default_params(plba_track_params *p);
+/* Runs on the context's stream; needs no uploaded window and leaves one intact; its device buffers
+ * are kept and reused across calls. One workgroup per problem, the whole of optimizePose in one
+ * launch; the same problem gives bitwise the same result alone or anywhere in a batch. out: [n].
+ * pt_inlier [pt_off[n]] / ln_inlier [ln_off[n]] receive the inlier flags (each may be NULL).
+ * p == NULL: the defaults. PLBA_E_INVALID for a NULL batch / out / array that the line model reads,
+ * n < 0, decreasing (or negative) offsets, an iteration cap below 1, an unknown line model, a NULL
+ * prev with use_motion_model, or more than PLBA_TRACK_MAX_N matches of one kind in one problem;
+ * n == 0 does nothing and returns PLBA_OK. */
+int plba_track_pose(plba_ctx *ctx, const plba_track_batch *b, const plba_track_params *p,
+                    plba_track_out *out, uint8_t *pt_inlier, uint8_t *ln_inlier);
+
 /* ---- Descriptor matching, what feeds the relative pose above and every other matching step of
  * the back end:
  *   int StVO::match(desc1, desc2, nnr, matches_12)          (src2/matching.cpp:63-91)

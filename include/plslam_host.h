@@ -471,6 +471,11 @@ int plslam_set_stereo_fn(plslam_map *m, plslam_stereo_fn fn, void *user);
 /* tools/stereo_bench.py and the tests only, not a product path: a single-threaded restatement of
  * plba_stereo_associate's semantics on the CPU, with the hook's signature. */
 int plslam_stereo_cpu(void *user, const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
+/* tools/trackpose_bench.py and the tests only, not a product path: a single-threaded restatement of
+ * plba_track_pose's semantics (StereoFrameHandler::optimizePose) on the CPU, with that call's
+ * signature behind a user pointer. H, g and e are summed in match order. */
+int plslam_track_pose_cpu(void *user, const plba_track_batch *b, const plba_track_params *p, plba_track_out *out,
+                          uint8_t *pt_inlier, uint8_t *ln_inlier);
 /* ---- MapHandler::matchKF2KFPoints + matchKF2KFLines (src/mapHandler.cpp:237-366, :368-590, the
  * USE_LINE_PLUKER branch), the only place where map landmarks are created, between two keyframes that have
  * their features (plslam_set_keyframe_stereo with params.pluker, or plslam_set_keyframe_features +

@@ -1936,7 +1936,7 @@ int plba_destroy(plba_ctx *ctx) {
     if (ctx->h_ctrl) (void)hipHostFree(ctx->h_ctrl);
     ctx->bmemA.release(ctx->stream);
     ctx->bmemB.release(ctx->stream);
-    std::vector<ScratchBlock *> blocks{&ctx->pgo, &ctx->lc, &ctx->match, &ctx->bow_io};
+    std::vector<ScratchBlock *> blocks{&ctx->pgo, &ctx->lc, &ctx->track, &ctx->match, &ctx->bow_io};
     for (BowSlot &b : ctx->bow) blocks.insert(blocks.end(), {&b.voc, &b.db_word, &b.db_val});
     for (ScratchBlock *sb : blocks) sb->release(ctx->stream);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
@@ -2400,6 +2400,29 @@ void plba_lcpose_default_params(plba_lcpose_params *p) {
 int plba_lc_relative_pose(plba_ctx *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
                           uint8_t *pt_inlier, uint8_t *ln_inlier) {
     return ctx ? lc_relative_pose(ctx, b, pp, out, pt_inlier, ln_inlier) : PLBA_E_INVALID;
+}
+
+// ---------------------------------------------------------------- frame-to-frame pose
+// defaults here (src2/config.cpp:46-53, :80-86); the call itself is plba::track_pose (csrc/plba_assoc.hip)
+void plba_track_default_params(plba_track_params *p) {
+    if (!p) return;
+    p->homog_th = 1e-7;
+    p->min_error = 1e-7;
+    p->min_error_change = 1e-7;
+    p->inlier_k = 4.0;
+    p->min_features = 10;
+    p->max_iters = 5;
+    p->max_iters_ref = 10;
+    p->has_points = 1;
+    p->has_lines = 1;
+    p->use_motion_model = 0;
+    p->line_model = PLBA_TRACK_PLUCKER;
+    p->pad = 0;
+}
+
+int plba_track_pose(plba_ctx *ctx, const plba_track_batch *b, const plba_track_params *pp, plba_track_out *out,
+                    uint8_t *pt_inlier, uint8_t *ln_inlier) {
+    return ctx ? track_pose(ctx, b, pp, out, pt_inlier, ln_inlier) : PLBA_E_INVALID;
 }
 
 // descriptor matching and grid-guided matching (csrc/plba_assoc.hip)

@@ -1,5 +1,5 @@
 // plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose,
-// the two descriptor matchers, the stereo and the keyframe association, the median descriptor and
+// the frame-to-frame pose, the two descriptor matchers, the stereo and the keyframe association, the median descriptor and
 // place recognition. They share nothing with the solver (no Dev, no step graph, no window arena), so
 // they are a translation unit of their own: an edit to a matcher does not rebuild the factorisation
 // kernels. Each call is one upload, its kernels and one read-back through a ScratchBlock. A Staged
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "plba_lcpose.hpp"
+#include "plba_trackpose.hpp"
 #include "plba_match.hpp"
 #include "plba_gridmatch.hpp"
 #include "plba_stereo.hpp"
@@ -195,6 +196,66 @@ int lc_relative_pose(CtxBase *ctx, const plba_lcpose_batch *b, const plba_lcpose
     D.prm = prm;
     hipLaunchKernelGGL(k_lcpose, dim3(n), dim3(kLcNT), 0, ctx->stream, D); PLBA_LAUNCHED(ctx, "k_lcpose");
     if (const int rc = read_back(ctx, ctx->lc, B)) return rc;
+    B.fetch();
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- frame-to-frame pose
+// StereoFrameHandler::optimizePose (src2/stereoFrameHandler.cpp:307-405) for a batch of frame pairs:
+// one upload, one launch of k_trackpose (csrc/plba_trackpose.hpp, one workgroup per problem), one
+// read-back. The block is laid out by trackpose_plan (csrc/plba_assoc_plan.hpp).
+int track_pose(CtxBase *ctx, const plba_track_batch *b, const plba_track_params *pp, plba_track_out *out,
+               uint8_t *pt_inlier, uint8_t *ln_inlier) {
+    const char *const op = "track pose";
+    if (!b || b->n < 0) {
+        ctx->set_error("track pose: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    const int n = b->n;
+    if (n == 0) return PLBA_OK;
+    plba_track_params prm;
+    if (pp) prm = *pp;
+    else plba_track_default_params(&prm);
+    if (!out || !b->pt_off || !b->ln_off) {
+        ctx->set_error("track pose: NULL out / pt_off / ln_off");
+        return PLBA_E_INVALID;
+    }
+    if ((prm.line_model != PLBA_TRACK_PLUCKER && prm.line_model != PLBA_TRACK_ENDPOINTS) || prm.max_iters < 1 ||
+        prm.max_iters_ref < 1) {
+        ctx->set_error("track pose: unknown line model %d or an iteration cap below 1", prm.line_model);
+        return PLBA_E_INVALID;
+    }
+    const bool pluker = prm.line_model == PLBA_TRACK_PLUCKER, motion = prm.use_motion_model != 0;
+    int widest = 0;
+    for (const int32_t *off : {b->pt_off, b->ln_off})
+        if (const int rc = check_offsets(ctx, op, "match", "problem", off, n, &widest)) return rc;
+    if (widest > kTpMaxN) {
+        ctx->set_error("track pose: %d matches of one kind in one problem, PLBA_TRACK_MAX_N is %d", widest, kTpMaxN);
+        return PLBA_E_INVALID;
+    }
+    const size_t np = (size_t)b->pt_off[n], nl = (size_t)b->ln_off[n];
+    if ((np && (!b->pt_P || !b->pt_obs || !b->pt_sigma2)) ||
+        (nl && (!b->ln_sP || !b->ln_eP || !b->ln_seg || !b->ln_sigma2 || (pluker ? (!b->ln_NDc || !b->ln_obs) : !b->ln_le)))) {
+        ctx->set_error("track pose: NULL match array");
+        return PLBA_E_INVALID;
+    }
+    if (motion && !b->prev) {
+        ctx->set_error("track pose: use_motion_model without prev");
+        return PLBA_E_INVALID;
+    }
+    (void)hipSetDevice(ctx->opts.device);
+    TpDev D{};
+    Staged B;
+    trackpose_plan(B, D, b, pluker, motion, out, pt_inlier, ln_inlier);
+    if (const int rc = ctx->track.reserve(*ctx, B.total(), B.outputs_end(), op)) return rc;
+    B.stage(ctx->track.host, ctx->track.dev);
+    if (const int rc = upload(ctx, ctx->track, B)) return rc;
+    D.fx = b->fx, D.fy = b->fy, D.cx = b->cx, D.cy = b->cy;
+    D.prm = prm;
+    if (pluker) hipLaunchKernelGGL(k_trackpose<PLBA_TRACK_PLUCKER>, dim3(n), dim3(kTpNT), 0, ctx->stream, D);
+    else hipLaunchKernelGGL(k_trackpose<PLBA_TRACK_ENDPOINTS>, dim3(n), dim3(kTpNT), 0, ctx->stream, D);
+    PLBA_LAUNCHED(ctx, "k_trackpose");
+    if (const int rc = read_back(ctx, ctx->track, B)) return rc;
     B.fetch();
     return PLBA_OK;
 }

@@ -116,4 +116,24 @@ struct MedDev {
     int32_t n, dwords, n_short, n_short_wg;
 };
 
+// ---------------------------------------------------------------- csrc/plba_trackpose.hpp
+constexpr int kTpNT = 256;               // threads of a problem's workgroup
+constexpr int kTpMaxN = PLBA_TRACK_MAX_N;  // matches of one kind in one problem
+constexpr int kTpPrev = 53;              // doubles of a problem's motion-model input: DT, DT_cov, err_norm
+
+struct TpDev {
+    const int32_t *pt_off, *ln_off;      // [n+1] match ranges of each problem
+    const double *pt_P, *pt_obs, *pt_s2; // [.][3], [.][2], [.]
+    const double *ln_sP, *ln_eP;         // [.][3]
+    const double *ln_ND, *ln_le;         // [.][6] (Plücker model), [.][3] (endpoint model)
+    const double *ln_obs, *ln_seg;       // [.][4] spl_obs, epl_obs (Plücker model); [.][4] spl, epl
+    const double *ln_s2;                 // [.]
+    const double *prev;                  // [n][kTpPrev] (motion model)
+    plba_track_out *out;                 // [n]
+    uint8_t *pt_in, *ln_in;              // [.] inlier flags
+    double *pt_res, *ln_res;             // [.] the residual lists (device only)
+    double fx, fy, cx, cy;
+    plba_track_params prm;
+};
+
 }  // namespace plba

@@ -130,4 +130,19 @@ inline void medoid_plan(Staged &B, MedDev &D, size_t n, size_t total, size_t dw,
     B.out(D.medoid, n, medoid);
 }
 
+// The frame-to-frame pose's block: n problems over np point and nl line matches. An array that the
+// line model or the motion model does not read has no source and no rows.
+inline void trackpose_plan(Staged &B, TpDev &D, const plba_track_batch *b, bool pluker, bool motion, plba_track_out *out,
+                           uint8_t *pt_inlier, uint8_t *ln_inlier) {
+    const size_t n = (size_t)b->n, np = (size_t)b->pt_off[n], nl = (size_t)b->ln_off[n];
+    B.in(D.pt_off, n + 1, b->pt_off), B.in(D.ln_off, n + 1, b->ln_off);
+    B.in(D.pt_P, 3 * np, b->pt_P), B.in(D.pt_obs, 2 * np, b->pt_obs), B.in(D.pt_s2, np, b->pt_sigma2);
+    B.in(D.ln_sP, 3 * nl, b->ln_sP), B.in(D.ln_eP, 3 * nl, b->ln_eP);
+    B.in(D.ln_ND, pluker ? 6 * nl : 0, b->ln_NDc), B.in(D.ln_le, pluker ? 0 : 3 * nl, b->ln_le);
+    B.in(D.ln_obs, pluker ? 4 * nl : 0, b->ln_obs), B.in(D.ln_seg, 4 * nl, b->ln_seg), B.in(D.ln_s2, nl, b->ln_sigma2);
+    B.in(D.prev, motion ? (size_t)kTpPrev * n : 0, b->prev);
+    B.out(D.out, n, out), B.out(D.pt_in, np, pt_inlier), B.out(D.ln_in, nl, ln_inlier);
+    B.dev(D.pt_res, np), B.dev(D.ln_res, nl);
+}
+
 }  // namespace plba

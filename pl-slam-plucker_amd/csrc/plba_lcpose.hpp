@@ -25,6 +25,7 @@
 
 #include "../../include/plba.h"
 #include "plba_math.hpp"
+#include "plba_posegn.hpp"
 
 namespace plba {
 
@@ -44,34 +45,7 @@ struct LcDev {
 
 namespace lcp {
 #pragma clang fp contract(off)
-
-// T.block(0,0,3,3)·P + T.col(3).head(3) of a row-major 4x4 (or 3x4)
-__device__ __forceinline__ void xform(const double *T, const double *P, double *G) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) G[i] = ((T[4 * i] * P[0] + T[4 * i + 1] * P[1]) + T[4 * i + 2] * P[2]) + T[4 * i + 3];
-}
-
-// the six entries the reference writes for one projected point G and the image direction (a, b)
-// (:4724-4729, :4769-4774): fx scales both image directions
-__device__ __forceinline__ void jrow(const Cam &c, double hth, const double *G, double a, double b, double *J) {
-#pragma clang fp contract(off)
-    const double gx = G[0], gy = G[1], gz = G[2];
-    const double gz2 = gz * gz;
-    const double fgz2 = c.fx / fmax(hth, gz2);
-    J[0] = +fgz2 * a * gz;
-    J[1] = +fgz2 * b * gz;
-    J[2] = -fgz2 * (gx * a + gy * b);
-    J[3] = -fgz2 * (gx * gy * a + gy * gy * b + gz * gz * b);
-    J[4] = +fgz2 * (gx * gx * a + gz * gz * a + gx * gy * b);
-    J[5] = +fgz2 * (gx * gz * b - gy * gz * a);
-}
-
-__device__ __forceinline__ void project(const Cam &c, const double *G, double &u, double &v) {
-#pragma clang fp contract(off)
-    u = c.cx + c.fx * G[0] / G[2];
-    v = c.cy + c.fy * G[1] / G[2];
-}
+using namespace pgn;  // xform, project, jrow, Work, qr_solve, min_eig, the reduction (csrc/plba_posegn.hpp)
 
 // point residual (dx, dy) and the projected point
 __device__ __forceinline__ double point_res(const Cam &c, const double *T, const double *P, const double *obs, double *G,
@@ -112,146 +86,6 @@ __device__ __forceinline__ void accumulate(double *acc, const double *J, double 
     for (int i = 0; i < 6; ++i) acc[21 + i] += J[i] * r * w;
     acc[27] += r * r * w;
     acc[28] += 1.0;
-}
-
-// Thread 0's workspace (LDS: the small dense routines index it dynamically)
-struct Work {
-    double A[36], W[36], c[6], y[6];
-    int perm[6];
-};
-
-// x = H⁻¹g as Eigen's ColPivHouseholderQR solves it: Householder reflections with the largest
-// remaining column first, rank = the pivots above Eigen's threshold, the rest of x zero.
-__device__ void qr_solve(const double *H, const double *g, double *x, Work &w) {
-#pragma clang fp contract(off)
-    double *A = w.A, *c = w.c, *y = w.y;
-    int *perm = w.perm;
-    double maxn2 = 0.0;
-    bool finite = true;
-    for (int j = 0; j < 6; ++j) {
-        double s = 0.0;
-        for (int i = 0; i < 6; ++i) {
-            A[6 * i + j] = H[6 * i + j];
-            s += H[6 * i + j] * H[6 * i + j];
-            finite = finite && isfinite(H[6 * i + j]);
-        }
-        finite = finite && isfinite(g[j]);
-        maxn2 = fmax(maxn2, s);
-        perm[j] = j;
-        c[j] = g[j];
-    }
-    // A non-finite system (a match with z = 0) has no pivot to compare: Eigen drops no rank on a NaN
-    // norm and its reflections spread the NaN, so x is NaN. (fmax and the pivot search below would
-    // skip the NaN, find rank 0 and return x = 0, a step that looks converged.)
-    if (!finite) {
-        for (int i = 0; i < 6; ++i) x[i] = NAN;
-        return;
-    }
-    const double th = sqrt(maxn2) * DBL_EPSILON / 6.0, thr = th * th;
-    int nz = 6;
-    for (int k = 0; k < 6; ++k) {
-        int best = k;
-        double bn = -1.0;
-        for (int j = k; j < 6; ++j) {
-            double s = 0.0;
-            for (int i = k; i < 6; ++i) s += A[6 * i + j] * A[6 * i + j];
-            if (s > bn) {
-                bn = s;
-                best = j;
-            }
-        }
-        if (nz == 6 && bn < thr * (double)(6 - k)) nz = k;
-        if (best != k) {
-            for (int i = 0; i < 6; ++i) {
-                const double t = A[6 * i + k];
-                A[6 * i + k] = A[6 * i + best];
-                A[6 * i + best] = t;
-            }
-            const int t = perm[k];
-            perm[k] = perm[best];
-            perm[best] = t;
-        }
-        // makeHouseholderInPlace: v = [1; essential], H_k = I − τ·v·vᵀ
-        const double c0 = A[6 * k + k];
-        double tail = 0.0;
-        for (int i = k + 1; i < 6; ++i) tail += A[6 * i + k] * A[6 * i + k];
-        double tau = 0.0, beta = c0;
-        if (tail > DBL_MIN) {
-            beta = sqrt(c0 * c0 + tail);
-            if (c0 >= 0.0) beta = -beta;
-            for (int i = k + 1; i < 6; ++i) A[6 * i + k] /= (c0 - beta);
-            tau = (beta - c0) / beta;
-        } else {
-            for (int i = k + 1; i < 6; ++i) A[6 * i + k] = 0.0;
-        }
-        A[6 * k + k] = beta;
-        for (int j = k + 1; j <= 6; ++j) {  // the trailing columns, then Qᵀg (j == 6)
-            double s = (j < 6) ? A[6 * k + j] : c[k];
-            for (int i = k + 1; i < 6; ++i) s += A[6 * i + k] * ((j < 6) ? A[6 * i + j] : c[i]);
-            s *= tau;
-            if (j < 6) {
-                A[6 * k + j] -= s;
-                for (int i = k + 1; i < 6; ++i) A[6 * i + j] -= s * A[6 * i + k];
-            } else {
-                c[k] -= s;
-                for (int i = k + 1; i < 6; ++i) c[i] -= s * A[6 * i + k];
-            }
-        }
-    }
-    for (int i = 0; i < 6; ++i) x[i] = 0.0;
-    for (int i = nz - 1; i >= 0; --i) {
-        double s = c[i];
-        for (int j = i + 1; j < nz; ++j) s -= A[6 * i + j] * y[j];
-        y[i] = s / A[6 * i + i];
-    }
-    for (int i = 0; i < nz; ++i) x[perm[i]] = y[i];
-}
-
-// smallest eigenvalue of the symmetric 6x6 H by cyclic Jacobi rotations on its upper triangle
-__device__ double min_eig(const double *H, Work &w) {
-#pragma clang fp contract(off)
-    double *a = w.W;
-    for (int k = 0; k < 36; ++k) a[k] = H[k];
-    for (int sweep = 0; sweep < 50; ++sweep) {
-        double sm = 0.0;
-        for (int p = 0; p < 5; ++p)
-            for (int q = p + 1; q < 6; ++q) sm += fabs(a[6 * p + q]);
-        if (sm == 0.0) break;
-        for (int p = 0; p < 5; ++p)
-            for (int q = p + 1; q < 6; ++q) {
-                const double apq = a[6 * p + q], gg = 100.0 * fabs(apq);
-                const double app = a[6 * p + p], aqq = a[6 * q + q];
-                if (sweep > 3 && fabs(app) + gg == fabs(app) && fabs(aqq) + gg == fabs(aqq)) {
-                    a[6 * p + q] = 0.0;
-                    continue;
-                }
-                if (apq == 0.0) continue;
-                double h = aqq - app, t;
-                if (fabs(h) + gg == fabs(h)) {
-                    t = apq / h;
-                } else {
-                    const double theta = 0.5 * h / apq;
-                    t = 1.0 / (fabs(theta) + sqrt(1.0 + theta * theta));
-                    if (theta < 0.0) t = -t;
-                }
-                const double cs = 1.0 / sqrt(1.0 + t * t), sn = t * cs, tau = sn / (1.0 + cs);
-                h = t * apq;
-                a[6 * p + p] = app - h;
-                a[6 * q + q] = aqq + h;
-                a[6 * p + q] = 0.0;
-                for (int j = 0; j < 6; ++j) {
-                    if (j == p || j == q) continue;
-                    double *u = j < p ? &a[6 * j + p] : &a[6 * p + j];
-                    double *v = j < q ? &a[6 * j + q] : &a[6 * q + j];
-                    const double gu = *u, hv = *v;
-                    *u = gu - sn * (hv + gu * tau);
-                    *v = hv + sn * (gu - hv * tau);
-                }
-            }
-    }
-    double m = a[0];
-    for (int i = 1; i < 6; ++i) m = fmin(m, a[7 * i]);
-    return m;
 }
 
 }  // namespace lcp
@@ -315,23 +149,11 @@ __global__ __launch_bounds__(kLcNT) void k_lcpose(LcDev d) {
                 lcp::accumulate(acc, J, r);
             }
             // fixed-order reduction: butterfly inside the wave, the four waves in index order
-#pragma unroll
-            for (int k = 0; k < kLcAcc; ++k) {
-                double v = acc[k];
-#pragma unroll
-                for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-                if (lane == 0) s_part[wave][k] = v;
-            }
+            pgn::wave_reduce<kLcAcc, kLcWaves>(acc, s_part, lane, wave);
             __syncthreads();
             if (tid == 0) {
                 double S[kLcAcc];
-#pragma unroll
-                for (int k = 0; k < kLcAcc; ++k) {
-                    double v = s_part[0][k];
-#pragma unroll
-                    for (int wv = 1; wv < kLcWaves; ++wv) v += s_part[wv][k];
-                    S[k] = v;
-                }
+                pgn::block_sum<kLcAcc, kLcWaves>(s_part, S);
                 int stop = 0;
                 ++iters[phase];
                 if (S[28] == 0.0) {  // no active feature: rejected, T_inc stays

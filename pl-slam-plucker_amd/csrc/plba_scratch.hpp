@@ -63,6 +63,7 @@ struct CtxBase {
     // Blocks independent of the window arena (these calls leave an uploaded window intact):
     ScratchBlock pgo;    // pose graph (plba_pgo_optimize); host image: the four doubles read back per trial
     ScratchBlock lc;     // relative pose (plba_lc_relative_pose): inputs up, results and inlier flags down
+    ScratchBlock track;  // frame-to-frame pose (plba_track_pose): the same, and the residual lists
     ScratchBlock match;  // descriptor matching, grid-guided matching and stereo association share one
     BowSlot bow[2];      // place recognition: the vocabulary and the database of each slot
     ScratchBlock bow_io; // descriptors and the live rows up, scores down, the sort's scratch
@@ -129,6 +130,8 @@ inline int ScratchBlock::reserve(CtxBase &ctx, size_t dev_bytes, size_t host_byt
 // plba_stereo_associate,
 int lc_relative_pose(CtxBase *ctx, const plba_lcpose_batch *b, const plba_lcpose_params *pp, plba_lcpose_out *out,
                      uint8_t *pt_inlier, uint8_t *ln_inlier);
+int track_pose(CtxBase *ctx, const plba_track_batch *b, const plba_track_params *pp, plba_track_out *out,
+               uint8_t *pt_inlier, uint8_t *ln_inlier);
 int desc_match(CtxBase *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
 int grid_match(CtxBase *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
 int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp,

@@ -150,6 +150,38 @@ PLBA_ST_FN double st_overlap(double spl_obs, double epl_obs, double spl_proj, do
     return overlap;
 }
 
+// lineSegmentOverlap (:547-653), the 2-D one of the frame-to-frame pose: the share of the observed
+// segment (so, eo) that the projected one (sp, ep) covers. A vertical segment (|Δx| < 1) compares the
+// y coordinates, a horizontal one (|Δy| < 1) the x coordinates, any other the x coordinates of the
+// feet of the perpendiculars on the observed line.
+PLBA_ST_FN double st_overlap2d(const double *so, const double *eo, const double *sp, const double *ep) {
+    PLBA_ST_EXACT
+    double ls, le;
+    if (fabs(so[0] - eo[0]) < 1.0) {
+        const double l1 = eo[1] - so[1];
+        ls = (sp[1] - so[1]) / l1;
+        le = (ep[1] - so[1]) / l1;
+    } else if (fabs(so[1] - eo[1]) < 1.0) {
+        const double l0 = eo[0] - so[0];
+        ls = (sp[0] - so[0]) / l0;
+        le = (ep[0] - so[0]) / l0;
+    } else {
+        const double l0 = eo[0] - so[0];
+        const double a = so[1] - eo[1], b = eo[0] - so[0], c = so[0] * eo[1] - eo[0] * so[1];
+        const double lxy = 1.0 / (a * a + b * b);
+        const double xs = (b * (b * sp[0] - a * sp[1]) - a * c) * lxy;
+        const double xe = (b * (b * ep[0] - a * ep[1]) - a * c) * lxy;
+        ls = (xs - so[0]) / l0;
+        le = (xe - so[0]) / l0;
+    }
+    const double lmin = le < ls ? le : ls, lmax = ls < le ? le : ls;  // std::min / std::max
+    if (lmin < 0.0 && lmax > 1.0) return 1.0;
+    if (lmax < 0.0 || lmin > 1.0) return 0.0;
+    if (lmin < 0.0) return lmax;
+    if (lmax > 1.0) return 1.0 - lmin;
+    return lmax - lmin;
+}
+
 // :357-397 for the match l -> r of two segments (sx, sy, ex, ey); o: the kStLsDoubles of a line record
 // (NDc only with p.pluker)
 PLBA_ST_FN int st_line(const plba_stereo_params &p, const float *l, const float *r, double *o) {

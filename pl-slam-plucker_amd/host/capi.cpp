@@ -674,6 +674,12 @@ int plslam_stereo_cpu(void *user, const plba_stereo_batch *b, const plba_stereo_
     return stereoCpu(b, p, out);
 }
 
+int plslam_track_pose_cpu(void *user, const plba_track_batch *b, const plba_track_params *p, plba_track_out *out,
+                          uint8_t *pt_inlier, uint8_t *ln_inlier) {
+    (void)user;
+    return trackPoseCpu(b, p, out, pt_inlier, ln_inlier);
+}
+
 int plslam_set_keyframe_line_pluker(plslam_map *m, int32_t kf_idx, const double *NDc) {
     if (!m || !slot_ok(m->mh.map_keyframes, kf_idx)) return PLBA_E_INVALID;
     StereoFrame &f = m->mh.map_keyframes[kf_idx]->stereo_frame;

@@ -555,6 +555,9 @@ int gridMatchCpuWin(const plba_gridmatch_batch *b, const int32_t *win, int32_t *
 int descMedoidCpu(const plba_medoid_batch *b, int32_t *medoid);
 // stereo.cpp. tools/stereo_bench.py and the tests only: plba_stereo_associate's semantics, single-threaded, on the CPU
 int stereoCpu(const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out);
+// host/track_pose.cpp: plba_track_pose's semantics on the CPU, single-threaded, sums in match order
+int trackPoseCpu(const plba_track_batch *b, const plba_track_params *p, plba_track_out *out, uint8_t *pt_inlier,
+                 uint8_t *ln_inlier);
 // kf_match.cpp. tools/kfassoc_bench.py and the tests only: plba_kf_associate's semantics, single-threaded, on the CPU
 int kfAssocCpu(const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out);
 

@@ -333,6 +333,82 @@ def lcpose_out_to_dict(o: PlbaLcposeOut, pt_inlier, ln_inlier) -> dict:
                 pt_inlier=np.array(pt_inlier, np.uint8), ln_inlier=np.array(ln_inlier, np.uint8))
 
 
+# ---- frame-to-frame pose (plba_track_* / plba_track_pose)
+TRACK_MAX_N = 2048       # PLBA_TRACK_MAX_N: matches of one kind in one problem
+TRACK_PLUCKER = 0
+TRACK_ENDPOINTS = 1
+TRACK_OK, TRACK_FEW_BEFORE, TRACK_FIRST_NOT_GOOD, TRACK_FEW_AFTER, TRACK_FINAL_NOT_GOOD = range(5)
+TRACK_PREV = 53          # doubles of a problem's motion-model input: DT, DT_cov, err_norm
+
+
+class PlbaTrackBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pt_off", _ip), ("ln_off", _ip), ("pt_P", _dp), ("pt_obs", _dp), ("pt_sigma2", _dp),
+                ("ln_sP", _dp), ("ln_eP", _dp), ("ln_NDc", _dp), ("ln_le", _dp), ("ln_obs", _dp), ("ln_seg", _dp),
+                ("ln_sigma2", _dp), ("prev", _dp),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class PlbaTrackParams(C.Structure):
+    _fields_ = [("homog_th", C.c_double), ("min_error", C.c_double), ("min_error_change", C.c_double),
+                ("inlier_k", C.c_double), ("min_features", C.c_int32), ("max_iters", C.c_int32),
+                ("max_iters_ref", C.c_int32), ("has_points", C.c_int32), ("has_lines", C.c_int32),
+                ("use_motion_model", C.c_int32), ("line_model", C.c_int32), ("pad", C.c_int32)]
+
+
+class PlbaTrackOut(C.Structure):
+    _fields_ = [("branch", C.c_int32), ("iters_first", C.c_int32), ("iters_ref", C.c_int32),
+                ("n_inl_pt", C.c_int32), ("n_inl_ln", C.c_int32), ("pad", C.c_int32),
+                ("err_norm", C.c_double), ("s_p", C.c_double), ("s_l", C.c_double),
+                ("DT", C.c_double * 16), ("DT_cov", C.c_double * 36), ("DT_cov_eig", C.c_double * 6),
+                ("DT_solver", C.c_double * 16), ("H", C.c_double * 36)]
+
+
+def track_params(**kw) -> PlbaTrackParams:
+    """plba_track_default_params: src2/config.cpp:46-53, :80-86."""
+    p = PlbaTrackParams(homog_th=1e-7, min_error=1e-7, min_error_change=1e-7, inlier_k=4.0, min_features=10,
+                        max_iters=5, max_iters_ref=10, has_points=1, has_lines=1, use_motion_model=0,
+                        line_model=TRACK_PLUCKER, pad=0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+class TrackBatchView:
+    """Concatenates frame pairs (objects with the arrays of plba.trackpose.TrackProblem) into
+    contiguous arrays and the PlbaTrackBatch over them."""
+    FIELDS = (("pt_P", 3), ("pt_obs", 2), ("pt_sigma2", 1), ("ln_sP", 3), ("ln_eP", 3), ("ln_NDc", 6), ("ln_le", 3),
+              ("ln_obs", 4), ("ln_seg", 4), ("ln_sigma2", 1))
+
+    def __init__(self, problems):
+        def cat(name, w):
+            rows = [np.asarray(getattr(q, name), np.float64).reshape(-1, w) for q in problems]
+            return np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, w)))
+
+        self.arrays = {name: cat(name, w) for name, w in self.FIELDS}
+        self.pt_off = np.zeros(len(problems) + 1, np.int32)
+        self.ln_off = np.zeros(len(problems) + 1, np.int32)
+        for i, q in enumerate(problems):
+            self.pt_off[i + 1] = self.pt_off[i] + len(np.asarray(q.pt_P).reshape(-1, 3))
+            self.ln_off[i + 1] = self.ln_off[i] + len(np.asarray(q.ln_sP).reshape(-1, 3))
+        self.prev = np.ascontiguousarray(np.stack([np.asarray(q.prev, np.float64).reshape(TRACK_PREV) for q in problems])
+                                         if problems else np.zeros((0, TRACK_PREV)))
+        cam = problems[0].cam if problems else (1.0, 1.0, 0.0, 0.0)
+        if any(tuple(q.cam) != tuple(cam) for q in problems):
+            raise ValueError("the problems of one batch share one camera")
+        self.struct = PlbaTrackBatch(n=len(problems), pt_off=_ptr(self.pt_off, _ip), ln_off=_ptr(self.ln_off, _ip),
+                                     prev=_ptr(self.prev, _dp), fx=cam[0], fy=cam[1], cx=cam[2], cy=cam[3],
+                                     **{name: _ptr(a, _dp) for name, a in self.arrays.items()})
+
+
+def track_out_to_dict(o: PlbaTrackOut, pt_inlier, ln_inlier) -> dict:
+    return dict(branch=int(o.branch), iters_first=int(o.iters_first), iters_ref=int(o.iters_ref),
+                n_inl_pt=int(o.n_inl_pt), n_inl_ln=int(o.n_inl_ln), err_norm=float(o.err_norm),
+                s_p=float(o.s_p), s_l=float(o.s_l), DT=np.array(o.DT[:]).reshape(4, 4),
+                DT_cov=np.array(o.DT_cov[:]).reshape(6, 6), DT_cov_eig=np.array(o.DT_cov_eig[:]),
+                DT_solver=np.array(o.DT_solver[:]).reshape(4, 4), H=np.array(o.H[:]).reshape(6, 6),
+                pt_inlier=np.array(pt_inlier, np.uint8), ln_inlier=np.array(ln_inlier, np.uint8))
+
+
 # ---- descriptor matching (plba_match_batch / plba_desc_match)
 _fp = C.POINTER(C.c_float)
 

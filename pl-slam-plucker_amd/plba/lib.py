@@ -31,6 +31,7 @@ EXPORTED = [
     "plba_hlm_default_params", "plba_hlm_lba",
     "plba_pgo_default_params", "plba_pgo_optimize",
     "plba_lcpose_default_params", "plba_lc_relative_pose",
+    "plba_track_default_params", "plba_track_pose",
     "plba_desc_match", "plba_grid_match", "plba_stereo_default_params", "plba_stereo_associate",
     "plba_kfassoc_default_params", "plba_kf_associate", "plba_desc_medoid",
     "plba_bow_set_vocab", "plba_bow_insert", "plba_bow_remove", "plba_bow_get",
@@ -97,6 +98,10 @@ def load(path: Optional[str] = None):
     L.plba_lcpose_default_params.restype = None
     L.plba_lc_relative_pose.argtypes = [vp, C.POINTER(capi.PlbaLcposeBatch), C.POINTER(capi.PlbaLcposeParams),
                                         C.POINTER(capi.PlbaLcposeOut), bp, bp]
+    L.plba_track_default_params.argtypes = [C.POINTER(capi.PlbaTrackParams)]
+    L.plba_track_default_params.restype = None
+    L.plba_track_pose.argtypes = [vp, C.POINTER(capi.PlbaTrackBatch), C.POINTER(capi.PlbaTrackParams),
+                                  C.POINTER(capi.PlbaTrackOut), bp, bp]
     L.plba_desc_match.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
     L.plba_grid_match.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
     L.plba_stereo_default_params.argtypes = [C.POINTER(capi.PlbaStereoParams)]
@@ -115,7 +120,8 @@ def load(path: Optional[str] = None):
     for name in EXPORTED:
         f = getattr(L, name)
         if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
-                        "plba_lcpose_default_params", "plba_stereo_default_params", "plba_kfassoc_default_params"):
+                        "plba_lcpose_default_params", "plba_stereo_default_params", "plba_kfassoc_default_params",
+                        "plba_track_default_params"):
             f.restype = C.c_int
     _lib = L
     return L
@@ -324,6 +330,24 @@ class Solver:
         self._check(self.L.plba_lc_relative_pose(self.ctx, C.byref(bv.struct), C.byref(params), out,
                                                  _p(pin, C.c_uint8), _p(lin, C.c_uint8)), "plba_lc_relative_pose")
         return [capi.lcpose_out_to_dict(out[i], pin[bv.pt_off[i]:bv.pt_off[i + 1]], lin[bv.ln_off[i]:bv.ln_off[i + 1]])
+                for i in range(n)]
+
+    def track_pose(self, problems, params=None) -> list:
+        """Frame-to-frame pose (plba_track_pose; StereoFrameHandler::optimizePose,
+        src2/stereoFrameHandler.cpp:307-405) of a batch of frame pairs (plba.trackpose.TrackProblem),
+        each solved by one workgroup of one launch. One dict per problem, with its inlier flags.
+        Needs no uploaded window and leaves one intact."""
+        if params is None:
+            params = capi.PlbaTrackParams()
+            self.L.plba_track_default_params(C.byref(params))
+        bv = capi.TrackBatchView(list(problems))
+        n = bv.struct.n
+        out = (capi.PlbaTrackOut * max(n, 1))()
+        pin = np.zeros(max(int(bv.pt_off[-1]), 1), np.uint8)
+        lin = np.zeros(max(int(bv.ln_off[-1]), 1), np.uint8)
+        self._check(self.L.plba_track_pose(self.ctx, C.byref(bv.struct), C.byref(params), out,
+                                           _p(pin, C.c_uint8), _p(lin, C.c_uint8)), "plba_track_pose")
+        return [capi.track_out_to_dict(out[i], pin[bv.pt_off[i]:bv.pt_off[i + 1]], lin[bv.ln_off[i]:bv.ln_off[i + 1]])
                 for i in range(n)]
 
     def desc_match(self, pairs, nnr, best_lr: bool = True, desc_bytes=None) -> list:
