@@ -829,6 +829,124 @@ void plba_kfassoc_default_params(plba_kfassoc_params *p);
 int plba_kf_associate(plba_ctx *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *p,
                       const plba_kfassoc_out *out);
 
+/* ---- Map-to-keyframe association, the second half of lookForCommonMatches, run for every new keyframe:
+ *   MapHandler::matchMap2KFPoints()    (src/mapHandler.cpp:697-797)
+ *   MapHandler::matchMap2KFLines()     (:799-921, the endpoint-line arithmetic of :885-907)
+ * up to, and without, the sequential part that changes the map (idx, addMapPointObservation /
+ * addMapLineObservation, full_graph): the match of every candidate landmark, the epipolar test and the
+ * geometry an accepted observation needs, indexed by candidate row. A call takes a batch of keyframes;
+ * keyframe f is the matcher's problems 2 f (points) and 2 f + 1 (lines). The candidate landmarks are the
+ * query side (1), the keyframe's unmatched features the train side (2). The caller passes as candidates
+ * the landmarks with local && kf_obs_list.back() != kf_idx (:712, :813) and as features those with idx ==
+ * -1 (:730, :835), in the reference's order: filters on map state, which stay the caller's.
+ * Sums and products are those of the keyframe-to-keyframe block above: a sum of three is t0 + (t1 + t2),
+ * R x + t is (R_i0 x0 + (R_i1 x1 + R_i2 x2)) + t_i, the norm of x is sqrt(x0 x0 + (x1 x1 + x2 x2)).
+ * Visibility (:714-716, :815-820). Q = Twf.R X + Twf.t; u = cx + fx * Q0 / Q2, v = cy + fy * Q1 / Q2 (the
+ * product first, then the quotient). A row is visible iff u > 0 && u < width && v > 0 && v < height && Q2 >
+ * 0.0; a line iff both endpoints of ls_X (line3D: start, then end) pass. NaN compares false: a landmark
+ * that is not finite is invisible, not refused.
+ * Query cells. inv_width = cols / (double)width, inv_height = rows / (double)height. A visible point has
+ * the cell ((int)(u * inv_width), (int)(v * inv_height)) (:719). A visible line has the cells of both
+ * projected endpoints in grid units (:823-824), unlike matchKF2KFLines, which leaves them in pixels.
+ * Train side. Exactly that of plba_kf_associate for its current keyframe: a point feature is entered in
+ * the cell ((int)(pl0 * inv_width), (int)(pl1 * inv_height)) (:748), a line feature in the cells of
+ * getLineCoords over (spl * inv, epl * inv) with the direction normalize(((epl0 - spl0) * inv_width, (epl1
+ * - spl1) * inv_height)) (:857-863). A feature coordinate must be finite and at most one image size
+ * outside the image, which bounds the walk.
+ * Invisible rows. The reference compacts the visible rows in map order and matches the compacted list
+ * (:718-720, :822-825). Here every output is indexed by candidate row and equals what the reference
+ * computes on the compacted list with the indices mapped back: an invisible row is inert in both
+ * matchers. In the grid stage it has the cell (-2^30, -2^30), whose clipped window is empty, so it is seen
+ * by no column and touches neither `distances` nor matches_21; in the brute-force stage it has no
+ * nearest feature and is no feature's nearest row (the fallback runs only where at least two rows are
+ * visible: grid count < min < n_visible). matchGrid's order-dependent left/right check
+ * and match()'s lowest-index ties depend only on the relative order of the visible rows, which is kept.
+ * Matching. With fast_matching, matchGrid as plba_grid_match defines it, window (ws, ws, ws, ws), ratio
+ * min_ratio_12_p for points and lines alike (matching.cpp:160, :241). Without it the grid count is 0.
+ * Fallback (:759-764, :874-879). It runs iff n_visible > min && grid count < min, min = min_pt_matches or
+ * min_ls_matches: both size tests of the reference read the number of visible landmarks, and, unlike
+ * matchKF2KF*, the feature side's size is not tested. It is match() as plba_desc_match defines it with the
+ * ratio (float)min_ratio_12_p or (float)min_ratio_12_l, and its result stands alone, as in
+ * plba_kf_associate. n_visible is known only on the device: the decision is taken there.
+ * Point test and record [6], for a row with a match i1 -> i2 (:770-784): err = sqrt(du du + dv dv), du =
+ * u - pl0, dv = v - pl1; accepted iff err < max_kf_epip_p. dir = T_kf_w.R (P / |P|) + T_kf_w.t, each
+ * component of P divided by the norm: the translation is added to a direction, kept from the reference.
+ * The record is u, v, err, dir[3].
+ * Line test and record [9] (:885-907), (su, sv) and (eu, ev) the projections of the two endpoints: err0 =
+ * (le0 * su + le1 * sv) + le2, err1 = (le0 * eu + le1 * ev) + le2; accepted iff err0 < max_kf_epip_l && err1
+ * < max_kf_epip_l. The test is signed, kept from the reference: a large negative error passes. mid =
+ * y / |y| with y = T_kf_w.R m + T_kf_w.t, m_i = 0.5 * (sP_i + eP_i): the observation direction of an
+ * endpoint-line build (:899-901), always computed. The record is su, sv, eu, ev, err0, err1, mid[3].
+ * An invisible or unmatched row has a zero record and is not accepted; NaN compares false in both tests.
+ * Defined where the reference is not: an empty side gives no match and does not disturb the batch (the
+ * reference returns before matching, :736, :841; the fallback flag is still n_visible > min && grid count
+ * < min). Arithmetic: doubles, only + - * / sqrt, one rounding per operation, as in the stereo block. */
+typedef struct plba_mapassoc_params {
+    int32_t cols, rows;                 /* GRID_COLS 64, GRID_ROWS 48                            */
+    int32_t width, height;              /* the image size, > 0                                   */
+    int32_t fast_matching;              /* SlamConfig::fastMatching(): 1 as the shipped yaml has */
+    int32_t ws;                         /* Config::matchingF2FWs()       3 (src2/config.cpp:92)  */
+    int32_t best_lr;                    /* Config::bestLRMatches()       1 (src2/config.cpp:51)  */
+    int32_t min_pt_matches;             /* SlamConfig::minPointMatches() 10                      */
+    int32_t min_ls_matches;             /* SlamConfig::minLineMatches()   6                      */
+    int32_t pad;
+    double  min_ratio_12_p;             /* Config::minRatio12P()       0.9 (:60)                 */
+    double  min_ratio_12_l;             /* Config::minRatio12L()       0.9 (:68)                 */
+    double  line_sim_th;                /* Config::lineSimTh()        0.75 (:63)                 */
+    double  max_kf_epip_p;              /* SlamConfig::maxKFEpipP()    1.0 (src/slamConfig.cpp:51) */
+    double  max_kf_epip_l;              /* SlamConfig::maxKFEpipL()    1.0 (:52)                 */
+    double  fx, fy, cx, cy;             /* PinholeStereoCamera                                   */
+} plba_mapassoc_params;
+typedef struct plba_mapassoc_batch {    /* n keyframes, concatenated; _m map candidates, _f features */
+    int32_t n;
+    int32_t desc_bytes;                 /* as in plba_match_batch                                */
+    const int32_t *pt_off_m, *pt_off_f; /* [n+1] point rows of keyframe f: [off[f], off[f+1])    */
+    const int32_t *ls_off_m, *ls_off_f; /* [n+1] line rows                                       */
+    const double  *Twf;                 /* [n][12] 3 x 4, row-major: world -> keyframe           */
+    const double  *T_kf_w;              /* [n][16] the keyframe's pose, row-major                */
+    const double  *pt_X;                /* [.][3] MapPoint::point3D                              */
+    const uint8_t *pdesc_m;             /* [.][desc_bytes] med_desc                              */
+    const double  *ls_X;                /* [.][6] MapLine::line3D: start, then end               */
+    const uint8_t *ldesc_m;
+    const double  *pt_pl;               /* [.][2]                                                */
+    const double  *pt_P;                /* [.][3]                                                */
+    const uint8_t *pdesc_f;
+    const double  *ls_spl, *ls_epl;     /* [.][2]                                                */
+    const double  *ls_le;               /* [.][3]                                                */
+    const double  *ls_sP, *ls_eP;       /* [.][3]                                                */
+    const uint8_t *ldesc_f;
+} plba_mapassoc_batch;
+/* Indexed by candidate row, not compacted. The five per-problem arrays are required; any other array
+ * may be NULL and is then skipped. n_matches is the reference's return value, counted after the epipolar
+ * test; n_accepted counts the accepted flags and so equals it (the matcher's own count is the number of
+ * rows with m12 >= 0). */
+typedef struct plba_mapassoc_out {
+    int32_t *n_visible, *n_grid, *n_matches, *fallback, *n_accepted; /* [2n]: 2 f points, 2 f + 1 lines */
+    uint8_t *pt_visible;                /* [pt_off_m[n]]                                         */
+    int32_t *pt_m12;                    /* [.] the feature row, local to the keyframe, or -1     */
+    uint8_t *pt_accepted;               /* [.]                                                   */
+    double  *pt_rec;                    /* [.][6] u, v, err, dir                                 */
+    uint8_t *ls_visible;                /* [ls_off_m[n]]                                         */
+    int32_t *ls_m12;
+    uint8_t *ls_accepted;
+    double  *ls_rec;                    /* [.][9] su, sv, eu, ev, err0, err1, mid                */
+} plba_mapassoc_out;
+/* src/slamConfig.cpp and src2/config.cpp as plba_kfassoc_default_params takes them; width, height and the
+ * camera are zero and must be set. */
+void plba_mapassoc_default_params(plba_mapassoc_params *p);
+/* Runs on the context's stream in a fixed number of launches (the cells, the matcher's three, the
+ * fallback's bound, the brute-force matcher's two, which return at once where a problem does not fall
+ * back, and the geometry) with one upload and one read-back; needs no uploaded window and leaves one
+ * intact; shares plba_desc_match's device block and pinned host image. PLBA_E_INVALID, checked on the host
+ * before anything is launched, for a NULL batch, params, out, per-problem output or offset array, a NULL
+ * input array where rows exist, n < 0, decreasing or negative offsets, a bad desc_bytes, cols, rows, width
+ * or height <= 0, ws < 0 or ws >= 2^30, more than 65535 feature rows or more than 65535 * 256 candidate
+ * rows in a problem, a Twf or T_kf_w that is not finite, or a feature coordinate (pt_pl, ls_spl, ls_epl)
+ * that is not finite or outside the bound above. A landmark that is not finite is invisible, not refused.
+ * n == 0 does nothing and returns PLBA_OK. */
+int plba_map_associate(plba_ctx *ctx, const plba_mapassoc_batch *b, const plba_mapassoc_params *p,
+                       const plba_mapassoc_out *out);
+
 /* ---- Place recognition, the step of loopClosure() that decides whether to look for a loop at all:
  *   DBoW2 TemplatedVocabulary<FORB>::transform(features, v)   (TemplatedVocabulary.h:1046-1084, :1198-1239)
  *   BowVector::addWeight / normalize(L1)                       (BowVector.cpp:34-84)

@@ -437,6 +437,30 @@ int plslam_match_map_to_kf(plslam_map *m, int32_t kf_idx, const double *Twf, con
 int plslam_local_mapping_step_kf(plslam_map *m, int32_t kf_idx, const plslam_mapmatch_params *params,
                                  plslam_mapmatch_stats *match_stats, plslam_lba_stats *stats, int32_t *n_pt_removed,
                                  int32_t *n_ln_removed);
+/* The same association around ONE plba_map_associate call (or the hook): matchMap2KFPoints +
+ * matchMap2KFLines with the projection, the in-image test, the cells, both matchers, the fallback's decision
+ * and the epipolar tests on the device. The candidates (local, kf_obs_list.back() != kf_idx) and the
+ * keyframe's features with idx -1 are gathered in the reference's order, the call is made, and the rows are
+ * walked in i1 order, points before lines: the feature's idx, addMapPointObservation with the record's dir /
+ * addMapLineObservation, full_graph. It fills the statistics of plslam_match_map_to_kf (fallback is 0 where a
+ * kind has no unmatched feature, as there) and leaves the map as that call leaves it, up to the order of a
+ * three-term sum in the stored direction. A kind takes part when the keyframe has features of it. Every
+ * candidate's descriptor size and observers are checked, not only the visible ones'. params NULL = the
+ * defaults; params->width == 0 and height == 0: the image size and the camera of plslam_set_camera; the grid
+ * is params->cols x rows. plslam_match_map_to_kf stays the yardstick and is unchanged. */
+int plslam_match_map_to_kf_assoc(plslam_map *m, int32_t kf_idx, const double *Twf, const plba_mapassoc_params *params,
+                                 plslam_mapmatch_stats *stats);
+/* plslam_match_map_to_kf_assoc(kf_idx, NULL, params), then plslam_local_mapping_step. */
+int plslam_local_mapping_step_kf_assoc(plslam_map *m, int32_t kf_idx, const plba_mapassoc_params *params,
+                                       plslam_mapmatch_stats *match_stats, plslam_lba_stats *stats, int32_t *n_pt_removed,
+                                       int32_t *n_ln_removed);
+/* Association hook, in the style of plslam_set_kfassoc_fn: NULL = plba_map_associate. */
+typedef int (*plslam_mapassoc_fn)(void *user, const plba_mapassoc_batch *b, const plba_mapassoc_params *p,
+                                  const plba_mapassoc_out *out);
+int plslam_set_mapassoc_fn(plslam_map *m, plslam_mapassoc_fn fn, void *user);
+/* tools/mapassoc_bench.py and the tests only, not a product path: a single-threaded restatement of
+ * plba_map_associate's semantics on the CPU, which compacts the visible landmarks as the reference does. */
+int plslam_map_assoc_cpu(void *user, const plba_mapassoc_batch *b, const plba_mapassoc_params *p, const plba_mapassoc_out *out);
 /* ---- StereoFrame::matchStereoPoints + matchStereoLines (src2/stereoFrame.cpp:121-174, :310-435): the
  * features of keyframe kf_idx from the detector output of its two images, with no StVO on the caller's
  * side. One plba_stereo_associate call (or the hook) with the one frame; the survivors are stored as

@@ -2477,6 +2477,29 @@ int plba_kf_associate(plba_ctx *ctx, const plba_kfassoc_batch *b, const plba_kfa
     return ctx ? kf_associate(ctx, b, p, out) : PLBA_E_INVALID;
 }
 
+// map-to-keyframe association (csrc/plba_assoc.hip, csrc/plba_mapassoc.hpp)
+void plba_mapassoc_default_params(plba_mapassoc_params *p) {
+    if (!p) return;
+    *p = plba_mapassoc_params{};
+    p->cols = 64;                  // GRID_COLS / GRID_ROWS (include2/stereoFrame.h:51-52)
+    p->rows = 48;
+    p->fast_matching = 1;          // config/config/config.yaml:5 (src/slamConfig.cpp:43 has false)
+    p->ws = 3;                     // src2/config.cpp:92
+    p->best_lr = 1;                // :51
+    p->min_pt_matches = 10;        // src/slamConfig.cpp:85-86
+    p->min_ls_matches = 6;
+    p->min_ratio_12_p = 0.9;       // src2/config.cpp:60
+    p->min_ratio_12_l = 0.9;       // :68
+    p->line_sim_th = 0.75;         // :63
+    p->max_kf_epip_p = 1.0;        // src/slamConfig.cpp:51-52
+    p->max_kf_epip_l = 1.0;
+}
+
+int plba_map_associate(plba_ctx *ctx, const plba_mapassoc_batch *b, const plba_mapassoc_params *p,
+                       const plba_mapassoc_out *out) {
+    return ctx ? map_associate(ctx, b, p, out) : PLBA_E_INVALID;
+}
+
 // median descriptor (csrc/plba_assoc.hip, csrc/plba_medoid.hpp)
 int plba_desc_medoid(plba_ctx *ctx, const plba_medoid_batch *b, int32_t *medoid) {
     if (!ctx) return PLBA_E_INVALID;

@@ -1,11 +1,11 @@
 // plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose,
-// the frame-to-frame pose, the two descriptor matchers, the stereo and the keyframe association, the median descriptor and
+// the frame-to-frame pose, the two descriptor matchers, the stereo, the keyframe and the map association, the median descriptor and
 // place recognition. They share nothing with the solver (no Dev, no step graph, no window arena), so
 // they are a translation unit of their own: an edit to a matcher does not rebuild the factorisation
 // kernels. Each call is one upload, its kernels and one read-back through a ScratchBlock. A Staged
 // (csrc/plba_layout.hpp) lays the block out: the call declares each array once, by its kernel-struct
 // field, role, count and host source or destination; stage() then fills the pinned image and the
-// fields, fetch() delivers the outputs. The two association calls run in phases (validate, plan,
+// fields, fetch() delivers the outputs. The three association calls run in phases (validate, plan,
 // fill, launch, scatter) over a plan of csrc/plba_assoc_plan.hpp, which needs no device.
 // The extern "C" symbols are forwarders in plba.hip.
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include "plba_gridmatch.hpp"
 #include "plba_stereo.hpp"
 #include "plba_kfassoc.hpp"
+#include "plba_mapassoc.hpp"
 #include "plba_bow.hpp"
 #include "plba_medoid.hpp"
 #include "plba_assoc_plan.hpp"
@@ -120,7 +121,7 @@ int grid_launch(CtxBase *ctx, const GmDev &D, int max_train) {
     return PLBA_OK;
 }
 
-// the arrays of a GmDev that the struct O owns (an StDev or a KfDev, whose kernels make the cells)
+// the arrays of a GmDev that the struct O owns (an StDev, a KfDev or a MaDev, whose kernels make the cells)
 template <typename Owner>
 void grid_bind(GmDev &D, const Owner &O) {
     D.off1 = O.off1; D.off2 = O.off2; D.kind = O.kind;
@@ -133,8 +134,13 @@ int desc_launch(CtxBase *ctx, const DmDev &M, int max_rows) {
     hipStream_t s = ctx->stream;
     if (max_rows > 0) {  // a workgroup past its pair's rows in its direction, or of a pair that its gate switches off, returns at once
         const dim3 grid(M.n, (max_rows + kDmNT - 1) / kDmNT, 2);
-        if (M.dwords <= 8) hipLaunchKernelGGL(k_desc_nn<8>, grid, dim3(kDmNT), 0, s, M);
-        else hipLaunchKernelGGL(k_desc_nn<16>, grid, dim3(kDmNT), 0, s, M);
+        if (M.skip1) {  // plba_map_associate: the side-1 rows with a flag take no part
+            if (M.dwords <= 8) hipLaunchKernelGGL((k_desc_nn<8, true>), grid, dim3(kDmNT), 0, s, M);
+            else hipLaunchKernelGGL((k_desc_nn<16, true>), grid, dim3(kDmNT), 0, s, M);
+        } else {
+            if (M.dwords <= 8) hipLaunchKernelGGL(k_desc_nn<8>, grid, dim3(kDmNT), 0, s, M);
+            else hipLaunchKernelGGL(k_desc_nn<16>, grid, dim3(kDmNT), 0, s, M);
+        }
         PLBA_LAUNCHED(ctx, "k_desc_nn");
     }
     hipLaunchKernelGGL(k_desc_cross, dim3(M.n), dim3(kDmNT), 0, s, M); PLBA_LAUNCHED(ctx, "k_desc_cross");
@@ -781,6 +787,210 @@ int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_p
     if (const int rc = kf_launch(ctx, P, b->desc_bytes, *pp)) return rc;
     if (const int rc = read_back(ctx, ctx->match, P.B)) return rc;
     return kf_scatter(ctx, P, out);
+}
+
+// ---------------------------------------------------------------- map-to-keyframe association
+// MapHandler::matchMap2KFPoints / matchMap2KFLines (src/mapHandler.cpp:697-797, :799-921) up to the
+// sequential part, for a batch of keyframes: one upload, k_map_cells, the grid matcher's three launches
+// with the window (ws, ws, ws, ws), k_map_gate, the brute-force matcher's two, gated per problem on the
+// device and blind to the invisible landmarks, k_map_geom (csrc/plba_mapassoc.hpp), one read-back.
+// Keyframe f is the matcher's problems 2 f (points) and 2 f + 1 (lines).
+namespace {
+
+// everything that refuses the call, and the table; no device call
+int map_validate(CtxBase *ctx, const plba_mapassoc_batch *b, const plba_mapassoc_params *pp, const plba_mapassoc_out *out,
+                 ProblemTable &T) {
+    const char *const op = "map association";
+    const int n = b->n;
+    if (n > (INT32_MAX - 1) / 2) {
+        ctx->set_error("map association: %d keyframes", n);
+        return PLBA_E_INVALID;
+    }
+    if (const int rc = check_desc_bytes(ctx, op, b->desc_bytes)) return rc;
+    if (!pp || !out || !out->n_visible || !out->n_grid || !out->n_matches || !out->fallback || !out->n_accepted ||
+        !b->pt_off_m || !b->pt_off_f || !b->ls_off_m || !b->ls_off_f || !b->Twf || !b->T_kf_w) {
+        ctx->set_error("map association: NULL params / out / n_visible / n_grid / n_matches / fallback / n_accepted / offsets / poses");
+        return PLBA_E_INVALID;
+    }
+    const plba_mapassoc_params &prm = *pp;
+    if (prm.cols <= 0 || prm.rows <= 0 || prm.width <= 0 || prm.height <= 0 || prm.ws < 0 || prm.ws >= (1 << 30)) {
+        ctx->set_error("map association: a grid of %d x %d cells, an image of %d x %d or a window of %d", prm.cols, prm.rows,
+                       prm.width, prm.height, prm.ws);
+        return PLBA_E_INVALID;
+    }
+    for (const int32_t *off : {b->pt_off_m, b->pt_off_f, b->ls_off_m, b->ls_off_f})
+        if (const int rc = check_offsets(ctx, op, "row", "keyframe", off, n)) return rc;
+    const int bad = T.init(b->pt_off_m, b->pt_off_f, b->ls_off_m, b->ls_off_f, n, prm.cols, prm.rows);
+    if (bad == T.kTooMany) {
+        ctx->set_error("map association: %zu candidate rows, %zu feature rows or %zu cells are more than %d", T.N1, T.N2, T.nc,
+                       INT32_MAX);
+        return PLBA_E_INVALID;
+    }
+    if ((T.cnt[0][0] && (!b->pt_X || !b->pdesc_m)) || (T.cnt[0][1] && (!b->pt_pl || !b->pt_P || !b->pdesc_f)) ||
+        (T.cnt[1][0] && (!b->ls_X || !b->ldesc_m)) ||
+        (T.cnt[1][1] && (!b->ls_spl || !b->ls_epl || !b->ls_le || !b->ls_sP || !b->ls_eP || !b->ldesc_f))) {
+        ctx->set_error("map association: NULL landmark, feature or descriptor array");
+        return PLBA_E_INVALID;
+    }
+    if (bad == T.kTooWide) {
+        ctx->set_error("map association: %d feature rows in a problem are more than %d", T.max_train, kGmMaxTrain);
+        return PLBA_E_INVALID;
+    }
+    if ((T.max_prev + kDmNT - 1) / kDmNT > 65535) {  // the row tiles are a grid's second dimension
+        ctx->set_error("map association: %d candidate rows in a problem are more than %d", T.max_prev, 65535 * kDmNT);
+        return PLBA_E_INVALID;
+    }
+    for (int k = 0; k < 2; ++k)
+        for (size_t e = 0; e < (size_t)n * (k ? 16 : 12); ++e)
+            if (!std::isfinite((k ? b->T_kf_w : b->Twf)[e])) {
+                ctx->set_error("map association: %s of keyframe %zu is not finite", k ? "T_kf_w" : "Twf", e / (k ? 16 : 12));
+                return PLBA_E_INVALID;
+            }
+    // the bound of a line feature's walk
+    const double *const fcoords[3] = {b->pt_pl, b->ls_spl, b->ls_epl};
+    for (int k = 0; k < 3; ++k) {
+        const int kd = k ? 1 : 0;
+        if (!T.cnt[kd][1]) continue;
+        const double *c = fcoords[k] + 2 * (size_t)T.offs[kd][1][0];
+        if (const int rc = check_coords<double, 2>(ctx, op, "feature", kd ? "line" : "point", c, T.cnt[kd][1], prm.width, prm.height))
+            return rc;
+    }
+    return PLBA_OK;
+}
+
+// the inputs into the staged image: the poses keyframe by keyframe, the matchers' inputs problem by problem, the rows
+void map_fill(const MaPlan &P, const plba_mapassoc_batch *b, const plba_mapassoc_params &prm) {
+    const ProblemTable &T = P.T;
+    const Staged &B = P.B;
+    const uint8_t *const descs[2][2] = {{b->pdesc_m, b->pdesc_f}, {b->ldesc_m, b->ldesc_f}};
+    double *pose = B.host(P.A.pose);
+    for (int f = 0; f < T.n; ++f) {
+        memcpy(pose + (size_t)kMaPoseDoubles * f, b->Twf + 12 * (size_t)f, 12 * sizeof(double));
+        memcpy(pose + (size_t)kMaPoseDoubles * f + 12, b->T_kf_w + 16 * (size_t)f, 16 * sizeof(double));
+    }
+    T.fill(B.host(P.A.off1), B.host(P.A.off2), B.host(P.A.kind), B.host(P.A.kbase1), B.host(P.A.kbase2), B.host(P.A.cbase),
+           descs, (size_t)b->desc_bytes, (uint8_t *)B.host(P.D.desc1), (uint8_t *)B.host(P.D.desc2));
+    int32_t *min_matches = B.host(P.A.min_matches), *ws = B.host(P.D.ws);
+    double *nnr = B.host(P.D.nnr), *sim_th = B.host(P.D.sim_th);
+    float *fnnr = B.host(P.M.nnr);
+    for (int p = 0; p < 2 * T.n; ++p) {
+        const int kd = p % 2;
+        min_matches[p] = kd ? prm.min_ls_matches : prm.min_pt_matches;
+        for (int e = 0; e < 4; ++e) ws[4 * p + e] = prm.ws;  // :751-754, :866-869
+        nnr[p] = prm.min_ratio_12_p;  // matching.cpp:160, :241: for lines too
+        sim_th[p] = prm.line_sim_th;
+        fnnr[p] = (float)(kd ? prm.min_ratio_12_l : prm.min_ratio_12_p);  // :762, :877
+    }
+    // the rows of each kind keep the caller's order from the first keyframe's offset
+    const size_t mp = (size_t)T.offs[0][0][0], ml = (size_t)T.offs[1][0][0], fp = (size_t)T.offs[0][1][0], fl = (size_t)T.offs[1][1][0];
+    if (T.cnt[0][0]) memcpy(B.host(P.A.q_pt), b->pt_X + 3 * mp, 3 * T.cnt[0][0] * sizeof(double));
+    if (T.cnt[1][0]) memcpy(B.host(P.A.q_ls), b->ls_X + 6 * ml, 6 * T.cnt[1][0] * sizeof(double));
+    double *t = B.host(P.A.t_pt);
+    for (size_t i = 0; i < T.cnt[0][1]; ++i, t += kMaTPtDoubles) {
+        memcpy(t, b->pt_pl + 2 * (fp + i), 2 * sizeof(double));
+        memcpy(t + 2, b->pt_P + 3 * (fp + i), 3 * sizeof(double));
+    }
+    t = B.host(P.A.t_ls);
+    for (size_t i = 0; i < T.cnt[1][1]; ++i, t += kMaTLsDoubles) {
+        memcpy(t, b->ls_spl + 2 * (fl + i), 2 * sizeof(double));
+        memcpy(t + 2, b->ls_epl + 2 * (fl + i), 2 * sizeof(double));
+        memcpy(t + 4, b->ls_le + 3 * (fl + i), 3 * sizeof(double));
+        memcpy(t + 7, b->ls_sP + 3 * (fl + i), 3 * sizeof(double));
+        memcpy(t + 10, b->ls_eP + 3 * (fl + i), 3 * sizeof(double));
+    }
+}
+
+// the scalars of the three structs, the matchers' arrays handed over from A, and the launches
+int map_launch(CtxBase *ctx, MaPlan &P, int desc_bytes, const plba_mapassoc_params &prm) {
+    MaDev &A = P.A;
+    GmDev &D = P.D;
+    DmDev &M = P.M;
+    const int np = 2 * P.T.n, max_rows = P.T.max_rows;
+    hipStream_t s = ctx->stream;
+    A.gm12 = D.m12; A.gcount = D.count; A.fm12 = M.m12;
+    A.inv_w = prm.cols / (double)prm.width;
+    A.inv_h = prm.rows / (double)prm.height;
+    A.stride = P.T.stride;
+    A.prm = prm;
+    grid_bind(D, A);
+    M.off1 = A.off1; M.off2 = A.off2; M.desc1 = D.desc1; M.desc2 = D.desc2;
+    M.n = np;
+    M.dwords = desc_bytes / 4;
+    M.best_lr = prm.best_lr != 0;
+    M.gate_count = D.count;
+    M.gate_min = A.gate_min;
+    M.skip1 = A.skip;
+    PLBA_CHECK(hipMemsetAsync(A.cnt, 0, sizeof(int32_t) * 2 * np, s));  // the two sums start at 0
+    if (prm.fast_matching) {
+        if (const int rc = grid_prepare(ctx, D, np, desc_bytes, prm.cols, prm.rows, prm.best_lr, P.key_bytes)) return rc;
+    } else {  // the grid count is 0 (:739)
+        PLBA_CHECK(hipMemsetAsync(D.count, 0, sizeof(int32_t) * np, s));
+    }
+    // a thread past its problem's rows only takes part in the count; with no row at all every count stays 0
+    hipLaunchKernelGGL(k_map_cells, dim3(np, std::max(1, (max_rows + kMaNT - 1) / kMaNT)), dim3(kMaNT), 0, s, A);
+    PLBA_LAUNCHED(ctx, "k_map_cells");
+    if (prm.fast_matching)
+        if (const int rc = grid_launch(ctx, D, P.T.max_train)) return rc;
+    hipLaunchKernelGGL(k_map_gate, dim3((np + kMaNT - 1) / kMaNT), dim3(kMaNT), 0, s, A, np); PLBA_LAUNCHED(ctx, "k_map_gate");
+    if (const int rc = desc_launch(ctx, M, max_rows)) return rc;  // a problem that keeps its grid matches is gated off
+    hipLaunchKernelGGL(k_map_geom, dim3(np, std::max(1, (P.T.max_prev + kMaNT - 1) / kMaNT)), dim3(kMaNT), 0, s, A);
+    PLBA_LAUNCHED(ctx, "k_map_geom");
+    return PLBA_OK;
+}
+
+// every candidate row's flags, match and record, to the keyframe's candidate offset in the caller's arrays
+int map_scatter(CtxBase *ctx, const MaPlan &P, const plba_mapassoc_out *out) {
+    const Staged &B = P.B;
+    const int32_t *cnt = B.host(P.A.cnt), *res = B.host(P.A.res), *m12 = B.host(P.A.m12), *off1 = B.host(P.A.off1),
+                  *kbase1 = B.host(P.A.kbase1);
+    const uint8_t *vis = B.host(P.A.vis), *acc = B.host(P.A.acc);
+    const double *ptd = B.host(P.A.ptd), *lsd = B.host(P.A.lsd);
+    for (int p = 0; p < 2 * P.T.n; ++p) {
+        const ProblemTable::Problem q = P.T.at(p);
+        const int kd = q.kind, a1 = q.a1, r1 = q.r1;
+        if (cnt[2 * p] < 0 || cnt[2 * p] > r1 || cnt[2 * p + 1] < 0 || cnt[2 * p + 1] > cnt[2 * p]) {
+            ctx->set_error("map association: the device returned %d visible and %d accepted rows for %d rows", cnt[2 * p],
+                           cnt[2 * p + 1], r1);
+            return PLBA_E_DEVICE;
+        }
+        out->n_visible[p] = cnt[2 * p];
+        out->n_grid[p] = res[2 * p];
+        out->fallback[p] = res[2 * p + 1];
+        out->n_matches[p] = out->n_accepted[p] = cnt[2 * p + 1];  // :793, :917: the count after the epipolar test
+        if (!r1) continue;
+        int32_t *om = kd ? out->ls_m12 : out->pt_m12;
+        uint8_t *ov = kd ? out->ls_visible : out->pt_visible, *oa = kd ? out->ls_accepted : out->pt_accepted;
+        if (om) memcpy(om + a1, m12 + off1[p], sizeof(int32_t) * r1);
+        if (ov) memcpy(ov + a1, vis + off1[p], r1);
+        if (oa) memcpy(oa + a1, acc + off1[p], r1);
+        if (!kd) {
+            if (out->pt_rec) memcpy(out->pt_rec + (size_t)kMaPtDoubles * a1, ptd + (size_t)kMaPtDoubles * kbase1[p], sizeof(double) * kMaPtDoubles * r1);
+        } else {
+            if (out->ls_rec) memcpy(out->ls_rec + (size_t)kMaLsDoubles * a1, lsd + (size_t)kMaLsDoubles * kbase1[p], sizeof(double) * kMaLsDoubles * r1);
+        }
+    }
+    return PLBA_OK;
+}
+
+}  // namespace
+
+int map_associate(CtxBase *ctx, const plba_mapassoc_batch *b, const plba_mapassoc_params *pp, const plba_mapassoc_out *out) {
+    if (!b || b->n < 0) {
+        ctx->set_error("map association: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    if (b->n == 0) return PLBA_OK;
+    MaPlan P;
+    if (const int rc = map_validate(ctx, b, pp, out, P.T)) return rc;
+    (void)hipSetDevice(ctx->opts.device);
+    P.declare((size_t)b->desc_bytes / 4);
+    if (const int rc = ctx->match.reserve(*ctx, P.B.total(), P.B.outputs_end(), "map association")) return rc;
+    P.B.stage(ctx->match.host, ctx->match.dev);
+    map_fill(P, b, *pp);
+    if (const int rc = upload(ctx, ctx->match, P.B)) return rc;
+    if (const int rc = map_launch(ctx, P, b->desc_bytes, *pp)) return rc;
+    if (const int rc = read_back(ctx, ctx->match, P.B)) return rc;
+    return map_scatter(ctx, P, out);
 }
 
 // ---------------------------------------------------------------- median descriptor

@@ -1,4 +1,4 @@
-// plba_assoc_args.hpp — the kernel-argument structs of the matchers, the two association calls and the
+// plba_assoc_args.hpp — the kernel-argument structs of the matchers, the three association calls and the
 // median descriptor, with the constants their host side sizes blocks and grids by. Standard C++ only:
 // no HIP type, no kernel, so the host-only plans (csrc/plba_assoc_plan.hpp) and the layout test
 // (tests/cpp/layout_check.cpp) read what the kernels read. Each kernel header includes this one and
@@ -24,6 +24,9 @@ struct DmDev {
     int32_t n, dwords, best_lr;
     // plba_kf_associate's fallback: a pair runs only if gate_count[pair] < gate_min[pair]; NULL: every pair
     const int32_t *gate_count, *gate_min;
+    // plba_map_associate's invisible landmarks: [off1[n]], nonzero where the side-1 row takes no part (it gets
+    // nn12 = -1 and is never a side-2 row's nearest); NULL: every row takes part
+    const uint8_t *skip1;
 };
 
 // ---------------------------------------------------------------- csrc/plba_gridmatch.hpp
@@ -106,6 +109,45 @@ struct KfDev {
     int32_t stride, pad;           // stride: cells of a current line, max(cols, rows)
     plba_kfassoc_params prm;
 };
+
+// ---------------------------------------------------------------- csrc/plba_mapassoc.hpp
+constexpr int kMaNT = 256;  // threads of the three kernels
+constexpr int kMaPtDoubles = 6;    // a point record: u, v, err, dir[3]
+constexpr int kMaLsDoubles = 9;    // a line record: su, sv, eu, ev, err0, err1, mid[3]
+constexpr int kMaPoseDoubles = 28;  // a keyframe's poses: Twf[12], T_kf_w[16]
+constexpr int kMaQLsDoubles = 6;    // a candidate line row: line3D
+constexpr int kMaTPtDoubles = 5;    // a point feature row: pl[2], P[3]
+constexpr int kMaTLsDoubles = 13;   // a line feature row: spl[2], epl[2], le[3], sP[3], eP[3]
+
+struct MaDev {
+    const int32_t *off1, *off2;    // [2n+1] candidate / feature row ranges of each problem
+    const int32_t *kind;           // [2n] 0 points, 1 lines
+    const int32_t *kbase1, *kbase2;  // [2n] first candidate / feature row of the problem within its kind
+    const int32_t *cbase;          // [2n+1] first cell of the problem's feature rows
+    const int32_t *min_matches;    // [2n] min_pt_matches or min_ls_matches
+    const double *pose;            // [n][kMaPoseDoubles]
+    const double *q_pt, *q_ls;     // candidate rows: [.][3], [.][kMaQLsDoubles]
+    const double *t_pt, *t_ls;     // feature rows: [.][kMaTPtDoubles], [.][kMaTLsDoubles]
+    int32_t *cell1, *cell1e;       // [off1[2n]][2]
+    int32_t *cell_off2;            // [off2[2n]+1]
+    int32_t *cells2;               // [cbase[2n]][2]
+    double *dir2;                  // [off2[2n]][2]
+    uint8_t *skip;                 // [off1[2n]] 1 where the candidate is invisible: DmDev::skip1
+    int32_t *gate_min;             // [2n] the fallback's bound on the grid count, or INT_MIN: DmDev::gate_min
+    const int32_t *gm12, *gcount;  // the grid matcher's result
+    const int32_t *fm12;           // the brute-force matcher's, where it ran
+    int32_t *cnt;                  // [2n][2] visible candidates, accepted rows: summed with integer atomics from 0
+    int32_t *res;                  // [2n][2] grid count, fallback
+    int32_t *m12;                  // [off1[2n]]
+    uint8_t *vis, *acc;            // [off1[2n]] visible, accepted
+    double *ptd, *lsd;             // point records [.][kMaPtDoubles], line records [.][kMaLsDoubles]
+    double inv_w, inv_h;           // cols / (double)width, rows / (double)height
+    int32_t stride, pad;           // stride: cells of a line feature, max(cols, rows)
+    plba_mapassoc_params prm;
+};
+// the kernels read the struct as an argument: 29 pointers, two doubles, two ints and the parameters, no padding
+static_assert(sizeof(plba_mapassoc_params) == 10 * 4 + 9 * 8, "plba_mapassoc_params has no padding");
+static_assert(sizeof(MaDev) == 29 * sizeof(void *) + 2 * 8 + 2 * 4 + sizeof(plba_mapassoc_params), "MaDev has no padding");
 
 // ---------------------------------------------------------------- csrc/plba_medoid.hpp
 struct MedDev {

@@ -1,4 +1,4 @@
-// plba_assoc_plan.hpp — the host decisions of the stereo and the keyframe association (and the median
+// plba_assoc_plan.hpp — the host decisions of the stereo, the keyframe and the map association (and the median
 // descriptor) that need no device: the problem table of a batch and the block layout of a call, array
 // by array in block order. Standard C++ only, like csrc/plba_layout.hpp, so that
 // tests/cpp/layout_check.cpp runs what csrc/plba_assoc.hip runs.
@@ -120,6 +120,29 @@ struct KfPlan {
         B.out(K.ptd, kKfPtDoubles * T.cnt[0][0]), B.out(K.lsd, kKfLsDoubles * T.cnt[1][0]), B.out(K.rej, T.cnt[1][0]);
         key_bytes = grid_workset(B, D, K, T);
         B.dev(M.nn12, N1), B.dev(M.nn21, N2), B.dev(M.m12, N1), B.dev(M.count, P);
+    }
+};
+
+struct MaPlan {
+    ProblemTable T;  // side 1: the candidate landmarks, side 2: the keyframe's unmatched features
+    MaDev A{};  // owns the arrays that several kernels use; the matchers' structs are bound from it
+    GmDev D{};
+    DmDev M{};
+    Staged B;
+    size_t key_bytes = 0;
+
+    void declare(size_t dw) {
+        const size_t P = 2 * (size_t)T.n, N1 = T.N1, N2 = T.N2;
+        B.in(A.off1, P + 1), B.in(A.off2, P + 1), B.in(A.kind, P), B.in(A.kbase1, P), B.in(A.kbase2, P), B.in(A.cbase, P + 1);
+        B.in(A.min_matches, P), B.in(D.ws, 4 * P), B.in(D.nnr, P), B.in(D.sim_th, P), B.in(M.nnr, P);
+        B.in(A.pose, (size_t)kMaPoseDoubles * T.n), B.in(D.desc1, dw * N1), B.in(D.desc2, dw * N2);
+        B.in(A.q_pt, 3 * T.cnt[0][0]), B.in(A.q_ls, kMaQLsDoubles * T.cnt[1][0]);
+        B.in(A.t_pt, kMaTPtDoubles * T.cnt[0][1]), B.in(A.t_ls, kMaTLsDoubles * T.cnt[1][1]);
+        B.out(A.cnt, 2 * P), B.out(A.res, 2 * P), B.out(A.m12, N1), B.out(A.vis, N1), B.out(A.acc, N1);
+        B.out(A.ptd, kMaPtDoubles * T.cnt[0][0]), B.out(A.lsd, kMaLsDoubles * T.cnt[1][0]);
+        key_bytes = grid_workset(B, D, A, T);
+        B.dev(M.nn12, N1), B.dev(M.nn21, N2), B.dev(M.m12, N1), B.dev(M.count, P);
+        B.dev(A.skip, N1), B.dev(A.gate_min, P);
     }
 };
 

@@ -27,12 +27,41 @@
 
 namespace plba {
 
+// The train side of problem p, row i of its n2: the CSR entry, and for a point (c: pl[2]) its one cell,
+// for a line (c: spl[2], epl[2]) its direction and its rasterised cells. Dev is the struct that owns the
+// cells, a KfDev or plba_map_associate's MaDev (csrc/plba_mapassoc.hpp), which enters a keyframe's
+// unmatched features exactly as the current keyframe's features are entered here.
+template <typename Dev>
+__device__ inline void kf_train_row(const Dev &D, int p, int i, int n2, const double *c) {
+    const bool line = D.kind[p] != 0;
+    const int cols = D.prm.cols, rows = D.prm.rows;
+    const size_t g = (size_t)(D.off2[p] + i);
+    const int per = line ? D.stride : 1;
+    const int first = D.cbase[p] + i * per;
+    D.cell_off2[g] = first;
+    // = cbase[p + 1]: the next problem's first train row writes the same value to the same entry, on purpose
+    if (i == n2 - 1) D.cell_off2[g + 1] = first + per;
+    int32_t *dst = D.cells2 + 2 * (size_t)first;
+    if (line) {
+        kf_line_dir(c, c + 2, D.inv_w, D.inv_h, D.dir2 + 2 * g);
+        const double x1 = c[0] * D.inv_w, y1 = c[1] * D.inv_h, x2 = c[2] * D.inv_w, y2 = c[3] * D.inv_h;
+        const int m = st_line_cells(x1, y1, x2, y2, cols, rows, st_max_steps(cols, rows), dst, per);
+        for (int e = m; e < per; ++e) {
+            dst[2 * e] = -1;
+            dst[2 * e + 1] = -1;
+        }
+    } else {
+        const double gx = c[0] * D.inv_w, gy = c[1] * D.inv_h;
+        dst[0] = (int)gx;
+        dst[1] = (int)gy;
+    }
+}
+
 __global__ __launch_bounds__(kKfNT) void k_kf_cells(KfDev D) {
     const int p = blockIdx.x, i = blockIdx.y * kKfNT + threadIdx.x;
     const int o1 = D.off1[p], n1 = D.off1[p + 1] - o1;
-    const int o2 = D.off2[p], n2 = D.off2[p + 1] - o2;
+    const int n2 = D.off2[p + 1] - D.off2[p];
     const bool line = D.kind[p] != 0;
-    const int cols = D.prm.cols, rows = D.prm.rows;
     const double *DT = D.pose + (size_t)(p >> 1) * kKfPoseDoubles;
     if (i < n1) {
         const size_t g = (size_t)(o1 + i), k = (size_t)(D.kbase1[p] + i);
@@ -45,28 +74,8 @@ __global__ __launch_bounds__(kKfNT) void k_kf_cells(KfDev D) {
         }
     }
     if (i < n2) {
-        const size_t g = (size_t)(o2 + i), k = (size_t)(D.kbase2[p] + i);
-        const int per = line ? D.stride : 1;
-        const int first = D.cbase[p] + i * per;
-        D.cell_off2[g] = first;
-        // = cbase[p + 1]: the next problem's first current row writes the same value to the same entry, on purpose
-        if (i == n2 - 1) D.cell_off2[g + 1] = first + per;
-        int32_t *dst = D.cells2 + 2 * (size_t)first;
-        if (line) {
-            const double *c = D.t_ls + k * kKfTLsDoubles;
-            kf_line_dir(c, c + 2, D.inv_w, D.inv_h, D.dir2 + 2 * g);
-            const double x1 = c[0] * D.inv_w, y1 = c[1] * D.inv_h, x2 = c[2] * D.inv_w, y2 = c[3] * D.inv_h;
-            const int m = st_line_cells(x1, y1, x2, y2, cols, rows, st_max_steps(cols, rows), dst, per);
-            for (int e = m; e < per; ++e) {
-                dst[2 * e] = -1;
-                dst[2 * e + 1] = -1;
-            }
-        } else {
-            const double *c = D.t_pt + k * kKfTPtDoubles;
-            const double gx = c[0] * D.inv_w, gy = c[1] * D.inv_h;
-            dst[0] = (int)gx;
-            dst[1] = (int)gy;
-        }
+        const size_t k = (size_t)(D.kbase2[p] + i);
+        kf_train_row(D, p, i, n2, line ? D.t_ls + k * kKfTLsDoubles : D.t_pt + k * kKfTPtDoubles);
     }
 }
 

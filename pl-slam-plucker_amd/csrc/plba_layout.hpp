@@ -79,7 +79,7 @@ private:
         const void *src;
         void *dst;
     };
-    // The most arrays of one call. kf_associate declares 38, the most today: raise this with the
+    // The most arrays of one call. map_associate declares 41, the most today: raise this with the
     // entry point that needs more. One too many, a role out of order or a host() of an undeclared field
     // is a mistake in the entry point's own text, so it aborts at that entry point's first call.
     static constexpr int kMax = 48;

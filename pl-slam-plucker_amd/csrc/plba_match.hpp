@@ -21,8 +21,12 @@
 // the result does not depend on the launch geometry.
 // plba_kf_associate launches both kernels over every problem with a gate (DmDev::gate_count): a
 // workgroup of a problem that does not fall back returns at once and writes nothing.
+// plba_map_associate launches the MASK instantiation of k_desc_nn with DmDev::skip1, a flag per side-1
+// row: a flagged row is what a row removed from the list would be. As a query (direction 0) it gets -1;
+// as a train row (direction 1) the scan passes over it, and the scan keeps the order of the others, so
+// ties still go to the lowest index among them. Without the flags the kernel is the one it was.
 // Defined where the reference is not: fewer than 2 train rows give no match in that direction (the
-// reference reads matches_[idx][1] out of range).
+// reference reads matches_[idx][1] out of range); with MASK, fewer than 2 unflagged ones.
 #pragma once
 
 #include <limits.h>
@@ -38,10 +42,11 @@ __device__ inline bool dm_gated_off(const DmDev &D, int pair) {
     return D.gate_count && !(D.gate_count[pair] < D.gate_min[pair]);
 }
 
-// W: dwords of a row in registers and in LDS (8 or 16), dwords <= W
-template <int W>
+// W: dwords of a row in registers and in LDS (8 or 16), dwords <= W. MASK: D.skip1 is read
+template <int W, bool MASK = false>
 __global__ __launch_bounds__(kDmNT) void k_desc_nn(DmDev D) {
     __shared__ __attribute__((aligned(16))) uint32_t tile[kDmTile * W];
+    __shared__ uint8_t tskip[MASK ? kDmTile : 1];  // direction 1: the flags of the tile's side-1 rows
     const int pair = blockIdx.x, dir = blockIdx.z, tid = threadIdx.x;
     const int32_t *qoff = dir ? D.off2 : D.off1, *toff = dir ? D.off1 : D.off2;
     const int q0 = qoff[pair], nq = qoff[pair + 1] - q0;
@@ -85,8 +90,11 @@ __global__ __launch_bounds__(kDmNT) void k_desc_nn(DmDev D) {
         } else {
             for (int e = tid; e < rows * dw; e += kDmNT) tile[(e / dw) * W + (e % dw)] = src[e];
         }
+        if (MASK && dir)
+            for (int e = tid; e < rows; e += kDmNT) tskip[e] = D.skip1[t0 + base + e];
         __syncthreads();
         for (int j = 0; j < rows; ++j) {
+            if (MASK && dir && tskip[j]) continue;  // uniform over the workgroup
             const uint4 *t4 = (const uint4 *)(tile + j * W);
             int d = 0;
 #pragma unroll
@@ -107,7 +115,10 @@ __global__ __launch_bounds__(kDmNT) void k_desc_nn(DmDev D) {
     if (owner) {
         // matching.cpp:54 — a float product and a float compare
         const float lhs = (float)d0, rhs = (float)d1 * D.nnr[pair];
-        (dir ? D.nn21 : D.nn12)[q0 + row] = (nt >= 2 && lhs < rhs) ? i0 : -1;
+        // two rows were scanned: nt >= 2, or with MASK a second distance was kept
+        const bool two = MASK ? d1 != INT_MAX : nt >= 2;
+        const bool skipped = MASK && !dir && D.skip1[q0 + row] != 0;
+        (dir ? D.nn21 : D.nn12)[q0 + row] = (two && !skipped && lhs < rhs) ? i0 : -1;
     }
 }
 

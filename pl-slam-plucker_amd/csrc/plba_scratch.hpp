@@ -137,6 +137,7 @@ int grid_match(CtxBase *ctx, const plba_gridmatch_batch *b, int32_t *matches_12,
 int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp,
                      const plba_stereo_out *out);
 int kf_associate(CtxBase *ctx, const plba_kfassoc_batch *b, const plba_kfassoc_params *pp, const plba_kfassoc_out *out);
+int map_associate(CtxBase *ctx, const plba_mapassoc_batch *b, const plba_mapassoc_params *pp, const plba_mapassoc_out *out);
 int desc_medoid(CtxBase *ctx, int n, const int32_t *list_ptr, const uint8_t *desc, int desc_bytes, int32_t *medoid);
 // and of plba_bow_set_vocab / _insert / _remove / _get
 int bow_set_vocab(CtxBase *ctx, int slot, const plba_bow_vocab *v);

@@ -644,6 +644,53 @@ int plslam_local_mapping_step_kf(plslam_map *m, int32_t kf_idx, const plslam_map
     return PLBA_OK;
 }
 
+namespace {
+plba_mapassoc_params mapassoc_params(const plba_mapassoc_params *p) {
+    plba_mapassoc_params d;
+    plba_mapassoc_default_params(&d);
+    return p ? *p : d;
+}
+}  // namespace
+
+int plslam_match_map_to_kf_assoc(plslam_map *m, int32_t kf_idx, const double *Twf, const plba_mapassoc_params *params,
+                                 plslam_mapmatch_stats *stats) {
+    if (!m) return PLBA_E_INVALID;
+    Mat4 T;
+    if (Twf) std::memcpy(T.data(), Twf, sizeof(double) * 16);
+    MapMatchStats st;
+    const int rc = m->mh.matchMapToKfAssoc(kf_idx, Twf ? &T : nullptr, mapassoc_params(params), &st);
+    if (rc) return rc;
+    export_mapmatch_stats(st, stats);
+    return PLBA_OK;
+}
+
+int plslam_local_mapping_step_kf_assoc(plslam_map *m, int32_t kf_idx, const plba_mapassoc_params *params,
+                                       plslam_mapmatch_stats *match_stats, plslam_lba_stats *stats, int32_t *n_pt_removed,
+                                       int32_t *n_ln_removed) {
+    if (!m) return PLBA_E_INVALID;
+    MapMatchStats ms;
+    LbaStats st;
+    CullStats cs;
+    const int rc = m->mh.localMappingStepKfAssoc(kf_idx, mapassoc_params(params), &ms, &st, &cs);
+    if (rc) return rc;
+    export_mapmatch_stats(ms, match_stats);
+    copy_stats(st, stats);
+    if (n_pt_removed) *n_pt_removed = cs.points_removed;
+    if (n_ln_removed) *n_ln_removed = cs.lines_removed;
+    return PLBA_OK;
+}
+
+int plslam_set_mapassoc_fn(plslam_map *m, plslam_mapassoc_fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    m->mh.setMapAssocFn(fn, user);
+    return PLBA_OK;
+}
+
+int plslam_map_assoc_cpu(void *user, const plba_mapassoc_batch *b, const plba_mapassoc_params *p, const plba_mapassoc_out *out) {
+    (void)user;
+    return mapAssocCpu(b, p, out);
+}
+
 int plslam_grid_match_cpu(void *user, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches) {
     (void)user;
     return gridMatchCpu(b, matches_12, n_matches);

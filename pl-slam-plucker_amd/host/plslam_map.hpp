@@ -293,6 +293,7 @@ struct KfMatchStats {
     std::vector<std::array<int, 2>> pt_pairs, ls_pairs;
 };
 using KfAssocFn = int (*)(void *user, const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out);
+using MapAssocFn = int (*)(void *user, const plba_mapassoc_batch *b, const plba_mapassoc_params *p, const plba_mapassoc_out *out);
 
 // One loopClosureFuseLandmarks call (fuse_landmarks.cpp), per kind [points, lines]. The four cases in the
 // reference's order: observation added to the later landmark (:5552), to the earlier one (:5567), a new
@@ -416,6 +417,15 @@ class MapHandler {
     int localMappingStepKf(int kf_idx, const MapMatchParams &p, MapMatchStats *ms = nullptr, LbaStats *stats = nullptr,
                            CullStats *cs = nullptr);
     void setGridMatchFn(GridMatchFn fn, void *user) { grid_fn_ = fn; grid_user_ = user; }
+    // map_assoc.cpp. The same association around ONE plba_map_associate call (or the hook): the candidates
+    // (local, not yet seen by the keyframe) and the features with idx -1 are gathered, the call projects,
+    // tests, matches and gates them, and the rows are walked in i1 order, points before lines, as
+    // matchMapToKf walks them. It refuses what matchMapToKf refuses and fills the same statistics.
+    int matchMapToKfAssoc(int kf_idx, const Mat4 *Twf, const plba_mapassoc_params &p, MapMatchStats *stats = nullptr);
+    // matchMapToKfAssoc, then localMappingStep
+    int localMappingStepKfAssoc(int kf_idx, const plba_mapassoc_params &p, MapMatchStats *ms = nullptr, LbaStats *stats = nullptr,
+                                CullStats *cs = nullptr);
+    void setMapAssocFn(MapAssocFn fn, void *user) { mapassoc_fn_ = fn; mapassoc_user_ = user; }
     // stereo.cpp. StereoFrame::matchStereoPoints + matchStereoLines (src2/stereoFrame.cpp:121-174, :310-435)
     // for keyframe kf_idx from the detector output of its two images: one plba_stereo_associate call (or the
     // hook), stored as plslam_set_keyframe_features + plslam_set_keyframe_line_endpoints would store it.
@@ -508,6 +518,8 @@ class MapHandler {
     void *stereo_user_ = nullptr;
     KfAssocFn kfassoc_fn_ = nullptr;
     void *kfassoc_user_ = nullptr;
+    MapAssocFn mapassoc_fn_ = nullptr;
+    void *mapassoc_user_ = nullptr;
     BowFn bow_fn_ = nullptr;
     void *bow_user_ = nullptr;
     int bowCall(BowCall &c);                 // the hook, or plba_bow_* on the map's context
@@ -560,5 +572,7 @@ int trackPoseCpu(const plba_track_batch *b, const plba_track_params *p, plba_tra
                  uint8_t *ln_inlier);
 // kf_match.cpp. tools/kfassoc_bench.py and the tests only: plba_kf_associate's semantics, single-threaded, on the CPU
 int kfAssocCpu(const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out);
+// map_assoc.cpp. tools/mapassoc_bench.py and the tests only: plba_map_associate's semantics, single-threaded, on the CPU
+int mapAssocCpu(const plba_mapassoc_batch *b, const plba_mapassoc_params *p, const plba_mapassoc_out *out);
 
 }  // namespace plslam

@@ -767,3 +767,114 @@ class KfassocBatchView:
                      ls_rejected=self.o["ls_rejected"][c:d].copy())
             res.append(r)
         return res
+
+
+# ---- map-to-keyframe association (plba_mapassoc_params / _batch / _out / plba_map_associate)
+class PlbaMapassocParams(C.Structure):
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("fast_matching", C.c_int32), ("ws", C.c_int32), ("best_lr", C.c_int32), ("min_pt_matches", C.c_int32),
+                ("min_ls_matches", C.c_int32), ("pad", C.c_int32),
+                ("min_ratio_12_p", C.c_double), ("min_ratio_12_l", C.c_double), ("line_sim_th", C.c_double),
+                ("max_kf_epip_p", C.c_double), ("max_kf_epip_l", C.c_double),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class PlbaMapassocBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("pt_off_m", _ip), ("pt_off_f", _ip), ("ls_off_m", _ip),
+                ("ls_off_f", _ip), ("Twf", _dp), ("T_kf_w", _dp), ("pt_X", _dp), ("pdesc_m", _bp), ("ls_X", _dp),
+                ("ldesc_m", _bp), ("pt_pl", _dp), ("pt_P", _dp), ("pdesc_f", _bp), ("ls_spl", _dp), ("ls_epl", _dp),
+                ("ls_le", _dp), ("ls_sP", _dp), ("ls_eP", _dp), ("ldesc_f", _bp)]
+
+
+class PlbaMapassocOut(C.Structure):
+    _fields_ = [("n_visible", _ip), ("n_grid", _ip), ("n_matches", _ip), ("fallback", _ip), ("n_accepted", _ip),
+                ("pt_visible", _bp), ("pt_m12", _ip), ("pt_accepted", _bp), ("pt_rec", _dp),
+                ("ls_visible", _bp), ("ls_m12", _ip), ("ls_accepted", _bp), ("ls_rec", _dp)]
+
+
+def mapassoc_params(params=None, **kw) -> PlbaMapassocParams:
+    """PlbaMapassocParams from a dict and / or keywords: plba_mapassoc_default_params, then the entries
+    (width, height, fx, fy, cx and cy have no default)."""
+    if isinstance(params, PlbaMapassocParams) and not kw:
+        return params
+    from . import lib   # lib imports this module
+    p = PlbaMapassocParams()
+    lib.load().plba_mapassoc_default_params(C.byref(p))
+    for k, v in {**dict(params or {}), **kw}.items():
+        if k not in dict(PlbaMapassocParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+class MapassocBatchView:
+    """Concatenates keyframes into contiguous arrays, the PlbaMapassocBatch over them and the output arrays
+    of a call. A keyframe is a dict: Twf [3][4], T_kf_w [4][4]; of the candidate landmarks pt_X [n][3], pdesc_m,
+    ls_X [n][6] (line3D), ldesc_m; of the unmatched features pt_pl [n][2], pt_P [n][3], pdesc_f, ls_spl, ls_epl
+    [n][2], ls_le, ls_sP, ls_eP [n][3], ldesc_f. A missing row key is an empty side."""
+
+    # key: (columns, the side's row-count key)
+    ROWS = (("pt_X", 3, "pt_m"), ("ls_X", 6, "ls_m"), ("pt_pl", 2, "pt_f"), ("pt_P", 3, "pt_f"), ("ls_spl", 2, "ls_f"),
+            ("ls_epl", 2, "ls_f"), ("ls_le", 3, "ls_f"), ("ls_sP", 3, "ls_f"), ("ls_eP", 3, "ls_f"))
+    DESC = (("pdesc_m", "pt_m"), ("ldesc_m", "ls_m"), ("pdesc_f", "pt_f"), ("ldesc_f", "ls_f"))
+    LEAD = {"pt_m": "pt_X", "ls_m": "ls_X", "pt_f": "pt_pl", "ls_f": "ls_spl"}
+    POSES = (("Twf", 12), ("T_kf_w", 16))
+
+    def __init__(self, problems, desc_bytes=None):
+        problems = list(problems)
+        if desc_bytes is None:
+            desc_bytes = next((np.asarray(f[k]).shape[1] for f in problems for k, _ in self.DESC
+                               if k in f and np.asarray(f[k]).ndim == 2 and np.asarray(f[k]).shape[1]), 32)
+        self.desc_bytes = db = int(desc_bytes)
+        self.n = n = len(problems)
+        cnt = {s: [len(np.asarray(f.get(k, np.zeros((0, 1))))) for f in problems] for s, k in self.LEAD.items()}
+        self.off = {}
+        for s, c in cnt.items():
+            self.off[s] = np.zeros(n + 1, np.int32)
+            self.off[s][1:] = np.cumsum(c, dtype=np.int64)
+        self.a = {}
+
+        def cat(key, per, dtype, side):
+            parts = [np.asarray(f.get(key, np.zeros((0, per))), dtype).reshape(-1, per) for f in problems]
+            if [len(p) for p in parts] != cnt[side]:
+                raise ValueError(f"{key}: one row per landmark or feature")
+            return np.ascontiguousarray(np.concatenate(parts + [np.zeros((0, per), dtype)]))
+
+        for key, per, side in self.ROWS:
+            self.a[key] = cat(key, per, np.float64, side)
+        for key, side in self.DESC:
+            self.a[key] = cat(key, db, np.uint8, side)
+        for key, per in self.POSES:
+            self.a[key] = np.ascontiguousarray(
+                np.concatenate([np.asarray(f[key], np.float64).reshape(-1)[:per].reshape(1, per) for f in problems] +
+                               [np.zeros((0, per))]))
+        kinds = {np.dtype(np.int32): _ip, np.dtype(np.float64): _dp, np.dtype(np.uint8): _bp}
+        self.struct = PlbaMapassocBatch(
+            n=n, desc_bytes=db, pt_off_m=_ptr(self.off["pt_m"], _ip), pt_off_f=_ptr(self.off["pt_f"], _ip),
+            ls_off_m=_ptr(self.off["ls_m"], _ip), ls_off_f=_ptr(self.off["ls_f"], _ip),
+            **{k: _ptr(v, kinds[v.dtype]) for k, v in self.a.items()})
+        npt, nls, P = max(int(self.off["pt_m"][-1]), 1), max(int(self.off["ls_m"][-1]), 1), max(2 * n, 1)
+        # every row is written: a fill that no result can equal shows one that was not
+        self.o = {k: np.full(P, -7, np.int32) for k in self.COUNTS}
+        self.o.update(pt_visible=np.full(npt, 7, np.uint8), pt_m12=np.full(npt, -7, np.int32),
+                      pt_accepted=np.full(npt, 7, np.uint8), pt_rec=np.full((npt, 6), np.nan),
+                      ls_visible=np.full(nls, 7, np.uint8), ls_m12=np.full(nls, -7, np.int32),
+                      ls_accepted=np.full(nls, 7, np.uint8), ls_rec=np.full((nls, 9), np.nan))
+        self.out = PlbaMapassocOut(**{k: v.ctypes.data_as(kinds[v.dtype]) for k, v in self.o.items()})
+
+    COUNTS = ("n_visible", "n_grid", "n_matches", "fallback", "n_accepted")
+    PT = ("pt_visible", "pt_m12", "pt_accepted", "pt_rec")
+    LS = ("ls_visible", "ls_m12", "ls_accepted", "ls_rec")
+
+    def results(self) -> list:
+        """One dict per keyframe: n_visible, n_grid, n_matches, fallback, n_accepted as (points, lines), and the
+        candidate rows' pt_visible, pt_m12, pt_accepted, pt_rec, ls_visible, ls_m12, ls_accepted, ls_rec, copied."""
+        res = []
+        for f in range(self.n):
+            a, b = self.off["pt_m"][f:f + 2]
+            c, d = self.off["ls_m"][f:f + 2]
+            r = {k: (int(self.o[k][2 * f]), int(self.o[k][2 * f + 1])) for k in self.COUNTS}
+            r.update({k: self.o[k][a:b].copy() for k in self.PT})
+            r.update({k: self.o[k][c:d].copy() for k in self.LS})
+            res.append(r)
+        return res

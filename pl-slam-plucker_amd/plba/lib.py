@@ -33,7 +33,8 @@ EXPORTED = [
     "plba_lcpose_default_params", "plba_lc_relative_pose",
     "plba_track_default_params", "plba_track_pose",
     "plba_desc_match", "plba_grid_match", "plba_stereo_default_params", "plba_stereo_associate",
-    "plba_kfassoc_default_params", "plba_kf_associate", "plba_desc_medoid",
+    "plba_kfassoc_default_params", "plba_kf_associate", "plba_mapassoc_default_params", "plba_map_associate",
+    "plba_desc_medoid",
     "plba_bow_set_vocab", "plba_bow_insert", "plba_bow_remove", "plba_bow_get",
 ]
 
@@ -112,6 +113,10 @@ def load(path: Optional[str] = None):
     L.plba_kfassoc_default_params.restype = None
     L.plba_kf_associate.argtypes = [vp, C.POINTER(capi.PlbaKfassocBatch), C.POINTER(capi.PlbaKfassocParams),
                                     C.POINTER(capi.PlbaKfassocOut)]
+    L.plba_mapassoc_default_params.argtypes = [C.POINTER(capi.PlbaMapassocParams)]
+    L.plba_mapassoc_default_params.restype = None
+    L.plba_map_associate.argtypes = [vp, C.POINTER(capi.PlbaMapassocBatch), C.POINTER(capi.PlbaMapassocParams),
+                                     C.POINTER(capi.PlbaMapassocOut)]
     L.plba_desc_medoid.argtypes = [vp, C.POINTER(capi.PlbaMedoidBatch), ip]
     L.plba_bow_set_vocab.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaBowVocab)]
     L.plba_bow_insert.argtypes = [vp, C.c_int32, C.c_int32, bp, C.c_int32, dp, ip, C.c_int32, ip]
@@ -121,7 +126,7 @@ def load(path: Optional[str] = None):
         f = getattr(L, name)
         if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
                         "plba_lcpose_default_params", "plba_stereo_default_params", "plba_kfassoc_default_params",
-                        "plba_track_default_params"):
+                        "plba_track_default_params", "plba_mapassoc_default_params"):
             f.restype = C.c_int
     _lib = L
     return L
@@ -402,6 +407,20 @@ class Solver:
         prm = capi.kfassoc_params(params)
         self._check(self.L.plba_kf_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
                     "plba_kf_associate")
+        return bv.results()
+
+    def map_associate(self, problems, params, desc_bytes=None) -> list:
+        """Map-to-keyframe association (plba_map_associate; MapHandler::matchMap2KFPoints / Lines,
+        src/mapHandler.cpp:697-921, up to the sequential part) of a batch of keyframes
+        (capi.MapassocBatchView) in one call. params: a dict over plba_mapassoc_default_params with width,
+        height, fx, fy, cx, cy (or a capi.PlbaMapassocParams). One dict per keyframe, indexed by candidate
+        row: n_visible, n_grid, n_matches, fallback, n_accepted as (points, lines); pt_visible, pt_m12,
+        pt_accepted, pt_rec [.][6]; ls_visible, ls_m12, ls_accepted, ls_rec [.][9]. Needs no uploaded window
+        and leaves one intact."""
+        bv = problems if isinstance(problems, capi.MapassocBatchView) else capi.MapassocBatchView(problems, desc_bytes)
+        prm = capi.mapassoc_params(params)
+        self._check(self.L.plba_map_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
+                    "plba_map_associate")
         return bv.results()
 
     def desc_medoid(self, list_ptr, desc, desc_bytes=None) -> np.ndarray:

@@ -284,6 +284,15 @@ KFASSOC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaKfassocBatch), 
                          C.POINTER(capi.PlbaKfassocOut))
 
 
+MAPASSOC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(capi.PlbaMapassocBatch), C.POINTER(capi.PlbaMapassocParams),
+                          C.POINTER(capi.PlbaMapassocOut))
+
+
+def mapassoc_params(**kw) -> capi.PlbaMapassocParams:
+    """The reference's defaults (plba_mapassoc_default_params) with ``kw`` over them."""
+    return capi.mapassoc_params(None, **kw)
+
+
 class PlslamMapMatchParams(C.Structure):
     _fields_ = [("fast_matching", C.c_int32), ("ws", C.c_int32), ("min_pt_matches", C.c_int32),
                 ("min_ls_matches", C.c_int32), ("best_lr", C.c_int32), ("has_points", C.c_int32),
@@ -357,6 +366,7 @@ HOST_EXPORTED = [
     "plslam_match_kf_to_kf", "plslam_look_for_common_matches", "plslam_set_keyframe_line_pluker", "plslam_set_kfassoc_fn",
     "plslam_set_keyframe_line_endpoints", "plslam_set_camera", "plslam_set_grid_match_fn",
     "plslam_mapmatch_default_params", "plslam_match_map_to_kf", "plslam_local_mapping_step_kf",
+    "plslam_match_map_to_kf_assoc", "plslam_local_mapping_step_kf_assoc", "plslam_set_mapassoc_fn", "plslam_map_assoc_cpu",
     "plslam_set_bow_fn", "plslam_bow_cpu", "plslam_set_vocabulary", "plslam_remove_keyframe", "plslam_insert_kf_bow",
     "plslam_get_conf_matrix_row", "plslam_set_conf_matrix", "plslam_look_for_loop_candidates", "plslam_loop_closure_kf",
     "plslam_bow_cpu_new", "plslam_bow_cpu_free", "plslam_lc_search_default_params",
@@ -554,6 +564,13 @@ def load_host(path: Optional[str] = None):
                                          C.POINTER(PlslamMapMatchStats)]
     L.plslam_local_mapping_step_kf.argtypes = [vp, C.c_int32, C.POINTER(PlslamMapMatchParams),
                                                C.POINTER(PlslamMapMatchStats), C.POINTER(PlslamLbaStats), ip, ip]
+    L.plslam_match_map_to_kf_assoc.argtypes = [vp, C.c_int32, dp, C.POINTER(capi.PlbaMapassocParams),
+                                               C.POINTER(PlslamMapMatchStats)]
+    L.plslam_local_mapping_step_kf_assoc.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaMapassocParams),
+                                                     C.POINTER(PlslamMapMatchStats), C.POINTER(PlslamLbaStats), ip, ip]
+    L.plslam_set_mapassoc_fn.argtypes = [vp, MAPASSOC_FN, vp]
+    L.plslam_map_assoc_cpu.argtypes = [vp, C.POINTER(capi.PlbaMapassocBatch), C.POINTER(capi.PlbaMapassocParams),
+                                       C.POINTER(capi.PlbaMapassocOut)]
     fp = C.POINTER(C.c_float)
     L.plslam_set_bow_fn.argtypes = [vp, vp, vp]    # the hook as an address: plslam_bow_cpu itself can be passed
     L.plslam_bow_cpu_new.argtypes = []
@@ -628,6 +645,16 @@ def kf_assoc_cpu(pairs, params, desc_bytes=None) -> list:
     rc = load_host().plslam_kf_assoc_cpu(None, C.byref(bv.struct), C.byref(prm), C.byref(bv.out))
     if rc != 0:
         raise PlbaError(f"plslam_kf_assoc_cpu failed: {rc}")
+    return bv.results()
+
+
+def map_assoc_cpu(problems, params, desc_bytes=None) -> list:
+    """plslam_map_assoc_cpu on the keyframes of Solver.map_associate (tests and tools/mapassoc_bench.py)."""
+    bv = problems if isinstance(problems, capi.MapassocBatchView) else capi.MapassocBatchView(problems, desc_bytes)
+    prm = capi.mapassoc_params(params)
+    rc = load_host().plslam_map_assoc_cpu(None, C.byref(bv.struct), C.byref(prm), C.byref(bv.out))
+    if rc != 0:
+        raise PlbaError(f"plslam_map_assoc_cpu failed: {rc}")
     return bv.results()
 
 
@@ -1262,6 +1289,49 @@ class HostMap:
             self.h, kf_idx, T.ctypes.data_as(C.POINTER(C.c_double)) if T is not None else None,
             C.byref(params) if params is not None else None, C.byref(st)), "match_map_to_kf")
         return st.as_dict()
+
+    def set_mapassoc_fn(self, fn):
+        """fn(batch, params, out) -> int; "cpu" for plslam_map_assoc_cpu; None for the MI355X backend
+        (plba_map_associate)."""
+        if fn is None:
+            self._macb = None
+            self._check(self.L.plslam_set_mapassoc_fn(self.h, C.cast(None, MAPASSOC_FN), None), "set_mapassoc_fn")
+            return
+        if fn == "cpu":
+            self._macb = C.cast(self.L.plslam_map_assoc_cpu, MAPASSOC_FN)
+        else:
+            def tramp(user, bp_, pp, op):
+                try:
+                    return int(fn(bp_.contents, pp.contents, op.contents))
+                except Exception:  # never unwind through C
+                    import traceback
+                    traceback.print_exc()
+                    return -1
+            self._macb = MAPASSOC_FN(tramp)
+        self._check(self.L.plslam_set_mapassoc_fn(self.h, self._macb, None), "set_mapassoc_fn")
+
+    def match_map_to_kf_assoc(self, kf_idx: int, Twf=None, params=None) -> dict:
+        """match_map_to_kf around one plba_map_associate call (or the hook of set_mapassoc_fn). ``params``: a
+        dict over plba_mapassoc_default_params (or a capi.PlbaMapassocParams); without width / height the
+        camera of set_camera is used. Returns the statistics of match_map_to_kf."""
+        st = PlslamMapMatchStats()
+        T = None if Twf is None else np.ascontiguousarray(np.asarray(Twf, np.float64).reshape(16))
+        prm = capi.mapassoc_params(params)
+        self._check(self.L.plslam_match_map_to_kf_assoc(
+            self.h, kf_idx, T.ctypes.data_as(C.POINTER(C.c_double)) if T is not None else None, C.byref(prm), C.byref(st)),
+            "match_map_to_kf_assoc")
+        return st.as_dict()
+
+    def local_mapping_step_kf_assoc(self, kf_idx: int, params=None) -> dict:
+        """match_map_to_kf_assoc, then local_mapping_step."""
+        ms, st = PlslamMapMatchStats(), PlslamLbaStats()
+        a, b = C.c_int32(), C.c_int32()
+        prm = capi.mapassoc_params(params)
+        self._check(self.L.plslam_local_mapping_step_kf_assoc(self.h, kf_idx, C.byref(prm), C.byref(ms), C.byref(st),
+                                                              C.byref(a), C.byref(b)), "local_mapping_step_kf_assoc")
+        d = st.as_dict()
+        d["points_removed"], d["lines_removed"], d["match"] = a.value, b.value, ms.as_dict()
+        return d
 
     def local_mapping_step_kf(self, kf_idx: int, params: Optional[PlslamMapMatchParams] = None) -> dict:
         """match_map_to_kf, then local_mapping_step."""
