@@ -487,6 +487,79 @@ void plba_track_default_params(plba_track_params *p);
 int plba_track_pose(plba_ctx *ctx, const plba_track_batch *b, const plba_track_params *p,
                     plba_track_out *out, uint8_t *pt_inlier, uint8_t *ln_inlier);
 
+/* ---- Frame-to-frame tracking: f2fTracking() followed by optimizePose() in one call
+ *   void StereoFrameHandler::f2fTracking()   (src2/stereoFrameHandler.cpp:106-180)
+ *   void StereoFrameHandler::optimizePose()  (:307-405)
+ * for a batch of K frame pairs, from the features that plba_stereo_associate leaves for a frame to
+ * the pose. Per pair and kind: matches_12 = match(prev desc, curr desc, nnr) as plba_desc_match
+ * defines it (:141, :164); the previous rows with a match, in increasing i1, are matched_pt /
+ * matched_ls (:150, :177), each with the current row's pl (:148), spl / epl (:173-174) and le
+ * (:175) as its observation; n_pt / n_ls are their counts (:126-127) and the pose problem of the
+ * pair is exactly these rows in this order, solved as plba_track_pose solves it: the result is
+ * bitwise what plba_track_pose returns for the same rows. has_points = 0 or an empty side gives
+ * no point matches (:137), the same for lines (:160). cur_from_prev is the previous row whose idx
+ * the reference copies into a current row (:151, :178): the loop runs in increasing i1 and the
+ * last write wins, so it is the largest i1 with matches_12[i1] == i2 (without best_lr several
+ * previous rows can share a current row, and all of them enter the pose problem); the caller does
+ * curr.idx[i2] = prev.idx[cur_from_prev[i2]]. Nothing is kept between calls.
+ * On the device: one upload, k_desc_nn and k_desc_cross over 2K problems, k_f2f_gather (an
+ * in-order compaction, one workgroup per pair and kind), k_trackpose, k_f2f_scatter (the inlier
+ * flags back to previous-row order), one read-back; no host synchronisation in between. */
+typedef struct plba_frames_batch {      /* K frame pairs, concatenated per kind and side */
+    int32_t n;                          /* pairs                                                     */
+    int32_t pad;
+    const int32_t *pt_off1, *pt_off2;   /* [n+1] point rows of the previous / current frame; each of
+                                           the four arrays starts at 0                               */
+    const int32_t *ln_off1, *ln_off2;   /* [n+1] line rows                                           */
+    /* previous frame */
+    const uint8_t *prev_pdesc;          /* [pt_off1[n]][desc_bytes]                                  */
+    const double *prev_pt_P;            /* [.][3]                                                    */
+    const double *prev_pt_sigma2;       /* [.]                                                       */
+    const uint8_t *prev_ldesc;          /* [ln_off1[n]][desc_bytes]                                  */
+    const double *prev_ln_sP, *prev_ln_eP;  /* [.][3]                                                */
+    const double *prev_ln_NDc;          /* [.][6]; PLBA_TRACK_PLUCKER only                           */
+    const double *prev_ln_seg;          /* [.][4] spl, epl                                           */
+    const double *prev_ln_sigma2;       /* [.]                                                       */
+    /* current frame */
+    const uint8_t *cur_pdesc;           /* [pt_off2[n]][desc_bytes]                                  */
+    const double *cur_pt_pl;            /* [.][2]                                                    */
+    const uint8_t *cur_ldesc;           /* [ln_off2[n]][desc_bytes]                                  */
+    const double *cur_ln_seg;           /* [.][4] spl, epl; PLBA_TRACK_PLUCKER only                  */
+    const double *cur_ln_le;            /* [.][3]; PLBA_TRACK_ENDPOINTS only                         */
+    const double *prev;                 /* [n][53] as in plba_track_batch; use_motion_model only     */
+    double fx, fy, cx, cy;
+} plba_frames_batch;
+
+typedef struct plba_frames_params {
+    plba_track_params track;
+    float   nnr_pt, nnr_ln;    /* Config::minRatio12P() / minRatio12L() as floats                    */
+    int32_t best_lr;           /* Config::bestLRMatches(): 1 = cross-check                           */
+    int32_t desc_bytes;        /* as in plba_match_batch                                             */
+} plba_frames_params;
+
+typedef struct plba_frames_out {
+    plba_track_out *out;                /* [n]                                                       */
+    int32_t *pt_m12, *ln_m12;           /* [pt_off1[n]], [ln_off1[n]] matches_12 per previous row,
+                                           local to the pair, or -1                                  */
+    int32_t *n_pt, *n_ln;               /* [n] n_inliers_pt / n_inliers_ls (:126-127)                */
+    uint8_t *pt_inlier, *ln_inlier;     /* per PREVIOUS row, 0 for an unmatched row; may be NULL     */
+    int32_t *pt_cur_from_prev, *ln_cur_from_prev;  /* [pt_off2[n]], [ln_off2[n]] or -1               */
+} plba_frames_out;
+
+/* track: plba_track_default_params; nnr_pt = nnr_ln = 0.9f (src2/config.cpp:60, :68), best_lr = 1 (:51),
+ * desc_bytes = 32 */
+void plba_frames_default_params(plba_frames_params *p);
+/* Runs on the context's stream; needs no uploaded window and leaves one intact; shares
+ * plba_desc_match's device block and pinned host image. p == NULL: the defaults. PLBA_E_INVALID,
+ * checked on the host before any launch, for everything plba_desc_match and plba_track_pose refuse
+ * (a NULL batch / out / array that is read, n < 0, decreasing offsets, a bad desc_bytes, an
+ * iteration cap below 1, an unknown line model, a NULL prev with use_motion_model), for an offset
+ * array that does not start at 0, and for a pair whose PREVIOUS frame has more than
+ * PLBA_TRACK_MAX_N rows of one kind (matches cannot exceed previous rows; nothing is ever
+ * truncated). n == 0 does nothing and returns PLBA_OK. */
+int plba_track_frames(plba_ctx *ctx, const plba_frames_batch *b, const plba_frames_params *p,
+                      const plba_frames_out *out);
+
 /* ---- Descriptor matching, what feeds the relative pose above and every other matching step of
  * the back end:
  *   int StVO::match(desc1, desc2, nnr, matches_12)          (src2/matching.cpp:63-91)

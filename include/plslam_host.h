@@ -500,6 +500,11 @@ int plslam_stereo_cpu(void *user, const plba_stereo_batch *b, const plba_stereo_
  * signature behind a user pointer. H, g and e are summed in match order. */
 int plslam_track_pose_cpu(void *user, const plba_track_batch *b, const plba_track_params *p, plba_track_out *out,
                           uint8_t *pt_inlier, uint8_t *ln_inlier);
+/* tools/trackframes_bench.py and the tests only, not a product path: a single-threaded restatement of
+ * plba_track_frames' semantics (f2fTracking + optimizePose) on the CPU, composed of plslam_desc_match_cpu,
+ * the scatter loops of src2/stereoFrameHandler.cpp:144-152 / :167-179 and plslam_track_pose_cpu, with that
+ * call's signature behind a user pointer. */
+int plslam_track_frames_cpu(void *user, const plba_frames_batch *b, const plba_frames_params *p, const plba_frames_out *out);
 /* ---- MapHandler::matchKF2KFPoints + matchKF2KFLines (src/mapHandler.cpp:237-366, :368-590, the
  * USE_LINE_PLUKER branch), the only place where map landmarks are created, between two keyframes that have
  * their features (plslam_set_keyframe_stereo with params.pluker, or plslam_set_keyframe_features +

@@ -2425,6 +2425,21 @@ int plba_track_pose(plba_ctx *ctx, const plba_track_batch *b, const plba_track_p
     return ctx ? track_pose(ctx, b, pp, out, pt_inlier, ln_inlier) : PLBA_E_INVALID;
 }
 
+// frame-to-frame tracking: the matcher's defaults (src2/config.cpp:51, :60, :68) on top of the pose's; the
+// call itself is plba::track_frames (csrc/plba_assoc.hip, csrc/plba_trackframes.hpp)
+void plba_frames_default_params(plba_frames_params *p) {
+    if (!p) return;
+    plba_track_default_params(&p->track);
+    p->nnr_pt = 0.9f;
+    p->nnr_ln = 0.9f;
+    p->best_lr = 1;
+    p->desc_bytes = 32;
+}
+
+int plba_track_frames(plba_ctx *ctx, const plba_frames_batch *b, const plba_frames_params *pp, const plba_frames_out *out) {
+    return ctx ? track_frames(ctx, b, pp, out) : PLBA_E_INVALID;
+}
+
 // descriptor matching and grid-guided matching (csrc/plba_assoc.hip)
 int plba_desc_match(plba_ctx *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches) {
     return ctx ? desc_match(ctx, b, matches_12, n_matches) : PLBA_E_INVALID;

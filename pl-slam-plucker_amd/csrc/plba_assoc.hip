@@ -1,5 +1,5 @@
 // plba_assoc.hip — host side of the data-association entry points: the loop-closure relative pose,
-// the frame-to-frame pose, the two descriptor matchers, the stereo, the keyframe and the map association, the median descriptor and
+// the frame-to-frame pose and tracking, the two descriptor matchers, the stereo, the keyframe and the map association, the median descriptor and
 // place recognition. They share nothing with the solver (no Dev, no step graph, no window arena), so
 // they are a translation unit of their own: an edit to a matcher does not rebuild the factorisation
 // kernels. Each call is one upload, its kernels and one read-back through a ScratchBlock. A Staged
@@ -17,6 +17,7 @@
 
 #include "plba_lcpose.hpp"
 #include "plba_trackpose.hpp"
+#include "plba_trackframes.hpp"
 #include "plba_match.hpp"
 #include "plba_gridmatch.hpp"
 #include "plba_stereo.hpp"
@@ -315,6 +316,135 @@ int desc_match(CtxBase *ctx, const plba_match_batch *b, int32_t *matches_12, int
     if (const int rc = desc_launch(ctx, D, max_rows)) return rc;
     if (const int rc = read_back(ctx, ctx->match, B)) return rc;
     B.fetch();
+    return PLBA_OK;
+}
+
+// ---------------------------------------------------------------- frame-to-frame tracking
+// StereoFrameHandler::f2fTracking + optimizePose (src2/stereoFrameHandler.cpp:106-180, :307-405) for a
+// batch of frame pairs: one upload, the matcher's two launches over the points and the lines of every
+// pair, k_f2f_gather, k_trackpose, k_f2f_scatter (csrc/plba_trackframes.hpp), one read-back. The block
+// is laid out by TfPlan (csrc/plba_assoc_plan.hpp).
+namespace {
+
+// everything that is refused, before any device call; T is initialised on the way
+int frames_validate(CtxBase *ctx, const plba_frames_batch *b, const plba_frames_params &prm, const plba_frames_out *out,
+                    ProblemTable &T) {
+    const char *const op = "track frames";
+    const int n = b->n;
+    const plba_track_params &tp = prm.track;
+    if (const int rc = check_desc_bytes(ctx, op, prm.desc_bytes)) return rc;
+    if (!out || !out->out || !out->n_pt || !out->n_ln || !b->pt_off1 || !b->pt_off2 || !b->ln_off1 || !b->ln_off2) {
+        ctx->set_error("track frames: NULL out / n_pt / n_ln / offsets");
+        return PLBA_E_INVALID;
+    }
+    if ((tp.line_model != PLBA_TRACK_PLUCKER && tp.line_model != PLBA_TRACK_ENDPOINTS) || tp.max_iters < 1 ||
+        tp.max_iters_ref < 1) {
+        ctx->set_error("track frames: unknown line model %d or an iteration cap below 1", tp.line_model);
+        return PLBA_E_INVALID;
+    }
+    if (n > (INT32_MAX - 1) / 2) {
+        ctx->set_error("track frames: %d pairs are more than %d", n, (INT32_MAX - 1) / 2);
+        return PLBA_E_INVALID;
+    }
+    const bool pluker = tp.line_model == PLBA_TRACK_PLUCKER;
+    int widest_prev = 0, widest = 0;
+    const int32_t *const offs[4] = {b->pt_off1, b->ln_off1, b->pt_off2, b->ln_off2};
+    for (int a = 0; a < 4; ++a) {
+        if (const int rc = check_offsets(ctx, op, a % 2 ? "line" : "point", "pair", offs[a], n, a < 2 ? &widest_prev : &widest))
+            return rc;
+        if (offs[a][0] != 0) {
+            ctx->set_error("track frames: %s offsets start at %d, not at 0", a % 2 ? "line" : "point", offs[a][0]);
+            return PLBA_E_INVALID;
+        }
+    }
+    if (widest_prev > kTpMaxN) {
+        ctx->set_error("track frames: a previous frame has %d rows of one kind, PLBA_TRACK_MAX_N is %d", widest_prev, kTpMaxN);
+        return PLBA_E_INVALID;
+    }
+    widest = std::max(widest, widest_prev);
+    if ((widest + kDmNT - 1) / kDmNT > 65535) {  // the matcher's row tiles are its grid's second dimension
+        ctx->set_error("track frames: a set of %d rows is more than %d", widest, 65535 * kDmNT);
+        return PLBA_E_INVALID;
+    }
+    if (T.init(b->pt_off1, b->pt_off2, b->ln_off1, b->ln_off2, n, 0, 0) == ProblemTable::kTooMany) {
+        ctx->set_error("track frames: more than %d rows on one side of the batch", INT32_MAX);
+        return PLBA_E_INVALID;
+    }
+    const size_t p1 = T.cnt[0][0], p2 = T.cnt[0][1], l1 = T.cnt[1][0], l2 = T.cnt[1][1];
+    if ((p1 && (!b->prev_pdesc || !b->prev_pt_P || !b->prev_pt_sigma2 || !out->pt_m12)) ||
+        (p2 && (!b->cur_pdesc || !b->cur_pt_pl || !out->pt_cur_from_prev)) ||
+        (l1 && (!b->prev_ldesc || !b->prev_ln_sP || !b->prev_ln_eP || !b->prev_ln_seg || !b->prev_ln_sigma2 || !out->ln_m12 ||
+                (pluker && !b->prev_ln_NDc))) ||
+        (l2 && (!b->cur_ldesc || !out->ln_cur_from_prev || (pluker ? !b->cur_ln_seg : !b->cur_ln_le)))) {
+        ctx->set_error("track frames: NULL feature or output array");
+        return PLBA_E_INVALID;
+    }
+    if (tp.use_motion_model && !b->prev) {
+        ctx->set_error("track frames: use_motion_model without prev");
+        return PLBA_E_INVALID;
+    }
+    return PLBA_OK;
+}
+
+// the scalars of the three structs, the arrays they share, and the launches
+int frames_launch(CtxBase *ctx, TfPlan &Q, const plba_frames_batch *b, const plba_frames_params &prm) {
+    TfDev &F = Q.F;
+    DmDev &M = Q.M;
+    TpDev &P = Q.P;
+    const int n = Q.T.n;
+    hipStream_t s = ctx->stream;
+    M.off1 = F.off1; M.off2 = F.off2;
+    M.n = 2 * n;
+    M.dwords = prm.desc_bytes / 4;
+    M.best_lr = prm.best_lr != 0;
+    F.m12 = M.m12; F.count = M.count;
+    F.tin[0] = P.pt_in; F.tin[1] = P.ln_in;
+    for (int kd = 0; kd < 2; ++kd) F.cap[kd] = (int32_t)Q.T.cnt[kd][0];
+    F.on[0] = prm.track.has_points != 0; F.on[1] = prm.track.has_lines != 0;
+    F.n = n;
+    F.pluker = prm.track.line_model == PLBA_TRACK_PLUCKER;
+    P.pt_off = F.g_off[0]; P.ln_off = F.g_off[1];
+    P.pt_P = F.g_pt_P; P.pt_obs = F.g_pt_obs; P.pt_s2 = F.g_pt_s2;
+    P.ln_sP = F.g_ln_sP; P.ln_eP = F.g_ln_eP; P.ln_ND = F.g_ln_ND; P.ln_le = F.g_ln_le;
+    P.ln_obs = F.g_ln_obs; P.ln_seg = F.g_ln_seg; P.ln_s2 = F.g_ln_s2;
+    P.fx = b->fx, P.fy = b->fy, P.cx = b->cx, P.cy = b->cy;
+    P.prm = prm.track;
+    if (const int rc = desc_launch(ctx, M, Q.T.max_rows)) return rc;
+    hipLaunchKernelGGL(k_f2f_gather, dim3(2 * n), dim3(kTfNT), 0, s, F); PLBA_LAUNCHED(ctx, "k_f2f_gather");
+    if (F.pluker) hipLaunchKernelGGL(k_trackpose<PLBA_TRACK_PLUCKER>, dim3(n), dim3(kTpNT), 0, s, P);
+    else hipLaunchKernelGGL(k_trackpose<PLBA_TRACK_ENDPOINTS>, dim3(n), dim3(kTpNT), 0, s, P);
+    PLBA_LAUNCHED(ctx, "k_trackpose");
+    hipLaunchKernelGGL(k_f2f_scatter, dim3(2 * n), dim3(kTfNT), 0, s, F); PLBA_LAUNCHED(ctx, "k_f2f_scatter");
+    return PLBA_OK;
+}
+
+}  // namespace
+
+int track_frames(CtxBase *ctx, const plba_frames_batch *b, const plba_frames_params *pp, const plba_frames_out *out) {
+    if (!b || b->n < 0) {
+        ctx->set_error("track frames: NULL batch or n < 0");
+        return PLBA_E_INVALID;
+    }
+    if (b->n == 0) return PLBA_OK;
+    plba_frames_params prm;
+    if (pp) prm = *pp;
+    else plba_frames_default_params(&prm);
+    TfPlan Q;
+    if (const int rc = frames_validate(ctx, b, prm, out, Q.T)) return rc;
+    (void)hipSetDevice(ctx->opts.device);
+    Q.declare((size_t)prm.desc_bytes / 4, b, prm.track.line_model == PLBA_TRACK_PLUCKER, prm.track.use_motion_model != 0, out);
+    if (const int rc = ctx->match.reserve(*ctx, Q.B.total(), Q.B.outputs_end(), "track frames")) return rc;
+    Q.B.stage(ctx->match.host, ctx->match.dev);
+    const uint8_t *const descs[2][2] = {{b->prev_pdesc, b->cur_pdesc}, {b->prev_ldesc, b->cur_ldesc}};
+    std::vector<int32_t> kind(2 * (size_t)b->n), cbase(2 * (size_t)b->n + 1);  // the table's, not read on the device
+    Q.T.fill(Q.B.host(Q.F.off1), Q.B.host(Q.F.off2), kind.data(), Q.B.host(Q.F.kb1), Q.B.host(Q.F.kb2), cbase.data(), descs,
+             (size_t)prm.desc_bytes, (uint8_t *)Q.B.host(Q.M.desc1), (uint8_t *)Q.B.host(Q.M.desc2));
+    float *nnr = Q.B.host(Q.M.nnr);
+    for (int k = 0; k < b->n; ++k) nnr[2 * k] = prm.nnr_pt, nnr[2 * k + 1] = prm.nnr_ln;
+    if (const int rc = upload(ctx, ctx->match, Q.B)) return rc;
+    if (const int rc = frames_launch(ctx, Q, b, prm)) return rc;
+    if (const int rc = read_back(ctx, ctx->match, Q.B)) return rc;
+    Q.B.fetch();
     return PLBA_OK;
 }
 

@@ -178,4 +178,32 @@ struct TpDev {
     plba_track_params prm;
 };
 
+// ---------------------------------------------------------------- csrc/plba_trackframes.hpp
+constexpr int kTfNT = 256;  // threads of both kernels
+
+// A pair is the matcher's problems 2 k (its points) and 2 k + 1 (its lines). Arrays of two are [kind].
+struct TfDev {
+    const int32_t *off1, *off2;    // [2n+1] previous / current row ranges of each problem, as the matcher reads them
+    const int32_t *kb1, *kb2;      // [2n] first previous / current row of the problem within its kind
+    const int32_t *m12, *count;    // the matcher's result: [off1[2n]], [2n]
+    const double *p_P, *p_s2;      // previous point rows: [.][3], [.]
+    const double *l_sP, *l_eP;     // previous line rows: [.][3]
+    const double *l_ND, *l_seg, *l_s2;  // [.][6] (Plücker model), [.][4], [.]
+    const double *c_pl;            // current point rows: [.][2]
+    const double *c_seg, *c_le;    // current line rows: [.][4] (Plücker model), [.][3] (endpoint model)
+    int32_t *om12[2];              // per previous row of the kind: matches_12
+    uint8_t *inl[2];               // per previous row of the kind: the inlier flag, 0 where there is no match
+    int32_t *cfp[2];               // per current row of the kind: cur_from_prev
+    int32_t *nm[2];                // [n] matches of the pair
+    int32_t *src[2];               // per match row: its i1 within the pair
+    // k_trackpose's inputs, which k_f2f_gather writes (the TpDev of the call points to the same arrays)
+    int32_t *g_off[2];             // [n+1] match ranges of each pair
+    double *g_pt_P, *g_pt_obs, *g_pt_s2;
+    double *g_ln_sP, *g_ln_eP, *g_ln_ND, *g_ln_le, *g_ln_obs, *g_ln_seg, *g_ln_s2;
+    const uint8_t *tin[2];         // k_trackpose's inlier flags, per match row
+    int32_t cap[2];                // previous rows of the kind over the batch: no match row lies beyond
+    int32_t on[2];                 // has_points, has_lines
+    int32_t n, pluker;
+};
+
 }  // namespace plba

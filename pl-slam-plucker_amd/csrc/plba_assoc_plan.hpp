@@ -168,4 +168,42 @@ inline void trackpose_plan(Staged &B, TpDev &D, const plba_track_batch *b, bool 
     B.dev(D.pt_res, np), B.dev(D.ln_res, nl);
 }
 
+// Frame-to-frame tracking: the matcher's problems (side 1: a pair's previous rows, side 2: its current
+// rows), the feature rows as the caller holds them (per kind, pairs back to back: a problem's kbase), and
+// the pose's inputs, which k_f2f_gather writes on the device. A pair has at most as many matches of a
+// kind as previous rows, so the pose's arrays are as long as the previous rows of the kind over the
+// batch. An array that the line model or the motion model does not read has no source and no rows.
+struct TfPlan {
+    ProblemTable T;
+    TfDev F{};
+    DmDev M{};
+    TpDev P{};
+    Staged B;
+
+    void declare(size_t dw, const plba_frames_batch *b, bool pluker, bool motion, const plba_frames_out *o) {
+        const size_t np = 2 * (size_t)T.n, n = (size_t)T.n, N1 = T.N1, N2 = T.N2;
+        const size_t p1 = T.cnt[0][0], p2 = T.cnt[0][1], l1 = T.cnt[1][0], l2 = T.cnt[1][1];
+        B.in(F.off1, np + 1), B.in(F.off2, np + 1), B.in(F.kb1, np), B.in(F.kb2, np), B.in(M.nnr, np);
+        B.in(M.desc1, dw * N1), B.in(M.desc2, dw * N2);
+        B.in(F.p_P, 3 * p1, b->prev_pt_P), B.in(F.p_s2, p1, b->prev_pt_sigma2);
+        B.in(F.l_sP, 3 * l1, b->prev_ln_sP), B.in(F.l_eP, 3 * l1, b->prev_ln_eP);
+        B.in(F.l_ND, pluker ? 6 * l1 : 0, b->prev_ln_NDc), B.in(F.l_seg, 4 * l1, b->prev_ln_seg), B.in(F.l_s2, l1, b->prev_ln_sigma2);
+        B.in(F.c_pl, 2 * p2, b->cur_pt_pl);
+        B.in(F.c_seg, pluker ? 4 * l2 : 0, b->cur_ln_seg), B.in(F.c_le, pluker ? 0 : 3 * l2, b->cur_ln_le);
+        B.in(P.prev, motion ? (size_t)kTpPrev * n : 0, b->prev);
+        B.out(P.out, n, o->out);
+        B.out(F.om12[0], p1, o->pt_m12), B.out(F.om12[1], l1, o->ln_m12);
+        B.out(F.nm[0], n, o->n_pt), B.out(F.nm[1], n, o->n_ln);
+        B.out(F.inl[0], p1, o->pt_inlier), B.out(F.inl[1], l1, o->ln_inlier);
+        B.out(F.cfp[0], p2, o->pt_cur_from_prev), B.out(F.cfp[1], l2, o->ln_cur_from_prev);
+        B.dev(M.nn12, N1), B.dev(M.nn21, N2), B.dev(M.m12, N1), B.dev(M.count, np);
+        B.dev(F.g_off[0], n + 1), B.dev(F.g_off[1], n + 1), B.dev(F.src[0], p1), B.dev(F.src[1], l1);
+        B.dev(F.g_pt_P, 3 * p1), B.dev(F.g_pt_obs, 2 * p1), B.dev(F.g_pt_s2, p1);
+        B.dev(F.g_ln_sP, 3 * l1), B.dev(F.g_ln_eP, 3 * l1);
+        B.dev(F.g_ln_ND, pluker ? 6 * l1 : 0), B.dev(F.g_ln_le, pluker ? 0 : 3 * l1);
+        B.dev(F.g_ln_obs, pluker ? 4 * l1 : 0), B.dev(F.g_ln_seg, 4 * l1), B.dev(F.g_ln_s2, l1);
+        B.dev(P.pt_in, p1), B.dev(P.ln_in, l1), B.dev(P.pt_res, p1), B.dev(P.ln_res, l1);
+    }
+};
+
 }  // namespace plba

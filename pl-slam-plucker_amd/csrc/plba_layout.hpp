@@ -79,10 +79,10 @@ private:
         const void *src;
         void *dst;
     };
-    // The most arrays of one call. map_associate declares 41, the most today: raise this with the
+    // The most arrays of one call. track_frames declares 49, the most today: raise this with the
     // entry point that needs more. One too many, a role out of order or a host() of an undeclared field
     // is a mistake in the entry point's own text, so it aborts at that entry point's first call.
-    static constexpr int kMax = 48;
+    static constexpr int kMax = 56;
     Array arr_[kMax];
     int n_ = 0, role_ = 0;
     size_t end_[3] = {0, 0, 0};  // of the inputs, the outputs, everything

@@ -133,6 +133,7 @@ int lc_relative_pose(CtxBase *ctx, const plba_lcpose_batch *b, const plba_lcpose
 int track_pose(CtxBase *ctx, const plba_track_batch *b, const plba_track_params *pp, plba_track_out *out,
                uint8_t *pt_inlier, uint8_t *ln_inlier);
 int desc_match(CtxBase *ctx, const plba_match_batch *b, int32_t *matches_12, int32_t *n_matches);
+int track_frames(CtxBase *ctx, const plba_frames_batch *b, const plba_frames_params *pp, const plba_frames_out *out);
 int grid_match(CtxBase *ctx, const plba_gridmatch_batch *b, int32_t *matches_12, int32_t *n_matches);
 int stereo_associate(CtxBase *ctx, const plba_stereo_batch *b, const plba_stereo_params *pp,
                      const plba_stereo_out *out);

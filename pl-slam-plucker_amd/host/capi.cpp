@@ -727,6 +727,11 @@ int plslam_track_pose_cpu(void *user, const plba_track_batch *b, const plba_trac
     return trackPoseCpu(b, p, out, pt_inlier, ln_inlier);
 }
 
+int plslam_track_frames_cpu(void *user, const plba_frames_batch *b, const plba_frames_params *p, const plba_frames_out *out) {
+    (void)user;
+    return trackFramesCpu(b, p, out);
+}
+
 int plslam_set_keyframe_line_pluker(plslam_map *m, int32_t kf_idx, const double *NDc) {
     if (!m || !slot_ok(m->mh.map_keyframes, kf_idx)) return PLBA_E_INVALID;
     StereoFrame &f = m->mh.map_keyframes[kf_idx]->stereo_frame;

@@ -570,6 +570,8 @@ int stereoCpu(const plba_stereo_batch *b, const plba_stereo_params *p, const plb
 // host/track_pose.cpp: plba_track_pose's semantics on the CPU, single-threaded, sums in match order
 int trackPoseCpu(const plba_track_batch *b, const plba_track_params *p, plba_track_out *out, uint8_t *pt_inlier,
                  uint8_t *ln_inlier);
+// host/track_frames.cpp: plba_track_frames' semantics on the CPU, composed of descMatchCpu and trackPoseCpu
+int trackFramesCpu(const plba_frames_batch *b, const plba_frames_params *p, const plba_frames_out *out);
 // kf_match.cpp. tools/kfassoc_bench.py and the tests only: plba_kf_associate's semantics, single-threaded, on the CPU
 int kfAssocCpu(const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out);
 // map_assoc.cpp. tools/mapassoc_bench.py and the tests only: plba_map_associate's semantics, single-threaded, on the CPU

@@ -442,6 +442,98 @@ class MatchBatchView:
             best_lr=int(bool(best_lr)), pad=0)
 
 
+# ---- frame-to-frame tracking (plba_frames_* / plba_track_frames)
+class PlbaFramesBatch(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32), ("pt_off1", _ip), ("pt_off2", _ip), ("ln_off1", _ip), ("ln_off2", _ip),
+                ("prev_pdesc", _bp), ("prev_pt_P", _dp), ("prev_pt_sigma2", _dp),
+                ("prev_ldesc", _bp), ("prev_ln_sP", _dp), ("prev_ln_eP", _dp), ("prev_ln_NDc", _dp), ("prev_ln_seg", _dp),
+                ("prev_ln_sigma2", _dp),
+                ("cur_pdesc", _bp), ("cur_pt_pl", _dp), ("cur_ldesc", _bp), ("cur_ln_seg", _dp), ("cur_ln_le", _dp),
+                ("prev", _dp), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
+
+
+class PlbaFramesParams(C.Structure):
+    _fields_ = [("track", PlbaTrackParams), ("nnr_pt", C.c_float), ("nnr_ln", C.c_float), ("best_lr", C.c_int32),
+                ("desc_bytes", C.c_int32)]
+
+
+class PlbaFramesOut(C.Structure):
+    _fields_ = [("out", C.POINTER(PlbaTrackOut)), ("pt_m12", _ip), ("ln_m12", _ip), ("n_pt", _ip), ("n_ln", _ip),
+                ("pt_inlier", _bp), ("ln_inlier", _bp), ("pt_cur_from_prev", _ip), ("ln_cur_from_prev", _ip)]
+
+
+def frames_params(track=None, nnr_pt=0.9, nnr_ln=0.9, best_lr=True, desc_bytes=32) -> PlbaFramesParams:
+    """plba_frames_default_params (src2/config.cpp:51, :60, :68) over ``track`` (a PlbaTrackParams; None: its defaults)."""
+    p = PlbaFramesParams(nnr_pt=nnr_pt, nnr_ln=nnr_ln, best_lr=int(bool(best_lr)), desc_bytes=int(desc_bytes))
+    C.memmove(C.byref(p.track), C.byref(track if track is not None else track_params()), C.sizeof(PlbaTrackParams))
+    return p
+
+
+class FramesBatchView:
+    """Concatenates frame pairs (objects with the arrays of plba.trackframes.FramePair) into contiguous
+    arrays per kind and side, the PlbaFramesBatch over them, and the output arrays with their PlbaFramesOut."""
+    F64 = (("prev_pt_P", 3, "pt1"), ("prev_pt_sigma2", 1, "pt1"), ("prev_ln_sP", 3, "ln1"), ("prev_ln_eP", 3, "ln1"),
+           ("prev_ln_NDc", 6, "ln1"), ("prev_ln_seg", 4, "ln1"), ("prev_ln_sigma2", 1, "ln1"), ("cur_pt_pl", 2, "pt2"),
+           ("cur_ln_seg", 4, "ln2"), ("cur_ln_le", 3, "ln2"))
+    DESC = (("prev_pdesc", "pt1"), ("prev_ldesc", "ln1"), ("cur_pdesc", "pt2"), ("cur_ldesc", "ln2"))
+
+    def __init__(self, pairs, desc_bytes=32):
+        pairs = list(pairs)
+        db = int(desc_bytes)
+        self.off = {}
+        for name, key in self.DESC:
+            rows = [np.asarray(getattr(q, name), np.uint8) for q in pairs]
+            rows = [r if r.ndim == 2 else r.reshape(-1, db) for r in rows]   # (rows of their own width are the caller's claim)
+            off = np.zeros(len(pairs) + 1, np.int32)
+            off[1:] = np.cumsum([len(r) for r in rows], dtype=np.int64)
+            self.off[key] = off
+            setattr(self, name, np.ascontiguousarray(np.concatenate([r.reshape(-1) for r in rows] + [np.zeros(1, np.uint8)])))
+        self.arrays = {}
+        for name, w, key in self.F64:
+            rows = [np.asarray(getattr(q, name), np.float64).reshape(-1, w) for q in pairs]
+            a = np.ascontiguousarray(np.concatenate(rows + [np.zeros((0, w))]))
+            if len(a) != self.off[key][-1]:
+                raise ValueError(f"{name} has {len(a)} rows, the descriptors have {self.off[key][-1]}")
+            self.arrays[name] = a
+        self.prev = np.ascontiguousarray(np.stack([np.asarray(q.prev, np.float64).reshape(TRACK_PREV) for q in pairs])
+                                         if pairs else np.zeros((0, TRACK_PREV)))
+        cam = pairs[0].cam if pairs else (1.0, 1.0, 0.0, 0.0)
+        if any(tuple(q.cam) != tuple(cam) for q in pairs):
+            raise ValueError("the pairs of one batch share one camera")
+        n = len(pairs)
+        self.struct = PlbaFramesBatch(
+            n=n, pad=0, pt_off1=_ptr(self.off["pt1"], _ip), pt_off2=_ptr(self.off["pt2"], _ip),
+            ln_off1=_ptr(self.off["ln1"], _ip), ln_off2=_ptr(self.off["ln2"], _ip),
+            prev=_ptr(self.prev, _dp), fx=cam[0], fy=cam[1], cx=cam[2], cy=cam[3],
+            **{name: _ptr(getattr(self, name), _bp) for name, _ in self.DESC},
+            **{name: _ptr(a, _dp) for name, a in self.arrays.items()})
+        # the outputs (an array of no rows still has an address)
+        i32 = lambda k, fill: np.full(max(int(self.off[k][-1]), 1), fill, np.int32)
+        self.out = (PlbaTrackOut * max(n, 1))()
+        self.pt_m12, self.ln_m12 = i32("pt1", -1), i32("ln1", -1)
+        self.pt_cfp, self.ln_cfp = i32("pt2", -1), i32("ln2", -1)
+        self.n_pt, self.n_ln = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        self.pt_inl = np.zeros(max(int(self.off["pt1"][-1]), 1), np.uint8)
+        self.ln_inl = np.zeros(max(int(self.off["ln1"][-1]), 1), np.uint8)
+        self.out_struct = PlbaFramesOut(
+            out=self.out, pt_m12=_ptr(self.pt_m12, _ip), ln_m12=_ptr(self.ln_m12, _ip), n_pt=_ptr(self.n_pt, _ip),
+            n_ln=_ptr(self.n_ln, _ip), pt_inlier=_ptr(self.pt_inl, _bp), ln_inlier=_ptr(self.ln_inl, _bp),
+            pt_cur_from_prev=_ptr(self.pt_cfp, _ip), ln_cur_from_prev=_ptr(self.ln_cfp, _ip))
+
+    def results(self) -> list:
+        """One dict per pair: the fields of track_out_to_dict (the inlier flags per PREVIOUS row) and pt_m12,
+        ln_m12, n_pt, n_ln, pt_cur_from_prev, ln_cur_from_prev."""
+        o = self.off
+        res = []
+        for k in range(self.struct.n):
+            s = lambda a, key: a[o[key][k]:o[key][k + 1]].copy()
+            d = track_out_to_dict(self.out[k], s(self.pt_inl, "pt1"), s(self.ln_inl, "ln1"))
+            d.update(pt_m12=s(self.pt_m12, "pt1"), ln_m12=s(self.ln_m12, "ln1"), n_pt=int(self.n_pt[k]), n_ln=int(self.n_ln[k]),
+                     pt_cur_from_prev=s(self.pt_cfp, "pt2"), ln_cur_from_prev=s(self.ln_cfp, "ln2"))
+            res.append(d)
+        return res
+
+
 # ---- median descriptor (plba_medoid_batch / plba_desc_medoid)
 class PlbaMedoidBatch(C.Structure):
     _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("list_ptr", _ip), ("desc", _bp)]

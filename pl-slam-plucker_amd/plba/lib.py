@@ -31,7 +31,7 @@ EXPORTED = [
     "plba_hlm_default_params", "plba_hlm_lba",
     "plba_pgo_default_params", "plba_pgo_optimize",
     "plba_lcpose_default_params", "plba_lc_relative_pose",
-    "plba_track_default_params", "plba_track_pose",
+    "plba_track_default_params", "plba_track_pose", "plba_frames_default_params", "plba_track_frames",
     "plba_desc_match", "plba_grid_match", "plba_stereo_default_params", "plba_stereo_associate",
     "plba_kfassoc_default_params", "plba_kf_associate", "plba_mapassoc_default_params", "plba_map_associate",
     "plba_desc_medoid",
@@ -103,6 +103,10 @@ def load(path: Optional[str] = None):
     L.plba_track_default_params.restype = None
     L.plba_track_pose.argtypes = [vp, C.POINTER(capi.PlbaTrackBatch), C.POINTER(capi.PlbaTrackParams),
                                   C.POINTER(capi.PlbaTrackOut), bp, bp]
+    L.plba_frames_default_params.argtypes = [C.POINTER(capi.PlbaFramesParams)]
+    L.plba_frames_default_params.restype = None
+    L.plba_track_frames.argtypes = [vp, C.POINTER(capi.PlbaFramesBatch), C.POINTER(capi.PlbaFramesParams),
+                                    C.POINTER(capi.PlbaFramesOut)]
     L.plba_desc_match.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
     L.plba_grid_match.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
     L.plba_stereo_default_params.argtypes = [C.POINTER(capi.PlbaStereoParams)]
@@ -126,7 +130,7 @@ def load(path: Optional[str] = None):
         f = getattr(L, name)
         if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
                         "plba_lcpose_default_params", "plba_stereo_default_params", "plba_kfassoc_default_params",
-                        "plba_track_default_params", "plba_mapassoc_default_params"):
+                        "plba_track_default_params", "plba_mapassoc_default_params", "plba_frames_default_params"):
             f.restype = C.c_int
     _lib = L
     return L
@@ -354,6 +358,23 @@ class Solver:
                                            _p(pin, C.c_uint8), _p(lin, C.c_uint8)), "plba_track_pose")
         return [capi.track_out_to_dict(out[i], pin[bv.pt_off[i]:bv.pt_off[i + 1]], lin[bv.ln_off[i]:bv.ln_off[i + 1]])
                 for i in range(n)]
+
+    def track_frames(self, pairs, params=None) -> list:
+        """Frame-to-frame tracking (plba_track_frames; StereoFrameHandler::f2fTracking + optimizePose,
+        src2/stereoFrameHandler.cpp:106-180, :307-405) of a batch of frame pairs (plba.trackframes.FramePair):
+        the descriptors and features of the previous and of the current frame go in, and the matching, the
+        gather of the matched rows and the pose run on the device in one call. ``params``: a
+        capi.PlbaFramesParams (capi.frames_params), None for the defaults. One dict per pair: the fields of
+        track_pose with the inlier flags per PREVIOUS row (0 where it has no match), pt_m12 / ln_m12
+        (matches_12), n_pt / n_ln, and pt_cur_from_prev / ln_cur_from_prev, the previous row whose idx a
+        current row inherits or -1. Needs no uploaded window and leaves one intact."""
+        if params is None:
+            params = capi.PlbaFramesParams()
+            self.L.plba_frames_default_params(C.byref(params))
+        bv = capi.FramesBatchView(pairs, params.desc_bytes)
+        self._check(self.L.plba_track_frames(self.ctx, C.byref(bv.struct), C.byref(params), C.byref(bv.out_struct)),
+                    "plba_track_frames")
+        return bv.results()
 
     def desc_match(self, pairs, nnr, best_lr: bool = True, desc_bytes=None) -> list:
         """Descriptor matching (plba_desc_match; StVO::match / matchNNR, src2/matching.cpp:41-91) of a

@@ -362,7 +362,7 @@ HOST_EXPORTED = [
     "plslam_verify_loop_candidates", "plslam_desc_match_cpu",
     "plslam_line_cells", "plslam_grid_match_cpu",
     "plslam_set_keyframe_stereo", "plslam_set_stereo_fn", "plslam_stereo_cpu", "plslam_kf_assoc_cpu",
-    "plslam_track_pose_cpu",
+    "plslam_track_pose_cpu", "plslam_track_frames_cpu",
     "plslam_match_kf_to_kf", "plslam_look_for_common_matches", "plslam_set_keyframe_line_pluker", "plslam_set_kfassoc_fn",
     "plslam_set_keyframe_line_endpoints", "plslam_set_camera", "plslam_set_grid_match_fn",
     "plslam_mapmatch_default_params", "plslam_match_map_to_kf", "plslam_local_mapping_step_kf",
