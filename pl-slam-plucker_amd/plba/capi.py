@@ -11,6 +11,7 @@ from .synth import Graph
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _bp = C.POINTER(C.c_uint8)
+_fp = C.POINTER(C.c_float)
 
 
 class PlbaGraph(C.Structure):
@@ -265,6 +266,123 @@ class PgoResultBuffers:
                     lambda_final=s.lambda_final, solve_ms=s.solve_ms, trace=trace_to_array(self.trace, s.n_trace))
 
 
+# ---- the batched calls: one base for their views, one constructor for their params
+_KINDS = {np.dtype(np.int32): _ip, np.dtype(np.float32): _fp, np.dtype(np.float64): _dp, np.dtype(np.uint8): _bp}
+_F8, _F4, _U1, _I4 = np.float64, np.float32, np.uint8, np.int32
+DESC = None                     # in a table, a column count of desc_bytes
+_LEFT_OUT = np.zeros((0, 0))    # the rows of a key that a dict-style problem leaves out
+
+
+def _field(q, key, default=None):
+    """An array of a problem: the entry of a dict (``default`` where the key is left out) or the attribute of an object."""
+    if not isinstance(q, dict):
+        return getattr(q, key)
+    return q[key] if default is None else q.get(key, default)
+
+
+def _params_from(struct_cls, default_fn_name, params=None, **kw):
+    """``params`` itself if it is a struct_cls already; else the library's defaults, then the entries of the
+    dict ``params`` and the keywords (KeyError for a name that is no field)."""
+    if isinstance(params, struct_cls) and not kw:
+        return params
+    from . import lib   # lib imports this module
+    p = struct_cls()
+    getattr(lib.load(), default_fn_name)(C.byref(p))
+    for k, v in {**dict(params or {}), **kw}.items():
+        if k not in dict(struct_cls._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+class _BatchView:
+    """Concatenates the problems of a batch into contiguous arrays, fills the batch struct over them and
+    allocates the output arrays of a call. A view class declares the tables, with the struct's field names:
+
+    SIDES  (key, the field of its [n+1] int32 offsets): the kinds of rows that a problem has.
+    ROWS   (field, columns, dtype, side): one row per feature, the problems' rows one after the other. The
+           first array of a side leads: every other one has its row count in every problem.
+    PER    (field, width): float64, one row per problem.
+    OUT    (field of OUT_STRUCT, side or "n" or "2n", trailing shape, dtype, fill): one row per row of the
+           side, per problem or per half problem (points, lines), holding ``fill`` until a call writes it.
+
+    A problem is a dict, where a row key left out is an empty side, or an object. Every array that a struct
+    points to stays referenced: off[side], a[field] and o[field], each also an attribute under its field's name."""
+    STRUCT = OUT_STRUCT = None
+    SIDES = ROWS = PER = OUT = ()
+    SHORT = "{key}: one row per feature"
+    CAMERA = None   # what the message calls the problems ("pairs") if each has a .cam that one batch shares
+
+    def _build(self, problems, desc_bytes=None, **scalars):
+        problems = list(problems)
+        self.n = n = len(problems)
+        if desc_bytes is None:
+            desc_bytes = self._desc_width(problems, 32)
+        self.desc_bytes = db = int(desc_bytes)
+        self.a, self.off, self.o, cnt = {}, {}, {}, {}
+        for key, per, dtype, side in self.ROWS:
+            per = db if per is DESC else per
+            parts = [np.asarray(_field(q, key, _LEFT_OUT), dtype).reshape(-1, per) for q in problems]
+            rows = [len(p) for p in parts]
+            if rows != cnt.setdefault(side, rows):
+                raise ValueError(self.SHORT.format(key=key, rows=sum(rows), lead=sum(cnt[side])))
+            # (the row of no length: an empty batch still has an address)
+            self.a[key] = np.ascontiguousarray(np.concatenate(parts + [np.zeros((0, per), dtype)]))
+        for side, _ in self.SIDES:
+            self.off[side] = np.zeros(n + 1, np.int32)
+            self.off[side][1:] = np.cumsum(cnt[side], dtype=np.int64)
+        for key, per in self.PER:
+            parts = [np.asarray(_field(q, key), np.float64).reshape(-1, per) for q in problems]
+            self.a[key] = np.ascontiguousarray(np.concatenate(parts + [np.zeros((0, per))]))
+            if len(self.a[key]) != n:
+                raise ValueError(f"{key}: {per} values per problem")
+        if self.CAMERA:
+            cam = problems[0].cam if problems else (1.0, 1.0, 0.0, 0.0)
+            if any(tuple(q.cam) != tuple(cam) for q in problems):
+                raise ValueError(f"the {self.CAMERA} of one batch share one camera")
+            scalars.update(zip(("fx", "fy", "cx", "cy"), cam))
+        if hasattr(self.STRUCT, "desc_bytes"):
+            scalars["desc_bytes"] = db
+        named = {**{f: self.off[s] for s, f in self.SIDES}, **self.a}
+        self.struct = self.STRUCT(n=n, **scalars, **{k: _ptr(v, _KINDS[v.dtype]) for k, v in named.items()})
+        for key, side, shape, dtype, fill in self.OUT:
+            rows = n if side == "n" else 2 * n if side == "2n" else int(self.off[side][-1])
+            self.o[key] = np.full((max(rows, 1),) + tuple(db if s is DESC else s for s in shape), fill, dtype)
+        if self.OUT_STRUCT is not None:
+            self.out = self.out_struct = self.OUT_STRUCT(**{k: _ptr(v, _KINDS[v.dtype]) for k, v in self.o.items()})
+
+    def _desc_width(self, problems, default):
+        """The width of the first 2-D descriptor array that has one."""
+        found = (np.asarray(_field(q, key, _LEFT_OUT)) for q in problems for key, per, _, _ in self.ROWS if per is DESC)
+        return next((d.shape[1] for d in found if d.ndim == 2 and d.shape[1]), default)
+
+    def __getattr__(self, name):
+        d = self.__dict__
+        for side, field in self.SIDES:
+            if field == name and side in d.get("off", ()):
+                return d["off"][side]
+        for table in ("a", "o"):
+            if name in d.get(table, ()):
+                return d[table][name]
+        raise AttributeError(name)
+
+    def results(self) -> list:
+        """One dict per problem, every output under its field's name: the rows of the problem's side, copied;
+        the int of a per-problem output; the (points, lines) ints of a per-half-problem one."""
+        res = []
+        for f in range(self.n):
+            r = {}
+            for key, side, *_ in self.OUT:
+                if side == "n":
+                    r[key] = int(self.o[key][f])
+                elif side == "2n":
+                    r[key] = (int(self.o[key][2 * f]), int(self.o[key][2 * f + 1]))
+                else:
+                    r[key] = self.o[key][self.off[side][f]:self.off[side][f + 1]].copy()
+            res.append(r)
+        return res
+
+
 # ---- loop-closure relative pose (plba_lcpose_* / plba_lc_relative_pose)
 LCPOSE_ROBUST_GN = 0
 LCPOSE_GN = 1
@@ -299,29 +417,18 @@ def lcpose_params(**kw) -> PlbaLcposeParams:
     return p
 
 
-class LcposeBatchView:
-    """Concatenates candidate pairs (objects with pt_P, pt_obs, ln_sP, ln_eP, ln_le and cam, e.g.
-    plba.lcpose.LcProblem) into contiguous arrays and the PlbaLcposeBatch over them."""
+class LcposeBatchView(_BatchView):
+    """The PlbaLcposeBatch over candidate pairs (objects with pt_P, pt_obs, ln_sP, ln_eP, ln_le and cam, e.g.
+    plba.lcpose.LcProblem)."""
+    STRUCT = PlbaLcposeBatch
+    SIDES = (("pt", "pt_off"), ("ln", "ln_off"))
+    ROWS = (("pt_P", 3, _F8, "pt"), ("pt_obs", 2, _F8, "pt"), ("ln_sP", 3, _F8, "ln"), ("ln_eP", 3, _F8, "ln"),
+            ("ln_le", 3, _F8, "ln"))
+    SHORT = "{key}: one row per match"
+    CAMERA = "candidates"
 
     def __init__(self, problems):
-        def cat(name, w):
-            rows = [np.asarray(getattr(q, name), np.float64).reshape(-1, w) for q in problems]
-            return np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, w)))
-
-        self.pt_P, self.pt_obs = cat("pt_P", 3), cat("pt_obs", 2)
-        self.ln_sP, self.ln_eP, self.ln_le = cat("ln_sP", 3), cat("ln_eP", 3), cat("ln_le", 3)
-        self.pt_off = np.zeros(len(problems) + 1, np.int32)
-        self.ln_off = np.zeros(len(problems) + 1, np.int32)
-        for i, q in enumerate(problems):
-            self.pt_off[i + 1] = self.pt_off[i] + len(np.asarray(q.pt_P).reshape(-1, 3))
-            self.ln_off[i + 1] = self.ln_off[i] + len(np.asarray(q.ln_sP).reshape(-1, 3))
-        cam = problems[0].cam if problems else (1.0, 1.0, 0.0, 0.0)
-        if any(tuple(q.cam) != tuple(cam) for q in problems):
-            raise ValueError("the candidates of one batch share one camera")
-        self.struct = PlbaLcposeBatch(
-            n=len(problems), pt_off=_ptr(self.pt_off, _ip), ln_off=_ptr(self.ln_off, _ip),
-            pt_P=_ptr(self.pt_P, _dp), pt_obs=_ptr(self.pt_obs, _dp), ln_sP=_ptr(self.ln_sP, _dp),
-            ln_eP=_ptr(self.ln_eP, _dp), ln_le=_ptr(self.ln_le, _dp), fx=cam[0], fy=cam[1], cx=cam[2], cy=cam[3])
+        self._build(problems)
 
 
 def lcpose_out_to_dict(o: PlbaLcposeOut, pt_inlier, ln_inlier) -> dict:
@@ -373,31 +480,19 @@ def track_params(**kw) -> PlbaTrackParams:
     return p
 
 
-class TrackBatchView:
-    """Concatenates frame pairs (objects with the arrays of plba.trackpose.TrackProblem) into
-    contiguous arrays and the PlbaTrackBatch over them."""
+class TrackBatchView(_BatchView):
+    """The PlbaTrackBatch over frame pairs (objects with the arrays of plba.trackpose.TrackProblem)."""
     FIELDS = (("pt_P", 3), ("pt_obs", 2), ("pt_sigma2", 1), ("ln_sP", 3), ("ln_eP", 3), ("ln_NDc", 6), ("ln_le", 3),
               ("ln_obs", 4), ("ln_seg", 4), ("ln_sigma2", 1))
+    STRUCT = PlbaTrackBatch
+    SIDES = LcposeBatchView.SIDES
+    ROWS = tuple((name, w, _F8, name[:2]) for name, w in FIELDS)
+    PER = (("prev", TRACK_PREV),)
+    SHORT = LcposeBatchView.SHORT
+    CAMERA = "problems"
 
     def __init__(self, problems):
-        def cat(name, w):
-            rows = [np.asarray(getattr(q, name), np.float64).reshape(-1, w) for q in problems]
-            return np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, w)))
-
-        self.arrays = {name: cat(name, w) for name, w in self.FIELDS}
-        self.pt_off = np.zeros(len(problems) + 1, np.int32)
-        self.ln_off = np.zeros(len(problems) + 1, np.int32)
-        for i, q in enumerate(problems):
-            self.pt_off[i + 1] = self.pt_off[i] + len(np.asarray(q.pt_P).reshape(-1, 3))
-            self.ln_off[i + 1] = self.ln_off[i] + len(np.asarray(q.ln_sP).reshape(-1, 3))
-        self.prev = np.ascontiguousarray(np.stack([np.asarray(q.prev, np.float64).reshape(TRACK_PREV) for q in problems])
-                                         if problems else np.zeros((0, TRACK_PREV)))
-        cam = problems[0].cam if problems else (1.0, 1.0, 0.0, 0.0)
-        if any(tuple(q.cam) != tuple(cam) for q in problems):
-            raise ValueError("the problems of one batch share one camera")
-        self.struct = PlbaTrackBatch(n=len(problems), pt_off=_ptr(self.pt_off, _ip), ln_off=_ptr(self.ln_off, _ip),
-                                     prev=_ptr(self.prev, _dp), fx=cam[0], fy=cam[1], cx=cam[2], cy=cam[3],
-                                     **{name: _ptr(a, _dp) for name, a in self.arrays.items()})
+        self._build(problems)
 
 
 def track_out_to_dict(o: PlbaTrackOut, pt_inlier, ln_inlier) -> dict:
@@ -410,36 +505,22 @@ def track_out_to_dict(o: PlbaTrackOut, pt_inlier, ln_inlier) -> dict:
 
 
 # ---- descriptor matching (plba_match_batch / plba_desc_match)
-_fp = C.POINTER(C.c_float)
-
-
 class PlbaMatchBatch(C.Structure):
     _fields_ = [("n", C.c_int32), ("desc_bytes", C.c_int32), ("off1", _ip), ("off2", _ip), ("desc1", _bp),
                 ("desc2", _bp), ("nnr", _fp), ("best_lr", C.c_int32), ("pad", C.c_int32)]
 
 
-class MatchBatchView:
-    """Concatenates descriptor-set pairs [(desc1 [n1][desc_bytes] uint8, desc2 [n2][desc_bytes]), ...]
-    into contiguous arrays and the PlbaMatchBatch over them. ``nnr``: one ratio, or one per pair."""
+class MatchBatchView(_BatchView):
+    """The PlbaMatchBatch over descriptor-set pairs [(desc1 [n1][desc_bytes] uint8, desc2 [n2][desc_bytes]), ...].
+    ``nnr``: one ratio, or one per pair."""
+    STRUCT = PlbaMatchBatch
+    SIDES = (("1", "off1"), ("2", "off2"))
+    ROWS = (("desc1", DESC, _U1, "1"), ("desc2", DESC, _U1, "2"))
 
     def __init__(self, pairs, nnr, best_lr: bool = True, desc_bytes=None):
-        pairs = [(np.asarray(a, np.uint8), np.asarray(b, np.uint8)) for a, b in pairs]
-        if desc_bytes is None:
-            desc_bytes = next((x.shape[1] for p in pairs for x in p if x.ndim == 2 and x.shape[1]), 32)
-        pairs = [(a.reshape(-1, desc_bytes), b.reshape(-1, desc_bytes)) for a, b in pairs]
-        self.desc_bytes = int(desc_bytes)
-        empty = np.zeros((0, desc_bytes), np.uint8)
-        self.desc1 = np.ascontiguousarray(np.concatenate([a for a, _ in pairs] + [empty]))
-        self.desc2 = np.ascontiguousarray(np.concatenate([b for _, b in pairs] + [empty]))
-        self.off1 = np.zeros(len(pairs) + 1, np.int32)
-        self.off2 = np.zeros(len(pairs) + 1, np.int32)
-        self.off1[1:] = np.cumsum([len(a) for a, _ in pairs], dtype=np.int64)
-        self.off2[1:] = np.cumsum([len(b) for _, b in pairs], dtype=np.int64)
-        self.nnr = np.ascontiguousarray(np.broadcast_to(np.asarray(nnr, np.float32), (len(pairs),)))
-        self.struct = PlbaMatchBatch(
-            n=len(pairs), desc_bytes=self.desc_bytes, off1=_ptr(self.off1, _ip), off2=_ptr(self.off2, _ip),
-            desc1=_ptr(self.desc1, _bp), desc2=_ptr(self.desc2, _bp), nnr=_ptr(self.nnr, _fp),
-            best_lr=int(bool(best_lr)), pad=0)
+        self._build([dict(desc1=a, desc2=b) for a, b in pairs], desc_bytes, best_lr=int(bool(best_lr)))
+        self.nnr = np.ascontiguousarray(np.broadcast_to(np.asarray(nnr, np.float32), (self.n,)))
+        self.struct.nnr = _ptr(self.nnr, _fp)
 
 
 # ---- frame-to-frame tracking (plba_frames_* / plba_track_frames)
@@ -469,68 +550,36 @@ def frames_params(track=None, nnr_pt=0.9, nnr_ln=0.9, best_lr=True, desc_bytes=3
     return p
 
 
-class FramesBatchView:
-    """Concatenates frame pairs (objects with the arrays of plba.trackframes.FramePair) into contiguous
-    arrays per kind and side, the PlbaFramesBatch over them, and the output arrays with their PlbaFramesOut."""
-    F64 = (("prev_pt_P", 3, "pt1"), ("prev_pt_sigma2", 1, "pt1"), ("prev_ln_sP", 3, "ln1"), ("prev_ln_eP", 3, "ln1"),
-           ("prev_ln_NDc", 6, "ln1"), ("prev_ln_seg", 4, "ln1"), ("prev_ln_sigma2", 1, "ln1"), ("cur_pt_pl", 2, "pt2"),
-           ("cur_ln_seg", 4, "ln2"), ("cur_ln_le", 3, "ln2"))
-    DESC = (("prev_pdesc", "pt1"), ("prev_ldesc", "ln1"), ("cur_pdesc", "pt2"), ("cur_ldesc", "ln2"))
+class FramesBatchView(_BatchView):
+    """The PlbaFramesBatch over frame pairs (objects with the arrays of plba.trackframes.FramePair), and the
+    output arrays with their PlbaFramesOut. The descriptors lead: every other array of a kind and side has
+    their row count."""
+    STRUCT, OUT_STRUCT = PlbaFramesBatch, PlbaFramesOut
+    SIDES = (("pt1", "pt_off1"), ("pt2", "pt_off2"), ("ln1", "ln_off1"), ("ln2", "ln_off2"))
+    ROWS = (("prev_pdesc", DESC, _U1, "pt1"), ("prev_ldesc", DESC, _U1, "ln1"), ("cur_pdesc", DESC, _U1, "pt2"),
+            ("cur_ldesc", DESC, _U1, "ln2"), ("prev_pt_P", 3, _F8, "pt1"), ("prev_pt_sigma2", 1, _F8, "pt1"),
+            ("prev_ln_sP", 3, _F8, "ln1"), ("prev_ln_eP", 3, _F8, "ln1"), ("prev_ln_NDc", 6, _F8, "ln1"),
+            ("prev_ln_seg", 4, _F8, "ln1"), ("prev_ln_sigma2", 1, _F8, "ln1"), ("cur_pt_pl", 2, _F8, "pt2"),
+            ("cur_ln_seg", 4, _F8, "ln2"), ("cur_ln_le", 3, _F8, "ln2"))
+    PER = (("prev", TRACK_PREV),)
+    OUT = (("pt_m12", "pt1", (), _I4, -1), ("ln_m12", "ln1", (), _I4, -1), ("n_pt", "n", (), _I4, 0),
+           ("n_ln", "n", (), _I4, 0), ("pt_inlier", "pt1", (), _U1, 0), ("ln_inlier", "ln1", (), _U1, 0),
+           ("pt_cur_from_prev", "pt2", (), _I4, -1), ("ln_cur_from_prev", "ln2", (), _I4, -1))
+    SHORT = "{key} has {rows} rows, the descriptors have {lead}"
+    CAMERA = "pairs"
 
     def __init__(self, pairs, desc_bytes=32):
         pairs = list(pairs)
-        db = int(desc_bytes)
-        self.off = {}
-        for name, key in self.DESC:
-            rows = [np.asarray(getattr(q, name), np.uint8) for q in pairs]
-            rows = [r if r.ndim == 2 else r.reshape(-1, db) for r in rows]   # (rows of their own width are the caller's claim)
-            off = np.zeros(len(pairs) + 1, np.int32)
-            off[1:] = np.cumsum([len(r) for r in rows], dtype=np.int64)
-            self.off[key] = off
-            setattr(self, name, np.ascontiguousarray(np.concatenate([r.reshape(-1) for r in rows] + [np.zeros(1, np.uint8)])))
-        self.arrays = {}
-        for name, w, key in self.F64:
-            rows = [np.asarray(getattr(q, name), np.float64).reshape(-1, w) for q in pairs]
-            a = np.ascontiguousarray(np.concatenate(rows + [np.zeros((0, w))]))
-            if len(a) != self.off[key][-1]:
-                raise ValueError(f"{name} has {len(a)} rows, the descriptors have {self.off[key][-1]}")
-            self.arrays[name] = a
-        self.prev = np.ascontiguousarray(np.stack([np.asarray(q.prev, np.float64).reshape(TRACK_PREV) for q in pairs])
-                                         if pairs else np.zeros((0, TRACK_PREV)))
-        cam = pairs[0].cam if pairs else (1.0, 1.0, 0.0, 0.0)
-        if any(tuple(q.cam) != tuple(cam) for q in pairs):
-            raise ValueError("the pairs of one batch share one camera")
-        n = len(pairs)
-        self.struct = PlbaFramesBatch(
-            n=n, pad=0, pt_off1=_ptr(self.off["pt1"], _ip), pt_off2=_ptr(self.off["pt2"], _ip),
-            ln_off1=_ptr(self.off["ln1"], _ip), ln_off2=_ptr(self.off["ln2"], _ip),
-            prev=_ptr(self.prev, _dp), fx=cam[0], fy=cam[1], cx=cam[2], cy=cam[3],
-            **{name: _ptr(getattr(self, name), _bp) for name, _ in self.DESC},
-            **{name: _ptr(a, _dp) for name, a in self.arrays.items()})
-        # the outputs (an array of no rows still has an address)
-        i32 = lambda k, fill: np.full(max(int(self.off[k][-1]), 1), fill, np.int32)
-        self.out = (PlbaTrackOut * max(n, 1))()
-        self.pt_m12, self.ln_m12 = i32("pt1", -1), i32("ln1", -1)
-        self.pt_cfp, self.ln_cfp = i32("pt2", -1), i32("ln2", -1)
-        self.n_pt, self.n_ln = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-        self.pt_inl = np.zeros(max(int(self.off["pt1"][-1]), 1), np.uint8)
-        self.ln_inl = np.zeros(max(int(self.off["ln1"][-1]), 1), np.uint8)
-        self.out_struct = PlbaFramesOut(
-            out=self.out, pt_m12=_ptr(self.pt_m12, _ip), ln_m12=_ptr(self.ln_m12, _ip), n_pt=_ptr(self.n_pt, _ip),
-            n_ln=_ptr(self.n_ln, _ip), pt_inlier=_ptr(self.pt_inl, _bp), ln_inlier=_ptr(self.ln_inl, _bp),
-            pt_cur_from_prev=_ptr(self.pt_cfp, _ip), ln_cur_from_prev=_ptr(self.ln_cfp, _ip))
+        # (2-D descriptors keep their rows: their own width is the caller's claim, desc_bytes cuts the flat ones)
+        self._build(pairs, self._desc_width(pairs, desc_bytes))
+        self.out = self.out_struct.out = (PlbaTrackOut * max(self.n, 1))()   # (here .out is not the out struct)
 
     def results(self) -> list:
         """One dict per pair: the fields of track_out_to_dict (the inlier flags per PREVIOUS row) and pt_m12,
         ln_m12, n_pt, n_ln, pt_cur_from_prev, ln_cur_from_prev."""
-        o = self.off
-        res = []
-        for k in range(self.struct.n):
-            s = lambda a, key: a[o[key][k]:o[key][k + 1]].copy()
-            d = track_out_to_dict(self.out[k], s(self.pt_inl, "pt1"), s(self.ln_inl, "ln1"))
-            d.update(pt_m12=s(self.pt_m12, "pt1"), ln_m12=s(self.ln_m12, "ln1"), n_pt=int(self.n_pt[k]), n_ln=int(self.n_ln[k]),
-                     pt_cur_from_prev=s(self.pt_cfp, "pt2"), ln_cur_from_prev=s(self.ln_cfp, "ln2"))
-            res.append(d)
+        res = super().results()
+        for k, r in enumerate(res):
+            r.update(track_out_to_dict(self.out[k], r.pop("pt_inlier"), r.pop("ln_inlier")))
         return res
 
 
@@ -599,28 +648,17 @@ class PlbaGridMatchBatch(C.Structure):
                 ("dir2", _dp), ("kind", _ip), ("ws", _ip), ("nnr", _dp), ("line_sim_th", _dp)]
 
 
-class GridMatchBatchView:
-    """Concatenates matchGrid problems into contiguous arrays and the PlbaGridMatchBatch over them.
+class GridMatchBatchView(_BatchView):
+    """The PlbaGridMatchBatch over matchGrid problems.
     A problem is a dict: kind (0 points, 1 lines), ws, nnr, line_sim_th (lines), desc1 [n1][desc_bytes]
     uint8, cell1 [n1][2] int, cell1_end [n1][2] (lines), desc2 [n2][desc_bytes], cells2 (one [k][2] int
     array per train row) and dir2 [n2][2] (lines)."""
+    STRUCT, SIDES, ROWS = PlbaGridMatchBatch, MatchBatchView.SIDES, MatchBatchView.ROWS
 
     def __init__(self, problems, cols: int = 64, rows: int = 48, best_lr: bool = True, desc_bytes=None):
         problems = list(problems)
-        if desc_bytes is None:
-            desc_bytes = next((np.asarray(p[k]).shape[1] for p in problems for k in ("desc1", "desc2")
-                               if np.asarray(p[k]).ndim == 2 and np.asarray(p[k]).shape[1]), 32)
-        self.desc_bytes = db = int(desc_bytes)
-        n = len(problems)
-        d1 = [np.asarray(p["desc1"], np.uint8).reshape(-1, db) for p in problems]
-        d2 = [np.asarray(p["desc2"], np.uint8).reshape(-1, db) for p in problems]
-        self.off1 = np.zeros(n + 1, np.int32)
-        self.off2 = np.zeros(n + 1, np.int32)
-        self.off1[1:] = np.cumsum([len(a) for a in d1], dtype=np.int64)
-        self.off2[1:] = np.cumsum([len(a) for a in d2], dtype=np.int64)
-        self.desc1 = np.ascontiguousarray(np.concatenate(d1 + [np.zeros((0, db), np.uint8)]))
-        self.desc2 = np.ascontiguousarray(np.concatenate(d2 + [np.zeros((0, db), np.uint8)]))
-        n1, n2 = int(self.off1[-1]), int(self.off2[-1])
+        self._build(problems, desc_bytes, cols=int(cols), rows=int(rows), best_lr=int(bool(best_lr)))
+        n, n1, n2 = self.n, int(self.off1[-1]), int(self.off2[-1])
         self.cell1 = np.zeros((n1, 2), np.int32)
         self.cell1_end = np.zeros((n1, 2), np.int32)
         self.dir2 = np.zeros((n2, 2), np.float64)
@@ -631,7 +669,7 @@ class GridMatchBatchView:
             if p["kind"] == 1:
                 self.cell1_end[a:b] = np.asarray(p["cell1_end"], np.int32).reshape(-1, 2)
                 self.dir2[self.off2[k]:self.off2[k + 1]] = np.asarray(p["dir2"], np.float64).reshape(-1, 2)
-            if len(p["cells2"]) != len(d2[k]):
+            if len(p["cells2"]) != self.off2[k + 1] - self.off2[k]:
                 raise ValueError("one cell list per train row")
             for c in p["cells2"]:
                 c = np.asarray(c, np.int32).reshape(-1, 2)
@@ -644,13 +682,9 @@ class GridMatchBatchView:
         self.ws = np.array([int(p["ws"]) for p in problems], np.int32).reshape(n)
         self.nnr = np.array([float(p["nnr"]) for p in problems], np.float64).reshape(n)
         self.line_sim_th = np.array([float(p.get("line_sim_th", 0.75)) for p in problems], np.float64).reshape(n)
-        self.struct = PlbaGridMatchBatch(
-            n=n, desc_bytes=db, cols=int(cols), rows=int(rows), best_lr=int(bool(best_lr)), pad=0,
-            off1=_ptr(self.off1, _ip), off2=_ptr(self.off2, _ip), desc1=_ptr(self.desc1, _bp),
-            desc2=_ptr(self.desc2, _bp), cell1=_ptr(self.cell1, _ip), cell1_end=_ptr(self.cell1_end, _ip),
-            cell_off2=_ptr(self.cell_off2, _ip), cells2=_ptr(self.cells2, _ip), dir2=_ptr(self.dir2, _dp),
-            kind=_ptr(self.kind, _ip), ws=_ptr(self.ws, _ip), nnr=_ptr(self.nnr, _dp),
-            line_sim_th=_ptr(self.line_sim_th, _dp))
+        for k in ("cell1", "cell1_end", "cell_off2", "cells2", "dir2", "kind", "ws", "nnr", "line_sim_th"):
+            v = getattr(self, k)
+            setattr(self.struct, k, _ptr(v, _KINDS[v.dtype]))
 
 
 # ---- stereo association (plba_stereo_params / plba_stereo_batch / plba_stereo_out / plba_stereo_associate)
@@ -678,77 +712,42 @@ class PlbaStereoOut(C.Structure):
 def stereo_params(params=None) -> PlbaStereoParams:
     """PlbaStereoParams from a dict: plba_stereo_default_params, then the dict's entries (width, height,
     fx, fy, cx, cy and b have no default)."""
-    if isinstance(params, PlbaStereoParams):
-        return params
-    from . import lib   # lib imports this module
-    p = PlbaStereoParams()
-    lib.load().plba_stereo_default_params(C.byref(p))
-    for k, v in dict(params or {}).items():
-        if k not in dict(PlbaStereoParams._fields_):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return _params_from(PlbaStereoParams, "plba_stereo_default_params", params)
 
 
-class StereoBatchView:
-    """Concatenates stereo frames into contiguous arrays, the PlbaStereoBatch over them and the output
-    arrays of a call. A frame is a dict: pt_l [n][2] / pt_r float32, pdesc_l / pdesc_r [n][desc_bytes] uint8,
-    ls_l / ls_r [n][4] float32 (sx, sy, ex, ey), ldesc_l / ldesc_r; a missing key is an empty side."""
-
-    KEYS = (("pt_l", 2), ("pt_r", 2), ("ls_l", 4), ("ls_r", 4))
-    DESC = {"pt_l": "pdesc_l", "pt_r": "pdesc_r", "ls_l": "ldesc_l", "ls_r": "ldesc_r"}
+class StereoBatchView(_BatchView):
+    """The PlbaStereoBatch over stereo frames and the output arrays of a call (.o, .out). A frame is a dict:
+    pt_l [n][2] / pt_r float32, pdesc_l / pdesc_r [n][desc_bytes] uint8, ls_l / ls_r [n][4] float32 (sx, sy, ex, ey),
+    ldesc_l / ldesc_r; a missing key is an empty side. .co[side] and .desc[side] are a side's coordinates and
+    descriptors."""
+    STRUCT, OUT_STRUCT = PlbaStereoBatch, PlbaStereoOut
+    SIDES = (("pt_l", "pt_off_l"), ("pt_r", "pt_off_r"), ("ls_l", "ls_off_l"), ("ls_r", "ls_off_r"))
+    ROWS = (("pt_l", 2, _F4, "pt_l"), ("pdesc_l", DESC, _U1, "pt_l"), ("pt_r", 2, _F4, "pt_r"), ("pdesc_r", DESC, _U1, "pt_r"),
+            ("ls_l", 4, _F4, "ls_l"), ("ldesc_l", DESC, _U1, "ls_l"), ("ls_r", 4, _F4, "ls_r"), ("ldesc_r", DESC, _U1, "ls_r"))
+    # rows past a frame's count are never written: a fill that no result can equal shows it
+    OUT = (("n_pt", "n", (), _I4, 0), ("n_ls", "n", (), _I4, 0),
+           ("pt_src", "pt_l", (), _I4, -7), ("pt_pl", "pt_l", (2,), _F8, np.nan), ("pt_disp", "pt_l", (), _F8, np.nan),
+           ("pt_P", "pt_l", (3,), _F8, np.nan), ("pdesc", "pt_l", (DESC,), _U1, 0),
+           ("ls_src", "ls_l", (), _I4, -7), ("ls_spl", "ls_l", (2,), _F8, np.nan), ("ls_epl", "ls_l", (2,), _F8, np.nan),
+           ("ls_sdisp", "ls_l", (), _F8, np.nan), ("ls_edisp", "ls_l", (), _F8, np.nan), ("ls_sP", "ls_l", (3,), _F8, np.nan),
+           ("ls_eP", "ls_l", (3,), _F8, np.nan), ("ls_le", "ls_l", (3,), _F8, np.nan), ("ls_NDc", "ls_l", (6,), _F8, np.nan),
+           ("ldesc", "ls_l", (DESC,), _U1, 0))
+    SHORT = "one descriptor row per feature"
 
     def __init__(self, frames, desc_bytes=None):
-        frames = list(frames)
-        if desc_bytes is None:
-            desc_bytes = next((np.asarray(f[k]).shape[1] for f in frames for k in self.DESC.values()
-                               if k in f and np.asarray(f[k]).ndim == 2 and np.asarray(f[k]).shape[1]), 32)
-        self.desc_bytes = db = int(desc_bytes)
-        self.n = n = len(frames)
-        self.off, self.co, self.desc = {}, {}, {}
-        for key, per in self.KEYS:
-            co = [np.asarray(f.get(key, np.zeros((0, per))), np.float32).reshape(-1, per) for f in frames]
-            de = [np.asarray(f.get(self.DESC[key], np.zeros((0, db))), np.uint8).reshape(-1, db) for f in frames]
-            if any(len(a) != len(d) for a, d in zip(co, de)):
-                raise ValueError("one descriptor row per feature")
-            off = np.zeros(n + 1, np.int32)
-            off[1:] = np.cumsum([len(a) for a in co], dtype=np.int64)
-            self.off[key] = off
-            self.co[key] = np.ascontiguousarray(np.concatenate(co + [np.zeros((0, per), np.float32)]))
-            self.desc[key] = np.ascontiguousarray(np.concatenate(de + [np.zeros((0, db), np.uint8)]))
-        self.struct = PlbaStereoBatch(
-            n=n, desc_bytes=db, pt_off_l=_ptr(self.off["pt_l"], _ip), pt_off_r=_ptr(self.off["pt_r"], _ip),
-            ls_off_l=_ptr(self.off["ls_l"], _ip), ls_off_r=_ptr(self.off["ls_r"], _ip),
-            pt_l=_ptr(self.co["pt_l"], _fp), pt_r=_ptr(self.co["pt_r"], _fp), pdesc_l=_ptr(self.desc["pt_l"], _bp),
-            pdesc_r=_ptr(self.desc["pt_r"], _bp), ls_l=_ptr(self.co["ls_l"], _fp), ls_r=_ptr(self.co["ls_r"], _fp),
-            ldesc_l=_ptr(self.desc["ls_l"], _bp), ldesc_r=_ptr(self.desc["ls_r"], _bp))
-        npt, nls = max(int(self.off["pt_l"][-1]), 1), max(int(self.off["ls_l"][-1]), 1)
-        # rows past a frame's count are never written: a fill that no result can equal shows it
-        self.o = dict(
-            n_pt=np.zeros(max(n, 1), np.int32), n_ls=np.zeros(max(n, 1), np.int32),
-            pt_src=np.full(npt, -7, np.int32), pt_pl=np.full((npt, 2), np.nan), pt_disp=np.full(npt, np.nan),
-            pt_P=np.full((npt, 3), np.nan), pdesc=np.zeros((npt, db), np.uint8),
-            ls_src=np.full(nls, -7, np.int32), ls_spl=np.full((nls, 2), np.nan), ls_epl=np.full((nls, 2), np.nan),
-            ls_sdisp=np.full(nls, np.nan), ls_edisp=np.full(nls, np.nan), ls_sP=np.full((nls, 3), np.nan),
-            ls_eP=np.full((nls, 3), np.nan), ls_le=np.full((nls, 3), np.nan), ls_NDc=np.full((nls, 6), np.nan),
-            ldesc=np.zeros((nls, db), np.uint8))
-        kinds = {np.dtype(np.int32): _ip, np.dtype(np.float64): _dp, np.dtype(np.uint8): _bp}
-        self.out = PlbaStereoOut(**{k: v.ctypes.data_as(kinds[v.dtype]) for k, v in self.o.items()})
-
-    PT = ("pt_src", "pt_pl", "pt_disp", "pt_P", "pdesc")
-    LS = ("ls_src", "ls_spl", "ls_epl", "ls_sdisp", "ls_edisp", "ls_sP", "ls_eP", "ls_le", "ls_NDc", "ldesc")
+        self._build(frames, desc_bytes)
+        self.co = {side: self.a[side] for side, _ in self.SIDES}
+        self.desc = {side: self.a[key] for key, per, _, side in self.ROWS if per is DESC}
 
     def results(self, pluker: bool) -> list:
         """One dict per frame: n_pt, n_ls and the first n_pt / n_ls rows of every output array (ls_NDc only
         with pluker), copied."""
-        res = []
-        for f in range(self.n):
-            kp, kl = int(self.o["n_pt"][f]), int(self.o["n_ls"][f])
-            a, b = int(self.off["pt_l"][f]), int(self.off["ls_l"][f])
-            r = dict(n_pt=kp, n_ls=kl)
-            r.update({k: self.o[k][a:a + kp].copy() for k in self.PT})
-            r.update({k: self.o[k][b:b + kl].copy() for k in self.LS if pluker or k != "ls_NDc"})
-            res.append(r)
+        res = super().results()
+        for r in res:
+            for key, side, *_ in self.OUT[2:]:
+                r[key] = r[key][:r["n_pt" if side == "pt_l" else "n_ls"]]
+            if not pluker:
+                del r["ls_NDc"]
         return res
 
 
@@ -778,87 +777,31 @@ class PlbaKfassocOut(C.Structure):
 def kfassoc_params(params=None) -> PlbaKfassocParams:
     """PlbaKfassocParams from a dict: plba_kfassoc_default_params, then the dict's entries (width, height,
     fx, fy, cx and cy have no default)."""
-    if isinstance(params, PlbaKfassocParams):
-        return params
-    from . import lib   # lib imports this module
-    p = PlbaKfassocParams()
-    lib.load().plba_kfassoc_default_params(C.byref(p))
-    for k, v in dict(params or {}).items():
-        if k not in dict(PlbaKfassocParams._fields_):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return _params_from(PlbaKfassocParams, "plba_kfassoc_default_params", params)
 
 
-class KfassocBatchView:
-    """Concatenates keyframe pairs into contiguous arrays, the PlbaKfassocBatch over them and the output
-    arrays of a call. A pair is a dict: DT [3][4], T_prev / T_curr / Tcw_prev / Tcw_curr [4][4]; of the previous
+class KfassocBatchView(_BatchView):
+    """The PlbaKfassocBatch over keyframe pairs and the output arrays of a call (.o, .out). A pair is a dict:
+    DT [3][4], T_prev / T_curr / Tcw_prev / Tcw_curr [4][4]; of the previous
     keyframe pt_P_p [n][3], pdesc_p, ls_sP_p, ls_eP_p [n][3], ls_NDc_p [n][6], ls_spl_p, ls_epl_p [n][2], ldesc_p,
     ls_lm_NDw [n][6], ls_new [n] uint8; of the current one pt_pl_c [n][2], pt_P_c [n][3], pdesc_c, ls_spl_c,
-    ls_epl_c [n][2], ldesc_c. A missing feature key is an empty side."""
-
-    # key: (columns, dtype, the side's row-count key)
-    ROWS = (("pt_P_p", 3, "pt_p"), ("ls_sP_p", 3, "ls_p"), ("ls_eP_p", 3, "ls_p"), ("ls_NDc_p", 6, "ls_p"),
-            ("ls_spl_p", 2, "ls_p"), ("ls_epl_p", 2, "ls_p"), ("ls_lm_NDw", 6, "ls_p"), ("pt_pl_c", 2, "pt_c"),
-            ("pt_P_c", 3, "pt_c"), ("ls_spl_c", 2, "ls_c"), ("ls_epl_c", 2, "ls_c"))
-    DESC = (("pdesc_p", "pt_p"), ("ldesc_p", "ls_p"), ("pdesc_c", "pt_c"), ("ldesc_c", "ls_c"))
-    LEAD = {"pt_p": "pt_P_p", "ls_p": "ls_sP_p", "pt_c": "pt_pl_c", "ls_c": "ls_spl_c"}
-    POSES = (("DT", 12), ("T_prev", 16), ("T_curr", 16), ("Tcw_prev", 16), ("Tcw_curr", 16))
+    ls_epl_c [n][2], ldesc_c. A missing feature key is an empty side. results(): one dict per pair with n_grid,
+    n_matches, fallback as (points, lines), and the previous rows' pt_m12, pt_rec, ls_m12, ls_rec, ls_rejected."""
+    STRUCT, OUT_STRUCT = PlbaKfassocBatch, PlbaKfassocOut
+    SIDES = (("pt_p", "pt_off_p"), ("pt_c", "pt_off_c"), ("ls_p", "ls_off_p"), ("ls_c", "ls_off_c"))
+    ROWS = (("pt_P_p", 3, _F8, "pt_p"), ("ls_sP_p", 3, _F8, "ls_p"), ("ls_eP_p", 3, _F8, "ls_p"), ("ls_NDc_p", 6, _F8, "ls_p"),
+            ("ls_spl_p", 2, _F8, "ls_p"), ("ls_epl_p", 2, _F8, "ls_p"), ("ls_lm_NDw", 6, _F8, "ls_p"),
+            ("pt_pl_c", 2, _F8, "pt_c"), ("pt_P_c", 3, _F8, "pt_c"), ("ls_spl_c", 2, _F8, "ls_c"), ("ls_epl_c", 2, _F8, "ls_c"),
+            ("pdesc_p", DESC, _U1, "pt_p"), ("ldesc_p", DESC, _U1, "ls_p"), ("pdesc_c", DESC, _U1, "pt_c"),
+            ("ldesc_c", DESC, _U1, "ls_c"), ("ls_new", 1, _U1, "ls_p"))
+    PER = (("DT", 12), ("T_prev", 16), ("T_curr", 16), ("Tcw_prev", 16), ("Tcw_curr", 16))
+    # every row is written: a fill that no result can equal shows one that was not
+    OUT = (("n_grid", "2n", (), _I4, -7), ("n_matches", "2n", (), _I4, -7), ("fallback", "2n", (), _I4, -7),
+           ("pt_m12", "pt_p", (), _I4, -7), ("pt_rec", "pt_p", (9,), _F8, np.nan), ("ls_m12", "ls_p", (), _I4, -7),
+           ("ls_rec", "ls_p", (8,), _F8, np.nan), ("ls_rejected", "ls_p", (), _U1, 7))
 
     def __init__(self, pairs, desc_bytes=None):
-        pairs = list(pairs)
-        if desc_bytes is None:
-            desc_bytes = next((np.asarray(f[k]).shape[1] for f in pairs for k, _ in self.DESC
-                               if k in f and np.asarray(f[k]).ndim == 2 and np.asarray(f[k]).shape[1]), 32)
-        self.desc_bytes = db = int(desc_bytes)
-        self.n = n = len(pairs)
-        cnt = {s: [len(np.asarray(f.get(k, np.zeros((0, 1))))) for f in pairs] for s, k in self.LEAD.items()}
-        self.off = {}
-        for s, c in cnt.items():
-            self.off[s] = np.zeros(n + 1, np.int32)
-            self.off[s][1:] = np.cumsum(c, dtype=np.int64)
-        self.a = {}
-
-        def cat(key, per, dtype, side):
-            parts = [np.asarray(f.get(key, np.zeros((0, per))), dtype).reshape(-1, per) for f in pairs]
-            if [len(p) for p in parts] != cnt[side]:
-                raise ValueError(f"{key}: one row per feature")
-            return np.ascontiguousarray(np.concatenate(parts + [np.zeros((0, per), dtype)]))
-
-        for key, per, side in self.ROWS:
-            self.a[key] = cat(key, per, np.float64, side)
-        for key, side in self.DESC:
-            self.a[key] = cat(key, db, np.uint8, side)
-        self.a["ls_new"] = cat("ls_new", 1, np.uint8, "ls_p")
-        for key, per in self.POSES:
-            self.a[key] = np.ascontiguousarray(
-                np.concatenate([np.asarray(f[key], np.float64).reshape(1, per) for f in pairs] + [np.zeros((0, per))]))
-        kinds = {np.dtype(np.int32): _ip, np.dtype(np.float64): _dp, np.dtype(np.uint8): _bp}
-        self.struct = PlbaKfassocBatch(
-            n=n, desc_bytes=db, pt_off_p=_ptr(self.off["pt_p"], _ip), pt_off_c=_ptr(self.off["pt_c"], _ip),
-            ls_off_p=_ptr(self.off["ls_p"], _ip), ls_off_c=_ptr(self.off["ls_c"], _ip),
-            **{k: _ptr(v, kinds[v.dtype]) for k, v in self.a.items()})
-        npt, nls, P = max(int(self.off["pt_p"][-1]), 1), max(int(self.off["ls_p"][-1]), 1), max(2 * n, 1)
-        # every row is written: a fill that no result can equal shows one that was not
-        self.o = dict(n_grid=np.full(P, -7, np.int32), n_matches=np.full(P, -7, np.int32), fallback=np.full(P, -7, np.int32),
-                      pt_m12=np.full(npt, -7, np.int32), ls_m12=np.full(nls, -7, np.int32),
-                      pt_rec=np.full((npt, 9), np.nan), ls_rec=np.full((nls, 8), np.nan),
-                      ls_rejected=np.full(nls, 7, np.uint8))
-        self.out = PlbaKfassocOut(**{k: v.ctypes.data_as(kinds[v.dtype]) for k, v in self.o.items()})
-
-    def results(self) -> list:
-        """One dict per pair: n_grid, n_matches, fallback as (points, lines), and the previous rows' pt_m12,
-        pt_rec, ls_m12, ls_rec, ls_rejected, copied."""
-        res = []
-        for f in range(self.n):
-            a, b = self.off["pt_p"][f:f + 2]
-            c, d = self.off["ls_p"][f:f + 2]
-            r = {k: (int(self.o[k][2 * f]), int(self.o[k][2 * f + 1])) for k in ("n_grid", "n_matches", "fallback")}
-            r.update(pt_m12=self.o["pt_m12"][a:b].copy(), pt_rec=self.o["pt_rec"][a:b].copy(),
-                     ls_m12=self.o["ls_m12"][c:d].copy(), ls_rec=self.o["ls_rec"][c:d].copy(),
-                     ls_rejected=self.o["ls_rejected"][c:d].copy())
-            res.append(r)
-        return res
+        self._build(pairs, desc_bytes)
 
 
 # ---- map-to-keyframe association (plba_mapassoc_params / _batch / _out / plba_map_associate)
@@ -887,86 +830,29 @@ class PlbaMapassocOut(C.Structure):
 def mapassoc_params(params=None, **kw) -> PlbaMapassocParams:
     """PlbaMapassocParams from a dict and / or keywords: plba_mapassoc_default_params, then the entries
     (width, height, fx, fy, cx and cy have no default)."""
-    if isinstance(params, PlbaMapassocParams) and not kw:
-        return params
-    from . import lib   # lib imports this module
-    p = PlbaMapassocParams()
-    lib.load().plba_mapassoc_default_params(C.byref(p))
-    for k, v in {**dict(params or {}), **kw}.items():
-        if k not in dict(PlbaMapassocParams._fields_):
-            raise KeyError(k)
-        setattr(p, k, v)
-    return p
+    return _params_from(PlbaMapassocParams, "plba_mapassoc_default_params", params, **kw)
 
 
-class MapassocBatchView:
-    """Concatenates keyframes into contiguous arrays, the PlbaMapassocBatch over them and the output arrays
-    of a call. A keyframe is a dict: Twf [3][4], T_kf_w [4][4]; of the candidate landmarks pt_X [n][3], pdesc_m,
+class MapassocBatchView(_BatchView):
+    """The PlbaMapassocBatch over keyframes and the output arrays of a call (.o, .out). A keyframe is a dict:
+    Twf [3][4] (or [4][4]: its first three rows), T_kf_w [4][4]; of the candidate landmarks pt_X [n][3], pdesc_m,
     ls_X [n][6] (line3D), ldesc_m; of the unmatched features pt_pl [n][2], pt_P [n][3], pdesc_f, ls_spl, ls_epl
-    [n][2], ls_le, ls_sP, ls_eP [n][3], ldesc_f. A missing row key is an empty side."""
-
-    # key: (columns, the side's row-count key)
-    ROWS = (("pt_X", 3, "pt_m"), ("ls_X", 6, "ls_m"), ("pt_pl", 2, "pt_f"), ("pt_P", 3, "pt_f"), ("ls_spl", 2, "ls_f"),
-            ("ls_epl", 2, "ls_f"), ("ls_le", 3, "ls_f"), ("ls_sP", 3, "ls_f"), ("ls_eP", 3, "ls_f"))
-    DESC = (("pdesc_m", "pt_m"), ("ldesc_m", "ls_m"), ("pdesc_f", "pt_f"), ("ldesc_f", "ls_f"))
-    LEAD = {"pt_m": "pt_X", "ls_m": "ls_X", "pt_f": "pt_pl", "ls_f": "ls_spl"}
-    POSES = (("Twf", 12), ("T_kf_w", 16))
+    [n][2], ls_le, ls_sP, ls_eP [n][3], ldesc_f. A missing row key is an empty side. results(): one dict per
+    keyframe with n_visible, n_grid, n_matches, fallback, n_accepted as (points, lines), and the candidate rows'
+    pt_visible, pt_m12, pt_accepted, pt_rec, ls_visible, ls_m12, ls_accepted, ls_rec."""
+    STRUCT, OUT_STRUCT = PlbaMapassocBatch, PlbaMapassocOut
+    SIDES = (("pt_m", "pt_off_m"), ("pt_f", "pt_off_f"), ("ls_m", "ls_off_m"), ("ls_f", "ls_off_f"))
+    ROWS = (("pt_X", 3, _F8, "pt_m"), ("ls_X", 6, _F8, "ls_m"), ("pt_pl", 2, _F8, "pt_f"), ("pt_P", 3, _F8, "pt_f"),
+            ("ls_spl", 2, _F8, "ls_f"), ("ls_epl", 2, _F8, "ls_f"), ("ls_le", 3, _F8, "ls_f"), ("ls_sP", 3, _F8, "ls_f"),
+            ("ls_eP", 3, _F8, "ls_f"), ("pdesc_m", DESC, _U1, "pt_m"), ("ldesc_m", DESC, _U1, "ls_m"),
+            ("pdesc_f", DESC, _U1, "pt_f"), ("ldesc_f", DESC, _U1, "ls_f"))
+    PER = (("Twf", 12), ("T_kf_w", 16))
+    # every row is written: a fill that no result can equal shows one that was not
+    OUT = tuple((k, "2n", (), _I4, -7) for k in ("n_visible", "n_grid", "n_matches", "fallback", "n_accepted")) + (
+        ("pt_visible", "pt_m", (), _U1, 7), ("pt_m12", "pt_m", (), _I4, -7), ("pt_accepted", "pt_m", (), _U1, 7),
+        ("pt_rec", "pt_m", (6,), _F8, np.nan), ("ls_visible", "ls_m", (), _U1, 7), ("ls_m12", "ls_m", (), _I4, -7),
+        ("ls_accepted", "ls_m", (), _U1, 7), ("ls_rec", "ls_m", (9,), _F8, np.nan))
+    SHORT = "{key}: one row per landmark or feature"
 
     def __init__(self, problems, desc_bytes=None):
-        problems = list(problems)
-        if desc_bytes is None:
-            desc_bytes = next((np.asarray(f[k]).shape[1] for f in problems for k, _ in self.DESC
-                               if k in f and np.asarray(f[k]).ndim == 2 and np.asarray(f[k]).shape[1]), 32)
-        self.desc_bytes = db = int(desc_bytes)
-        self.n = n = len(problems)
-        cnt = {s: [len(np.asarray(f.get(k, np.zeros((0, 1))))) for f in problems] for s, k in self.LEAD.items()}
-        self.off = {}
-        for s, c in cnt.items():
-            self.off[s] = np.zeros(n + 1, np.int32)
-            self.off[s][1:] = np.cumsum(c, dtype=np.int64)
-        self.a = {}
-
-        def cat(key, per, dtype, side):
-            parts = [np.asarray(f.get(key, np.zeros((0, per))), dtype).reshape(-1, per) for f in problems]
-            if [len(p) for p in parts] != cnt[side]:
-                raise ValueError(f"{key}: one row per landmark or feature")
-            return np.ascontiguousarray(np.concatenate(parts + [np.zeros((0, per), dtype)]))
-
-        for key, per, side in self.ROWS:
-            self.a[key] = cat(key, per, np.float64, side)
-        for key, side in self.DESC:
-            self.a[key] = cat(key, db, np.uint8, side)
-        for key, per in self.POSES:
-            self.a[key] = np.ascontiguousarray(
-                np.concatenate([np.asarray(f[key], np.float64).reshape(-1)[:per].reshape(1, per) for f in problems] +
-                               [np.zeros((0, per))]))
-        kinds = {np.dtype(np.int32): _ip, np.dtype(np.float64): _dp, np.dtype(np.uint8): _bp}
-        self.struct = PlbaMapassocBatch(
-            n=n, desc_bytes=db, pt_off_m=_ptr(self.off["pt_m"], _ip), pt_off_f=_ptr(self.off["pt_f"], _ip),
-            ls_off_m=_ptr(self.off["ls_m"], _ip), ls_off_f=_ptr(self.off["ls_f"], _ip),
-            **{k: _ptr(v, kinds[v.dtype]) for k, v in self.a.items()})
-        npt, nls, P = max(int(self.off["pt_m"][-1]), 1), max(int(self.off["ls_m"][-1]), 1), max(2 * n, 1)
-        # every row is written: a fill that no result can equal shows one that was not
-        self.o = {k: np.full(P, -7, np.int32) for k in self.COUNTS}
-        self.o.update(pt_visible=np.full(npt, 7, np.uint8), pt_m12=np.full(npt, -7, np.int32),
-                      pt_accepted=np.full(npt, 7, np.uint8), pt_rec=np.full((npt, 6), np.nan),
-                      ls_visible=np.full(nls, 7, np.uint8), ls_m12=np.full(nls, -7, np.int32),
-                      ls_accepted=np.full(nls, 7, np.uint8), ls_rec=np.full((nls, 9), np.nan))
-        self.out = PlbaMapassocOut(**{k: v.ctypes.data_as(kinds[v.dtype]) for k, v in self.o.items()})
-
-    COUNTS = ("n_visible", "n_grid", "n_matches", "fallback", "n_accepted")
-    PT = ("pt_visible", "pt_m12", "pt_accepted", "pt_rec")
-    LS = ("ls_visible", "ls_m12", "ls_accepted", "ls_rec")
-
-    def results(self) -> list:
-        """One dict per keyframe: n_visible, n_grid, n_matches, fallback, n_accepted as (points, lines), and the
-        candidate rows' pt_visible, pt_m12, pt_accepted, pt_rec, ls_visible, ls_m12, ls_accepted, ls_rec, copied."""
-        res = []
-        for f in range(self.n):
-            a, b = self.off["pt_m"][f:f + 2]
-            c, d = self.off["ls_m"][f:f + 2]
-            r = {k: (int(self.o[k][2 * f]), int(self.o[k][2 * f + 1])) for k in self.COUNTS}
-            r.update({k: self.o[k][a:b].copy() for k in self.PT})
-            r.update({k: self.o[k][c:d].copy() for k in self.LS})
-            res.append(r)
-        return res
+        self._build([{**f, "Twf": np.asarray(f["Twf"], np.float64).reshape(-1)[:12]} for f in problems], desc_bytes)

@@ -21,25 +21,64 @@ _lib = None
 
 PLBA_ERRORS = {-1: "PLBA_E_INVALID", -2: "PLBA_E_DEVICE", -3: "PLBA_E_STATE", -4: "PLBA_E_NOMEM", -5: "PLBA_E_COMM"}
 
-EXPORTED = [
-    "plba_default_opts", "plba_create", "plba_destroy", "plba_last_error", "plba_upload", "plba_reset_estimates",
-    "plba_set_edge_levels", "plba_set_robust", "plba_initialize_optimization", "plba_optimize",
-    "plba_refresh_edge_errors", "plba_get_edge_chi2", "plba_download", "plba_lba_plucker", "plba_get_trace",
-    "plba_synchronize", "plba_enable_kernel_timing", "plba_kernel_times", "plba_structure_stats",
-    "plba_shard_plan", "plba_comm_unique_id", "plba_comm_init_rccl", "plba_comm_init_host",
-    "plba_comm_info", "plba_factor_plan",
-    "plba_hlm_default_params", "plba_hlm_lba",
-    "plba_pgo_default_params", "plba_pgo_optimize",
-    "plba_lcpose_default_params", "plba_lc_relative_pose",
-    "plba_track_default_params", "plba_track_pose", "plba_frames_default_params", "plba_track_frames",
-    "plba_desc_match", "plba_grid_match", "plba_stereo_default_params", "plba_stereo_associate",
-    "plba_kfassoc_default_params", "plba_kf_associate", "plba_mapassoc_default_params", "plba_map_associate",
-    "plba_desc_medoid",
-    "plba_bow_set_vocab", "plba_bow_insert", "plba_bow_remove", "plba_bow_get",
-]
-
 # int (*plba_host_allreduce_fn)(void *user, double *buf, int64_t n)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
+
+# every function load() binds, with its argtypes. plba_default_opts and every *_default_params return void,
+# plba_last_error a string, the others an int
+_P, _vp, _i32 = C.POINTER, C.c_void_p, C.c_int32
+_dp, _bp, _ip = _P(C.c_double), _P(C.c_uint8), _P(C.c_int32)
+ARGTYPES = {
+    "plba_default_opts": [_P(capi.PlbaOpts)],
+    "plba_create": [_P(_vp), _P(capi.PlbaOpts)],
+    "plba_destroy": [_vp],
+    "plba_last_error": [_vp],
+    "plba_upload": [_vp, _P(capi.PlbaGraph)],
+    "plba_reset_estimates": [_vp],
+    "plba_set_edge_levels": [_vp, _bp, _bp],
+    "plba_set_robust": [_vp, _i32],
+    "plba_initialize_optimization": [_vp, _i32],
+    "plba_optimize": [_vp, _i32, _ip, _dp],
+    "plba_refresh_edge_errors": [_vp, _i32],
+    "plba_get_edge_chi2": [_vp, _dp, _bp, _dp],
+    "plba_download": [_vp, _dp, _dp, _dp],
+    "plba_lba_plucker": [_vp, _P(capi.PlbaResult)],
+    "plba_get_trace": [_vp, _P(capi.PlbaIterTrace), _i32, _ip],
+    "plba_synchronize": [_vp],
+    "plba_enable_kernel_timing": [_vp, _i32],
+    "plba_kernel_times": [_vp, _P(C.c_char_p), _dp, _ip, _i32, _ip],
+    "plba_structure_stats": [_vp, _P(C.c_int64), _i32],
+    "plba_shard_plan": [_P(capi.PlbaGraph), _i32, _ip, _ip],
+    "plba_comm_unique_id": [_bp],
+    "plba_comm_init_rccl": [_vp, _i32, _i32, _bp],
+    "plba_comm_init_host": [_vp, _i32, _i32, HOST_ALLREDUCE_FN, _vp],
+    "plba_comm_info": [_vp, _ip, _i32],
+    "plba_factor_plan": [_i32, _i32, _i32, _i32, _ip, _i32],
+    "plba_hlm_default_params": [_P(capi.PlbaHlmParams)],
+    "plba_hlm_lba": [_vp, _P(capi.PlbaHlmState), _P(capi.PlbaHlmParams), _P(capi.PlbaHlmResult)],
+    "plba_pgo_default_params": [_P(capi.PlbaPgoParams)],
+    "plba_pgo_optimize": [_vp, _P(capi.PlbaPgoGraph), _P(capi.PlbaPgoParams), _P(capi.PlbaPgoResult)],
+    "plba_lcpose_default_params": [_P(capi.PlbaLcposeParams)],
+    "plba_lc_relative_pose": [_vp, _P(capi.PlbaLcposeBatch), _P(capi.PlbaLcposeParams), _P(capi.PlbaLcposeOut), _bp, _bp],
+    "plba_track_default_params": [_P(capi.PlbaTrackParams)],
+    "plba_track_pose": [_vp, _P(capi.PlbaTrackBatch), _P(capi.PlbaTrackParams), _P(capi.PlbaTrackOut), _bp, _bp],
+    "plba_frames_default_params": [_P(capi.PlbaFramesParams)],
+    "plba_track_frames": [_vp, _P(capi.PlbaFramesBatch), _P(capi.PlbaFramesParams), _P(capi.PlbaFramesOut)],
+    "plba_desc_match": [_vp, _P(capi.PlbaMatchBatch), _ip, _ip],
+    "plba_grid_match": [_vp, _P(capi.PlbaGridMatchBatch), _ip, _ip],
+    "plba_stereo_default_params": [_P(capi.PlbaStereoParams)],
+    "plba_stereo_associate": [_vp, _P(capi.PlbaStereoBatch), _P(capi.PlbaStereoParams), _P(capi.PlbaStereoOut)],
+    "plba_kfassoc_default_params": [_P(capi.PlbaKfassocParams)],
+    "plba_kf_associate": [_vp, _P(capi.PlbaKfassocBatch), _P(capi.PlbaKfassocParams), _P(capi.PlbaKfassocOut)],
+    "plba_mapassoc_default_params": [_P(capi.PlbaMapassocParams)],
+    "plba_map_associate": [_vp, _P(capi.PlbaMapassocBatch), _P(capi.PlbaMapassocParams), _P(capi.PlbaMapassocOut)],
+    "plba_desc_medoid": [_vp, _P(capi.PlbaMedoidBatch), _ip],
+    "plba_bow_set_vocab": [_vp, _i32, _P(capi.PlbaBowVocab)],
+    "plba_bow_insert": [_vp, _i32, _i32, _bp, _i32, _dp, _ip, _i32, _ip],
+    "plba_bow_remove": [_vp, _i32, _i32],
+    "plba_bow_get": [_vp, _i32, _i32, _ip, _dp, _i32, _ip],
+}
+EXPORTED = list(ARGTYPES)
 
 
 class PlbaError(RuntimeError):
@@ -56,82 +95,11 @@ def load(path: Optional[str] = None):
         raise PlbaError(f"libplba.so not found at {path}: run `make -C pl-slam-plucker_amd` "
                         "(or __graft_entry__.build()) first")
     L = C.CDLL(path)
-    vp = C.c_void_p
-    dp = C.POINTER(C.c_double)
-    bp = C.POINTER(C.c_uint8)
-    ip = C.POINTER(C.c_int32)
-    L.plba_default_opts.argtypes = [C.POINTER(capi.PlbaOpts)]
-    L.plba_default_opts.restype = None
-    L.plba_create.argtypes = [C.POINTER(vp), C.POINTER(capi.PlbaOpts)]
-    L.plba_destroy.argtypes = [vp]
-    L.plba_last_error.argtypes = [vp]
-    L.plba_last_error.restype = C.c_char_p
-    L.plba_upload.argtypes = [vp, C.POINTER(capi.PlbaGraph)]
-    L.plba_reset_estimates.argtypes = [vp]
-    L.plba_set_edge_levels.argtypes = [vp, bp, bp]
-    L.plba_set_robust.argtypes = [vp, C.c_int32]
-    L.plba_initialize_optimization.argtypes = [vp, C.c_int32]
-    L.plba_optimize.argtypes = [vp, C.c_int32, ip, dp]
-    L.plba_refresh_edge_errors.argtypes = [vp, C.c_int32]
-    L.plba_get_edge_chi2.argtypes = [vp, dp, bp, dp]
-    L.plba_download.argtypes = [vp, dp, dp, dp]
-    L.plba_lba_plucker.argtypes = [vp, C.POINTER(capi.PlbaResult)]
-    L.plba_get_trace.argtypes = [vp, C.POINTER(capi.PlbaIterTrace), C.c_int32, ip]
-    L.plba_synchronize.argtypes = [vp]
-    L.plba_enable_kernel_timing.argtypes = [vp, C.c_int32]
-    L.plba_kernel_times.argtypes = [vp, C.POINTER(C.c_char_p), dp, ip, C.c_int32, ip]
-    L.plba_structure_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]
-    L.plba_shard_plan.argtypes = [C.POINTER(capi.PlbaGraph), C.c_int32, ip, ip]
-    L.plba_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
-    L.plba_comm_init_rccl.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
-    L.plba_comm_init_host.argtypes = [vp, C.c_int32, C.c_int32, HOST_ALLREDUCE_FN, vp]
-    L.plba_comm_info.argtypes = [vp, ip, C.c_int32]
-    L.plba_factor_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32]
-    L.plba_hlm_default_params.argtypes = [C.POINTER(capi.PlbaHlmParams)]
-    L.plba_hlm_default_params.restype = None
-    L.plba_hlm_lba.argtypes = [vp, C.POINTER(capi.PlbaHlmState), C.POINTER(capi.PlbaHlmParams),
-                               C.POINTER(capi.PlbaHlmResult)]
-    L.plba_pgo_default_params.argtypes = [C.POINTER(capi.PlbaPgoParams)]
-    L.plba_pgo_default_params.restype = None
-    L.plba_pgo_optimize.argtypes = [vp, C.POINTER(capi.PlbaPgoGraph), C.POINTER(capi.PlbaPgoParams),
-                                    C.POINTER(capi.PlbaPgoResult)]
-    L.plba_lcpose_default_params.argtypes = [C.POINTER(capi.PlbaLcposeParams)]
-    L.plba_lcpose_default_params.restype = None
-    L.plba_lc_relative_pose.argtypes = [vp, C.POINTER(capi.PlbaLcposeBatch), C.POINTER(capi.PlbaLcposeParams),
-                                        C.POINTER(capi.PlbaLcposeOut), bp, bp]
-    L.plba_track_default_params.argtypes = [C.POINTER(capi.PlbaTrackParams)]
-    L.plba_track_default_params.restype = None
-    L.plba_track_pose.argtypes = [vp, C.POINTER(capi.PlbaTrackBatch), C.POINTER(capi.PlbaTrackParams),
-                                  C.POINTER(capi.PlbaTrackOut), bp, bp]
-    L.plba_frames_default_params.argtypes = [C.POINTER(capi.PlbaFramesParams)]
-    L.plba_frames_default_params.restype = None
-    L.plba_track_frames.argtypes = [vp, C.POINTER(capi.PlbaFramesBatch), C.POINTER(capi.PlbaFramesParams),
-                                    C.POINTER(capi.PlbaFramesOut)]
-    L.plba_desc_match.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
-    L.plba_grid_match.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
-    L.plba_stereo_default_params.argtypes = [C.POINTER(capi.PlbaStereoParams)]
-    L.plba_stereo_default_params.restype = None
-    L.plba_stereo_associate.argtypes = [vp, C.POINTER(capi.PlbaStereoBatch), C.POINTER(capi.PlbaStereoParams),
-                                        C.POINTER(capi.PlbaStereoOut)]
-    L.plba_kfassoc_default_params.argtypes = [C.POINTER(capi.PlbaKfassocParams)]
-    L.plba_kfassoc_default_params.restype = None
-    L.plba_kf_associate.argtypes = [vp, C.POINTER(capi.PlbaKfassocBatch), C.POINTER(capi.PlbaKfassocParams),
-                                    C.POINTER(capi.PlbaKfassocOut)]
-    L.plba_mapassoc_default_params.argtypes = [C.POINTER(capi.PlbaMapassocParams)]
-    L.plba_mapassoc_default_params.restype = None
-    L.plba_map_associate.argtypes = [vp, C.POINTER(capi.PlbaMapassocBatch), C.POINTER(capi.PlbaMapassocParams),
-                                     C.POINTER(capi.PlbaMapassocOut)]
-    L.plba_desc_medoid.argtypes = [vp, C.POINTER(capi.PlbaMedoidBatch), ip]
-    L.plba_bow_set_vocab.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaBowVocab)]
-    L.plba_bow_insert.argtypes = [vp, C.c_int32, C.c_int32, bp, C.c_int32, dp, ip, C.c_int32, ip]
-    L.plba_bow_remove.argtypes = [vp, C.c_int32, C.c_int32]
-    L.plba_bow_get.argtypes = [vp, C.c_int32, C.c_int32, ip, dp, C.c_int32, ip]
-    for name in EXPORTED:
+    for name, argtypes in ARGTYPES.items():
         f = getattr(L, name)
-        if name not in ("plba_default_opts", "plba_last_error", "plba_hlm_default_params", "plba_pgo_default_params",
-                        "plba_lcpose_default_params", "plba_stereo_default_params", "plba_kfassoc_default_params",
-                        "plba_track_default_params", "plba_mapassoc_default_params", "plba_frames_default_params"):
-            f.restype = C.c_int
+        f.argtypes = argtypes
+        void = name == "plba_default_opts" or name.endswith("_default_params")
+        f.restype = None if void else C.c_char_p if name == "plba_last_error" else C.c_int
     _lib = L
     return L
 
@@ -323,41 +291,49 @@ class Solver:
                     "plba_pgo_optimize")
         return rb.as_dict()
 
+    def _pose_batch(self, name, defaults, bv, params, params_cls, out_cls, to_dict) -> list:
+        """The calls that give one ``out_cls`` per problem and an inlier flag per point and line row."""
+        if params is None:
+            params = params_cls()
+            getattr(self.L, defaults)(C.byref(params))
+        n = bv.struct.n
+        out = (out_cls * max(n, 1))()
+        pin = np.zeros(max(int(bv.pt_off[-1]), 1), np.uint8)
+        lin = np.zeros(max(int(bv.ln_off[-1]), 1), np.uint8)
+        self._check(getattr(self.L, name)(self.ctx, C.byref(bv.struct), C.byref(params), out, _p(pin, C.c_uint8),
+                                          _p(lin, C.c_uint8)), name)
+        return [to_dict(out[i], pin[bv.pt_off[i]:bv.pt_off[i + 1]], lin[bv.ln_off[i]:bv.ln_off[i + 1]]) for i in range(n)]
+
+    def _match(self, name, bv) -> list:
+        """The calls that give matches_12 per query row and a count per problem."""
+        n = bv.struct.n
+        m12 = np.full(max(int(bv.off1[-1]), 1), -1, np.int32)
+        cnt = np.zeros(max(n, 1), np.int32)
+        self._check(getattr(self.L, name)(self.ctx, C.byref(bv.struct), _p(m12, C.c_int32), _p(cnt, C.c_int32)), name)
+        return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+
+    def _associate(self, name, view_cls, params_fn, problems, params, desc_bytes):
+        """The calls over a view that holds its own outputs: (the view, the params struct) after the call."""
+        bv = problems if isinstance(problems, view_cls) else view_cls(problems, desc_bytes)
+        prm = params_fn(params)
+        self._check(getattr(self.L, name)(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)), name)
+        return bv, prm
+
     def lc_relative_pose(self, problems, params=None) -> list:
         """Loop-closure relative pose (plba_lc_relative_pose; computeRelativePoseRobustGN /
         computeRelativePoseGN, src/mapHandler.cpp:4677-5068 / :4413-4675) of a batch of candidate
         pairs (plba.lcpose.LcProblem), verified in one launch. One dict per candidate, with its
         inlier flags. Needs no uploaded window and leaves one intact."""
-        if params is None:
-            params = capi.PlbaLcposeParams()
-            self.L.plba_lcpose_default_params(C.byref(params))
-        bv = capi.LcposeBatchView(list(problems))
-        n = bv.struct.n
-        out = (capi.PlbaLcposeOut * max(n, 1))()
-        pin = np.zeros(max(int(bv.pt_off[-1]), 1), np.uint8)
-        lin = np.zeros(max(int(bv.ln_off[-1]), 1), np.uint8)
-        self._check(self.L.plba_lc_relative_pose(self.ctx, C.byref(bv.struct), C.byref(params), out,
-                                                 _p(pin, C.c_uint8), _p(lin, C.c_uint8)), "plba_lc_relative_pose")
-        return [capi.lcpose_out_to_dict(out[i], pin[bv.pt_off[i]:bv.pt_off[i + 1]], lin[bv.ln_off[i]:bv.ln_off[i + 1]])
-                for i in range(n)]
+        return self._pose_batch("plba_lc_relative_pose", "plba_lcpose_default_params", capi.LcposeBatchView(problems),
+                                params, capi.PlbaLcposeParams, capi.PlbaLcposeOut, capi.lcpose_out_to_dict)
 
     def track_pose(self, problems, params=None) -> list:
         """Frame-to-frame pose (plba_track_pose; StereoFrameHandler::optimizePose,
         src2/stereoFrameHandler.cpp:307-405) of a batch of frame pairs (plba.trackpose.TrackProblem),
         each solved by one workgroup of one launch. One dict per problem, with its inlier flags.
         Needs no uploaded window and leaves one intact."""
-        if params is None:
-            params = capi.PlbaTrackParams()
-            self.L.plba_track_default_params(C.byref(params))
-        bv = capi.TrackBatchView(list(problems))
-        n = bv.struct.n
-        out = (capi.PlbaTrackOut * max(n, 1))()
-        pin = np.zeros(max(int(bv.pt_off[-1]), 1), np.uint8)
-        lin = np.zeros(max(int(bv.ln_off[-1]), 1), np.uint8)
-        self._check(self.L.plba_track_pose(self.ctx, C.byref(bv.struct), C.byref(params), out,
-                                           _p(pin, C.c_uint8), _p(lin, C.c_uint8)), "plba_track_pose")
-        return [capi.track_out_to_dict(out[i], pin[bv.pt_off[i]:bv.pt_off[i + 1]], lin[bv.ln_off[i]:bv.ln_off[i + 1]])
-                for i in range(n)]
+        return self._pose_batch("plba_track_pose", "plba_track_default_params", capi.TrackBatchView(problems),
+                                params, capi.PlbaTrackParams, capi.PlbaTrackOut, capi.track_out_to_dict)
 
     def track_frames(self, pairs, params=None) -> list:
         """Frame-to-frame tracking (plba_track_frames; StereoFrameHandler::f2fTracking + optimizePose,
@@ -382,13 +358,7 @@ class Solver:
         pair in one launch. ``nnr``: one ratio or one per pair (taken as float32). One
         (matches_12, n_matches) per pair: the desc2 row of each desc1 row or -1, and their count.
         Needs no uploaded window and leaves one intact."""
-        bv = capi.MatchBatchView(pairs, nnr, best_lr, desc_bytes)
-        n = bv.struct.n
-        m12 = np.full(max(int(bv.off1[-1]), 1), -1, np.int32)
-        cnt = np.zeros(max(n, 1), np.int32)
-        self._check(self.L.plba_desc_match(self.ctx, C.byref(bv.struct), _p(m12, C.c_int32), _p(cnt, C.c_int32)),
-                    "plba_desc_match")
-        return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+        return self._match("plba_desc_match", capi.MatchBatchView(pairs, nnr, best_lr, desc_bytes))
 
     def grid_match(self, problems, cols: int = 64, rows: int = 48, best_lr: bool = True, desc_bytes=None) -> list:
         """Grid-guided descriptor matching (plba_grid_match; both StVO::matchGrid overloads,
@@ -396,13 +366,7 @@ class Solver:
         problems mixed) over a cols x rows grid, in one call. One (matches_12, n_matches) per problem:
         the train row of each query row or -1, and their count. Needs no uploaded window and leaves
         one intact."""
-        bv = capi.GridMatchBatchView(problems, cols, rows, best_lr, desc_bytes)
-        n = bv.struct.n
-        m12 = np.full(max(int(bv.off1[-1]), 1), -1, np.int32)
-        cnt = np.zeros(max(n, 1), np.int32)
-        self._check(self.L.plba_grid_match(self.ctx, C.byref(bv.struct), _p(m12, C.c_int32), _p(cnt, C.c_int32)),
-                    "plba_grid_match")
-        return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
+        return self._match("plba_grid_match", capi.GridMatchBatchView(problems, cols, rows, best_lr, desc_bytes))
 
     def stereo_associate(self, frames, params, desc_bytes=None) -> list:
         """Stereo association (plba_stereo_associate; StereoFrame::matchStereoPoints / matchStereoLines,
@@ -411,10 +375,8 @@ class Solver:
         capi.PlbaStereoParams). One dict per frame: n_pt, n_ls and the survivors' rows in increasing left
         index (pt_src, pt_pl, pt_disp, pt_P, pdesc; ls_src, ls_spl, ls_epl, ls_sdisp, ls_edisp, ls_sP, ls_eP,
         ls_le, ls_NDc with pluker, ldesc). Needs no uploaded window and leaves one intact."""
-        bv = frames if isinstance(frames, capi.StereoBatchView) else capi.StereoBatchView(frames, desc_bytes)
-        prm = capi.stereo_params(params)
-        self._check(self.L.plba_stereo_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
-                    "plba_stereo_associate")
+        bv, prm = self._associate("plba_stereo_associate", capi.StereoBatchView, capi.stereo_params, frames, params,
+                                  desc_bytes)
         return bv.results(bool(prm.pluker))
 
     def kf_associate(self, pairs, params, desc_bytes=None) -> list:
@@ -424,11 +386,8 @@ class Solver:
         height, fx, fy, cx, cy (or a capi.PlbaKfassocParams). One dict per pair, indexed by previous row:
         n_grid, n_matches, fallback as (points, lines); pt_m12, pt_rec [.][9]; ls_m12, ls_rec [.][8],
         ls_rejected. Needs no uploaded window and leaves one intact."""
-        bv = pairs if isinstance(pairs, capi.KfassocBatchView) else capi.KfassocBatchView(pairs, desc_bytes)
-        prm = capi.kfassoc_params(params)
-        self._check(self.L.plba_kf_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
-                    "plba_kf_associate")
-        return bv.results()
+        return self._associate("plba_kf_associate", capi.KfassocBatchView, capi.kfassoc_params, pairs, params,
+                               desc_bytes)[0].results()
 
     def map_associate(self, problems, params, desc_bytes=None) -> list:
         """Map-to-keyframe association (plba_map_associate; MapHandler::matchMap2KFPoints / Lines,
@@ -438,11 +397,8 @@ class Solver:
         row: n_visible, n_grid, n_matches, fallback, n_accepted as (points, lines); pt_visible, pt_m12,
         pt_accepted, pt_rec [.][6]; ls_visible, ls_m12, ls_accepted, ls_rec [.][9]. Needs no uploaded window
         and leaves one intact."""
-        bv = problems if isinstance(problems, capi.MapassocBatchView) else capi.MapassocBatchView(problems, desc_bytes)
-        prm = capi.mapassoc_params(params)
-        self._check(self.L.plba_map_associate(self.ctx, C.byref(bv.struct), C.byref(prm), C.byref(bv.out)),
-                    "plba_map_associate")
-        return bv.results()
+        return self._associate("plba_map_associate", capi.MapassocBatchView, capi.mapassoc_params, problems, params,
+                               desc_bytes)[0].results()
 
     def desc_medoid(self, list_ptr, desc, desc_bytes=None) -> np.ndarray:
         """Median descriptor (plba_desc_medoid; the descriptor half of updateAverageDescDir,
