@@ -14,21 +14,16 @@
 namespace plslam {
 
 int MapHandler::bowCall(BowCall &c) {
-    if (bow_fn_) {
-        const int rc = bow_fn_(bow_user_, &c);
-        if (rc) setError("place-recognition hook returned %d (op %d, slot %d)", rc, c.op, c.slot);
-        return rc;
-    }
-    int rc = ensureCtx();
-    if (rc) return rc;
-    switch (c.op) {
-    case BOW_SET_VOCAB: rc = plba_bow_set_vocab(ctx_, c.slot, c.vocab); break;
-    case BOW_INSERT: rc = plba_bow_insert(ctx_, c.slot, c.kf_id, c.desc, c.n_desc, c.scores, c.ids, c.cap, &c.n); break;
-    case BOW_REMOVE: rc = plba_bow_remove(ctx_, c.slot, c.kf_id); break;
-    case BOW_GET: rc = plba_bow_get(ctx_, c.slot, c.kf_id, c.word_ids, c.values, c.cap, &c.n); break;
-    default: rc = PLBA_E_INVALID;
-    }
-    if (rc) setError("plba: %s", plba_last_error(ctx_));
+    const int rc = backend(bow_, "place-recognition", [&](plba_ctx *ctx) -> int {
+        switch (c.op) {
+        case BOW_SET_VOCAB: return plba_bow_set_vocab(ctx, c.slot, c.vocab);
+        case BOW_INSERT: return plba_bow_insert(ctx, c.slot, c.kf_id, c.desc, c.n_desc, c.scores, c.ids, c.cap, &c.n);
+        case BOW_REMOVE: return plba_bow_remove(ctx, c.slot, c.kf_id);
+        case BOW_GET: return plba_bow_get(ctx, c.slot, c.kf_id, c.word_ids, c.values, c.cap, &c.n);
+        default: return PLBA_E_INVALID;
+        }
+    }, &c);
+    if (rc && bow_.fn) setError("%s (op %d, slot %d)", std::string(err_).c_str(), c.op, c.slot);
     return rc;
 }
 

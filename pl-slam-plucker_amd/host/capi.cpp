@@ -28,6 +28,13 @@ void place(std::vector<T *> &v, int idx, T *p) {
     delete v[idx];
     v[idx] = p;
 }
+// every plslam_set_*_fn / plslam_set_*_solver: the hook (or nullptr) to the MapHandler's setter
+template <class Fn>
+int set_hook(plslam_map *m, void (MapHandler::*set)(Fn, void *), Fn fn, void *user) {
+    if (!m) return PLBA_E_INVALID;
+    (m->mh.*set)(fn, user);
+    return PLBA_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -45,11 +52,7 @@ int plslam_map_destroy(plslam_map *m) {
 
 const char *plslam_map_last_error(plslam_map *m) { return m ? m->mh.lastError().c_str() : "null map"; }
 
-int plslam_set_solver(plslam_map *m, plslam_solve_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setSolver(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_solver(plslam_map *m, plslam_solve_fn fn, void *user) { return set_hook(m, &MapHandler::setSolver, fn, user); }
 
 int plslam_add_keyframe(plslam_map *m, int32_t kf_idx, const double T_kf_w[16], int32_t n_pt_feat,
                         const int32_t *pt_idx, int32_t n_ls_feat, const int32_t *ls_idx) {
@@ -223,11 +226,7 @@ int plslam_get_keyframe_x(plslam_map *m, int32_t kf_idx, double x[6]) {
     return PLBA_OK;
 }
 
-int plslam_set_hlm_solver(plslam_map *m, plslam_hlm_solve_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setHlmSolver(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_hlm_solver(plslam_map *m, plslam_hlm_solve_fn fn, void *user) { return set_hook(m, &MapHandler::setHlmSolver, fn, user); }
 
 static int hand_rolled_local_ba(plslam_map *m, plslam_hlm_stats *stats, bool endpoints);
 
@@ -292,11 +291,7 @@ int plslam_set_pgo_params(plslam_map *m, int32_t min_lm_ess_graph, int32_t max_i
     return PLBA_OK;
 }
 
-int plslam_set_pgo_solver(plslam_map *m, plslam_pgo_solve_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setPgoSolver(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_pgo_solver(plslam_map *m, plslam_pgo_solve_fn fn, void *user) { return set_hook(m, &MapHandler::setPgoSolver, fn, user); }
 
 namespace {
 void export_pgo_stats(const PgoStats &st, plslam_pgo_stats *stats) {
@@ -350,22 +345,14 @@ int plslam_fuse_landmarks(plslam_map *m, plslam_fuse_stats *stats) {
     return PLBA_OK;
 }
 
-int plslam_set_medoid_fn(plslam_map *m, plslam_medoid_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setMedoidFn(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_medoid_fn(plslam_map *m, plslam_medoid_fn fn, void *user) { return set_hook(m, &MapHandler::setMedoidFn, fn, user); }
 
 int plslam_desc_medoid_cpu(void *user, const plba_medoid_batch *b, int32_t *medoid) {
     (void)user;
     return descMedoidCpu(b, medoid);
 }
 
-int plslam_set_lcpose_solver(plslam_map *m, plslam_lcpose_solve_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setLcposeSolver(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_lcpose_solver(plslam_map *m, plslam_lcpose_solve_fn fn, void *user) { return set_hook(m, &MapHandler::setLcposeSolver, fn, user); }
 
 int plslam_set_lcpose_params(plslam_map *m, const plba_lcpose_params *p) {
     if (!m) return PLBA_E_INVALID;
@@ -429,11 +416,7 @@ int plslam_set_keyframe_features(plslam_map *m, int32_t kf_idx, int32_t desc_byt
     return PLBA_OK;
 }
 
-int plslam_set_match_fn(plslam_map *m, plslam_match_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setMatchFn(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_match_fn(plslam_map *m, plslam_match_fn fn, void *user) { return set_hook(m, &MapHandler::setMatchFn, fn, user); }
 
 namespace {
 MatchParams match_params(const plslam_match_params *mp) {
@@ -468,11 +451,7 @@ int plslam_verify_loop_candidates(plslam_map *m, int32_t kf_curr_idx, int32_t n,
 // ---- place recognition (bow.cpp)
 static_assert(sizeof(plslam_bow_call) == sizeof(BowCall), "plslam_bow_call and BowCall share one layout");
 
-int plslam_set_bow_fn(plslam_map *m, plslam_bow_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setBowFn(reinterpret_cast<BowFn>(fn), user);
-    return PLBA_OK;
-}
+int plslam_set_bow_fn(plslam_map *m, plslam_bow_fn fn, void *user) { return set_hook(m, &MapHandler::setBowFn, reinterpret_cast<BowFn>(fn), user); }
 
 void *plslam_bow_cpu_new(void) { return bowCpuNew(); }
 void plslam_bow_cpu_free(void *db) { bowCpuFree(static_cast<BowCpuDb *>(db)); }
@@ -580,11 +559,7 @@ int plslam_set_camera(plslam_map *m, double fx, double fy, double cx, double cy,
     return PLBA_OK;
 }
 
-int plslam_set_grid_match_fn(plslam_map *m, plslam_grid_match_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setGridMatchFn(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_grid_match_fn(plslam_map *m, plslam_grid_match_fn fn, void *user) { return set_hook(m, &MapHandler::setGridMatchFn, fn, user); }
 
 void plslam_mapmatch_default_params(plslam_mapmatch_params *p) {
     if (!p) return;
@@ -680,11 +655,7 @@ int plslam_local_mapping_step_kf_assoc(plslam_map *m, int32_t kf_idx, const plba
     return PLBA_OK;
 }
 
-int plslam_set_mapassoc_fn(plslam_map *m, plslam_mapassoc_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setMapAssocFn(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_mapassoc_fn(plslam_map *m, plslam_mapassoc_fn fn, void *user) { return set_hook(m, &MapHandler::setMapAssocFn, fn, user); }
 
 int plslam_map_assoc_cpu(void *user, const plba_mapassoc_batch *b, const plba_mapassoc_params *p, const plba_mapassoc_out *out) {
     (void)user;
@@ -710,11 +681,7 @@ int plslam_set_keyframe_stereo(plslam_map *m, int32_t kf_idx, const plslam_stere
     return PLBA_OK;
 }
 
-int plslam_set_stereo_fn(plslam_map *m, plslam_stereo_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setStereoFn(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_stereo_fn(plslam_map *m, plslam_stereo_fn fn, void *user) { return set_hook(m, &MapHandler::setStereoFn, fn, user); }
 
 int plslam_stereo_cpu(void *user, const plba_stereo_batch *b, const plba_stereo_params *p, const plba_stereo_out *out) {
     (void)user;
@@ -793,11 +760,7 @@ int plslam_look_for_common_matches(plslam_map *m, int32_t kf_prev_idx, int32_t k
     return PLBA_OK;
 }
 
-int plslam_set_kfassoc_fn(plslam_map *m, plslam_kfassoc_fn fn, void *user) {
-    if (!m) return PLBA_E_INVALID;
-    m->mh.setKfAssocFn(fn, user);
-    return PLBA_OK;
-}
+int plslam_set_kfassoc_fn(plslam_map *m, plslam_kfassoc_fn fn, void *user) { return set_hook(m, &MapHandler::setKfAssocFn, fn, user); }
 
 int plslam_kf_assoc_cpu(void *user, const plba_kfassoc_batch *b, const plba_kfassoc_params *p, const plba_kfassoc_out *out) {
     (void)user;

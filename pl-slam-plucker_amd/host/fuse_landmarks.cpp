@@ -203,7 +203,7 @@ int MapHandler::fuseLandmarks(FuseStats *stats) {
                     return PLBA_E_INVALID;
                 }
         }
-        if (!medoid_fn_)
+        if (!medoid_.fn)
             for (const auto &e : len)
                 if (e.second > PLBA_MEDOID_MAX_N) {
                     setError("fuseLandmarks: %s landmark %d would have %ld descriptors, more than %d", what, e.first, e.second,
@@ -448,17 +448,7 @@ int MapHandler::fuseLandmarks(FuseStats *stats) {
         b.list_ptr = list_ptr.data();
         b.desc = desc.data();
         const auto tm = clk::now();
-        int rc;
-        if (medoid_fn_) {
-            rc = medoid_fn_(medoid_user_, &b, medoid.data());
-            if (rc) setError("medoid hook returned %d", rc);
-        } else {
-            rc = ensureCtx();
-            if (!rc) {
-                rc = plba_desc_medoid(ctx_, &b, medoid.data());
-                if (rc) setError("plba: %s", plba_last_error(ctx_));
-            }
-        }
+        int rc = backend(medoid_, "medoid", [&](plba_ctx *ctx) { return plba_desc_medoid(ctx, &b, medoid.data()); }, &b, medoid.data());
         st.medoid_ms = std::chrono::duration<double, std::milli>(clk::now() - tm).count();
         for (size_t k = 0; !rc && k < live.size(); ++k)
             if (medoid[k] < 0 || medoid[k] >= list_ptr[k + 1] - list_ptr[k]) {

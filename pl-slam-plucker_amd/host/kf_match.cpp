@@ -235,17 +235,8 @@ int MapHandler::matchKfToKf(int kf_prev_idx, int kf_curr_idx, const Mat4 *DT_in,
     std::vector<uint8_t> rej((size_t)nl1 + 1, 0);
     plba_kfassoc_out o{n_grid, n_matches, fallback, pt_m12.data(), ls_m12.data(), pt_rec.data(), ls_rec.data(), rej.data()};
     const auto t0 = std::chrono::steady_clock::now();
-    int rc;
-    if (kfassoc_fn_) {
-        rc = kfassoc_fn_(kfassoc_user_, &b, &p, &o);
-        if (rc) setError("keyframe association hook returned %d", rc);
-    } else {
-        rc = ensureCtx();
-        if (!rc) {
-            rc = plba_kf_associate(ctx_, &b, &p, &o);
-            if (rc) setError("plba: %s", plba_last_error(ctx_));
-        }
-    }
+    const int rc = backend(kfassoc_, "keyframe association", [&](plba_ctx *ctx) { return plba_kf_associate(ctx, &b, &p, &o); },
+                           &b, &p, &o);
     if (rc) return rc;
     st.match_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (int i1 = 0; i1 < np1 + nl1; ++i1) {  // what a hook returns is checked before the map changes

@@ -281,15 +281,8 @@ int MapHandler::loopClosurePGO(bool ess, PgoStats *stats, bool fuse, FuseStats *
     plba_pgo_result r{};
     r.v_T = v_out.data();
     const auto t0 = clk::now();
-    int rc;
-    if (pgo_fn_) {
-        rc = pgo_fn_(pgo_user_, &g, &p, &r);
-        if (rc) setError("pose-graph solver hook returned %d", rc);
-    } else {
-        rc = ensureCtx();
-        if (!rc) rc = plba_pgo_optimize(ctx_, &g, &p, &r);
-        if (rc) setError("plba: %s", plba_last_error(ctx_));
-    }
+    const int rc = backend(pgo_, "pose-graph solver", [&](plba_ctx *ctx) { return plba_pgo_optimize(ctx, &g, &p, &r); },
+                           &g, &p, &r);
     if (rc) return rc;
     st.solve_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     st.iterations = r.iterations;
@@ -443,18 +436,9 @@ bool MapHandler::inlierRatioGate(const LcCandidate &c, double lc_inlier_ratio, i
 }
 
 int MapHandler::lcRelativePose(const plba_lcpose_batch &b, plba_lcpose_out *out, uint8_t *pin, uint8_t *lin) {
-    int rc;
-    if (lcpose_fn_) {
-        rc = lcpose_fn_(lcpose_user_, &b, &lcpose_params, out, pin, lin);
-        if (rc) setError("relative-pose solver hook returned %d", rc);
-    } else {
-        rc = ensureCtx();
-        if (!rc) {
-            rc = plba_lc_relative_pose(ctx_, &b, &lcpose_params, out, pin, lin);
-            if (rc) setError("plba: %s", plba_last_error(ctx_));
-        }
-    }
-    return rc;
+    return backend(lcpose_, "relative-pose solver",
+                   [&](plba_ctx *ctx) { return plba_lc_relative_pose(ctx, &b, &lcpose_params, out, pin, lin); },
+                   &b, &lcpose_params, out, pin, lin);
 }
 
 // What isLoopClosure holds after its matching (:4327-4380) for one pair of keyframes.
@@ -534,17 +518,8 @@ int MapHandler::buildLoopCandidates(int kf1_idx, int n, const int32_t *kf_prev_i
     b.desc1 = d1.data(); b.desc2 = d2.data();
     b.nnr = nnr.data();
     b.best_lr = mp.best_lr ? 1 : 0;
-    int rc;
-    if (match_fn_) {
-        rc = match_fn_(match_user_, &b, m12.data(), cnt.data());
-        if (rc) setError("matcher hook returned %d", rc);
-    } else {
-        rc = ensureCtx();
-        if (!rc) {
-            rc = plba_desc_match(ctx_, &b, m12.data(), cnt.data());
-            if (rc) setError("plba: %s", plba_last_error(ctx_));
-        }
-    }
+    const int rc = backend(match_, "matcher", [&](plba_ctx *ctx) { return plba_desc_match(ctx, &b, m12.data(), cnt.data()); },
+                           &b, m12.data(), cnt.data());
     if (rc) return rc;
     for (int k = 0; k < n; ++k) {
         const StereoFrame &f0 = *frame(kf_prev_idx[k]);

@@ -277,17 +277,8 @@ int MapHandler::matchMapToKfAssoc(int kf_idx, const Mat4 *Twf_in, const plba_map
     plba_mapassoc_out o{n_visible, n_grid, n_matches, fallback, n_accepted, pt_vis.data(), pt_m12.data(), pt_acc.data(),
                         pt_rec.data(), ls_vis.data(), ls_m12.data(), ls_acc.data(), ls_rec.data()};
     const auto t0 = std::chrono::steady_clock::now();
-    int rc;
-    if (mapassoc_fn_) {
-        rc = mapassoc_fn_(mapassoc_user_, &b, &p, &o);
-        if (rc) setError("map association hook returned %d", rc);
-    } else {
-        rc = ensureCtx();
-        if (!rc) {
-            rc = plba_map_associate(ctx_, &b, &p, &o);
-            if (rc) setError("plba: %s", plba_last_error(ctx_));
-        }
-    }
+    const int rc = backend(mapassoc_, "map association", [&](plba_ctx *ctx) { return plba_map_associate(ctx, &b, &p, &o); },
+                           &b, &p, &o);
     if (rc) return rc;
     st.match_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (int i1 = 0; i1 < n1p + n1l; ++i1) {  // what a hook returns is checked before the map changes

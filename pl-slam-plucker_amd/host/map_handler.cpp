@@ -801,28 +801,12 @@ int MapHandler::ensureCtx() {
 }
 
 int MapHandler::solve(const plba_graph &g, plba_result &r) {
-    if (solve_fn_) {
-        const int rc = solve_fn_(solve_user_, &g, &r);
-        if (rc) setError("solver hook returned %d", rc);
-        return rc;
-    }
-    if (!ctx_) {
-        plba_opts o;
-        if (have_opts_) o = opts_;
-        else plba_default_opts(&o);
-        const int rc = plba_create(&ctx_, &o);
-        if (rc) {
-            setError("plba_create failed (%d): no usable MI355X device", rc);
-            ctx_ = nullptr;
-            return rc;
-        }
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = plba_upload(ctx_, &g);
-    last_upload_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (!rc) rc = plba_lba_plucker(ctx_, &r);
-    if (rc) setError("plba: %s", plba_last_error(ctx_));
-    return rc;
+    return backend(solve_, "solver", [&](plba_ctx *ctx) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = plba_upload(ctx, &g);
+        last_upload_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return rc ? rc : plba_lba_plucker(ctx, &r);
+    }, &g, &r);
 }
 
 void MapHandler::storePosition(int kind, int idx, const double *pos) {
@@ -951,7 +935,7 @@ int MapHandler::localBundleAdjustmentForPlukerWithG2O(LbaStats *stats) {
     rc = solve(g, r);  // A1c (:6119-6152) on the device
     if (rc) return rc;
     const auto t2 = clk::now();
-    st.upload_ms = solve_fn_ ? 0.0 : last_upload_ms_;
+    st.upload_ms = solve_.fn ? 0.0 : last_upload_ms_;
     st.dirty_landmarks = last_dirty_;
     st.iters[0] = r.iters[0]; st.iters[1] = r.iters[1];
     st.chi2[0] = r.chi2[0]; st.chi2[1] = r.chi2[1];
@@ -1183,16 +1167,10 @@ int MapHandler::handRolledLocalBa(HlmStats *stats, bool endpoints) {
         r.ln_line3d = l3d_out.data();
     }
     const auto t1 = clk::now();
-    int rc;
-    if (hlm_fn_) {
-        rc = hlm_fn_(hlm_user_, &g, &hs, &prm, &r);
-        if (rc) setError("hand-rolled LM solver hook returned %d", rc);
-    } else {
-        rc = ensureCtx();
-        if (!rc) rc = plba_upload(ctx_, &g);
-        if (!rc) rc = plba_hlm_lba(ctx_, &hs, &prm, &r);
-        if (rc) setError("plba: %s", plba_last_error(ctx_));
-    }
+    const int rc = backend(hlm_, "hand-rolled LM solver", [&](plba_ctx *ctx) {
+        const int up = plba_upload(ctx, &g);
+        return up ? up : plba_hlm_lba(ctx, &hs, &prm, &r);
+    }, &g, &hs, &prm, &r);
     if (rc) return rc;
     const auto t2 = clk::now();
     st.linearizations = r.linearizations; st.solves = r.solves; st.accepted = r.accepted;

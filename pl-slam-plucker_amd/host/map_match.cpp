@@ -325,17 +325,8 @@ int MapHandler::matchMapToKf(int kf_idx, const Mat4 *Twf_in, const MapMatchParam
         b.off1 = off1; b.off2 = off2; b.desc1 = desc1.data(); b.desc2 = desc2.data();
         b.cell1 = cell1.data(); b.cell1_end = cell1_end.data(); b.cell_off2 = cell_off2.data(); b.cells2 = cells2.data();
         b.dir2 = dir2.data(); b.kind = kind; b.ws = ws; b.nnr = nnr; b.line_sim_th = th;
-        int rc;
-        if (grid_fn_) {
-            rc = grid_fn_(grid_user_, &b, m12.data(), matches);
-            if (rc) setError("grid matcher hook returned %d", rc);
-        } else {
-            rc = ensureCtx();
-            if (!rc) {
-                rc = plba_grid_match(ctx_, &b, m12.data(), matches);
-                if (rc) setError("plba: %s", plba_last_error(ctx_));
-            }
-        }
+        const int rc = backend(grid_, "grid matcher", [&](plba_ctx *ctx) { return plba_grid_match(ctx, &b, m12.data(), matches); },
+                               &b, m12.data(), matches);
         if (rc) return rc;
     }
     st.grid_matches[0] = matches[0];
@@ -358,17 +349,8 @@ int MapHandler::matchMapToKf(int kf_idx, const Mat4 *Twf_in, const MapMatchParam
         plba_match_batch mb{2, db, o1, o2, d1.data(), d2.data(), nnr, p.best_lr ? 1 : 0, 0};
         std::vector<int32_t> fm((size_t)(a1 + b1) + 1, -1);
         int32_t cnt[2] = {0, 0};
-        int rc;
-        if (match_fn_) {
-            rc = match_fn_(match_user_, &mb, fm.data(), cnt);
-            if (rc) setError("matcher hook returned %d", rc);
-        } else {
-            rc = ensureCtx();
-            if (!rc) {
-                rc = plba_desc_match(ctx_, &mb, fm.data(), cnt);
-                if (rc) setError("plba: %s", plba_last_error(ctx_));
-            }
-        }
+        const int rc = backend(match_, "matcher", [&](plba_ctx *ctx) { return plba_desc_match(ctx, &mb, fm.data(), cnt); },
+                               &mb, fm.data(), cnt);
         if (rc) return rc;
         if (st.fallback[0]) std::copy(fm.begin(), fm.begin() + a1, m12.begin());
         if (st.fallback[1]) std::copy(fm.begin() + a1, fm.begin() + a1 + b1, m12.begin() + n1p);

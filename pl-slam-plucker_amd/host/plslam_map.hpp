@@ -313,6 +313,13 @@ struct CullStats {
     int points_removed = 0, lines_removed = 0;
 };
 
+// A caller's replacement for one device call (the CPU tests, the benchmarks' baselines); unset: the MI355X backend.
+template <class Fn>
+struct Hook {
+    Fn fn = nullptr;
+    void *user = nullptr;
+};
+
 // include/mapHandler.h:141-151 (the members the LBA uses)
 class MapHandler {
   public:
@@ -373,7 +380,7 @@ class MapHandler {
     // (plba_desc_medoid, or the hook). What the reference leaves undefined is listed in the file's header.
     // Anything invalid returns PLBA_E_INVALID before the map is touched.
     int fuseLandmarks(FuseStats *stats = nullptr);
-    void setMedoidFn(MedoidFn fn, void *user) { medoid_fn_ = fn; medoid_user_ = user; }
+    void setMedoidFn(MedoidFn fn, void *user) { medoid_ = {fn, user}; }
     // include/mapHandler.h:186-200
     std::vector<Vec3i> lc_idxs, lc_idx_list;
     std::vector<Vec6> lc_poses, lc_pose_list;
@@ -394,12 +401,12 @@ class MapHandler {
     // n_matches [n][2]; each may be nullptr.
     int verifyLoopCandidates(int kf_curr_idx, int n, const int32_t *kf_prev_idx, const MatchParams &mp,
                              double lc_inlier_ratio, int32_t *accepted, double *pose_inc, int32_t *n_matches);
-    void setMatchFn(MatchFn fn, void *user) { match_fn_ = fn; match_user_ = user; }
+    void setMatchFn(MatchFn fn, void *user) { match_ = {fn, user}; }
     // bow.cpp. Place recognition: insertKFBowVectorP / L / PL (src/mapHandler.cpp:4118-4239) over the
     // database of plba_bow_* (or the hook), the float conf_matrix (include/mapHandler.h:153),
     // lookForLoopCandidates (:4241-4301) and loopClosure() whole (:4053-4116).
     std::vector<std::vector<float>> conf_matrix;
-    void setBowFn(BowFn fn, void *user) { bow_fn_ = fn; bow_user_ = user; }
+    void setBowFn(BowFn fn, void *user) { bow_ = {fn, user}; }
     int setVocabulary(int slot, const plba_bow_vocab *v);
     int removeKeyframe(int kf_idx);
     int insertKfBow(int kf_idx, bool has_points, bool has_lines);
@@ -416,7 +423,7 @@ class MapHandler {
     // matchMapToKf, then localMappingStep
     int localMappingStepKf(int kf_idx, const MapMatchParams &p, MapMatchStats *ms = nullptr, LbaStats *stats = nullptr,
                            CullStats *cs = nullptr);
-    void setGridMatchFn(GridMatchFn fn, void *user) { grid_fn_ = fn; grid_user_ = user; }
+    void setGridMatchFn(GridMatchFn fn, void *user) { grid_ = {fn, user}; }
     // map_assoc.cpp. The same association around ONE plba_map_associate call (or the hook): the candidates
     // (local, not yet seen by the keyframe) and the features with idx -1 are gathered, the call projects,
     // tests, matches and gates them, and the rows are walked in i1 order, points before lines, as
@@ -425,7 +432,7 @@ class MapHandler {
     // matchMapToKfAssoc, then localMappingStep
     int localMappingStepKfAssoc(int kf_idx, const plba_mapassoc_params &p, MapMatchStats *ms = nullptr, LbaStats *stats = nullptr,
                                 CullStats *cs = nullptr);
-    void setMapAssocFn(MapAssocFn fn, void *user) { mapassoc_fn_ = fn; mapassoc_user_ = user; }
+    void setMapAssocFn(MapAssocFn fn, void *user) { mapassoc_ = {fn, user}; }
     // stereo.cpp. StereoFrame::matchStereoPoints + matchStereoLines (src2/stereoFrame.cpp:121-174, :310-435)
     // for keyframe kf_idx from the detector output of its two images: one plba_stereo_associate call (or the
     // hook), stored as plslam_set_keyframe_features + plslam_set_keyframe_line_endpoints would store it.
@@ -434,7 +441,7 @@ class MapHandler {
     // Anything invalid returns before the keyframe is touched.
     int setKeyframeStereo(int kf_idx, const StereoInput &in, const plba_stereo_params &prm, int32_t *pt_src, int32_t *ls_src,
                           StereoStats *stats = nullptr);
-    void setStereoFn(StereoFn fn, void *user) { stereo_fn_ = fn; stereo_user_ = user; }
+    void setStereoFn(StereoFn fn, void *user) { stereo_ = {fn, user}; }
     // kf_match.cpp. matchKF2KFPoints + matchKF2KFLines (src/mapHandler.cpp:237-366, :368-590, the
     // USE_LINE_PLUKER branch) between two keyframes with features: one plba_kf_associate call (or the hook),
     // then the rows in order as :283-363 and :434-589 walk them: a new landmark takes the index
@@ -450,17 +457,17 @@ class MapHandler {
     // matchKfToKf, then matchMapToKf of the current keyframe: lookForCommonMatches (:923-990) without the refinement
     int lookForCommonMatches(int kf_prev_idx, int kf_curr_idx, const plba_kfassoc_params &kp, const MapMatchParams &mp,
                              KfMatchStats *ks = nullptr, MapMatchStats *ms = nullptr);
-    void setKfAssocFn(KfAssocFn fn, void *user) { kfassoc_fn_ = fn; kfassoc_user_ = user; }
+    void setKfAssocFn(KfAssocFn fn, void *user) { kfassoc_ = {fn, user}; }
     void setCamera(double fx, double fy, double cx, double cy, int width, int height) {
         fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy; width_ = width; height_ = height;
     }
     std::vector<std::vector<Vec4i>> lc_pt_idxs, lc_ls_idxs;  // inlier-filtered rows, one list per loop (:4078-4079)
     plba_lcpose_params lcpose_params{1e-7, 1.0, 0.01, 0.3, 1.5, 35.0, 5, 10, PLBA_LCPOSE_ROBUST_GN, 0};
-    void setLcposeSolver(LcposeSolveFn fn, void *user) { lcpose_fn_ = fn; lcpose_user_ = user; }
+    void setLcposeSolver(LcposeSolveFn fn, void *user) { lcpose_ = {fn, user}; }
 
-    void setSolver(SolveFn fn, void *user) { solve_fn_ = fn; solve_user_ = user; }
-    void setPgoSolver(PgoSolveFn fn, void *user) { pgo_fn_ = fn; pgo_user_ = user; }
-    void setHlmSolver(HlmSolveFn fn, void *user) { hlm_fn_ = fn; hlm_user_ = user; }
+    void setSolver(SolveFn fn, void *user) { solve_ = {fn, user}; }
+    void setPgoSolver(PgoSolveFn fn, void *user) { pgo_ = {fn, user}; }
+    void setHlmSolver(HlmSolveFn fn, void *user) { hlm_ = {fn, user}; }
     const std::string &lastError() const { return err_; }
     void setError(const char *fmt, ...);
 
@@ -502,26 +509,32 @@ class MapHandler {
     plba_opts opts_{};
     bool have_opts_ = false;
     plba_ctx *ctx_ = nullptr;  // reused across LBA calls
-    SolveFn solve_fn_ = nullptr;
-    void *solve_user_ = nullptr;
-    HlmSolveFn hlm_fn_ = nullptr;
-    void *hlm_user_ = nullptr;
-    PgoSolveFn pgo_fn_ = nullptr;
-    void *pgo_user_ = nullptr;
-    LcposeSolveFn lcpose_fn_ = nullptr;
-    void *lcpose_user_ = nullptr;
-    MatchFn match_fn_ = nullptr;
-    void *match_user_ = nullptr;
-    GridMatchFn grid_fn_ = nullptr;
-    void *grid_user_ = nullptr;
-    StereoFn stereo_fn_ = nullptr;
-    void *stereo_user_ = nullptr;
-    KfAssocFn kfassoc_fn_ = nullptr;
-    void *kfassoc_user_ = nullptr;
-    MapAssocFn mapassoc_fn_ = nullptr;
-    void *mapassoc_user_ = nullptr;
-    BowFn bow_fn_ = nullptr;
-    void *bow_user_ = nullptr;
+    Hook<SolveFn> solve_;
+    Hook<HlmSolveFn> hlm_;
+    Hook<PgoSolveFn> pgo_;
+    Hook<LcposeSolveFn> lcpose_;
+    Hook<MatchFn> match_;
+    Hook<GridMatchFn> grid_;
+    Hook<StereoFn> stereo_;
+    Hook<KfAssocFn> kfassoc_;
+    Hook<MapAssocFn> mapassoc_;
+    Hook<MedoidFn> medoid_;
+    Hook<BowFn> bow_;
+    // One backend call: the hook with args when it is set, otherwise device(ctx_) on the map's context.
+    // A failure's message is "<what> hook returned <rc>", ensureCtx's own, or plba's last error.
+    template <class Fn, class Device, class... Args>
+    int backend(const Hook<Fn> &h, const char *what, Device &&device, Args &&...args) {
+        if (h.fn) {
+            const int rc = h.fn(h.user, std::forward<Args>(args)...);
+            if (rc) setError("%s hook returned %d", what, rc);
+            return rc;
+        }
+        int rc = ensureCtx();
+        if (rc) return rc;
+        rc = device(ctx_);
+        if (rc) setError("plba: %s", plba_last_error(ctx_));
+        return rc;
+    }
     int bowCall(BowCall &c);                 // the hook, or plba_bow_* on the map's context
     bool bow_vocab_[2] = {false, false};
     std::vector<uint8_t> bow_in_db_[2];      // [kf_idx] the keyframe has a live vector in the slot
@@ -535,8 +548,6 @@ class MapHandler {
                                 double &ratio_pt, double &ratio_ls);
     int lcRelativePose(const plba_lcpose_batch &b, plba_lcpose_out *out, uint8_t *pin, uint8_t *lin);
     int loopClosurePGO(bool ess, PgoStats *stats, bool fuse = false, FuseStats *fs = nullptr);
-    MedoidFn medoid_fn_ = nullptr;
-    void *medoid_user_ = nullptr;
     std::string err_;
     // per-call scratch reused across LBA calls (capacity kept; see Window::clear)
     Window win_;

@@ -152,17 +152,7 @@ int MapHandler::setKeyframeStereo(int kf_idx, const StereoInput &in, const plba_
     o.ls_src = lsrc.data(); o.ls_spl = spl.data(); o.ls_epl = epl.data(); o.ls_sdisp = sdisp.data(); o.ls_edisp = edisp.data();
     o.ls_sP = sP.data(); o.ls_eP = eP.data(); o.ls_le = le.data(); o.ls_NDc = NDc.data(); o.ldesc = ldesc.data();
     const auto t0 = std::chrono::steady_clock::now();
-    int rc;
-    if (stereo_fn_) {
-        rc = stereo_fn_(stereo_user_, &b, &prm, &o);
-        if (rc) setError("stereo hook returned %d", rc);
-    } else {
-        rc = ensureCtx();
-        if (!rc) {
-            rc = plba_stereo_associate(ctx_, &b, &prm, &o);
-            if (rc) setError("plba: %s", plba_last_error(ctx_));
-        }
-    }
+    const int rc = backend(stereo_, "stereo", [&](plba_ctx *ctx) { return plba_stereo_associate(ctx, &b, &prm, &o); }, &b, &prm, &o);
     if (rc) return rc;
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (n_pt < 0 || n_pt > in.n_pt_l || n_ls < 0 || n_ls > in.n_ls_l) {

@@ -343,38 +343,6 @@ class PlslamLcStats(C.Structure):
         return d
 
 
-HOST_EXPORTED = [
-    "plslam_map_create", "plslam_map_destroy", "plslam_map_last_error", "plslam_set_solver", "plslam_add_keyframe",
-    "plslam_add_point", "plslam_point_add_observation", "plslam_add_line", "plslam_line_add_observation",
-    "plslam_set_local", "plslam_set_full_graph", "plslam_get_full_graph", "plslam_kf_idx_set", "plslam_kf_idx_get",
-    "plslam_local_ba_plucker_g2o", "plslam_get_keyframe", "plslam_get_point", "plslam_get_line",
-    "plslam_pluker_to_orth", "plslam_orth_to_pluker",
-    "plslam_set_inlier", "plslam_set_params", "plslam_set_max_kf_idx", "plslam_kf_lines_idx_set", "plslam_kf_lines_idx_get",
-    "plslam_form_local_map", "plslam_remove_bad_landmarks_pluker", "plslam_local_mapping_step", "plslam_exists",
-    "plslam_set_keyframe_x", "plslam_get_keyframe_x", "plslam_set_hlm_solver", "plslam_set_hlm_params",
-    "plslam_local_ba_plucker", "plslam_local_ba",
-    "plslam_set_loop_closure", "plslam_get_lc_idx_list", "plslam_set_pgo_params", "plslam_set_pgo_solver",
-    "plslam_loop_closure_optimization", "plslam_set_line_geometry", "plslam_get_line_geometry",
-    "plslam_set_incremental", "plslam_mark_landmark_changed", "plslam_check_incremental_gather",
-    "plslam_set_lcpose_solver", "plslam_set_lcpose_params", "plslam_loop_closure_step", "plslam_get_lc_state",
-    "plslam_get_lc_pose_list", "plslam_get_lc_feature_idxs",
-    "plslam_set_keyframe_features", "plslam_set_match_fn", "plslam_loop_closure_step_kf",
-    "plslam_verify_loop_candidates", "plslam_desc_match_cpu",
-    "plslam_line_cells", "plslam_grid_match_cpu",
-    "plslam_set_keyframe_stereo", "plslam_set_stereo_fn", "plslam_stereo_cpu", "plslam_kf_assoc_cpu",
-    "plslam_track_pose_cpu", "plslam_track_frames_cpu",
-    "plslam_match_kf_to_kf", "plslam_look_for_common_matches", "plslam_set_keyframe_line_pluker", "plslam_set_kfassoc_fn",
-    "plslam_set_keyframe_line_endpoints", "plslam_set_camera", "plslam_set_grid_match_fn",
-    "plslam_mapmatch_default_params", "plslam_match_map_to_kf", "plslam_local_mapping_step_kf",
-    "plslam_match_map_to_kf_assoc", "plslam_local_mapping_step_kf_assoc", "plslam_set_mapassoc_fn", "plslam_map_assoc_cpu",
-    "plslam_set_bow_fn", "plslam_bow_cpu", "plslam_set_vocabulary", "plslam_remove_keyframe", "plslam_insert_kf_bow",
-    "plslam_get_conf_matrix_row", "plslam_set_conf_matrix", "plslam_look_for_loop_candidates", "plslam_loop_closure_kf",
-    "plslam_bow_cpu_new", "plslam_bow_cpu_free", "plslam_lc_search_default_params",
-    "plslam_fuse_landmarks", "plslam_set_medoid_fn", "plslam_desc_medoid_cpu", "plslam_loop_closure_optimization_fuse",
-    "plslam_set_lc_feature_idxs",
-]
-
-
 # ---- place recognition (plslam_bow_call / plslam_set_bow_fn / plslam_lc_search_params)
 BOW_SET_VOCAB, BOW_INSERT, BOW_REMOVE, BOW_GET = 0, 1, 2, 3
 
@@ -463,6 +431,138 @@ class SlamParams:
     min_lm_cov_graph: int = 75
     min_kf_local_map: int = 3
 
+
+# every function load_host() binds, with its argtypes; the return type is an int but for HOST_RESTYPES
+_P, _vp, _i32, _f64 = C.POINTER, C.c_void_p, C.c_int32, C.c_double
+_dp, _ip, _bp, _fp, _u32p = _P(C.c_double), _P(C.c_int32), _P(C.c_uint8), _P(C.c_float), _P(C.c_uint32)
+
+
+def _batch3(batch, params, out):   # a *_cpu restatement: user, batch, params, out
+    return [_vp, _P(batch), _P(params), _P(out)]
+
+
+HOST_ARGTYPES = {
+    "plslam_map_create": [_P(_vp), _f64, _f64, _f64, _f64, _P(capi.PlbaOpts)],
+    "plslam_map_destroy": [_vp],
+    "plslam_map_last_error": [_vp],
+    "plslam_set_solver": [_vp, SOLVE_FN, _vp],
+    "plslam_add_keyframe": [_vp, _i32, _dp, _i32, _ip, _i32, _ip],
+    "plslam_add_point": [_vp, _i32, _dp, _bp, _i32, _i32, _dp, _dp, _f64],
+    "plslam_point_add_observation": [_vp, _i32, _bp, _i32, _dp, _dp, _f64],
+    "plslam_add_line": [_vp, _i32, _dp, _bp, _i32, _i32, _dp, _f64],
+    "plslam_line_add_observation": [_vp, _i32, _bp, _i32, _dp, _f64],
+    "plslam_set_local": [_vp, _i32, _i32, _i32],
+    "plslam_set_full_graph": [_vp, _i32, _u32p],
+    "plslam_get_full_graph": [_vp, _i32, _u32p],
+    "plslam_kf_idx_set": [_vp, _i32, _ip, _i32],
+    "plslam_kf_idx_get": [_vp, _i32, _ip, _i32, _ip],
+    "plslam_local_ba_plucker_g2o": [_vp, _P(PlslamLbaStats)],
+    "plslam_get_keyframe": [_vp, _i32, _dp, _ip, _ip, _i32, _ip, _i32],
+    "plslam_get_point": [_vp, _i32, _dp, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _i32, _bp, _dp],
+    "plslam_get_line": [_vp, _i32, _dp, _ip, _ip, _ip, _ip, _dp, _dp, _i32, _bp],
+    "plslam_pluker_to_orth": [_dp, _dp],
+    "plslam_orth_to_pluker": [_dp, _dp],
+    "plslam_set_inlier": [_vp, _i32, _i32, _i32],
+    "plslam_set_params": [_vp, _i32, _i32, _i32],
+    "plslam_set_max_kf_idx": [_vp, _i32],
+    "plslam_kf_lines_idx_set": [_vp, _i32, _ip, _i32],
+    "plslam_kf_lines_idx_get": [_vp, _i32, _ip, _i32, _ip],
+    "plslam_form_local_map": [_vp, _i32],
+    "plslam_remove_bad_landmarks_pluker": [_vp, _ip, _ip],
+    "plslam_local_mapping_step": [_vp, _i32, _P(PlslamLbaStats), _ip, _ip],
+    "plslam_exists": [_vp, _i32, _i32, _ip],
+    "plslam_set_keyframe_x": [_vp, _i32, _dp],
+    "plslam_get_keyframe_x": [_vp, _i32, _dp],
+    "plslam_set_hlm_solver": [_vp, HLM_SOLVE_FN, _vp],
+    "plslam_set_hlm_params": [_vp, _P(capi.PlbaHlmParams), _i32],
+    "plslam_local_ba_plucker": [_vp, _P(PlslamHlmStats)],
+    "plslam_local_ba": [_vp, _P(PlslamHlmStats)],
+    "plslam_set_loop_closure": [_vp, _i32, _ip, _i32, _ip, _i32, _dp],
+    "plslam_get_lc_idx_list": [_vp, _ip, _i32, _ip],
+    "plslam_set_pgo_params": [_vp, _i32, _i32],
+    "plslam_set_pgo_solver": [_vp, PGO_SOLVE_FN, _vp],
+    "plslam_loop_closure_optimization": [_vp, _i32, _P(PlslamPgoStats)],
+    "plslam_set_line_geometry": [_vp, _i32, _dp, _dp],
+    "plslam_get_line_geometry": [_vp, _i32, _dp, _dp],
+    "plslam_set_incremental": [_vp, _i32],
+    "plslam_mark_landmark_changed": [_vp, _i32, _i32],
+    "plslam_check_incremental_gather": [_vp, _ip],
+    "plslam_set_lcpose_solver": [_vp, LCPOSE_SOLVE_FN, _vp],
+    "plslam_set_lcpose_params": [_vp, _P(capi.PlbaLcposeParams)],
+    "plslam_loop_closure_step": [_vp, _P(PlslamLcCandidate), _f64, _P(PlslamLcStats)],
+    "plslam_get_lc_state": [_vp, _ip],
+    "plslam_get_lc_pose_list": [_vp, _dp, _i32, _ip],
+    "plslam_get_lc_feature_idxs": [_vp, _i32, _i32, _ip, _i32, _ip],
+    "plslam_set_lc_feature_idxs": [_vp, _i32, _i32, _ip, _i32],
+    "plslam_set_keyframe_features": [_vp, _i32, _i32, _bp, _dp, _dp, _bp, _dp, _dp, _dp],
+    "plslam_set_match_fn": [_vp, MATCH_FN, _vp],
+    "plslam_loop_closure_step_kf": [_vp, _i32, _i32, _P(PlslamMatchParams), _f64, _P(PlslamLcStats)],
+    "plslam_verify_loop_candidates": [_vp, _i32, _i32, _ip, _P(PlslamMatchParams), _f64, _ip, _dp, _ip],
+    "plslam_desc_match_cpu": [_vp, _P(capi.PlbaMatchBatch), _ip, _ip],
+    "plslam_line_cells": [_f64, _f64, _f64, _f64, _ip, _i32, _ip],
+    "plslam_grid_match_cpu": [_vp, _P(capi.PlbaGridMatchBatch), _ip, _ip],
+    "plslam_set_keyframe_stereo": [_vp, _i32, _P(PlslamStereoFrame), _P(capi.PlbaStereoParams), _ip, _ip,
+                                   _P(PlslamStereoStats)],
+    "plslam_set_stereo_fn": [_vp, STEREO_FN, _vp],
+    "plslam_stereo_cpu": _batch3(capi.PlbaStereoBatch, capi.PlbaStereoParams, capi.PlbaStereoOut),
+    "plslam_kf_assoc_cpu": _batch3(capi.PlbaKfassocBatch, capi.PlbaKfassocParams, capi.PlbaKfassocOut),
+    "plslam_track_pose_cpu": _batch3(capi.PlbaTrackBatch, capi.PlbaTrackParams, capi.PlbaTrackOut) + [_bp, _bp],
+    "plslam_track_frames_cpu": _batch3(capi.PlbaFramesBatch, capi.PlbaFramesParams, capi.PlbaFramesOut),
+    "plslam_match_kf_to_kf": [_vp, _i32, _i32, _dp, _P(capi.PlbaKfassocParams), _P(PlslamKfMatchStats)],
+    "plslam_look_for_common_matches": [_vp, _i32, _i32, _P(capi.PlbaKfassocParams), _P(PlslamMapMatchParams),
+                                       _P(PlslamKfMatchStats), _P(PlslamMapMatchStats)],
+    "plslam_set_keyframe_line_pluker": [_vp, _i32, _dp],
+    "plslam_set_kfassoc_fn": [_vp, KFASSOC_FN, _vp],
+    "plslam_set_keyframe_line_endpoints": [_vp, _i32, _dp, _dp],
+    "plslam_set_camera": [_vp, _f64, _f64, _f64, _f64, _i32, _i32],
+    "plslam_set_grid_match_fn": [_vp, GRID_MATCH_FN, _vp],
+    "plslam_mapmatch_default_params": [_P(PlslamMapMatchParams)],
+    "plslam_match_map_to_kf": [_vp, _i32, _dp, _P(PlslamMapMatchParams), _P(PlslamMapMatchStats)],
+    "plslam_local_mapping_step_kf": [_vp, _i32, _P(PlslamMapMatchParams), _P(PlslamMapMatchStats), _P(PlslamLbaStats),
+                                     _ip, _ip],
+    "plslam_match_map_to_kf_assoc": [_vp, _i32, _dp, _P(capi.PlbaMapassocParams), _P(PlslamMapMatchStats)],
+    "plslam_local_mapping_step_kf_assoc": [_vp, _i32, _P(capi.PlbaMapassocParams), _P(PlslamMapMatchStats),
+                                           _P(PlslamLbaStats), _ip, _ip],
+    "plslam_set_mapassoc_fn": [_vp, MAPASSOC_FN, _vp],
+    "plslam_map_assoc_cpu": _batch3(capi.PlbaMapassocBatch, capi.PlbaMapassocParams, capi.PlbaMapassocOut),
+    "plslam_set_bow_fn": [_vp, _vp, _vp],    # the hook as an address: plslam_bow_cpu itself can be passed
+    "plslam_bow_cpu_new": [],
+    "plslam_bow_cpu_free": [_vp],
+    "plslam_bow_cpu": [_vp, _P(PlslamBowCall)],
+    "plslam_set_vocabulary": [_vp, _i32, _P(capi.PlbaBowVocab)],
+    "plslam_remove_keyframe": [_vp, _i32],
+    "plslam_insert_kf_bow": [_vp, _i32, _i32, _i32],
+    "plslam_get_conf_matrix_row": [_vp, _i32, _fp, _i32, _ip],
+    "plslam_set_conf_matrix": [_vp, _i32, _fp],
+    "plslam_look_for_loop_candidates": [_vp, _i32, _P(PlslamLcSearchParams), _ip, _ip],
+    "plslam_loop_closure_kf": [_vp, _i32, _P(PlslamLcSearchParams), _P(PlslamMatchParams), _f64, _P(PlslamLcStats)],
+    "plslam_lc_search_default_params": [_P(PlslamLcSearchParams)],
+    "plslam_fuse_landmarks": [_vp, _P(PlslamFuseStats)],
+    "plslam_set_medoid_fn": [_vp, MEDOID_FN, _vp],
+    "plslam_desc_medoid_cpu": [_vp, _P(capi.PlbaMedoidBatch), _ip],
+    "plslam_loop_closure_optimization_fuse": [_vp, _i32, _P(PlslamPgoStats), _P(PlslamFuseStats)],
+}
+HOST_RESTYPES = {"plslam_map_last_error": C.c_char_p, "plslam_bow_cpu_new": _vp, "plslam_pluker_to_orth": None,
+                 "plslam_orth_to_pluker": None, "plslam_mapmatch_default_params": None, "plslam_bow_cpu_free": None,
+                 "plslam_lc_search_default_params": None}
+HOST_EXPORTED = list(HOST_ARGTYPES)
+
+# The hooks of a MapHandler: the setter, the hook's type, which of its arguments (after ``user``) the Python
+# callable gets as .contents, and the C function that "cpu" stands for where the library has one.
+HOOKS = {
+    "solver": ("plslam_set_solver", SOLVE_FN, (0, 1), None),
+    "hlm": ("plslam_set_hlm_solver", HLM_SOLVE_FN, (0, 1, 2, 3), None),
+    "pgo": ("plslam_set_pgo_solver", PGO_SOLVE_FN, (0, 1, 2), None),
+    "lcpose": ("plslam_set_lcpose_solver", LCPOSE_SOLVE_FN, (0, 1), None),
+    "match": ("plslam_set_match_fn", MATCH_FN, (0,), None),
+    "medoid": ("plslam_set_medoid_fn", MEDOID_FN, (0,), "plslam_desc_medoid_cpu"),
+    "stereo": ("plslam_set_stereo_fn", STEREO_FN, (0, 1, 2), "plslam_stereo_cpu"),
+    "kfassoc": ("plslam_set_kfassoc_fn", KFASSOC_FN, (0, 1, 2), "plslam_kf_assoc_cpu"),
+    "grid": ("plslam_set_grid_match_fn", GRID_MATCH_FN, (0,), "plslam_grid_match_cpu"),
+    "mapassoc": ("plslam_set_mapassoc_fn", MAPASSOC_FN, (0, 1, 2), "plslam_map_assoc_cpu"),
+    "bow": ("plslam_set_bow_fn", BOW_FN, (0,), None),
+}
+
 _hl = None
 
 
@@ -474,130 +574,10 @@ def load_host(path: Optional[str] = None):
     if not os.path.exists(path):
         raise PlbaError(f"libplslam_host.so not found at {path}: run `make -C pl-slam-plucker_amd/host`")
     L = C.CDLL(path)
-    vp, dp, ip, bp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
-    u32p = C.POINTER(C.c_uint32)
-    L.plslam_map_create.argtypes = [C.POINTER(vp), C.c_double, C.c_double, C.c_double, C.c_double,
-                                    C.POINTER(capi.PlbaOpts)]
-    L.plslam_map_destroy.argtypes = [vp]
-    L.plslam_map_last_error.argtypes = [vp]
-    L.plslam_map_last_error.restype = C.c_char_p
-    L.plslam_set_solver.argtypes = [vp, SOLVE_FN, vp]
-    L.plslam_add_keyframe.argtypes = [vp, C.c_int32, dp, C.c_int32, ip, C.c_int32, ip]
-    L.plslam_add_point.argtypes = [vp, C.c_int32, dp, bp, C.c_int32, C.c_int32, dp, dp, C.c_double]
-    L.plslam_point_add_observation.argtypes = [vp, C.c_int32, bp, C.c_int32, dp, dp, C.c_double]
-    L.plslam_add_line.argtypes = [vp, C.c_int32, dp, bp, C.c_int32, C.c_int32, dp, C.c_double]
-    L.plslam_line_add_observation.argtypes = [vp, C.c_int32, bp, C.c_int32, dp, C.c_double]
-    L.plslam_set_local.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
-    L.plslam_set_full_graph.argtypes = [vp, C.c_int32, u32p]
-    L.plslam_get_full_graph.argtypes = [vp, C.c_int32, u32p]
-    L.plslam_kf_idx_set.argtypes = [vp, C.c_int32, ip, C.c_int32]
-    L.plslam_kf_idx_get.argtypes = [vp, C.c_int32, ip, C.c_int32, ip]
-    L.plslam_local_ba_plucker_g2o.argtypes = [vp, C.POINTER(PlslamLbaStats)]
-    L.plslam_get_keyframe.argtypes = [vp, C.c_int32, dp, ip, ip, C.c_int32, ip, C.c_int32]
-    L.plslam_get_point.argtypes = [vp, C.c_int32, dp, ip, ip, ip, ip, dp, dp, dp, C.c_int32, bp, dp]
-    L.plslam_get_line.argtypes = [vp, C.c_int32, dp, ip, ip, ip, ip, dp, dp, C.c_int32, bp]
-    L.plslam_pluker_to_orth.argtypes = [dp, dp]
-    L.plslam_pluker_to_orth.restype = None
-    L.plslam_orth_to_pluker.argtypes = [dp, dp]
-    L.plslam_orth_to_pluker.restype = None
-    L.plslam_set_inlier.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
-    L.plslam_set_params.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
-    L.plslam_set_max_kf_idx.argtypes = [vp, C.c_int32]
-    L.plslam_kf_lines_idx_set.argtypes = [vp, C.c_int32, ip, C.c_int32]
-    L.plslam_kf_lines_idx_get.argtypes = [vp, C.c_int32, ip, C.c_int32, ip]
-    L.plslam_form_local_map.argtypes = [vp, C.c_int32]
-    L.plslam_remove_bad_landmarks_pluker.argtypes = [vp, ip, ip]
-    L.plslam_local_mapping_step.argtypes = [vp, C.c_int32, C.POINTER(PlslamLbaStats), ip, ip]
-    L.plslam_exists.argtypes = [vp, C.c_int32, C.c_int32, ip]
-    L.plslam_set_keyframe_x.argtypes = [vp, C.c_int32, dp]
-    L.plslam_get_keyframe_x.argtypes = [vp, C.c_int32, dp]
-    L.plslam_set_hlm_solver.argtypes = [vp, HLM_SOLVE_FN, vp]
-    L.plslam_set_hlm_params.argtypes = [vp, C.POINTER(capi.PlbaHlmParams), C.c_int32]
-    L.plslam_local_ba_plucker.argtypes = [vp, C.POINTER(PlslamHlmStats)]
-    L.plslam_local_ba.argtypes = [vp, C.POINTER(PlslamHlmStats)]
-    L.plslam_set_loop_closure.argtypes = [vp, C.c_int32, ip, C.c_int32, ip, C.c_int32, dp]
-    L.plslam_get_lc_idx_list.argtypes = [vp, ip, C.c_int32, ip]
-    L.plslam_set_pgo_params.argtypes = [vp, C.c_int32, C.c_int32]
-    L.plslam_set_pgo_solver.argtypes = [vp, PGO_SOLVE_FN, vp]
-    L.plslam_loop_closure_optimization.argtypes = [vp, C.c_int32, C.POINTER(PlslamPgoStats)]
-    L.plslam_set_line_geometry.argtypes = [vp, C.c_int32, dp, dp]
-    L.plslam_get_line_geometry.argtypes = [vp, C.c_int32, dp, dp]
-    L.plslam_set_incremental.argtypes = [vp, C.c_int32]
-    L.plslam_mark_landmark_changed.argtypes = [vp, C.c_int32, C.c_int32]
-    L.plslam_check_incremental_gather.argtypes = [vp, ip]
-    L.plslam_set_lcpose_solver.argtypes = [vp, LCPOSE_SOLVE_FN, vp]
-    L.plslam_set_lcpose_params.argtypes = [vp, C.POINTER(capi.PlbaLcposeParams)]
-    L.plslam_loop_closure_step.argtypes = [vp, C.POINTER(PlslamLcCandidate), C.c_double, C.POINTER(PlslamLcStats)]
-    L.plslam_get_lc_state.argtypes = [vp, ip]
-    L.plslam_get_lc_pose_list.argtypes = [vp, dp, C.c_int32, ip]
-    L.plslam_get_lc_feature_idxs.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32, ip]
-    bp = C.POINTER(C.c_uint8)
-    L.plslam_set_keyframe_features.argtypes = [vp, C.c_int32, C.c_int32, bp, dp, dp, bp, dp, dp, dp]
-    L.plslam_set_match_fn.argtypes = [vp, MATCH_FN, vp]
-    L.plslam_loop_closure_step_kf.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(PlslamMatchParams), C.c_double,
-                                              C.POINTER(PlslamLcStats)]
-    L.plslam_verify_loop_candidates.argtypes = [vp, C.c_int32, C.c_int32, ip, C.POINTER(PlslamMatchParams), C.c_double,
-                                                ip, dp, ip]
-    L.plslam_desc_match_cpu.argtypes = [vp, C.POINTER(capi.PlbaMatchBatch), ip, ip]
-    L.plslam_line_cells.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, ip, C.c_int32, ip]
-    L.plslam_grid_match_cpu.argtypes = [vp, C.POINTER(capi.PlbaGridMatchBatch), ip, ip]
-    L.plslam_set_keyframe_stereo.argtypes = [vp, C.c_int32, C.POINTER(PlslamStereoFrame), C.POINTER(capi.PlbaStereoParams),
-                                             ip, ip, C.POINTER(PlslamStereoStats)]
-    L.plslam_set_stereo_fn.argtypes = [vp, STEREO_FN, vp]
-    L.plslam_stereo_cpu.argtypes = [vp, C.POINTER(capi.PlbaStereoBatch), C.POINTER(capi.PlbaStereoParams),
-                                    C.POINTER(capi.PlbaStereoOut)]
-    L.plslam_match_kf_to_kf.argtypes = [vp, C.c_int32, C.c_int32, dp, C.POINTER(capi.PlbaKfassocParams),
-                                        C.POINTER(PlslamKfMatchStats)]
-    L.plslam_look_for_common_matches.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(capi.PlbaKfassocParams),
-                                                 C.POINTER(PlslamMapMatchParams), C.POINTER(PlslamKfMatchStats),
-                                                 C.POINTER(PlslamMapMatchStats)]
-    L.plslam_set_keyframe_line_pluker.argtypes = [vp, C.c_int32, dp]
-    L.plslam_set_kfassoc_fn.argtypes = [vp, KFASSOC_FN, vp]
-    L.plslam_kf_assoc_cpu.argtypes = [vp, C.POINTER(capi.PlbaKfassocBatch), C.POINTER(capi.PlbaKfassocParams),
-                                      C.POINTER(capi.PlbaKfassocOut)]
-    L.plslam_set_keyframe_line_endpoints.argtypes = [vp, C.c_int32, dp, dp]
-    L.plslam_set_camera.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32]
-    L.plslam_set_grid_match_fn.argtypes = [vp, GRID_MATCH_FN, vp]
-    L.plslam_mapmatch_default_params.argtypes = [C.POINTER(PlslamMapMatchParams)]
-    L.plslam_mapmatch_default_params.restype = None
-    L.plslam_match_map_to_kf.argtypes = [vp, C.c_int32, dp, C.POINTER(PlslamMapMatchParams),
-                                         C.POINTER(PlslamMapMatchStats)]
-    L.plslam_local_mapping_step_kf.argtypes = [vp, C.c_int32, C.POINTER(PlslamMapMatchParams),
-                                               C.POINTER(PlslamMapMatchStats), C.POINTER(PlslamLbaStats), ip, ip]
-    L.plslam_match_map_to_kf_assoc.argtypes = [vp, C.c_int32, dp, C.POINTER(capi.PlbaMapassocParams),
-                                               C.POINTER(PlslamMapMatchStats)]
-    L.plslam_local_mapping_step_kf_assoc.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaMapassocParams),
-                                                     C.POINTER(PlslamMapMatchStats), C.POINTER(PlslamLbaStats), ip, ip]
-    L.plslam_set_mapassoc_fn.argtypes = [vp, MAPASSOC_FN, vp]
-    L.plslam_map_assoc_cpu.argtypes = [vp, C.POINTER(capi.PlbaMapassocBatch), C.POINTER(capi.PlbaMapassocParams),
-                                       C.POINTER(capi.PlbaMapassocOut)]
-    fp = C.POINTER(C.c_float)
-    L.plslam_set_bow_fn.argtypes = [vp, vp, vp]    # the hook as an address: plslam_bow_cpu itself can be passed
-    L.plslam_bow_cpu_new.argtypes = []
-    L.plslam_bow_cpu_new.restype = vp
-    L.plslam_bow_cpu_free.argtypes = [vp]
-    L.plslam_bow_cpu_free.restype = None
-    L.plslam_bow_cpu.argtypes = [vp, C.POINTER(PlslamBowCall)]
-    L.plslam_set_vocabulary.argtypes = [vp, C.c_int32, C.POINTER(capi.PlbaBowVocab)]
-    L.plslam_remove_keyframe.argtypes = [vp, C.c_int32]
-    L.plslam_insert_kf_bow.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
-    L.plslam_get_conf_matrix_row.argtypes = [vp, C.c_int32, fp, C.c_int32, ip]
-    L.plslam_set_conf_matrix.argtypes = [vp, C.c_int32, fp]
-    L.plslam_look_for_loop_candidates.argtypes = [vp, C.c_int32, C.POINTER(PlslamLcSearchParams), ip, ip]
-    L.plslam_loop_closure_kf.argtypes = [vp, C.c_int32, C.POINTER(PlslamLcSearchParams), C.POINTER(PlslamMatchParams),
-                                         C.c_double, C.POINTER(PlslamLcStats)]
-    L.plslam_lc_search_default_params.argtypes = [C.POINTER(PlslamLcSearchParams)]
-    L.plslam_lc_search_default_params.restype = None
-    L.plslam_fuse_landmarks.argtypes = [vp, C.POINTER(PlslamFuseStats)]
-    L.plslam_set_medoid_fn.argtypes = [vp, MEDOID_FN, vp]
-    L.plslam_desc_medoid_cpu.argtypes = [vp, C.POINTER(capi.PlbaMedoidBatch), ip]
-    L.plslam_loop_closure_optimization_fuse.argtypes = [vp, C.c_int32, C.POINTER(PlslamPgoStats), C.POINTER(PlslamFuseStats)]
-    L.plslam_set_lc_feature_idxs.argtypes = [vp, C.c_int32, C.c_int32, ip, C.c_int32]
-    for n in HOST_EXPORTED:
-        if n not in ("plslam_map_last_error", "plslam_pluker_to_orth", "plslam_orth_to_pluker",
-                     "plslam_mapmatch_default_params", "plslam_bow_cpu_new", "plslam_bow_cpu_free",
-                     "plslam_lc_search_default_params"):
-            getattr(L, n).restype = C.c_int
+    for name, argtypes in HOST_ARGTYPES.items():
+        f = getattr(L, name)
+        f.argtypes = argtypes
+        f.restype = HOST_RESTYPES.get(name, C.c_int)
     _hl = L
     return L
 
@@ -615,16 +595,28 @@ def line_cells(x1: float, y1: float, x2: float, y2: float) -> np.ndarray:
     return out[:n.value]
 
 
+def _cpu_call(name: str, *args):
+    """One of the library's *_cpu restatements (user pointer NULL); raises on a non-zero status."""
+    rc = getattr(load_host(), name)(None, *args)
+    if rc != 0:
+        raise PlbaError(f"{name} failed: {rc}")
+
+
+def _assoc_cpu(name: str, view_cls, params_fn, problems, params, desc_bytes):
+    """The restatements over a view that holds its own outputs: (the view, the params struct) after the call."""
+    bv = problems if isinstance(problems, view_cls) else view_cls(problems, desc_bytes)
+    prm = params_fn(params)
+    _cpu_call(name, C.byref(bv.struct), C.byref(prm), C.byref(bv.out))
+    return bv, prm
+
+
 def grid_match_cpu(problems, cols: int = 64, rows: int = 48, best_lr: bool = True, desc_bytes=None) -> list:
     """plslam_grid_match_cpu on the problems of Solver.grid_match (tests and tools/gridmatch_bench.py)."""
     bv = capi.GridMatchBatchView(problems, cols, rows, best_lr, desc_bytes)
     n = bv.struct.n
-    ip = C.POINTER(C.c_int32)
     m12 = np.full(max(int(bv.off1[-1]), 1), -1, np.int32)
     cnt = np.zeros(max(n, 1), np.int32)
-    rc = load_host().plslam_grid_match_cpu(None, C.byref(bv.struct), m12.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
-    if rc != 0:
-        raise PlbaError(f"plslam_grid_match_cpu failed: {rc}")
+    _cpu_call("plslam_grid_match_cpu", C.byref(bv.struct), m12.ctypes.data_as(_ip), cnt.ctypes.data_as(_ip))
     return [(m12[bv.off1[i]:bv.off1[i + 1]].copy(), int(cnt[i])) for i in range(n)]
 
 
@@ -632,45 +624,40 @@ def desc_medoid_cpu(list_ptr, desc, desc_bytes=None) -> np.ndarray:
     """plslam_desc_medoid_cpu on the lists of Solver.desc_medoid (tests and tools/fuse_bench.py)."""
     bv = capi.MedoidBatchView(list_ptr, desc, desc_bytes)
     out = np.full(max(bv.struct.n, 1), -1, np.int32)
-    rc = load_host().plslam_desc_medoid_cpu(None, C.byref(bv.struct), out.ctypes.data_as(C.POINTER(C.c_int32)))
-    if rc != 0:
-        raise PlbaError(f"plslam_desc_medoid_cpu failed: {rc}")
+    _cpu_call("plslam_desc_medoid_cpu", C.byref(bv.struct), out.ctypes.data_as(_ip))
     return out[:bv.struct.n].copy()
 
 
 def kf_assoc_cpu(pairs, params, desc_bytes=None) -> list:
     """plslam_kf_assoc_cpu on the pairs of Solver.kf_associate (tests and tools/kfassoc_bench.py)."""
-    bv = pairs if isinstance(pairs, capi.KfassocBatchView) else capi.KfassocBatchView(pairs, desc_bytes)
-    prm = capi.kfassoc_params(params)
-    rc = load_host().plslam_kf_assoc_cpu(None, C.byref(bv.struct), C.byref(prm), C.byref(bv.out))
-    if rc != 0:
-        raise PlbaError(f"plslam_kf_assoc_cpu failed: {rc}")
-    return bv.results()
+    return _assoc_cpu("plslam_kf_assoc_cpu", capi.KfassocBatchView, capi.kfassoc_params, pairs, params, desc_bytes)[0].results()
 
 
 def map_assoc_cpu(problems, params, desc_bytes=None) -> list:
     """plslam_map_assoc_cpu on the keyframes of Solver.map_associate (tests and tools/mapassoc_bench.py)."""
-    bv = problems if isinstance(problems, capi.MapassocBatchView) else capi.MapassocBatchView(problems, desc_bytes)
-    prm = capi.mapassoc_params(params)
-    rc = load_host().plslam_map_assoc_cpu(None, C.byref(bv.struct), C.byref(prm), C.byref(bv.out))
-    if rc != 0:
-        raise PlbaError(f"plslam_map_assoc_cpu failed: {rc}")
-    return bv.results()
+    return _assoc_cpu("plslam_map_assoc_cpu", capi.MapassocBatchView, capi.mapassoc_params, problems, params,
+                      desc_bytes)[0].results()
 
 
 def stereo_cpu(frames, params, desc_bytes=None) -> list:
     """plslam_stereo_cpu on the frames of Solver.stereo_associate (tests and tools/stereo_bench.py)."""
-    bv = frames if isinstance(frames, capi.StereoBatchView) else capi.StereoBatchView(frames, desc_bytes)
-    prm = capi.stereo_params(params)
-    rc = load_host().plslam_stereo_cpu(None, C.byref(bv.struct), C.byref(prm), C.byref(bv.out))
-    if rc != 0:
-        raise PlbaError(f"plslam_stereo_cpu failed: {rc}")
+    bv, prm = _assoc_cpu("plslam_stereo_cpu", capi.StereoBatchView, capi.stereo_params, frames, params, desc_bytes)
     return bv.results(bool(prm.pluker))
 
 
 def _d(a):
     a = np.ascontiguousarray(a, np.float64)
-    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+    return a, a.ctypes.data_as(_dp)
+
+
+def _mat4(T):
+    """An optional (4, 4) matrix, row-major: (the array to keep alive, its pointer), or (None, None)."""
+    return (None, None) if T is None else _d(np.asarray(T, np.float64).reshape(16))
+
+
+def _ref(params):
+    """An optional params struct: byref, or NULL for the library's defaults."""
+    return C.byref(params) if params is not None else None
 
 
 class HostMap:
@@ -686,7 +673,7 @@ class HostMap:
         o.corrected_line_jacobian = int(corrected_line_jacobian)
         self.h = C.c_void_p()
         self._check(self.L.plslam_map_create(C.byref(self.h), m.fx, m.fy, m.cx, m.cy, C.byref(o)), "create")
-        self._cb = None
+        self._hooks = {}     # hook name -> the callback object the C side holds, kept alive until replaced
         self._kf_feat = {}   # kf_idx -> (point features, line features), as given to plslam_add_keyframe
         self.n_kf = len(m.keyframes)
         self.n_pt = len(m.points)
@@ -806,23 +793,37 @@ class HostMap:
             else:
                 self.n_ln += n
 
+    def _set_hook(self, name: str, fn):
+        """Installs ``fn`` as hook ``name`` of HOOKS: None clears it (the MI355X backend), "cpu" is the library's
+        own CPU restatement, passed straight through, and a callable runs behind a trampoline that never lets
+        an exception unwind through C: the traceback is printed and the hook returns -1."""
+        setter, ftype, deref, cpu = HOOKS[name]
+        if fn is None:
+            cb = C.cast(None, ftype)
+        elif isinstance(fn, str):
+            if fn != "cpu" or cpu is None:
+                raise ValueError(f"{setter}: {fn!r} is neither a callable nor a CPU restatement of this hook")
+            cb = C.cast(getattr(self.L, cpu), ftype)
+        else:
+            def tramp(user, *args):
+                try:
+                    return int(fn(*(a.contents if i in deref else a for i, a in enumerate(args))))
+                except Exception:  # never unwind through C
+                    import traceback
+                    traceback.print_exc()
+                    return -1
+            cb = ftype(tramp)
+        set_fn = getattr(self.L, setter)
+        self._check(set_fn(self.h, cb if set_fn.argtypes[1] is ftype else C.cast(cb, C.c_void_p), None), setter[7:])
+        self._hooks[name] = cb
+
+    @property
+    def _cb(self):
+        return self._hooks.get("solver")
+
     def set_solver(self, fn: Optional[Callable]):
         """fn(graph: PlbaGraph, result: PlbaResult) -> int, or None for the MI355X backend."""
-        if fn is None:
-            self._cb = None
-            self._check(self.L.plslam_set_solver(self.h, C.cast(None, SOLVE_FN), None), "set_solver")
-            return
-
-        def tramp(user, gp, rp):
-            try:
-                return int(fn(gp.contents, rp.contents))
-            except Exception as e:  # never unwind through C
-                import traceback
-                traceback.print_exc()
-                self._cb_error = e
-                return -1
-        self._cb = SOLVE_FN(tramp)
-        self._check(self.L.plslam_set_solver(self.h, self._cb, None), "set_solver")
+        self._set_hook("solver", fn)
 
     def set_incremental(self, on: bool):
         self._check(self.L.plslam_set_incremental(self.h, int(on)), "set_incremental")
@@ -845,23 +846,10 @@ class HostMap:
     # -- hand-rolled LM LBA (MapHandler::localBundleAdjustmentForPluker)
     def set_hlm_solver(self, fn: Optional[Callable]):
         """fn(graph, state, params, result) -> int, or None for the MI355X backend (plba_hlm_lba)."""
-        if fn is None:
-            self._hcb = None
-            self._check(self.L.plslam_set_hlm_solver(self.h, C.cast(None, HLM_SOLVE_FN), None), "set_hlm_solver")
-            return
-
-        def tramp(user, gp, sp, pp, rp):
-            try:
-                return int(fn(gp.contents, sp.contents, pp.contents, rp.contents))
-            except Exception:  # never unwind through C
-                import traceback
-                traceback.print_exc()
-                return -1
-        self._hcb = HLM_SOLVE_FN(tramp)
-        self._check(self.L.plslam_set_hlm_solver(self.h, self._hcb, None), "set_hlm_solver")
+        self._set_hook("hlm", fn)
 
     def set_hlm_params(self, params=None, vo_inserting_kf: bool = False):
-        self._check(self.L.plslam_set_hlm_params(self.h, C.byref(params) if params is not None else None,
+        self._check(self.L.plslam_set_hlm_params(self.h, _ref(params),
                                                  int(vo_inserting_kf)), "set_hlm_params")
 
     def local_ba_hlm(self) -> dict:
@@ -886,33 +874,23 @@ class HostMap:
         self._check(self.L.plslam_set_loop_closure(self.h, len(a), a.ctypes.data_as(ip), len(b), b.ctypes.data_as(ip),
                                                    len(c), c.ctypes.data_as(C.POINTER(C.c_double))), "set_loop_closure")
 
-    def lc_idx_list(self) -> np.ndarray:
+    def _sized(self, fn, what: str, width: int, ctype, *args) -> np.ndarray:
+        """The getters fn(h, *args, out, cap, n) that report their row count: asked for it, then for the rows."""
         n = C.c_int32(0)
-        self._check(self.L.plslam_get_lc_idx_list(self.h, None, 0, C.byref(n)), "get_lc_idx_list")
-        out = np.zeros((max(n.value, 1), 3), np.int32)
-        self._check(self.L.plslam_get_lc_idx_list(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), n.value,
-                                                  C.byref(n)), "get_lc_idx_list")
-        return out[:n.value]
+        self._check(fn(self.h, *args, None, 0, C.byref(n)), what)
+        out = np.zeros((max(n.value, 1), width), ctype)
+        self._check(fn(self.h, *args, out.ctypes.data_as(C.POINTER(ctype)), n.value, C.byref(n)), what)
+        return out[:max(n.value, 0)]
+
+    def lc_idx_list(self) -> np.ndarray:
+        return self._sized(self.L.plslam_get_lc_idx_list, "get_lc_idx_list", 3, C.c_int32)
 
     def set_pgo_params(self, min_lm_ess_graph: int = 150, max_iters_pgo: int = 100):
         self._check(self.L.plslam_set_pgo_params(self.h, min_lm_ess_graph, max_iters_pgo), "set_pgo_params")
 
     def set_pgo_solver(self, fn: Optional[Callable]):
         """fn(graph, params, result) -> int, or None for the MI355X backend (plba_pgo_optimize)."""
-        if fn is None:
-            self._pcb = None
-            self._check(self.L.plslam_set_pgo_solver(self.h, C.cast(None, PGO_SOLVE_FN), None), "set_pgo_solver")
-            return
-
-        def tramp(user, gp, pp, rp):
-            try:
-                return int(fn(gp.contents, pp.contents, rp.contents))
-            except Exception:  # never unwind through C
-                import traceback
-                traceback.print_exc()
-                return -1
-        self._pcb = PGO_SOLVE_FN(tramp)
-        self._check(self.L.plslam_set_pgo_solver(self.h, self._pcb, None), "set_pgo_solver")
+        self._set_hook("pgo", fn)
 
     def loop_closure(self, ess: bool = True) -> dict:
         st = PlslamPgoStats()
@@ -929,22 +907,7 @@ class HostMap:
     def set_medoid_fn(self, fn):
         """fn(batch, medoid) -> int; "cpu" for plslam_desc_medoid_cpu (no trampoline: the C function
         itself); None for the MI355X backend (plba_desc_medoid)."""
-        if fn is None:
-            self._medcb = None
-            self._check(self.L.plslam_set_medoid_fn(self.h, C.cast(None, MEDOID_FN), None), "set_medoid_fn")
-            return
-        if isinstance(fn, str) and fn == "cpu":
-            self._medcb = C.cast(self.L.plslam_desc_medoid_cpu, MEDOID_FN)
-        else:
-            def tramp(user, bp_, med):
-                try:
-                    return int(fn(bp_.contents, med))
-                except Exception:  # never unwind through C
-                    import traceback
-                    traceback.print_exc()
-                    return -1
-            self._medcb = MEDOID_FN(tramp)
-        self._check(self.L.plslam_set_medoid_fn(self.h, self._medcb, None), "set_medoid_fn")
+        self._set_hook("medoid", fn)
 
     def fuse_landmarks(self) -> dict:
         st = PlslamFuseStats()
@@ -962,24 +925,10 @@ class HostMap:
     def set_lcpose_solver(self, fn: Optional[Callable]):
         """fn(batch, params, out, pt_inlier, ln_inlier) -> int, or None for the MI355X backend
         (plba_lc_relative_pose)."""
-        if fn is None:
-            self._lcb = None
-            self._check(self.L.plslam_set_lcpose_solver(self.h, C.cast(None, LCPOSE_SOLVE_FN), None),
-                        "set_lcpose_solver")
-            return
-
-        def tramp(user, bp_, pp, op, pin, lin):
-            try:
-                return int(fn(bp_.contents, pp.contents, op, pin, lin))
-            except Exception:  # never unwind through C
-                import traceback
-                traceback.print_exc()
-                return -1
-        self._lcb = LCPOSE_SOLVE_FN(tramp)
-        self._check(self.L.plslam_set_lcpose_solver(self.h, self._lcb, None), "set_lcpose_solver")
+        self._set_hook("lcpose", fn)
 
     def set_lcpose_params(self, params=None):
-        self._check(self.L.plslam_set_lcpose_params(self.h, C.byref(params) if params is not None else None),
+        self._check(self.L.plslam_set_lcpose_params(self.h, _ref(params)),
                     "set_lcpose_params")
 
     def loop_closure_step(self, candidate=None, kf_prev_idx: int = 0, kf_curr_idx: int = 0, n_feat=None,
@@ -1032,20 +981,7 @@ class HostMap:
 
     def set_match_fn(self, fn: Optional[Callable]):
         """fn(batch, matches_12, n_matches) -> int, or None for the MI355X backend (plba_desc_match)."""
-        if fn is None:
-            self._mcb = None
-            self._check(self.L.plslam_set_match_fn(self.h, C.cast(None, MATCH_FN), None), "set_match_fn")
-            return
-
-        def tramp(user, bp_, m12, cnt):
-            try:
-                return int(fn(bp_.contents, m12, cnt))
-            except Exception:  # never unwind through C
-                import traceback
-                traceback.print_exc()
-                return -1
-        self._mcb = MATCH_FN(tramp)
-        self._check(self.L.plslam_set_match_fn(self.h, self._mcb, None), "set_match_fn")
+        self._set_hook("match", fn)
 
     # ---- place recognition: insertKFBowVector*, lookForLoopCandidates, loopClosure() whole
     def set_bow_cpu(self, bow_cpu: Optional["BowCpu"]):
@@ -1053,25 +989,13 @@ class HostMap:
         tests), or, with None, back to the MI355X backend (plba_bow_*)."""
         self._bow_cpu = bow_cpu
         if bow_cpu is None:
-            self._check(self.L.plslam_set_bow_fn(self.h, None, None), "set_bow_fn")
-            return
+            return self._set_hook("bow", None)
         fn = C.cast(self.L.plslam_bow_cpu, C.c_void_p)
         self._check(self.L.plslam_set_bow_fn(self.h, fn, bow_cpu.db), "set_bow_fn")
 
     def set_bow_fn(self, fn: Optional[Callable]):
         """fn(call: PlslamBowCall) -> int, or None for the MI355X backend."""
-        if fn is None:
-            return self.set_bow_cpu(None)
-
-        def tramp(user, cp):
-            try:
-                return int(fn(cp.contents))
-            except Exception:  # never unwind through C
-                import traceback
-                traceback.print_exc()
-                return -1
-        self._bcb = BOW_FN(tramp)
-        self._check(self.L.plslam_set_bow_fn(self.h, C.cast(self._bcb, C.c_void_p), None), "set_bow_fn")
+        self._set_hook("bow", fn)
 
     def set_vocabulary(self, slot: int, voc):
         vv = voc if isinstance(voc, capi.BowVocabView) else capi.BowVocabView(voc)
@@ -1102,7 +1026,7 @@ class HostMap:
     def look_for_loop_candidates(self, kf_curr_idx: int, params: Optional[PlslamLcSearchParams] = None):
         """lookForLoopCandidates: (is_candidate, kf_prev_idx)."""
         a, b = C.c_int32(0), C.c_int32(0)
-        self._check(self.L.plslam_look_for_loop_candidates(self.h, kf_curr_idx, C.byref(params) if params is not None else None,
+        self._check(self.L.plslam_look_for_loop_candidates(self.h, kf_curr_idx, _ref(params),
                                                            C.byref(a), C.byref(b)), "look_for_loop_candidates")
         return bool(a.value), b.value
 
@@ -1110,8 +1034,8 @@ class HostMap:
                         params: Optional[PlslamMatchParams] = None, lc_inlier_ratio: float = 30.0) -> dict:
         """loopClosure() whole: the candidate search, then isLoopClosure and the state machine."""
         st = PlslamLcStats()
-        self._check(self.L.plslam_loop_closure_kf(self.h, kf_curr_idx, C.byref(search) if search is not None else None,
-                                                  C.byref(params) if params is not None else None, lc_inlier_ratio,
+        self._check(self.L.plslam_loop_closure_kf(self.h, kf_curr_idx, _ref(search),
+                                                  _ref(params), lc_inlier_ratio,
                                                   C.byref(st)), "loop_closure_kf")
         return st.as_dict()
 
@@ -1121,7 +1045,7 @@ class HostMap:
         relative pose, lists and state machine."""
         st = PlslamLcStats()
         self._check(self.L.plslam_loop_closure_step_kf(self.h, kf_prev_idx, kf_curr_idx,
-                                                       C.byref(params) if params is not None else None,
+                                                       _ref(params),
                                                        lc_inlier_ratio, C.byref(st)), "loop_closure_step_kf")
         return st.as_dict()
 
@@ -1134,7 +1058,7 @@ class HostMap:
         acc, pose, cnt = np.zeros(max(k, 1), np.int32), np.zeros((max(k, 1), 6)), np.zeros((max(k, 1), 2), np.int32)
         ip = C.POINTER(C.c_int32)
         self._check(self.L.plslam_verify_loop_candidates(
-            self.h, kf_curr_idx, k, prev.ctypes.data_as(ip), C.byref(params) if params is not None else None,
+            self.h, kf_curr_idx, k, prev.ctypes.data_as(ip), _ref(params),
             lc_inlier_ratio, acc.ctypes.data_as(ip), pose.ctypes.data_as(C.POINTER(C.c_double)), cnt.ctypes.data_as(ip)),
             "verify_loop_candidates")
         return dict(accepted=acc[:k], pose_inc=pose[:k], n_matches=cnt[:k])
@@ -1152,22 +1076,7 @@ class HostMap:
     def set_stereo_fn(self, fn):
         """fn(batch, params, out) -> int; "cpu" for plslam_stereo_cpu; None for the MI355X backend
         (plba_stereo_associate)."""
-        if fn is None:
-            self._scb = None
-            self._check(self.L.plslam_set_stereo_fn(self.h, C.cast(None, STEREO_FN), None), "set_stereo_fn")
-            return
-        if fn == "cpu":
-            self._scb = C.cast(self.L.plslam_stereo_cpu, STEREO_FN)
-        else:
-            def tramp(user, bp_, pp, op):
-                try:
-                    return int(fn(bp_.contents, pp.contents, op.contents))
-                except Exception:  # never unwind through C
-                    import traceback
-                    traceback.print_exc()
-                    return -1
-            self._scb = STEREO_FN(tramp)
-        self._check(self.L.plslam_set_stereo_fn(self.h, self._scb, None), "set_stereo_fn")
+        self._set_hook("stereo", fn)
 
     def set_keyframe_stereo(self, kf_idx: int, frame: dict, params, desc_bytes=None) -> dict:
         """The features of keyframe ``kf_idx`` from the detector output of its two images (``frame``: a
@@ -1203,22 +1112,7 @@ class HostMap:
     def set_kfassoc_fn(self, fn):
         """fn(batch, params, out) -> int; "cpu" for plslam_kf_assoc_cpu; None for the MI355X backend
         (plba_kf_associate)."""
-        if fn is None:
-            self._kcb = None
-            self._check(self.L.plslam_set_kfassoc_fn(self.h, C.cast(None, KFASSOC_FN), None), "set_kfassoc_fn")
-            return
-        if fn == "cpu":
-            self._kcb = C.cast(self.L.plslam_kf_assoc_cpu, KFASSOC_FN)
-        else:
-            def tramp(user, bp_, pp, op):
-                try:
-                    return int(fn(bp_.contents, pp.contents, op.contents))
-                except Exception:  # never unwind through C
-                    import traceback
-                    traceback.print_exc()
-                    return -1
-            self._kcb = KFASSOC_FN(tramp)
-        self._check(self.L.plslam_set_kfassoc_fn(self.h, self._kcb, None), "set_kfassoc_fn")
+        self._set_hook("kfassoc", fn)
 
     def _kfmatch_stats(self, kf_prev_idx: int):
         n = self._kf_feat.get(kf_prev_idx, (0, 0))
@@ -1238,10 +1132,10 @@ class HostMap:
         T_prev)); ``params``: a dict over plba_kfassoc_default_params (or a capi.PlbaKfassocParams); without
         width / height the camera of set_camera is used. Returns the statistics with the accepted pairs."""
         st, pp, lp = self._kfmatch_stats(kf_prev_idx)
-        T = None if DT is None else np.ascontiguousarray(np.asarray(DT, np.float64).reshape(16))
+        T, Tp = _mat4(DT)
         prm = capi.kfassoc_params(params)
         self._check(self.L.plslam_match_kf_to_kf(
-            self.h, kf_prev_idx, kf_curr_idx, T.ctypes.data_as(C.POINTER(C.c_double)) if T is not None else None,
+            self.h, kf_prev_idx, kf_curr_idx, Tp,
             C.byref(prm), C.byref(st)), "match_kf_to_kf")
         return self._kfmatch_dict(st, pp, lp)
 
@@ -1253,7 +1147,7 @@ class HostMap:
         ms = PlslamMapMatchStats()
         prm = capi.kfassoc_params(kf_params)
         self._check(self.L.plslam_look_for_common_matches(
-            self.h, kf_prev_idx, kf_curr_idx, C.byref(prm), C.byref(map_params) if map_params is not None else None,
+            self.h, kf_prev_idx, kf_curr_idx, C.byref(prm), _ref(map_params),
             C.byref(st), C.byref(ms)), "look_for_common_matches")
         return dict(kf=self._kfmatch_dict(st, pp, lp), map=ms.as_dict())
 
@@ -1263,62 +1157,32 @@ class HostMap:
     def set_grid_match_fn(self, fn):
         """fn(batch, matches_12, n_matches) -> int; "cpu" for plslam_grid_match_cpu; None for the
         MI355X backend (plba_grid_match)."""
-        if fn is None:
-            self._gcb = None
-            self._check(self.L.plslam_set_grid_match_fn(self.h, C.cast(None, GRID_MATCH_FN), None), "set_grid_match_fn")
-            return
-        if fn == "cpu":
-            self._gcb = C.cast(self.L.plslam_grid_match_cpu, GRID_MATCH_FN)
-        else:
-            def tramp(user, bp_, m12, cnt):
-                try:
-                    return int(fn(bp_.contents, m12, cnt))
-                except Exception:  # never unwind through C
-                    import traceback
-                    traceback.print_exc()
-                    return -1
-            self._gcb = GRID_MATCH_FN(tramp)
-        self._check(self.L.plslam_set_grid_match_fn(self.h, self._gcb, None), "set_grid_match_fn")
+        self._set_hook("grid", fn)
 
     def match_map_to_kf(self, kf_idx: int, Twf=None, params: Optional[PlslamMapMatchParams] = None) -> dict:
         """matchMap2KFPoints + matchMap2KFLines for keyframe ``kf_idx``; ``Twf`` (4, 4) world ->
         keyframe, None for the inverse of its T_kf_w. Returns the statistics."""
         st = PlslamMapMatchStats()
-        T = None if Twf is None else np.ascontiguousarray(np.asarray(Twf, np.float64).reshape(16))
+        T, Tp = _mat4(Twf)
         self._check(self.L.plslam_match_map_to_kf(
-            self.h, kf_idx, T.ctypes.data_as(C.POINTER(C.c_double)) if T is not None else None,
-            C.byref(params) if params is not None else None, C.byref(st)), "match_map_to_kf")
+            self.h, kf_idx, Tp,
+            _ref(params), C.byref(st)), "match_map_to_kf")
         return st.as_dict()
 
     def set_mapassoc_fn(self, fn):
         """fn(batch, params, out) -> int; "cpu" for plslam_map_assoc_cpu; None for the MI355X backend
         (plba_map_associate)."""
-        if fn is None:
-            self._macb = None
-            self._check(self.L.plslam_set_mapassoc_fn(self.h, C.cast(None, MAPASSOC_FN), None), "set_mapassoc_fn")
-            return
-        if fn == "cpu":
-            self._macb = C.cast(self.L.plslam_map_assoc_cpu, MAPASSOC_FN)
-        else:
-            def tramp(user, bp_, pp, op):
-                try:
-                    return int(fn(bp_.contents, pp.contents, op.contents))
-                except Exception:  # never unwind through C
-                    import traceback
-                    traceback.print_exc()
-                    return -1
-            self._macb = MAPASSOC_FN(tramp)
-        self._check(self.L.plslam_set_mapassoc_fn(self.h, self._macb, None), "set_mapassoc_fn")
+        self._set_hook("mapassoc", fn)
 
     def match_map_to_kf_assoc(self, kf_idx: int, Twf=None, params=None) -> dict:
         """match_map_to_kf around one plba_map_associate call (or the hook of set_mapassoc_fn). ``params``: a
         dict over plba_mapassoc_default_params (or a capi.PlbaMapassocParams); without width / height the
         camera of set_camera is used. Returns the statistics of match_map_to_kf."""
         st = PlslamMapMatchStats()
-        T = None if Twf is None else np.ascontiguousarray(np.asarray(Twf, np.float64).reshape(16))
+        T, Tp = _mat4(Twf)
         prm = capi.mapassoc_params(params)
         self._check(self.L.plslam_match_map_to_kf_assoc(
-            self.h, kf_idx, T.ctypes.data_as(C.POINTER(C.c_double)) if T is not None else None, C.byref(prm), C.byref(st)),
+            self.h, kf_idx, Tp, C.byref(prm), C.byref(st)),
             "match_map_to_kf_assoc")
         return st.as_dict()
 
@@ -1329,20 +1193,16 @@ class HostMap:
         prm = capi.mapassoc_params(params)
         self._check(self.L.plslam_local_mapping_step_kf_assoc(self.h, kf_idx, C.byref(prm), C.byref(ms), C.byref(st),
                                                               C.byref(a), C.byref(b)), "local_mapping_step_kf_assoc")
-        d = st.as_dict()
-        d["points_removed"], d["lines_removed"], d["match"] = a.value, b.value, ms.as_dict()
-        return d
+        return self._step_dict(st, a, b, ms)
 
     def local_mapping_step_kf(self, kf_idx: int, params: Optional[PlslamMapMatchParams] = None) -> dict:
         """match_map_to_kf, then local_mapping_step."""
         ms, st = PlslamMapMatchStats(), PlslamLbaStats()
         a, b = C.c_int32(), C.c_int32()
-        self._check(self.L.plslam_local_mapping_step_kf(self.h, kf_idx, C.byref(params) if params is not None else None,
+        self._check(self.L.plslam_local_mapping_step_kf(self.h, kf_idx, _ref(params),
                                                         C.byref(ms), C.byref(st), C.byref(a), C.byref(b)),
                     "local_mapping_step_kf")
-        d = st.as_dict()
-        d["points_removed"], d["lines_removed"], d["match"] = a.value, b.value, ms.as_dict()
-        return d
+        return self._step_dict(st, a, b, ms)
 
     def lc_state(self) -> int:
         v = C.c_int32(0)
@@ -1350,21 +1210,11 @@ class HostMap:
         return v.value
 
     def lc_pose_list(self) -> np.ndarray:
-        n = C.c_int32(0)
-        self._check(self.L.plslam_get_lc_pose_list(self.h, None, 0, C.byref(n)), "get_lc_pose_list")
-        out = np.zeros((max(n.value, 1), 6))
-        self._check(self.L.plslam_get_lc_pose_list(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), n.value,
-                                                   C.byref(n)), "get_lc_pose_list")
-        return out[:n.value]
+        return self._sized(self.L.plslam_get_lc_pose_list, "get_lc_pose_list", 6, C.c_double)
 
     def lc_feature_idxs(self, kind: int, loop: int) -> np.ndarray:
         """The kept lc_pt_idx (kind 1) / lc_ls_idx (kind 2) rows of accepted loop ``loop``."""
-        n = C.c_int32(0)
-        self._check(self.L.plslam_get_lc_feature_idxs(self.h, kind, loop, None, 0, C.byref(n)), "get_lc_feature_idxs")
-        out = np.zeros((max(n.value, 1), 4), np.int32)
-        self._check(self.L.plslam_get_lc_feature_idxs(self.h, kind, loop, out.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                      n.value, C.byref(n)), "get_lc_feature_idxs")
-        return out[:n.value]
+        return self._sized(self.L.plslam_get_lc_feature_idxs, "get_lc_feature_idxs", 4, C.c_int32, kind, loop)
 
     def set_line_geometry(self, idx: int, line3d, med_obs_dir):
         a, pa = _d(line3d)
@@ -1399,8 +1249,15 @@ class HostMap:
         a, b = C.c_int32(), C.c_int32()
         self._check(self.L.plslam_local_mapping_step(self.h, kf_idx, C.byref(st), C.byref(a), C.byref(b)),
                     "local_mapping_step")
+        return self._step_dict(st, a, b)
+
+    @staticmethod
+    def _step_dict(st, n_pt_removed, n_ln_removed, ms=None) -> dict:
+        """What the local-mapping steps return: the LBA statistics, the culled counts and the match statistics."""
         d = st.as_dict()
-        d["points_removed"], d["lines_removed"] = a.value, b.value
+        d["points_removed"], d["lines_removed"] = n_pt_removed.value, n_ln_removed.value
+        if ms is not None:
+            d["match"] = ms.as_dict()
         return d
 
     def exists(self, kind: int, idx: int) -> bool:
@@ -1470,14 +1327,9 @@ class HostMap:
         fg = np.zeros_like(out.full_graph)
         self._check(L.plslam_get_full_graph(h, fg.shape[0], fg.ctypes.data_as(C.POINTER(C.c_uint32))), "full_graph")
         out.full_graph = fg
-        n = C.c_int32()
         for k in list(out.map_points_kf_idx.keys()):
-            buf = np.zeros(4096, np.int32)
-            self._check(L.plslam_kf_idx_get(h, k, buf.ctypes.data_as(ip), len(buf), C.byref(n)), "kf_idx_get")
-            out.map_points_kf_idx[k] = [int(v) for v in buf[:n.value]]
+            out.map_points_kf_idx[k] = self._sized(L.plslam_kf_idx_get, "kf_idx_get", 1, C.c_int32, k)[:, 0].tolist()
         for k in list(out.map_lines_kf_idx.keys()):
-            buf = np.zeros(4096, np.int32)
-            self._check(L.plslam_kf_lines_idx_get(h, k, buf.ctypes.data_as(ip), len(buf), C.byref(n)),
-                        "kf_lines_idx_get")
-            out.map_lines_kf_idx[k] = [int(v) for v in buf[:n.value]]
+            out.map_lines_kf_idx[k] = self._sized(L.plslam_kf_lines_idx_get, "kf_lines_idx_get", 1, C.c_int32,
+                                                  k)[:, 0].tolist()
         return out

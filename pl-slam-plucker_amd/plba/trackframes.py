@@ -132,9 +132,6 @@ def track_frames_cpu(pairs, params=None) -> list:
     single-threaded. The same dicts as Solver.track_frames."""
     from .slam_map import load_host
     H = load_host()
-    H.plslam_track_frames_cpu.argtypes = [C.c_void_p, C.POINTER(capi.PlbaFramesBatch), C.POINTER(capi.PlbaFramesParams),
-                                          C.POINTER(capi.PlbaFramesOut)]
-    H.plslam_track_frames_cpu.restype = C.c_int
     if params is None:
         params = capi.frames_params()
     bv = capi.FramesBatchView(pairs, params.desc_bytes)

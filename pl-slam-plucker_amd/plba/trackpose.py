@@ -122,9 +122,6 @@ def track_pose_cpu(problems, params=None) -> list:
     from .slam_map import load_host
     H = load_host()
     bp = C.POINTER(C.c_uint8)
-    H.plslam_track_pose_cpu.argtypes = [C.c_void_p, C.POINTER(capi.PlbaTrackBatch), C.POINTER(capi.PlbaTrackParams),
-                                        C.POINTER(capi.PlbaTrackOut), bp, bp]
-    H.plslam_track_pose_cpu.restype = C.c_int
     if params is None:
         params = capi.track_params()
     bv = capi.TrackBatchView(list(problems))

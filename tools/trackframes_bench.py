@@ -44,8 +44,6 @@ def child(batch: int, reps: int, model: int) -> None:
     ip, bp = C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
     out2 = (capi.PlbaTrackOut * batch)()
     H = load_host()
-    H.plslam_track_frames_cpu.argtypes = [C.c_void_p, C.POINTER(capi.PlbaFramesBatch), C.POINTER(capi.PlbaFramesParams),
-                                          C.POINTER(capi.PlbaFramesOut)]
 
     def timed(fn, n):
         ms = []

@@ -34,8 +34,6 @@ def child(batch: int, reps: int, model: int) -> None:
     pin, lin = np.zeros(int(bv.pt_off[-1]), np.uint8), np.zeros(int(bv.ln_off[-1]), np.uint8)
     bp = C.POINTER(C.c_uint8)
     H = load_host()
-    H.plslam_track_pose_cpu.argtypes = [C.c_void_p, C.POINTER(capi.PlbaTrackBatch), C.POINTER(capi.PlbaTrackParams),
-                                        C.POINTER(capi.PlbaTrackOut), bp, bp]
 
     def timed(fn, n):
         ms = []
